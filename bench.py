@@ -15,10 +15,17 @@ Weak scaling: every rank processes its own batch; the only data-path exchanges a
 float64 all-reduce per layer (the batch mean of the Z layer, admm_net.py:459) and the final gather of
 the peak-head outputs.  Inputs are resident in HBM before the timed region.
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with two extra objects:
+A plain run sets up, warms up, times --steps steps and prints ONE JSON line on rank 0 (metric, value, unit,
+higher_is_better, dtype, ms_per_step, config).  --full adds two objects to that line:
   roofline     -- dominant kernel: algorithmic flops per launch / average launch time (HIP events
                   recorded on the launch stream inside the timed region) vs the fp32 MFMA peak
-  cpu_baseline -- the oracle (CPU restatement, parity-pinned to the reference) on a bounded sample
+  cpu_baseline -- the oracle (CPU restatement, parity-pinned to the reference) on a bounded sample,
+                  the classical solver and the single-signal latency leg (--no-cpu-baseline drops them)
+
+--dump-outputs DIR writes, after the timed steps, what the last timed step returned on rank 0 as DIR/<name>.npy
+(float32 / float64): phi [rows, D, 2] (re, im), then head [3, rows, L] and spectrum [rows, nf, ntau], or for cfg5
+peaks [rows, 256, 3] and peak_counts [rows]; rows = a fixed seeded sample of DUMP_ROWS signals of the batch, whose
+positions are in signal_index.  Inputs and weights are seeded, so equal arguments give equal inputs.
 """
 import argparse
 import ctypes
@@ -100,6 +107,29 @@ def host_threads():
     return max(1, min(n, int(os.environ.get("ADMMNET_CPU_THREADS", "64"))))
 
 
+DUMP_ROWS = 2048                       # signals sampled for --dump-outputs (cfg3: 20 MB of files, cfg5: 17 MB)
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(path, phi, outs):
+    """--dump-outputs: phi and the step's other outputs (name: (tensor, batch dimension)) at a fixed seeded sample of
+    DUMP_ROWS signals, as float32 / float64 .npy files (complex as a trailing (re, im) axis, integers as float64)."""
+    B = phi.shape[0]
+    idx = np.arange(B) if B <= DUMP_ROWS else np.sort(np.random.default_rng(0).choice(B, DUMP_ROWS, replace=False))
+    sel = torch.from_numpy(idx).to(phi.device)
+    arrays = {"signal_index": idx.astype(np.float64)}
+    for name, (t, dim) in {"phi": (phi, 0), **outs}.items():
+        t = t.index_select(dim, sel)
+        a = (torch.view_as_real(t) if t.is_complex() else t).cpu().numpy()
+        arrays[name] = a if a.dtype in (np.float32, np.float64) else a.astype(np.float64)
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_MAX_BYTES, f"--dump-outputs would write {total} bytes"
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+    log(f"wrote {len(arrays)} arrays ({total / 1e6:.1f} MB) to {path}")
+
+
 def spawn_ranks(n):
     """A plain `python bench.py --gpus N`: start the N ranks as CHILD processes (torch.distributed.run, one per GPU) before
     anything here touches the GPU, relay their output and return their status.  `--standalone` lets the launcher pick its
@@ -122,6 +152,9 @@ def main():
     ap.add_argument("--workload", default="cfg3", choices=sorted(WORKLOADS))
     ap.add_argument("--batch", type=int, default=0, help="override the per-GPU batch")
     ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also the per-kernel roofline figures (HIP events in the timed steps) and the CPU legs")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's outputs as DIR/<name>.npy")
     args = ap.parse_args()
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -157,8 +190,9 @@ def main():
     model = cls(M=Nb, N=Nd, L=3, num_layers=K).eval()            # random init of the reference architecture
     # inputs are generated ON the device (csrc/synth.hip: the generate_data.py:133-221 recipe, one workgroup per sample)
     ty, tb, ts, _ = synth.make_batch_device(B, Nb, Nd, seed=20260104 + rank, device=dev)
-    nhost = min(B, 2048)                       # the CPU-baseline leg works on a copy of the first samples
-    y, b, s = (t[:nhost].cpu().numpy() for t in (ty, tb, ts))
+    if args.full:
+        nhost = min(B, 2048)                   # the CPU-baseline leg works on a copy of the first samples
+        y, b, s = (t[:nhost].cpu().numpy() for t in (ty, tb, ts))
     taus = torch.linspace(0.0, 1.0, ntau + 1, dtype=torch.float64)[:-1].to(dev)
     fs = torch.linspace(-0.5, 0.5, nf + 1, dtype=torch.float64)[:-1].to(dev)
     # cfg5: alt_peak_search's own coarse grid (np.arange(0, 1 - xstep, xstep) x np.arange(-.5, .5 - xstep, ystep),
@@ -178,12 +212,14 @@ def main():
         if post_search:
             pk, cnt = ops.peak_search(phi, Nd, Nb, ps_opts, max_peaks=256)    # xbase = Nd (delay), ybase = Nb (Doppler)
             tail = pk[:, :16].contiguous()                                     # the peak list is the final output
+            outs = {"peaks": (pk, 0), "peak_counts": (cnt, 0)}                 # name: (tensor, batch dimension)
         else:
             spec = ops.spectrum(phi, Nd, Nb, taus, fs)
             tail = head
+            outs = {"head": (head, 1), "spectrum": (spec, 0)}
         if world > 1:
             tail = sf._gather(tail, dim=0 if post_search else 1)               # final peak output over RCCL / xGMI
-        return phi, tail
+        return phi, tail, outs
 
     log(f"workload {args.workload}: grid {Nb}x{Nd} K={K} B={B}/GPU world={world}; warmup x{args.warmup}")
     for _ in range(args.warmup):
@@ -197,22 +233,25 @@ def main():
             dist.barrier()
             torch.cuda.synchronize(dev)
 
-    lib.admmnet_profile_enable(0 if os.environ.get("ADMMNET_BENCH_NOPROF") else 1)   # (developer: cost of the event pairs)
+    if args.full:      # per-class HIP-event pairs around every launch of the timed steps (for the roofline object)
+        lib.admmnet_profile_enable(0 if os.environ.get("ADMMNET_BENCH_NOPROF") else 1)   # (developer: cost of the event pairs)
     sync()
     t0 = time.perf_counter()
     for _ in range(args.steps):
+        out = None     # the previous step's outputs go back to the allocator first: every step runs in the same memory
         out = step()
     sync()
     dt = time.perf_counter() - t0
     log(f"timed {args.steps} steps: {dt:.3f} s")
-    NK = len(KERNELS)
-    ms = (ctypes.c_double * NK)()
-    cnt = (ctypes.c_int64 * NK)()
-    _lib.check(lib.admmnet_profile_read(ms, cnt, NK), "admmnet_profile_read")
-    dropped = int(lib.admmnet_profile_dropped())      # launches the event pool could not record (0 in a healthy run)
-    lib.admmnet_profile_enable(0)
-    if dropped:
-        log(f"WARNING: {dropped} launches were not recorded by the event profiler: per-step kernel sums withheld")
+    if args.full:
+        NK = len(KERNELS)
+        ms = (ctypes.c_double * NK)()
+        cnt = (ctypes.c_int64 * NK)()
+        _lib.check(lib.admmnet_profile_read(ms, cnt, NK), "admmnet_profile_read")
+        dropped = int(lib.admmnet_profile_dropped())      # launches the event pool could not record (0 in a healthy run)
+        lib.admmnet_profile_enable(0)
+        if dropped:
+            log(f"WARNING: {dropped} launches were not recorded by the event profiler: per-step kernel sums withheld")
     ranks = 1
     if world > 1:
         t = torch.tensor([dt], dtype=torch.float64, device=dev)
@@ -223,16 +262,19 @@ def main():
         ranks = int(one.item())
         assert ranks == dist.get_world_size() == world
     assert torch.isfinite(torch.view_as_real(out[0])).all()
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, out[0], out[2])
 
-    if rank == 0:
-        signals = B * world * args.steps
-        value = signals / dt
+    signals = B * world * args.steps
+    value = signals / dt
+    chunk = min(B, 8192)
+    roof = cpu = None
+    if rank == 0 and args.full:
         F = flops_per_signal(K, n, D, natoms)
         per = {KERNELS[i]: (ms[i], cnt[i]) for i in range(NK)}
         dom = max(("tridiag", "trideig", "backtransform", "rebuild", "gfunction"), key=lambda k_: per[k_][0])
         fast = dom == "gfunction"
         kf = 0.0 if fast else kernel_flops_per_matrix(n)[dom]
-        chunk = min(B, 8192)
         launches = max(per[dom][1], 1)
         avg_ms = per[dom][0] / launches
         mats_per_launch = B / math.ceil(B / chunk)          # every launch of a G-layer kernel works on one chunk
@@ -299,7 +341,6 @@ def main():
                 "profile_dropped_launches": dropped}
         if not fast:
             roof = roof_eig
-        cpu = None
         if world == 1 and not args.no_cpu_baseline:
             cpu = cpu_baseline(model, Nb, Nd, K, y, b, s, out[0], args.workload, head=not post_search)
             for key, leg in (("classical", classical_baseline), ("single_signal_latency", latency_leg)):
@@ -307,6 +348,7 @@ def main():
                     cpu[key] = leg()
                 except Exception as exc:               # noqa: BLE001
                     cpu[key] = {"error": f"{type(exc).__name__}: {exc}"}
+    if rank == 0:
         line = {"metric": "signals/sec (K-layer ADMM-Net forward)", "value": round(value, 2), "unit": "signals/s",
                 "n_gpus": ranks if world > 1 else 1, "steps": args.steps, "warmup": args.warmup,
                 "ms_per_step": round(dt / args.steps * 1e3, 3), "higher_is_better": True, "scaling": "weak",
@@ -319,8 +361,9 @@ def main():
                            "natoms": natoms, "batch_mean_scope": "global", "chunk": chunk,
                            "weights": "torch.manual_seed(0) default init",
                            "glayer": ("eigensolver pipeline (ADMMNET_SPECTRAL=0)" if os.environ.get("ADMMNET_SPECTRAL") == "0"
-                                      else "matrix function, checked per matrix; eigensolver on the rejected matrices")},
-                "roofline": roof, "cpu_baseline": cpu}
+                                      else "matrix function, checked per matrix; eigensolver on the rejected matrices")}}
+        if args.full:
+            line.update(roofline=roof, cpu_baseline=cpu)
         print(json.dumps(line), flush=True)
     if world > 1:
         dist.barrier()

@@ -13,7 +13,7 @@ W=${1:-cfg3}; B=${2:-4096}
 TAG=${TAG:-}
 OUT=gpurun_out/prof_r03${TAG}_$W
 rm -rf $OUT; mkdir -p $OUT
-CMD="python3 bench.py --workload $W --batch $B --warmup 1 --no-cpu-baseline"
+CMD="python3 bench.py --workload $W --batch $B --warmup 1 --full --no-cpu-baseline"
 rocprofv3 --kernel-trace --stats -d $OUT/kt -o $W -- $CMD --steps 3 > $OUT/${W}${TAG}_bench.json 2> $OUT/kt.err
 echo kt rc=$?
 for c in FETCH_SIZE WRITE_SIZE; do
@@ -25,7 +25,7 @@ echo sq rc=$?
 rocprofv3 --pmc SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_WAVE_CYCLES SQ_WAIT_INST_LDS SQ_INSTS_LDS SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE --kernel-trace -d $OUT/pmc_wait -o $W -- $CMD --steps 1 > /dev/null 2> $OUT/pmc_wait.err
 echo wait rc=$?
 if [ "$3" = "full" ]; then
-  rocprofv3 --kernel-trace --stats -d $OUT/full/kt -o ${W}_full -- python3 bench.py --workload $W --no-cpu-baseline > $OUT/${W}${TAG}_full_bench.json 2> $OUT/full.err
+  rocprofv3 --kernel-trace --stats -d $OUT/full/kt -o ${W}_full -- python3 bench.py --workload $W --full --no-cpu-baseline > $OUT/${W}${TAG}_full_bench.json 2> $OUT/full.err
   echo full rc=$?
 fi
 python3 profiles/r03/summarize.py $OUT $OUT/${W}${TAG}_b$B

@@ -13,7 +13,7 @@ for w in wls:
         if v != "-":
             env[var] = v
         r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", w, "--steps", "10", "--warmup", "2",
-                            "--no-cpu-baseline"] + (["--batch", "4096"] if w in ("cfg3", "cfg5") else []),
+                            "--full", "--no-cpu-baseline"] +(["--batch", "4096"] if w in ("cfg3", "cfg5") else []),
                            env=env, capture_output=True, text=True)
         try:
             d = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][0])

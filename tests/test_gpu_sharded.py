@@ -60,7 +60,7 @@ def test_bench_multi_gpu_entry_point_spawns_its_ranks():
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--workload", "cfg3", "--batch", "64",
-                        "--steps", "1", "--warmup", "1", "--no-cpu-baseline"], env=env, capture_output=True, text=True,
+                        "--steps", "1", "--warmup", "1", "--full", "--no-cpu-baseline"], env=env, capture_output=True, text=True,
                        timeout=540, cwd=ROOT)
     assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-4000:])
     lines = [ln for ln in r.stdout.splitlines() if ln.strip().startswith("{")]
@@ -82,7 +82,7 @@ def test_bench_accounts_for_every_launch_of_the_timed_region():
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE"):
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "cfg2", "--batch", "16384", "--steps",
-                        "120", "--warmup", "2", "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=540,
+                        "120", "--warmup", "2", "--full", "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=540,
                        cwd=ROOT)
     assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-4000:])
     line = json.loads([ln for ln in r.stdout.splitlines() if ln.strip().startswith("{")][0])
