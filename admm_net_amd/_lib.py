@@ -45,6 +45,9 @@ SYMBOLS = {
     "admmnet_glayer_workspace_bytes": (c_int64, [POINTER(Cfg), c_int64]),
     "admmnet_glayer_f32": (c_int32, [POINTER(Cfg), c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p,
                                      c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),
+    "admmnet_glayer_spectral_f32": (c_int32, [POINTER(Cfg), c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_void_p,
+                                              c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p,
+                                              c_void_p, c_int32, c_void_p]),
     "admmnet_eigh_workspace_bytes": (c_int64, [c_int32, c_int64]),
     "admmnet_eigh_c64": (c_int32, [c_int32, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int64,
                                    c_void_p, c_void_p]),

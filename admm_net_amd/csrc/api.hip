@@ -528,7 +528,7 @@ int admmnet_layer_front(const admmnet_cfg *cfg, const float *W, int32_t k, const
             const int prv = cur ^ 1;
             const float *lwp = k >= 1 ? W + (int64_t)(k - 1) * L.size() : lw;
             if ((rc = launch_spectral(D, nb, lw, phk, hk, ws.Z + b0 * n * n, Gk, ws.rn + b0, wc, status, sc, true,
-                                      fold ? ws.alpha + b0 : nullptr, fold ? ws.phi[prv] + b0 * D : nullptr,
+                                      spectral_waves(D, B), fold ? ws.alpha + b0 : nullptr, fold ? ws.phi[prv] + b0 * D : nullptr,
                                       fold ? ws.h[prv] + b0 * D : nullptr, fold ? lwp : nullptr, fold ? (k == 1 ? 2 : 1) : 0)))
                 return rc;
             wf.skip = wc.spec_flag;
@@ -668,6 +668,30 @@ int admmnet_glayer_f32(const admmnet_cfg *cfg, const float *lw, const void *phi,
         if (rc) return rc;
     }
     return ADMMNET_OK;
+}
+
+int admmnet_glayer_spectral_f32(const admmnet_cfg *cfg, const float *layer_weights, const void *phi, const float *h,
+                                void *Z, int32_t mode, const float *prev_layer_weights, const float *alpha,
+                                const void *phi_prev, const float *h_prev, int64_t B, void *G, float *rn_out,
+                                int32_t *flag, int32_t *status, int32_t waves, void *stream) {
+    int rc = check_cfg(cfg);
+    if (rc) return rc;
+    const int D = cfg->M * cfg->N;
+    if (D < 8 || B < 1 || !layer_weights || !phi || !h || !Z || !G || !rn_out || !flag || !status || mode < 0 || mode > 2 ||
+        (mode && (!prev_layer_weights || !alpha || !phi_prev || !h_prev)) || !(waves == 0 || waves == 4 || waves == 12)) {
+        set_error("glayer_spectral: bad argument (D=%d, mode=%d, waves=%d)", D, mode, waves);
+        return ADMMNET_E_ARG;
+    }
+    if (waves == 4 && D > 128) {
+        set_error("glayer_spectral: the 4-wave shape needs D <= 128 (D=%d)", D);
+        return ADMMNET_E_ARG;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    ADMM_HIP(hipMemsetAsync(status, 0, 4 * sizeof(int32_t), st));
+    return launch_spectral_fused(D, B, layer_weights, (const float2 *)phi, h, (float2 *)Z, (float2 *)G, rn_out, flag, status,
+                                 spectral_tol(), mode ? alpha : nullptr, mode ? (const float2 *)phi_prev : nullptr,
+                                 mode ? h_prev : nullptr, mode ? prev_layer_weights : nullptr, mode,
+                                 waves ? waves : spectral_waves(D, B), st);
 }
 
 int64_t admmnet_eigh_workspace_bytes(int32_t n, int64_t B) {

@@ -196,14 +196,19 @@ int launch_spectrum_main(const float2 *phi, int64_t B, int xbase, int ybase, con
 // spectral.hip
 bool use_spectral();
 bool use_spectral_fused();   // spectral_fused.hip: the whole evaluation in one kernel (default when the path is on)
+float spectral_tol();          // the model tolerance of the matrix-function checks (one value for every caller)
+// The workgroup shape of the fused kernel (4 or 12 waves per matrix), chosen once per CALL from the call's batch size B --
+// never from a chunk's size: the two shapes sum in different orders, and the bits of a signal must not depend on cfg.chunk.
+int spectral_waves(int D, int64_t B);
 int launch_spectral_fused(int D, int64_t nb, const float *lw, const float2 *phi, const float *h, float2 *Z, float2 *G,
                           float *rn, int *flag, int32_t *status, float tol, const float *alpha, const float2 *phi_prev,
-                          const float *h_prev, const float *lw_prev, int update_mode, hipStream_t st);
+                          const float *h_prev, const float *lw_prev, int update_mode, int waves, hipStream_t st);
 // update_mode 0: Z is current; 1 / 2: the fused kernel applies Z <- Z + alpha (G - C_prev) in its first sweep (2: stored Z still zero)
+// waves: spectral_waves(D, B) of the call the chunk belongs to
 int launch_spectral(int D, int64_t nb, const float *lw, const float2 *phi, const float *h, float2 *Z, float2 *G,
-                    float *rn, const Ws &ws, int32_t *status, hipStream_t st, bool lower_only, const float *alpha = nullptr,
-                    const float2 *phi_prev = nullptr, const float *h_prev = nullptr, const float *lw_prev = nullptr,
-                    int update_mode = 0);
+                    float *rn, const Ws &ws, int32_t *status, hipStream_t st, bool lower_only, int waves,
+                    const float *alpha = nullptr, const float2 *phi_prev = nullptr, const float *h_prev = nullptr,
+                    const float *lw_prev = nullptr, int update_mode = 0);
 // vdvh.hip (training route)
 int launch_vdvh(int n, int64_t nb, const float2 *V, const float *d, float2 *out, hipStream_t st);
 int launch_vhsv(int n, int64_t nb, const float2 *V, const float2 *S, float *q, hipStream_t st);

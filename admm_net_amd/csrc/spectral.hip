@@ -429,23 +429,28 @@ __global__ __launch_bounds__(SP_THREADS) void sp_assemble_kernel(int D, const fl
 
 // Scratch of its own (Ws::spec_*, carved only when the path is on).  Returns with flag[] filled; the caller runs the
 // eigen-pipeline with Ws::skip = flag.
+// model tolerance: the quadratic may miss f on the bulk by 1e-6 of the result's scale -- below the eigensolver route's own
+// rounding per layer (~2e-6) and without effect on the distance to the float64 oracle (3e-7, 1e-6 and 3e-6 measured the same:
+// tests/gpu_spectral_check.py); at K = 32 the tighter 3e-7 rejected 3.0 % of the matrix-layers, this one 0.4 %
+float spectral_tol() {
+    static const float tol = getenv("ADMMNET_SPECTRAL_TOL") ? (float)atof(getenv("ADMMNET_SPECTRAL_TOL")) : 1e-6f;
+    return tol;
+}
+
 int launch_spectral(int D, int64_t nb, const float *lw, const float2 *phi, const float *h, float2 *Z, float2 *G,
-                    float *rn, const Ws &ws, int32_t *status, hipStream_t st, bool lower_only, const float *alpha,
+                    float *rn, const Ws &ws, int32_t *status, hipStream_t st, bool lower_only, int waves, const float *alpha,
                     const float2 *phi_prev, const float *h_prev, const float *lw_prev, int update_mode) {
     ProfScope _prof(KC_GFUNC, st);
     if (nb <= 0) return ADMMNET_OK;
     const int n = D + 1;
-    // model tolerance: the quadratic may miss f on the bulk by 1e-6 of the result's scale -- below the eigensolver route's own
-    // rounding per layer (~2e-6) and without effect on the distance to the float64 oracle (3e-7, 1e-6 and 3e-6 measured the same:
-    // tests/gpu_spectral_check.py); at K = 32 the tighter 3e-7 rejected 3.0 % of the matrix-layers, this one 0.4 %
-    static const float tol = getenv("ADMMNET_SPECTRAL_TOL") ? (float)atof(getenv("ADMMNET_SPECTRAL_TOL")) : 1e-6f;
+    const float tol = spectral_tol();
     if (use_spectral_fused()) {
         if (!ws.spec_flag || !lower_only) {
             set_error("spectral: the fused kernel needs the flag buffer and the lower-triangle state");
             return ADMMNET_E_WORKSPACE;
         }
         return launch_spectral_fused(D, nb, lw, phi, h, Z, G, rn, ws.spec_flag, status, tol, alpha, phi_prev, h_prev, lw_prev,
-                                     update_mode, st);
+                                     update_mode, waves, st);
     }
     if (update_mode) {
         set_error("spectral: the multi-kernel form does not apply the Z update");

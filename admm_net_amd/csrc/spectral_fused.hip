@@ -821,21 +821,31 @@ static int sf_launch(int D, int64_t nb, const float *lw, const float2 *phi, cons
     return ADMMNET_OK;
 }
 
+// 256 threads per matrix, three matrices per CU -- once there are more than two matrices per CU to overlap (measured at 10 x 10,
+// K = 10: 1024 signals 3.45 vs 3.63 ms per forward, 4096 signals 8.3 vs 10.4 ms; but 256 signals 2.42 vs 2.03 ms and a single
+// signal 0.64 vs 0.53 ms: a lone matrix is served faster by twelve waves).  B is the batch of the CALL (layer_front), not the
+// size of a chunk: the shapes split the mirrored mat-vec and the block sums differently, so a per-chunk choice made a signal's
+// bits depend on cfg.chunk and on whether it fell into a ragged last chunk.
+int spectral_waves(int D, int64_t B) {
+    static const bool small_wg = !(getenv("ADMMNET_SF_SMALLWG") && atoi(getenv("ADMMNET_SF_SMALLWG")) == 0);
+    return (D <= 128 && small_wg && B > 512) ? 4 : SF_WAVES;
+}
+
 int launch_spectral_fused(int D, int64_t nb, const float *lw, const float2 *phi, const float *h, float2 *Z, float2 *G,
                           float *rn, int *flag, int32_t *status, float tol, const float *alpha, const float2 *phi_prev,
-                          const float *h_prev, const float *lw_prev, int update_mode, hipStream_t st) {
+                          const float *h_prev, const float *lw_prev, int update_mode, int waves, hipStream_t st) {
     const SfUpdate up{alpha, phi_prev, h_prev, lw_prev, update_mode};
     if (D < 2 || D > 256) {
         set_error("spectral: D=%d outside 2..256", D);
         return ADMMNET_E_ARG;
     }
+    if (!(waves == SF_WAVES || (waves == 4 && D <= 128))) {   // (4 waves: the shape of n <= 129 only -- never chosen, never tested above)
+        set_error("spectral: %d waves per matrix at D=%d (need 12, or 4 with D <= 128)", waves, D);
+        return ADMMNET_E_ARG;
+    }
     static const int iters = getenv("ADMMNET_SPECTRAL_ITERS") ? atoi(getenv("ADMMNET_SPECTRAL_ITERS")) : 5;   // (upper bound)
     const int NT = (D + 31) >> 5, ntri = NT * (NT + 1) / 2;
-    static const bool small_wg = !(getenv("ADMMNET_SF_SMALLWG") && atoi(getenv("ADMMNET_SF_SMALLWG")) == 0);
-    // 256 threads per matrix, three matrices per CU -- once there are more than two matrices per CU to overlap (measured at 10 x 10,
-    // K = 10: 1024 signals 3.45 vs 3.63 ms per forward, 4096 signals 8.3 vs 10.4 ms; but 256 signals 2.42 vs 2.03 ms and a single
-    // signal 0.64 vs 0.53 ms: a lone matrix is served faster by twelve waves)
-    if (D <= 128 && small_wg && nb > 512) {
+    if (waves == 4) {
         switch ((ntri + 3) / 4) {
             case 1: return sf_launch<1, 4>(D, nb, lw, phi, h, Z, G, rn, flag, status, tol, iters, up, st);
             case 2: return sf_launch<2, 4>(D, nb, lw, phi, h, Z, G, rn, flag, status, tol, iters, up, st);

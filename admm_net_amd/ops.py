@@ -119,6 +119,50 @@ def glayer(model, k: int, phi: torch.Tensor, h: torch.Tensor, Z=None):
     return G, w, rn
 
 
+def glayer_spectral(model, k: int, phi: torch.Tensor, h: torch.Tensor, Z: torch.Tensor, G: torch.Tensor, rn: torch.Tensor,
+                    mode: int = 0, alpha=None, phi_prev=None, h_prev=None, waves: int = 0):
+    """The matrix-function G-layer of layer k of ``model`` (csrc/spectral_fused.hip, admmnet_glayer_spectral_f32) on
+    caller-supplied state, IN PLACE: Z, G [B, n, n] complex64 and rn [B] float32 must be contiguous device tensors; only
+    their lower triangles are read or written, G and rn only for accepted matrices.
+
+    mode 0: Z is the state layer k reads.  mode 1: the Z-layer update of layer k-1, Z <- Z + alpha (G - C_prev), is applied
+    first (G holds G of layer k-1 on entry; alpha [B], phi_prev [B, D], h_prev [B, D] of layer k-1).  mode 2: as 1 with
+    the stored Z taken as zero.  waves: 0 = the forward's choice for a call of B signals, 12, or 4 (D <= 128).
+
+    Returns (flag [B] int32: 0 = accepted, else the check that rejected the matrix; status [4] int32)."""
+    _need_cuda(phi, "phi")
+    lib = _lib.load()
+    dev = phi.device
+    B, D = phi.shape
+    n = D + 1
+    for t, name, dt, shape in ((Z, "Z", torch.complex64, (B, n, n)), (G, "G", torch.complex64, (B, n, n)),
+                               (rn, "rn", torch.float32, (B,))):
+        if t.device != dev or t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous():
+            raise ValueError(f"{name} must be a contiguous {dt} tensor {shape} on {dev}")
+    if mode not in (0, 1, 2):
+        raise ValueError(f"mode must be 0, 1 or 2, got {mode}")
+    cfg = model.cfg()
+    with torch.cuda.device(dev):
+        W = model.packed_weights(dev)
+        lw = W[lib.admmnet_layer_weight_offset(ctypes.byref(cfg), k):]
+        lwp = W[lib.admmnet_layer_weight_offset(ctypes.byref(cfg), k - 1):] if mode else None
+        phi = phi.to(torch.complex64).contiguous()
+        h = h.to(torch.float32).contiguous()
+        if mode:
+            alpha = alpha.to(dev, torch.float32).contiguous()
+            phi_prev = phi_prev.to(dev, torch.complex64).contiguous()
+            h_prev = h_prev.to(dev, torch.float32).contiguous()
+        else:
+            alpha = phi_prev = h_prev = None
+        flag = torch.full((B,), -1, dtype=torch.int32, device=dev)
+        status = torch.full((4,), -1, dtype=torch.int32, device=dev)
+        _lib.check(lib.admmnet_glayer_spectral_f32(ctypes.byref(cfg), _ptr(lw), _ptr(phi), _ptr(h), _ptr(Z), mode, _ptr(lwp),
+                                                   _ptr(alpha), _ptr(phi_prev), _ptr(h_prev), B, _ptr(G), _ptr(rn),
+                                                   _ptr(flag), _ptr(status), waves, _stream(dev)),
+                   "admmnet_glayer_spectral_f32")
+    return flag, status
+
+
 def spectrum(phi: torch.Tensor, xbase: int, ybase: int, taus: torch.Tensor, fs: torch.Tensor):
     """|phi^H kron(s(f), conj d(tau))|^2 on the grid fs x taus (peakSearchUtils.py:9-60), float64.
 

@@ -47,7 +47,11 @@ typedef struct admmnet_cfg {
     int32_t L;          /* max targets of the PeakSearchLayer head (3)         */
     int32_t K;          /* num_layers                                          */
     int32_t has_head;   /* 1: ADMMNet (PeakSearchLayer), 0: PhiEstADMMNet       */
-    int32_t chunk;      /* signals per eigensolver work chunk (0 = auto)       */
+    int32_t chunk;      /* signals per eigensolver work chunk (0 = auto); a
+                           work split only: the bits of a signal depend on its
+                           inputs, the weights, the batch mean and the batch
+                           size B of the call, never on chunk (a rank of a
+                           sharded forward is one call)                       */
     int32_t reserved[2];
 } admmnet_cfg;
 
@@ -150,6 +154,30 @@ int admmnet_glayer_f32(const admmnet_cfg *cfg, const float *layer_weights,
                        void *G_out, float *w_out, float *rn_out,
                        void *workspace, int64_t workspace_bytes,
                        int32_t *status, void *stream);
+
+/* The matrix-function G-layer (csrc/spectral_fused.hip, the route of the forward's dense layers) on caller-supplied state,
+ * one matrix per signal, with the forward's own tolerance and pass cap; for tests and utilities, the forward does not
+ * call it.  Layout as in the workspace: n x n buffers per signal, only the lower triangle is read or written.
+ *   layer_weights       packed weights of layer k
+ *   phi [B][D] c64, h [B][D] f32    the inputs of layer k
+ *   Z [B][n][n] c64     mode 0: input (the state G-layer k reads);
+ *                       mode 1: in/out -- the Z-layer update of layer k-1 is applied first, Z <- Z + alpha_b (G - C_prev),
+ *                               C_prev = [[diag h_prev, phi_prev], [phi_prev^H, corner_z of layer k-1]], G = G of layer k-1;
+ *                       mode 2: as 1 with the stored Z taken as zero (never read, only written)
+ *   prev_layer_weights, alpha [B] f32, phi_prev [B][D] c64, h_prev [B][D] f32: layer k-1 (modes 1, 2; else ignored)
+ *   G [B][n][n] c64     G of layer k where the matrix is accepted (modes 1, 2: G of layer k-1 on entry); untouched otherwise
+ *   rn_out [B] f32      ||G - [[diag h, phi], [phi^H, corner_z]]||_F where accepted; untouched otherwise
+ *   flag [B] i32        0 = accepted, else the check that rejected it: 1 Ritz residual, 2 bulk not narrow against the
+ *                       gaps, 4 f not a quadratic on the bulk, 8 non-finite, 16 second-order term too large
+ *   status [4] i32      zeroed by the call; [1] = #rejected, [2] = #accepted, [3] = #(flag == 4)
+ *   waves               0: the forward's choice for a call of B signals; 12, or 4 (D <= 128): that workgroup shape
+ * D = M*N must be 8 .. 256. */
+int admmnet_glayer_spectral_f32(const admmnet_cfg *cfg, const float *layer_weights,
+                                const void *phi, const float *h, void *Z, int32_t mode,
+                                const float *prev_layer_weights, const float *alpha,
+                                const void *phi_prev, const float *h_prev, int64_t B,
+                                void *G, float *rn_out, int32_t *flag, int32_t *status,
+                                int32_t waves, void *stream);
 
 /* Batched Hermitian eigendecomposition of arbitrary complex64 Hermitian
  * matrices (torch.linalg.eigh at admm_net.py:303).  A [B][n][n] (only the

@@ -1,0 +1,475 @@
+"""GPU (-m gpu): the matrix-function G-layer kernel (csrc/spectral_fused.hip, sp_fused_kernel) layer by layer against the
+float64 oracle, through its own entry point admmnet_glayer_spectral_f32 (ops.glayer_spectral).
+
+The kernel evaluates G = V f(L) V^H of A = C - Z / rho without an eigendecomposition wherever its sampled checks accept the
+matrix, writes the residual norm rn = ||G - C_z||_F the Z-layer reads, and applies the previous layer's Z update
+Z <- Z + alpha (G_prev - C_prev) in its first sweep.  The forward only sees these through phi after K layers; here every output
+is compared per matrix and per element.
+
+Reference: oracle/admm_net_ref.py (g_layer, block_matrix, the eigenvalue map) evaluated in float64 on the float32-rounded
+inputs the kernel actually receives; the inputs are the per-layer states of an oracle forward (trace).
+
+Bounds (per accepted matrix, over the lower triangle):
+  * G:  max|G - G_ref| <= 2e-5 max|G_ref|  (the eigensolver route's bound, tests/test_gpu_parity.py::test_glayer_block_vs_oracle)
+  * rn: within 1e-5 relative of ||G_ref - C_z||_F
+  * the folded Z update, every matrix (rejected ones included: the eigensolver reads that Z): element-wise within
+    4 * 2^-24 * (|Z| + |alpha| (|G_prev| + |C_prev|)) of the expression evaluated in float64 on the same float32 operands
+    (three roundings: the difference, the product, the sum).
+"""
+import ctypes
+import functools
+import os
+
+import numpy as np
+import pytest
+import torch
+import torch.nn.functional as F
+
+import admm_net_amd as A
+from admm_net_amd import _lib, ops, synth
+from oracle import admm_net_ref as R
+from golden_util import load_fixture
+
+pytestmark = pytest.mark.gpu
+
+TOL_G, TOL_RN = 2e-5, 1e-5
+U32 = 2.0 ** -24
+S_CORNER_Z = 7          # slot of corner_z in a layer's packed weights (csrc/common.h)
+SENT_G = complex(3.25, -1.5)   # what the kernel must leave in G where it does not write
+SENT_RN = -7.0
+
+# (Nb, Nd): D = Nb * Nd, chosen at every instantiation and every column-chunk / tile boundary of the kernel
+GEOMS = [
+    ((2, 4), "D8_smallest"),
+    ((3, 11), "D33_NT2"),
+    ((8, 8), "D64_col64_alone"),
+    ((8, 10), "D80_W4TPW2"),
+    ((10, 10), "D100_ref"),
+    ((8, 16), "D128_cfg2"),
+    ((3, 43), "D129_padded_W12TPW2"),
+    ((12, 16), "D192_col192_alone"),
+    ((14, 16), "D224_W12TPW3"),
+    ((15, 17), "D255_four_chunks"),
+    ((16, 16), "D256_corner"),
+]
+CASES = [pytest.param(g, w, p, id=f"{name}-W{w}-p{p}") for g, name in GEOMS for w in ((4, 12) if g[0] * g[1] <= 128 else (12,))
+         for p in (0.0, 0.3, 1.0)]
+K_TRACE, B_TRACE = 3, 8
+
+
+@pytest.fixture(scope="module")
+def dev():
+    assert torch.cuda.is_available(), "these tests need the MI355X"
+    _lib.load()
+    return torch.device("cuda:0")
+
+
+def _bits(t):
+    t = t.detach().cpu().contiguous()
+    return torch.view_as_real(t).view(torch.int32) if t.is_complex() else t.view(torch.int32)
+
+
+@functools.lru_cache(maxsize=None)
+def _trace(Nb, Nd, perturb):
+    """An oracle forward (float64) of K_TRACE layers: per-layer phi, h, G, Z, rn, arho, A; the weights and the model."""
+    torch.set_num_threads(min(4, torch.get_num_threads()))
+    sd = R.make_weights(Nb, Nd, K_TRACE, seed=7, head=False, perturb=perturb)
+    y, b, s, _ = synth.make_batch(B_TRACE, Nb, Nd, seed=13)
+    tr = []
+    R.forward(sd, torch.from_numpy(y), torch.from_numpy(b), torch.from_numpy(s), Nb, Nd, K_TRACE, dtype="f64", trace=tr)
+    return sd, tr
+
+
+def _model(sd, Nb, Nd, K):
+    m = A.PhiEstADMMNet(M=Nb, N=Nd, num_layers=K).eval()
+    m.load_state_dict(sd)
+    return m
+
+
+def _corner(sd, key):
+    return float(1.0 / (F.softplus(sd[key].double()) ** 2 + R.EPS))
+
+
+def _reference(sd, k, phi, h, Z):
+    """G_ref, rn_ref (float64) of layer k on the given (float32-valued) inputs."""
+    sd64 = R.cast_weights(sd, "f64")
+    phi, h, Z = phi.to(torch.complex128), h.double(), Z.to(torch.complex128)
+    G = R.g_layer(sd64, k, phi, h, Z)
+    Cz = R.block_matrix(phi, h, _corner(sd, f"zLayers.{k}.lambda_param"))
+    return G, torch.linalg.norm(G - Cz, dim=(1, 2))
+
+
+def _tril(n):
+    return torch.tril(torch.ones(n, n, dtype=torch.bool))
+
+
+def _run(dev, m, k, phi, h, Z, G, rn, mode=0, prev=(None, None, None), waves=0):
+    """One call of the kernel on copies of the host tensors; returns the host images of (Z, G, rn, flag, status)."""
+    Zd, Gd, rnd = (t.to(dev).contiguous().clone() for t in (Z, G, rn))
+    flag, st = ops.glayer_spectral(m, k, phi.to(dev), h.to(dev), Zd, Gd, rnd, mode, *prev, waves=waves)
+    torch.cuda.synchronize()
+    return Zd.cpu(), Gd.cpu(), rnd.cpu(), flag.cpu(), st.cpu()
+
+
+def _g_errors(G, G_ref, tri):
+    """Per matrix: max|G - G_ref| / max|G_ref| over the lower triangle."""
+    d = (G.to(torch.complex128) - G_ref).abs()[:, tri]
+    return (d.max(1).values / G_ref.abs()[:, tri].max(1).values).numpy()
+
+
+def _check_accepted(G, rn, flag, G_ref, rn_ref, tri, what):
+    acc = (flag == 0).numpy()
+    err = _g_errors(G, G_ref, tri)
+    n = G.shape[-1]
+    for i in np.flatnonzero(acc):
+        assert err[i] <= TOL_G, (what, "G", i, err[i])
+        assert torch.all(G[i].diagonal().imag == 0), (what, "diag imag", i)
+        assert abs(float(rn[i]) - float(rn_ref[i])) <= TOL_RN * float(rn_ref[i]), (what, "rn", i, float(rn[i]), float(rn_ref[i]))
+    assert n == tri.shape[0]
+    return float(err[acc].max()) if acc.any() else 0.0
+
+
+def _check_status(flag, st):
+    f = flag.numpy()
+    assert (f >= 0).all() and set(np.unique(f)) <= {0, 1, 2, 4, 8, 16}, f
+    assert int(st[1]) == int((f != 0).sum()) and int(st[2]) == int((f == 0).sum()) and int(st[3]) == int((f == 4).sum()), (st, f)
+    assert int(st[0]) == 0
+
+
+def _mode0_inputs(tr, k):
+    t = tr[k]
+    phi, h = t["phi"].to(torch.complex64), t["h"].float()
+    Z = tr[k - 1]["Z"].to(torch.complex64) if k >= 1 else torch.zeros(phi.shape[0], phi.shape[1] + 1, phi.shape[1] + 1,
+                                                                           dtype=torch.complex64)
+    return phi, h, Z
+
+
+# ---------------------------------------------------------------------------------------------------------------- mode 0
+@pytest.mark.parametrize("grid,waves,perturb", CASES)
+def test_mode0_matches_the_oracle(dev, grid, waves, perturb):
+    """G and rn of every accepted matrix against the float64 oracle; the buffer contracts: the upper triangles of Z and G are
+    never read (NaN there changes no bit) and never written; rejected matrices leave G and rn alone; the status words count
+    the flags."""
+    Nb, Nd = grid
+    sd, tr = _trace(Nb, Nd, perturb)
+    m = _model(sd, Nb, Nd, K_TRACE)
+    n = Nb * Nd + 1
+    tri = _tril(n)
+    upper = ~tri
+    accepted, total, worst, flags = 0, 0, 0.0, []
+    for k in range(1, K_TRACE):
+        phi, h, Z = _mode0_inputs(tr, k)
+        B = phi.shape[0]
+        G0 = torch.full((B, n, n), SENT_G, dtype=torch.complex64)
+        rn0 = torch.full((B,), SENT_RN)
+        Zo, G, rn, flag, st = _run(dev, m, k, phi, h, Z, G0, rn0, waves=waves)
+        G_ref, rn_ref = _reference(sd, k, phi, h, Z)
+        worst = max(worst, _check_accepted(G, rn, flag, G_ref, rn_ref, tri, f"layer {k}"))
+        _check_status(flag, st)
+        assert torch.equal(_bits(Zo), _bits(Z))                                   # mode 0: Z is input only
+        assert torch.equal(_bits(G)[:, upper], _bits(G0)[:, upper])               # the upper triangle is never written
+        rej = flag != 0
+        assert torch.equal(_bits(G[rej]), _bits(G0[rej])) and torch.equal(_bits(rn[rej]), _bits(rn0[rej]))
+        # poisoned: NaN in the upper triangles of Z and of G
+        Zp, Gp = Z.clone(), G0.clone()
+        Zp[:, upper] = complex(float("nan"), float("nan"))
+        Gp[:, upper] = complex(float("nan"), float("nan"))
+        Zpo, Gpo, rnp, flagp, _ = _run(dev, m, k, phi, h, Zp, Gp, rn0, waves=waves)
+        assert torch.equal(flagp, flag)
+        assert torch.equal(_bits(Gpo)[:, tri], _bits(G)[:, tri]) and torch.equal(_bits(rnp), _bits(rn))
+        assert torch.equal(_bits(Gpo)[:, upper], _bits(Gp)[:, upper]) and torch.equal(_bits(Zpo), _bits(Zp))
+        accepted += int((flag == 0).sum())
+        total += B
+        flags += flag.tolist()
+    print(f"GERR mode0 D={Nb * Nd} W{waves} p={perturb}: worst {worst:.2e}, accepted {accepted}/{total} flags {flags}")
+    # the route really runs: at least half of the matrices at realistic weights; at perturb = 1.0 the scalar parameters move
+    # by O(1) and whole layers can put a kink of the eigenvalue map into the bulk -- rejecting those is the checks' job
+    assert accepted >= total / 2 or (perturb >= 1.0 and accepted > 0), (accepted, total, flags)
+
+
+# ------------------------------------------------------------------------------------------------------- mode 1 / 2: fold
+@pytest.mark.parametrize("grid,waves,perturb", CASES)
+def test_folded_z_update_matches_the_oracle(dev, grid, waves, perturb):
+    """Mode 2 (layer 1: the stored Z is still zero and must not be read) and mode 1 (layer 2): Z_{k-1} = Z_{k-2} +
+    alpha (G_{k-1} - C_{k-1}) is formed in the kernel's first sweep -- every element of the lower triangle of every matrix
+    (the border row with its conjugate, the corner with corner_z of layer k-1, the corner element of row 256 at n = 257) --
+    and G_k, rn_k are evaluated from it."""
+    Nb, Nd = grid
+    D = Nb * Nd
+    sd, tr = _trace(Nb, Nd, perturb)
+    m = _model(sd, Nb, Nd, K_TRACE)
+    W = m.packed_weights(dev).cpu()
+    lib = _lib.load()
+    n = D + 1
+    tri = _tril(n)
+    upper = ~tri
+    nan = complex(float("nan"), float("nan"))
+    worst = 0.0
+    for k in (1, 2):
+        mode = 2 if k == 1 else 1
+        phi, h = tr[k]["phi"].to(torch.complex64), tr[k]["h"].float()
+        p = tr[k - 1]
+        phi_p, h_p, G_p = p["phi"].to(torch.complex64), p["h"].float(), p["G"].to(torch.complex64)
+        alpha = p["arho"].float()
+        B = phi.shape[0]
+        Z = tr[k - 2]["Z"].to(torch.complex64) if k >= 2 else torch.zeros(B, n, n, dtype=torch.complex64)
+        corner_zp = float(W[lib.admmnet_layer_weight_offset(ctypes.byref(m.cfg()), k - 1) + S_CORNER_Z])
+        C_p = R.block_matrix(phi_p.to(torch.complex128), h_p.double(), corner_zp)
+        a64 = alpha.double().reshape(-1, 1, 1)
+        Z_exp = Z.to(torch.complex128) + a64 * (G_p.to(torch.complex128) - C_p)
+        bound = 4 * U32 * (Z.abs().double() + a64.abs() * (G_p.abs().double() + C_p.abs()))
+        rn0 = torch.full((B,), SENT_RN)
+        prev = (alpha, phi_p, h_p)
+        Zo, G, rn, flag, st = _run(dev, m, k, phi, h, Z, G_p, rn0, mode, prev, waves)
+        dz = (Zo.to(torch.complex128) - Z_exp).abs()
+        bad = (dz > bound) & tri
+        assert not bad.any(), ("fold", mode, [tuple(i.tolist()) for i in bad.nonzero()[:8]],
+                               float((dz - bound)[bad].max()) if bad.any() else 0.0)
+        G_ref, rn_ref = _reference(sd, k, phi, h, Z_exp)
+        worst = max(worst, _check_accepted(G, rn, flag, G_ref, rn_ref, tri, f"mode {mode}"))
+        _check_status(flag, st)
+        rej = flag != 0
+        assert torch.equal(_bits(G[rej]), _bits(G_p[rej])) and torch.equal(_bits(rn[rej]), _bits(rn0[rej]))
+        assert torch.equal(_bits(G)[:, upper], _bits(G_p)[:, upper]) and torch.equal(_bits(Zo)[:, upper], _bits(Z)[:, upper])
+        # poisoned: the upper triangles of Z and G_prev (mode 1), all of Z (mode 2)
+        Zp, Gp = Z.clone(), G_p.clone()
+        if mode == 2:
+            Zp[:] = nan
+        else:
+            Zp[:, upper] = nan
+        Gp[:, upper] = nan
+        Zpo, Gpo, rnp, flagp, _ = _run(dev, m, k, phi, h, Zp, Gp, rn0, mode, prev, waves)
+        assert torch.equal(flagp, flag)
+        assert torch.isfinite(Zpo[:, tri]).all() and torch.isfinite(Gpo[:, tri]).all()
+        assert torch.equal(_bits(Zpo)[:, tri], _bits(Zo)[:, tri]) and torch.equal(_bits(Gpo)[:, tri], _bits(G)[:, tri])
+        assert torch.equal(_bits(rnp), _bits(rn))
+        assert torch.equal(_bits(Gpo)[:, upper], _bits(Gp)[:, upper]) and torch.equal(_bits(Zpo)[:, upper], _bits(Zp)[:, upper])
+    print(f"GERR fold D={D} W{waves} p={perturb}: worst {worst:.2e}")
+
+
+# -------------------------------------------------------------------------------------------- independence and the shapes
+def _tile_inputs(Nb, Nd, idx):
+    sd, tr = _trace(Nb, Nd, 0.3)
+    phi, h, Z = _mode0_inputs(tr, 2)
+    idx = torch.as_tensor(idx)
+    return sd, phi[idx].contiguous(), h[idx].contiguous(), Z[idx].contiguous()
+
+
+@pytest.mark.parametrize("waves", [4, 12])
+def test_a_matrix_gives_the_same_bits_at_any_batch_position(dev, waves):
+    Nb, Nd, B = 10, 10, 12
+    n = Nb * Nd + 1
+    sd, phi, h, Z = _tile_inputs(Nb, Nd, list(range(B_TRACE)))
+    m = _model(sd, Nb, Nd, K_TRACE)
+    G0, rn0 = torch.full((B_TRACE, n, n), SENT_G, dtype=torch.complex64), torch.full((B_TRACE,), SENT_RN)
+    _, _, _, flag, _ = _run(dev, m, 2, phi, h, Z, G0, rn0, waves=waves)
+    x = int(np.flatnonzero(flag.numpy() == 0)[0]) if (flag == 0).any() else 0
+    others = [i for i in range(B_TRACE) if i != x]
+    idx = [others[i % len(others)] for i in range(B)]
+    for pos in (0, 5, B - 1):
+        idx[pos] = x
+    sd, phi, h, Z = _tile_inputs(Nb, Nd, idx)
+    G0, rn0 = torch.full((B, n, n), SENT_G, dtype=torch.complex64), torch.full((B,), SENT_RN)
+    _, G, rn, flag, _ = _run(dev, m, 2, phi, h, Z, G0, rn0, waves=waves)
+    for pos in (5, B - 1):
+        assert int(flag[pos]) == int(flag[0])
+        assert torch.equal(_bits(G[pos]), _bits(G[0])) and torch.equal(_bits(rn[pos]), _bits(rn[0]))
+
+
+@pytest.mark.parametrize("B,forced", [(10, 12), (600, 4)])
+def test_shape_choice_follows_the_batch_of_the_call(dev, B, forced):
+    """waves = 0 is the forward's own choice: 12 waves per matrix for a call of up to 512 signals, 4 (D <= 128) above."""
+    Nb, Nd = 10, 10
+    n = Nb * Nd + 1
+    sd, phi, h, Z = _tile_inputs(Nb, Nd, [i % B_TRACE for i in range(B)])
+    m = _model(sd, Nb, Nd, K_TRACE)
+    G0, rn0 = torch.full((B, n, n), SENT_G, dtype=torch.complex64), torch.full((B,), SENT_RN)
+    _, Ga, rna, fa, _ = _run(dev, m, 2, phi, h, Z, G0, rn0, waves=0)
+    _, Gb, rnb, fb, _ = _run(dev, m, 2, phi, h, Z, G0, rn0, waves=forced)
+    assert torch.equal(fa, fb) and torch.equal(_bits(Ga), _bits(Gb)) and torch.equal(_bits(rna), _bits(rnb))
+    assert (fa == 0).any()
+
+
+def test_bad_arguments_raise(dev):
+    sd, tr = _trace(8, 16, 0.3)
+    m = _model(sd, 8, 16, K_TRACE)
+    phi, h, Z = _mode0_inputs(tr, 1)
+    Zd, G = Z.to(dev), torch.zeros_like(Z).to(dev)
+    rn = torch.zeros(phi.shape[0], device=dev)
+    for kw in (dict(waves=8), dict(mode=3)):
+        with pytest.raises((_lib.AdmmNetError, ValueError)):
+            ops.glayer_spectral(m, 1, phi.to(dev), h.to(dev), Zd, G, rn, **kw)
+    sd2 = R.make_weights(16, 16, 2, seed=1, head=False)
+    m2 = _model(sd2, 16, 16, 2)
+    phi2 = torch.zeros(2, 256, dtype=torch.complex64, device=dev)
+    Z2 = torch.zeros(2, 257, 257, dtype=torch.complex64, device=dev)
+    with pytest.raises(_lib.AdmmNetError):   # the 4-wave shape covers n <= 129 only
+        ops.glayer_spectral(m2, 1, phi2, torch.zeros(2, 256, device=dev), Z2, Z2.clone(), torch.zeros(2, device=dev), waves=4)
+    sd3 = R.make_weights(2, 3, 2, seed=1, head=False)
+    m3 = _model(sd3, 2, 3, 2)
+    Z3 = torch.zeros(1, 7, 7, dtype=torch.complex64, device=dev)
+    with pytest.raises(_lib.AdmmNetError):   # D < 8 never reaches the route
+        ops.glayer_spectral(m3, 1, torch.zeros(1, 6, dtype=torch.complex64, device=dev), torch.zeros(1, 6, device=dev), Z3,
+                            Z3.clone(), torch.zeros(1, device=dev))
+
+
+# ----------------------------------------------------------------------------------- soundness of acceptance: surgery
+SURGERY_GEOMS = [((10, 10), "D100"), ((8, 16), "D128"), ((16, 16), "D256")]
+SURGERY = ([("bulk", s) for s in (0.0, 1e-3, 0.3, 3.0, 10.0)] + [("bulk_to_gap", 0.2)] +
+           [("gap_ratio", r) for r in (15.0, 18.0, 19.0, 21.0, 22.0, 25.0)] +
+           [("outliers_equal", 0.0), ("outliers_equal", 1e-6)] +
+           [("third_outlier", f) for f in (1.0, 1.01, 1.5, 3.0)] +
+           [("kink", t) for t in (0.0, 0.5, -0.5, 0.8, -0.8, 0.99, -0.99, 1.01, -1.01, 1.2, -1.2)])
+# must be rejected, every matrix.  (Scaling the realistic bulk by 10 or pulling a third eigenvalue to 3x the half-width is not
+# decisive: the gaps are 100 .. 2600 times the bulk's ||E^2||^(1/2), f stays a quadratic on the wider bulk, and the accepted
+# results meet the bound -- the universal assertion covers them.)
+DECISIVE = {("kink", 0.0), ("bulk_to_gap", 0.2)}
+SURGERY_K = 2
+
+
+def _split(w):
+    """Indices of the two outliers (furthest from the median) and of the bulk of one spectrum."""
+    o = np.argsort(-np.abs(w - np.median(w)))[:2]
+    bulk = np.setdiff1d(np.arange(w.size), o)
+    return o, bulk
+
+
+def _bulk_stats(wb):
+    c = wb.mean()                              # = (trace - l0 - l1) / (n - 2): the kernel's centre
+    return c, np.abs(wb - c).max(), float((((wb - c) ** 4).sum()) ** 0.25)   # centre, half-width, ||E^2||_F^(1/2)
+
+
+def _surgery_spectrum(w, kind, par):
+    w = w.copy()
+    o, bulk = _split(w)
+    c, r, delta = _bulk_stats(w[bulk])
+    g = np.abs(w[o] - c)
+    if kind == "bulk":
+        w[bulk] = c + par * (w[bulk] - c)
+    elif kind == "bulk_to_gap":   # the bulk widened until its ||E^2||^(1/2) is `par` of the smaller gap
+        w[bulk] = c + (par * g.min() / delta) * (w[bulk] - c)
+    elif kind == "gap_ratio":     # the nearer outlier moved to gap = par * delta (the check accepts above 20)
+        i = o[np.argmin(g)]
+        w[i] = c + np.sign(w[i] - c) * par * delta
+    elif kind == "outliers_equal":
+        far, near = o[np.argmax(g)], o[np.argmin(g)]
+        w[near] = w[far] * (1.0 + par)
+    elif kind == "third_outlier":
+        e = bulk[np.argmax(np.abs(w[bulk] - c))]
+        w[e] = c + np.sign(w[e] - c) * par * r
+    return w
+
+
+@functools.lru_cache(maxsize=None)
+def _surgery_base(Nb, Nd):
+    sd, tr = _trace(Nb, Nd, 0.3)
+    t = tr[SURGERY_K]
+    w, V = torch.linalg.eigh(t["A"])
+    return sd, t["phi"].to(torch.complex64), t["h"].float(), w.numpy(), V
+
+
+def _z_for(sd, phi, h, Ap):
+    """Z such that the kernel's A = C - Z / rho is A' (float64; rounded to float32 by the caller)."""
+    k = SURGERY_K
+    C = R.block_matrix(phi.to(torch.complex128), h.double(), _corner(sd, f"gLayers.{k}.lambda_param"))
+    rho = float(F.softplus(sd[f"gLayers.{k}.rho"].double()))
+    return ((rho + R.EPS) * (C - Ap)).to(torch.complex64)
+
+
+def _delta_check_consistent(w_act, flag, what):
+    """The `delta < 0.05 gap` check, against the float64 spectrum the kernel received: with the bulk's ||E^2||^(1/2) at
+    least 10 % above 0.05 of the smaller gap the matrix must be rejected by it or an earlier check (8, 1); 10 % below, it
+    must not be rejected by it."""
+    o, bulk = _split(w_act)
+    c, _, delta = _bulk_stats(w_act[bulk])
+    ratio = delta / np.abs(w_act[o] - c).min()
+    if ratio >= 0.055:
+        assert flag in (1, 2, 8), (what, "delta/gap", ratio, flag)
+    elif ratio <= 0.045:
+        assert flag != 2, (what, "delta/gap", ratio, flag)
+    return ratio
+
+
+@pytest.mark.parametrize("kind,par", [pytest.param(k, p, id=f"{k}={p:g}") for k, p in SURGERY])
+@pytest.mark.parametrize("grid", [pytest.param(g, id=name) for g, name in SURGERY_GEOMS])
+def test_accepted_matrices_are_accurate_under_spectral_surgery(dev, grid, kind, par):
+    """Realistic layer matrices A = V L V^H with L replaced (V kept, so the outliers stay aligned with the kernel's arrowhead
+    start vectors), fed as Z = rho (C - A'): every matrix the kernel accepts must meet the G bound; the decisive cases must be
+    rejected; the delta check must fire exactly where the spectrum says it should."""
+    Nb, Nd = grid
+    sd, phi, h, w, V = _surgery_base(Nb, Nd)
+    B, n = w.shape[0], w.shape[1]
+    tri = _tril(n)
+    if kind == "kink":   # one steep hidden unit of value_net in layer k: f has a kink at |lambda| = |c + t r|
+        runs = []
+        for b in range(4):
+            o, bulk = _split(w[b])
+            c, r, _ = _bulk_stats(w[b][bulk])
+            sd2 = {key: v.clone() for key, v in sd.items()}
+            p = f"gLayers.{SURGERY_K}.value_net."
+            slope, x = 4.0 / r, abs(c + par * r)
+            sd2[p + "0.weight"][0, 0] = slope
+            sd2[p + "0.bias"][0] = -slope * x
+            sd2[p + "2.weight"][0, 0] = 1.0
+            Z = _z_for(sd2, phi[b:b + 1], h[b:b + 1], (V[b:b + 1] * torch.from_numpy(w[b:b + 1]).unsqueeze(1)) @ V[b:b + 1].mH)
+            runs.append((sd2, b, Z))
+    else:
+        wp = np.stack([_surgery_spectrum(w[b], kind, par) for b in range(B)])
+        Ap = (V * torch.from_numpy(wp).unsqueeze(1)) @ V.mH
+        runs = [(sd, slice(0, B), _z_for(sd, phi, h, Ap))]
+    flags, errs, ratios = [], [], []
+    for sdx, sl, Z in runs:
+        ph, hh = phi[sl], h[sl]
+        if ph.dim() == 1:
+            ph, hh = ph.unsqueeze(0), hh.unsqueeze(0)
+        nb = ph.shape[0]
+        m = _model(sdx, Nb, Nd, K_TRACE)
+        G0, rn0 = torch.full((nb, n, n), SENT_G, dtype=torch.complex64), torch.full((nb,), SENT_RN)
+        _, G, rn, flag, st = _run(dev, m, SURGERY_K, ph, hh, Z, G0, rn0)
+        _check_status(flag, st)
+        sd64 = R.cast_weights(sdx, "f64")
+        G_ref, w_act, _ = R.g_layer(sd64, SURGERY_K, ph.to(torch.complex128), hh.double(), Z.to(torch.complex128),
+                                    return_eig=True)
+        Cz = R.block_matrix(ph.to(torch.complex128), hh.double(), _corner(sdx, f"zLayers.{SURGERY_K}.lambda_param"))
+        rn_ref = torch.linalg.norm(G_ref - Cz, dim=(1, 2))
+        err = _g_errors(G, G_ref, tri)
+        for i in range(nb):
+            f = int(flag[i])
+            ratios.append(_delta_check_consistent(w_act[i].numpy(), f, (kind, par, i)))
+            flags.append(f)
+            errs.append(float(err[i]))
+        _check_accepted(G, rn, flag, G_ref, rn_ref, tri, (kind, par))
+    acc = sum(f == 0 for f in flags)
+    worst = max([e for e, f in zip(errs, flags) if f == 0], default=0.0)
+    print(f"SURGERY D={Nb * Nd} {kind}={par:g}: accepted {acc}/{len(flags)} flags {flags} worst {worst:.2e} "
+          f"delta/gap {min(ratios):.3g}..{max(ratios):.3g}")
+    if (kind, par) in DECISIVE:
+        assert acc == 0, (kind, par, flags)
+
+
+# ------------------------------------------------------------------------------ reference-written per-layer fixtures
+@pytest.mark.parametrize("name", ["phiest_3x3_K3_default", "phiest_3x3_K3_perturbed", "phiest_4x4_K4_perturbed"])
+def test_reference_per_layer_fixtures(dev, golden_dir, name):
+    """The per-layer states the REFERENCE wrote (tests/golden/make_golden.py): L{k-1}:Z, L{k}:phi, L{k}:h in, L{k}:G out.
+    Every fixture has accepted matrices (phiest_4x4_K4_perturbed rejects all three of its layer-1 matrices: flags 16, 16, 4)."""
+    z, sd, (Nb, Nd, K, B, L, head, _) = load_fixture(os.path.join(golden_dir, name + ".npz"))
+    m = _model(sd, Nb, Nd, K)
+    n = Nb * Nd + 1
+    tri = _tril(n)
+    accepted = 0
+    for k in range(1, K):
+        phi = torch.from_numpy(z[f"L{k}:phi"]).to(torch.complex64)
+        h = torch.from_numpy(z[f"L{k}:h"]).float()
+        Z = torch.from_numpy(z[f"L{k - 1}:Z"]).to(torch.complex64).contiguous()
+        G_ref = torch.from_numpy(z[f"L{k}:G"]).to(torch.complex128)
+        G0, rn0 = torch.full((phi.shape[0], n, n), SENT_G, dtype=torch.complex64), torch.full((phi.shape[0],), SENT_RN)
+        _, G, rn, flag, st = _run(dev, m, k, phi, h, Z, G0, rn0)
+        _check_status(flag, st)
+        err = _g_errors(G, G_ref, tri)
+        ok = flag.numpy() == 0
+        assert (err[ok] <= TOL_G).all(), (k, err[ok])
+        rej = flag != 0
+        assert torch.equal(_bits(G[rej]), _bits(G0[rej]))
+        accepted += int(ok.sum())
+        print(f"FIXTURE {name} layer {k}: flags {flag.tolist()} worst {err[ok].max() if ok.any() else 0:.2e}")
+    print(f"FIXTURE {name}: accepted {accepted}")

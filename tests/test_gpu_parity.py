@@ -283,6 +283,38 @@ def test_chunking_is_invisible_on_the_large_matrix_pipeline(dev, grid):
         assert torch.equal(a0, a1)
 
 
+@pytest.mark.parametrize("chunk", [512, 600])
+@pytest.mark.parametrize("grid", [(10, 10), (8, 16)])
+def test_chunking_is_invisible_across_the_workgroup_shapes(dev, grid, chunk):
+    """The matrix-function kernel has two workgroup shapes at D <= 128 (4 waves per matrix for calls of more than 512
+    signals, 12 below) that sum in different orders: the shape must follow the call, not the chunk.  B = 1100 at chunk = 512
+    is the chunks 512, 512, 76; at chunk = 600 the chunks 600 and 500 lie on both sides of the switch."""
+    Nb, Nd = grid
+    K, B = 4, 1100
+    sd = R.make_weights(Nb, Nd, K, seed=9, head=False, perturb=0.3)
+    m = A.PhiEstADMMNet(M=Nb, N=Nd, num_layers=K).eval()
+    m.load_state_dict(sd)
+    args = synth.make_batch_device(B, Nb, Nd, seed=31, device=dev)[:3]
+    m.chunk = 0
+    ref = m(*args).cpu()
+    assert m.last_status[2] > 0
+    m.chunk = chunk
+    assert torch.equal(m(*args).cpu(), ref)
+
+
+def test_ragged_last_chunk_is_invisible_at_cfg2(dev):
+    """B = 8292 at the default chunk (8192) leaves a ragged tail of 100 signals -- the same bits as one chunk of 8292."""
+    Nb, Nd, K, B = 8, 16, 4, 8292
+    sd = R.make_weights(Nb, Nd, K, seed=10, head=False, perturb=0.3)
+    m = A.PhiEstADMMNet(M=Nb, N=Nd, num_layers=K).eval()
+    m.load_state_dict(sd)
+    args = synth.make_batch_device(B, Nb, Nd, seed=32, device=dev)[:3]
+    m.chunk = 0
+    ref = m(*args).cpu()
+    m.chunk = B
+    assert torch.equal(m(*args).cpu(), ref)
+
+
 def test_layer_api_and_sharded_single_rank(dev):
     Nb, Nd, K, B = 6, 6, 4, 20
     torch.manual_seed(4)
