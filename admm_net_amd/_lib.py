@@ -15,7 +15,8 @@ LIB_PATH = os.path.join(_HERE, "libadmmnet_hip.so")
 
 
 class Cfg(ctypes.Structure):
-    """struct admmnet_cfg (include/admmnet.h)."""
+    """struct admmnet_cfg (include/admmnet.h).  ``reserved[0]`` is the C struct's ``sub_batch`` (0 = one batch), the field
+    list keeps the two-int ``reserved`` of ABI version 1."""
     _fields_ = [("M", c_int32), ("N", c_int32), ("L", c_int32), ("K", c_int32),
                 ("has_head", c_int32), ("chunk", c_int32), ("reserved", c_int32 * 2)]
 

@@ -88,7 +88,21 @@ static int check_cfg(const admmnet_cfg *cfg) {
         set_error("unsupported L=%d", cfg->L);
         return ADMMNET_E_ARG;
     }
+    if (cfg->sub_batch < 0) {
+        set_error("sub_batch=%d (need 0 = one batch, or >= 1 signals per sub-batch)", cfg->sub_batch);
+        return ADMMNET_E_ARG;
+    }
     return ADMMNET_OK;
+}
+
+// Sub-batches (cfg->sub_batch = g > 0): the signals [j g, min((j + 1) g, B)) form group j, which takes its own batch mean.
+// group_size() is g capped at B (g >= B is one group); without sub-batches the whole call is one group of B.
+static int64_t group_size(const admmnet_cfg *cfg, int64_t B) {
+    return (cfg->sub_batch > 0 && cfg->sub_batch < B) ? cfg->sub_batch : B;
+}
+static int64_t group_count(const admmnet_cfg *cfg, int64_t B) {
+    const int64_t g = group_size(cfg, B);
+    return g > 0 ? (B + g - 1) / g : 1;
 }
 
 // Tridiagonal eigensolver: divide & conquer (default) or QL + rotation replay (ADMMNET_EIG=ql).
@@ -242,8 +256,9 @@ int carve_workspace(const admmnet_cfg *cfg, int64_t B, void *base, int64_t bytes
         for (int i = 0; i < 2; ++i) ws->h[i] = c.take<float>(B * D);
         ws->alpha = c.take<float>(B);
         ws->rn = c.take<float>(B);
-        ws->sum = c.take<double>(2);
-        ws->mean = c.take<float>(4);
+        const int64_t ng = group_count(cfg, B);   // (1 without sub-batches: the layout of a plain call)
+        ws->sum = c.take<double>(2 * ng);
+        ws->mean = c.take<float>(ng > 4 ? ng : 4);
         ws->headkv = c.take<float>((int64_t)2 * D * 128);
     }
     carve_chunk(c, D, pick_chunk(cfg, B), ws);
@@ -500,9 +515,17 @@ int admmnet_layer_front(const admmnet_cfg *cfg, const float *W, int32_t k, const
         ADMM_HIP(hipStreamWaitEvent(ss[1], e0, 0));
         ADMM_HIP(hipEventDestroy(e0));
     }
+    // The matrix-function kernel's shape follows the size of the matrix's group, as a separate call of that group would
+    // choose it (spectral_waves).  Full groups of g and a short last group may take different shapes: no chunk then
+    // straddles the start of the last group.  Without sub-batches both are spectral_waves(D, B) and nothing splits.
+    const int64_t gsz = group_size(cfg, B), last0 = (group_count(cfg, B) - 1) * gsz;
+    const int waves_full = spectral_waves(D, gsz), waves_last = spectral_waves(D, B - last0);
     int ci = 0;
-    for (int64_t b0 = 0; b0 < B; b0 += ws.chunk, ++ci) {
-        const int64_t nb = (B - b0 < ws.chunk) ? (B - b0) : ws.chunk;
+    int64_t nb = 0;
+    for (int64_t b0 = 0; b0 < B; b0 += nb, ++ci) {
+        nb = (B - b0 < ws.chunk) ? (B - b0) : ws.chunk;
+        if (waves_full != waves_last && b0 < last0 && b0 + nb > last0) nb = last0 - b0;
+        const int waves = b0 >= last0 ? waves_last : waves_full;
         const Ws &wc = sets[ci & 1];
         hipStream_t sc = ss[ci & 1];
         const bool lean = use_lean(D);
@@ -528,7 +551,7 @@ int admmnet_layer_front(const admmnet_cfg *cfg, const float *W, int32_t k, const
             const int prv = cur ^ 1;
             const float *lwp = k >= 1 ? W + (int64_t)(k - 1) * L.size() : lw;
             if ((rc = launch_spectral(D, nb, lw, phk, hk, ws.Z + b0 * n * n, Gk, ws.rn + b0, wc, status, sc, true,
-                                      spectral_waves(D, B), fold ? ws.alpha + b0 : nullptr, fold ? ws.phi[prv] + b0 * D : nullptr,
+                                      waves, fold ? ws.alpha + b0 : nullptr, fold ? ws.phi[prv] + b0 * D : nullptr,
                                       fold ? ws.h[prv] + b0 * D : nullptr, fold ? lwp : nullptr, fold ? (k == 1 ? 2 : 1) : 0)))
                 return rc;
             wf.skip = wc.spec_flag;
@@ -550,6 +573,7 @@ int admmnet_layer_front(const admmnet_cfg *cfg, const float *W, int32_t k, const
             ADMM_HIP(hipEventDestroy(e1));
         }
     }
+    if (cfg->sub_batch > 0) return launch_rn_group_sum(B, gsz, ws.rn, sum_out ? sum_out : ws.sum, st);
     return launch_rn_sum(B, ws.rn, sum_out ? sum_out : ws.sum, st);
 }
 
@@ -565,6 +589,9 @@ int admmnet_layer_back(const admmnet_cfg *cfg, const float *W, int32_t k, int64_
     carve_workspace(cfg, B, workspace, INT64_MAX, &ws, true);
     const int D = cfg->M * cfg->N;
     const LayerLayout L{D};
+    if (cfg->sub_batch > 0)   // mean_dev: one mean per group
+        return launch_zstep_groups(W + (int64_t)k * L.size(), D, B, group_size(cfg, B), ws.rn, mean_dev, ws.alpha,
+                                   (hipStream_t)stream);
     return launch_zstep(W + (int64_t)k * L.size(), D, B, ws.rn, mean_dev, ws.alpha, (hipStream_t)stream);
 }
 
@@ -578,9 +605,14 @@ int admmnet_layer_back_pair(const admmnet_cfg *cfg, const float *W, int32_t k, i
     }
     Ws ws;
     carve_workspace(cfg, B, workspace, INT64_MAX, &ws, true);
-    if ((rc = launch_mean_from_pair(sum_count_dev, ws.mean, (hipStream_t)stream))) return rc;
     const int D = cfg->M * cfg->N;
     const LayerLayout L{D};
+    if (cfg->sub_batch > 0) {   // sum_count_dev: one pair per group
+        if ((rc = launch_mean_from_pairs(sum_count_dev, group_count(cfg, B), ws.mean, (hipStream_t)stream))) return rc;
+        return launch_zstep_groups(W + (int64_t)k * L.size(), D, B, group_size(cfg, B), ws.rn, ws.mean, ws.alpha,
+                                   (hipStream_t)stream);
+    }
+    if ((rc = launch_mean_from_pair(sum_count_dev, ws.mean, (hipStream_t)stream))) return rc;
     return launch_zstep(W + (int64_t)k * L.size(), D, B, ws.rn, ws.mean, ws.alpha, (hipStream_t)stream);
 }
 
@@ -617,6 +649,10 @@ int admmnet_forward_f32(const admmnet_cfg *cfg, const float *W, const void *y, c
     for (int k = 0; k < cfg->K; ++k) {
         if ((rc = admmnet_layer_front(cfg, W, k, y, b, sigma, B, workspace, ws.sum, status, stream))) return rc;
         if (k < cfg->K - 1) {
+            if (cfg->sub_batch > 0) {   // ws.sum holds one pair per group
+                if ((rc = admmnet_layer_back_pair(cfg, W, k, B, workspace, ws.sum, stream))) return rc;
+                continue;
+            }
             if ((rc = launch_mean_from_sum(ws.sum, B, ws.mean, st))) return rc;
             if ((rc = admmnet_layer_back(cfg, W, k, B, workspace, ws.mean, stream))) return rc;
         }
@@ -696,7 +732,7 @@ int admmnet_glayer_spectral_f32(const admmnet_cfg *cfg, const float *layer_weigh
 
 int64_t admmnet_eigh_workspace_bytes(int32_t n, int64_t B) {
     if (n < 2 || n - 1 > kMaxD || B < 1) return -1;
-    admmnet_cfg cfg = {n - 1, 1, 3, 1, 0, 0, {0, 0}};
+    admmnet_cfg cfg = {n - 1, 1, 3, 1, 0, 0, 0, {0}};
     Ws ws;
     carve_workspace(&cfg, B, nullptr, 0, &ws, false);
     return ws.total_bytes;
@@ -716,7 +752,7 @@ int admmnet_eigh_c64(int32_t n, int64_t B, const void *A, float *w, void *V, voi
         return ADMMNET_E_ARG;
     }
     hipStream_t st = (hipStream_t)stream;
-    admmnet_cfg cfg = {n - 1, 1, 3, 1, 0, 0, {0, 0}};
+    admmnet_cfg cfg = {n - 1, 1, 3, 1, 0, 0, 0, {0}};
     Ws ws;
     int rc;
     if ((rc = carve_workspace(&cfg, B, workspace, workspace_bytes, &ws, false))) return rc;

@@ -86,8 +86,8 @@ struct Ws {
     float *h[2];              // [B][D]
     float *alpha;             // [B] adaptive step of the previous layer
     float *rn;                // [B] ||G - C||_F of the current layer
-    double *sum;              // [2] scratch for the batch sum
-    float *mean;              // [1] batch mean (single-rank path)
+    double *sum;              // [2] scratch for the batch sum ([ngroups][2] with sub-batches)
+    float *mean;              // [1] batch mean (single-rank path; [ngroups] with sub-batches)
     float *headkv;            // [2][D][128] batch independent K / V projections of the head
     // chunk-sized eigensolver buffers
     float2 *Mbuf;             // [chunk][D*D + D + 1]: M row-major, arrow a[D], corner (re only)
@@ -184,6 +184,12 @@ int launch_rn_sum(int64_t B, const float *rn, double *sum, hipStream_t st);
 int launch_mean_from_sum(const double *sum, int64_t B, float *mean, hipStream_t st);
 int launch_mean_from_pair(const double *sum_count, float *mean, hipStream_t st);   // mean = sum_count[0] / sum_count[1]
 int launch_zstep(const float *lw, int D, int64_t B, const float *rn, const float *mean, float *alpha, hipStream_t st);
+// sub-batches of g signals (admmnet_cfg.sub_batch): pairs [ceil(B / g)][2] = (sum, count) per group, each with the bits
+// launch_rn_sum gives that group alone; mean [ceil(B / g)]; zstep reads the mean of signal i's group i / g
+int launch_rn_group_sum(int64_t B, int64_t g, const float *rn, double *pairs, hipStream_t st);
+int launch_mean_from_pairs(const double *pairs, int64_t ngroups, float *mean, hipStream_t st);
+int launch_zstep_groups(const float *lw, int D, int64_t B, int64_t g, const float *rn, const float *mean, float *alpha,
+                        hipStream_t st);
 // head.hip
 int launch_head(const admmnet_cfg *cfg, const float *hw, int64_t B, const float2 *phi, float *kv,
                 float *out, hipStream_t st);

@@ -136,6 +136,7 @@ class _FusedBase(nn.Module):
             self.peakSearchLayer = PeakSearchLayer(M, N, L)
         # execution knobs (not part of the reference API)
         self._chunk = 0                # signals per eigensolver chunk (0 = library default); see the `chunk` property
+        self._sub_batch = None         # signals per independent sub-batch (None = the call is one batch); see `sub_batch`
         self.check_status = True       # one D2H read per forward: raise if the eigensolver failed
         self._wcache = None
         self._ws = None
@@ -155,9 +156,30 @@ class _FusedBase(nn.Module):
             self._chunk = value
             self._ws = None
 
+    @property
+    def sub_batch(self) -> Optional[int]:
+        """Signals per independent sub-batch (None = the whole call is one batch, the reference's semantics).  With g set,
+        a call on B signals evaluates the consecutive groups [i g, min((i + 1) g, B)) -- the last one may be shorter --
+        each with its own batch mean (admm_net.py:459), and every group gets exactly the outputs a separate call on it
+        returns: g = 256 reproduces the reference's DataLoader batches, g = 1 its single-signal scripts.  Honoured by the
+        fused forward, by ``forward_autograd`` and by ``sharded.ShardedForward``.  Not part of the state_dict.  Setting it
+        drops the cached workspace."""
+        return self._sub_batch
+
+    @sub_batch.setter
+    def sub_batch(self, value: Optional[int]):
+        if value is not None:
+            if isinstance(value, bool) or int(value) != value or not 1 <= int(value) <= 2 ** 31 - 1:
+                raise ValueError(f"sub_batch must be None or an int >= 1, got {value!r}")
+            value = int(value)
+        if value != self._sub_batch:
+            self._sub_batch = value
+            self._ws = None
+
     # ---- weights -----------------------------------------------------------
     def cfg(self) -> Cfg:
-        return Cfg(self.M, self.N, self.L, self.num_layers, int(self._HAS_HEAD), int(self.chunk), (ctypes.c_int32 * 2)(0, 0))
+        return Cfg(self.M, self.N, self.L, self.num_layers, int(self._HAS_HEAD), int(self.chunk),
+                   (ctypes.c_int32 * 2)(self.sub_batch or 0, 0))   # reserved[0] = admmnet_cfg.sub_batch
 
     def _raw_params(self):
         """Parameters in the raw order documented in include/admmnet.h."""
@@ -276,7 +298,7 @@ class _FusedBase(nn.Module):
         if pdev != dev:
             raise _lib.AdmmNetError(f"training runs on the GPU: parameters are on {pdev}, expected {dev} "
                                     "(move the model with .to(device) as train.py / trainPhi.py do)")
-        out = training.unrolled_forward(self, y.to(dev), b.to(dev), sigma.to(dev))
+        out = training.unrolled_forward(self, y.to(dev), b.to(dev), sigma.to(dev), sub_batch=self.sub_batch)
         if isinstance(out, tuple):
             return tuple(o.to(y.device) for o in out)
         return out.to(y.device)

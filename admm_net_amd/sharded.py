@@ -8,6 +8,12 @@ whole batch; ``scope='shard'`` uses each rank's own mean (zero communication,
 equals the reference evaluated on each sub-batch).  Nothing else crosses
 ranks until the optional final all-gather of the outputs.
 
+A model with ``sub_batch = g`` (independent groups of g signals, each with
+its own mean) needs no per-layer collective at all when every rank starts at
+a group boundary (``shard_bounds(..., sub_batch=g)``): each rank's own
+per-group (sum, count) pairs go straight back, in either scope.  One
+all-gather of the shard sizes per call checks the alignment.
+
 The layer engine is injected so the protocol can be exercised on CPU ranks
 (gloo) in tests; the product engine is ``HipLayerEngine`` (C ABI layer-at-a-time
 entry points of include/admmnet.h).
@@ -37,6 +43,8 @@ class HipLayerEngine:
         self.dev = dev
         D = model.M * model.N
         self.B = y.shape[0]
+        g = model.sub_batch
+        self.ngroups = -(-self.B // g) if g else 1   # (sum, count) pairs per layer: one per sub-batch
         self.y = y.detach().to(dev, torch.complex64).contiguous()
         self.b = b.detach().to(dev, torch.complex64).contiguous()
         self.sigma = sigma.detach().to(dev, torch.float32).reshape(-1).contiguous()
@@ -44,8 +52,8 @@ class HipLayerEngine:
             self.W = model.packed_weights(dev)
             self.ws = model.workspace(self.B, dev)
             self.status = torch.zeros(4, dtype=torch.int32, device=dev)
-            self.sumcnt = torch.zeros(2, dtype=torch.float64, device=dev)
-            self.mean = torch.zeros(4, dtype=torch.float32, device=dev)
+            self.sumcnt = torch.zeros(2 * self.ngroups, dtype=torch.float64, device=dev)
+            self.mean = torch.zeros(max(4, self.ngroups), dtype=torch.float32, device=dev)
             self.phi = torch.empty(self.B, D, dtype=torch.complex64, device=dev)
             self.head = (torch.empty(3, self.B, model.L, dtype=torch.float32, device=dev)
                          if model._HAS_HEAD else None)
@@ -60,7 +68,8 @@ class HipLayerEngine:
                                               _ptr(self.status), self._stream()), "admmnet_begin")
 
     def front(self, k: int) -> torch.Tensor:
-        """Runs layer k up to G; returns device float64 [2] = (local sum of r_b, local count)."""
+        """Runs layer k up to G; returns device float64 [2] = (local sum of r_b, local count), with sub-batches
+        [2 * ngroups]: that pair for every sub-batch."""
         with torch.cuda.device(self.dev):
             _lib.check(self.lib.admmnet_layer_front(ctypes.byref(self.cfg), _ptr(self.W), k, _ptr(self.y),
                                                     _ptr(self.b), _ptr(self.sigma), self.B, _ptr(self.ws),
@@ -69,8 +78,12 @@ class HipLayerEngine:
         return self.sumcnt
 
     def back(self, k: int, mean: torch.Tensor):
+        """ZLayer step from the batch mean, or with sub-batches from [ngroups] means."""
         with torch.cuda.device(self.dev):
-            self.mean[0] = mean.to(torch.float32)
+            if self.m.sub_batch:
+                self.mean[:self.ngroups] = mean.reshape(-1).to(torch.float32)
+            else:
+                self.mean[0] = mean.to(torch.float32)
             _lib.check(self.lib.admmnet_layer_back(ctypes.byref(self.cfg), _ptr(self.W), k, self.B, _ptr(self.ws),
                                                    _ptr(self.mean), self._stream()), "admmnet_layer_back")
 
@@ -92,11 +105,17 @@ class HipLayerEngine:
         return self.phi, self.head
 
 
-def shard_bounds(total: int, world: int, rank: int):
-    """Contiguous, as-even-as-possible split of ``total`` signals."""
-    base, rem = divmod(total, world)
-    lo = rank * base + min(rank, rem)
-    return lo, lo + base + (1 if rank < rem else 0)
+def shard_bounds(total: int, world: int, rank: int, sub_batch: Optional[int] = None):
+    """Contiguous, as-even-as-possible split of ``total`` signals; with ``sub_batch = g`` an as-even-as-possible split
+    of the ceil(total / g) groups, so every shard starts at a group boundary and only the last group may be short."""
+    if sub_batch is None:
+        base, rem = divmod(total, world)
+        lo = rank * base + min(rank, rem)
+        return lo, lo + base + (1 if rank < rem else 0)
+    if sub_batch < 1:
+        raise ValueError(f"sub_batch must be None or >= 1, got {sub_batch}")
+    glo, ghi = shard_bounds(-(-total // sub_batch), world, rank)
+    return min(glo * sub_batch, total), min(ghi * sub_batch, total)
 
 
 class ShardedForward:
@@ -116,14 +135,23 @@ class ShardedForward:
     def __call__(self, y_local, b_local, sigma_local, gather: bool = False):
         """Forward of this rank's shard.  Returns (phi, head) for the shard, or for the whole
         batch (rank order) when ``gather`` is set.  ``head`` is None for PhiEstADMMNet."""
-        eng = self.engine_factory(y_local, b_local, sigma_local)
         K = self.model.num_layers
         world = self._world()
+        g = getattr(self.model, "sub_batch", None)
+        if g and world > 1:
+            self._check_group_aligned(y_local.shape[0], g, world, y_local.device)
+        eng = self.engine_factory(y_local, b_local, sigma_local)
         eng.begin()
         for k in range(K):
             sc = eng.front(k)
             if k == K - 1:
                 break
+            if g:   # sub-batches never span ranks: each rank's own per-group pairs, no collective
+                if hasattr(eng, "back_pair") and sc.is_cuda and sc.dtype == torch.float64:
+                    eng.back_pair(k, sc)
+                else:
+                    eng.back(k, sc[0::2] / sc[1::2])
+                continue
             if self.scope == "global" and world > 1:
                 dist.all_reduce(sc, op=dist.ReduceOp.SUM, group=self.group)
             if hasattr(eng, "back_pair") and sc.is_cuda and sc.dtype == torch.float64:
@@ -139,6 +167,19 @@ class ShardedForward:
             if head is not None:
                 head = self._gather(head, dim=1)
         return phi, head
+
+    def _check_group_aligned(self, n_local: int, g: int, world: int, dev):
+        """Every shard must start at a group boundary of the whole batch, i.e. every rank before the last non-empty one
+        holds whole groups (shard_bounds(..., sub_batch=g) cuts that way).  Raises ValueError on every rank otherwise."""
+        sizes = [torch.zeros(1, dtype=torch.int64, device=dev) for _ in range(world)]
+        dist.all_gather(sizes, torch.tensor([n_local], dtype=torch.int64, device=dev), group=self.group)
+        sizes = [int(s.item()) for s in sizes]
+        start = 0
+        for r, n in enumerate(sizes):
+            if n and start % g:
+                raise ValueError(f"sub_batch={g}: the shard of rank {r} starts at signal {start}, inside a sub-batch "
+                                 f"(shard sizes {sizes}); split with shard_bounds(total, world, rank, sub_batch={g})")
+            start += n
 
     def _gather(self, t, dim):
         if t.is_complex():   # collectives move real tensors

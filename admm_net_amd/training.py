@@ -16,7 +16,9 @@ Gradient flow mirrors the reference as written:
     ``gLayers.k.lambda_param`` / ``zLayers.k.lambda_param`` receive no gradient;
   * the ``rho`` FEATURE of the step network is a detached number (admm_net.py:458), the multiplying
     ``rho_base`` is not (admm_net.py:469);
-  * the residual norm is divided by the mean over the batch the call sees (admm_net.py:459);
+  * the residual norm is divided by the mean over the batch the call sees (admm_net.py:459), or with ``sub_batch = g``
+    over each group of g consecutive signals: the gradients are then the sum of the per-group graphs' gradients, i.e.
+    gradient accumulation over those batches;
   * H, G, Z of the last layer are dead (admm_net.py:757-764): they are not evaluated, and, as in the
     reference, their parameters end up with ``grad = None``.
 There is no CPU fallback: without the HIP library ``ops.eigh`` raises.
@@ -128,7 +130,18 @@ def _g_layer(layer, phi, h, Z, solver, asm):
     return _Rebuild.apply(V, wp, asm)
 
 
-def _z_layer(layer, k, phi, h, G, Z):
+def _group_mean(rn: torch.Tensor, sub_batch: Optional[int]) -> torch.Tensor:
+    """The batch mean of admm_net.py:459 for every signal: over the whole call, or over its group of ``sub_batch``
+    consecutive signals (the last group may be shorter)."""
+    B = rn.shape[0]
+    if sub_batch is None or sub_batch >= B:
+        return rn.mean()
+    gid = torch.arange(B, device=rn.device) // sub_batch
+    sums = torch.zeros(int(gid[-1]) + 1, dtype=rn.dtype, device=rn.device).index_add(0, gid, rn)
+    return (sums / torch.bincount(gid).to(rn.dtype))[gid]
+
+
+def _z_layer(layer, k, phi, h, G, Z, sub_batch=None):
     """admm_net.py:388-474."""
     corner = (1.0 / (F.softplus(layer.lambda_param) ** 2 + EPS)).item()
     R = G - _block_matrix(phi, h, corner)
@@ -137,7 +150,7 @@ def _z_layer(layer, k, phi, h, G, Z):
     B = rn.shape[0]
     feat = torch.stack([torch.full((B,), k / 10.0, device=rn.device),
                         torch.full((B,), rho.item(), device=rn.device),
-                        rn / (rn.mean() + EPS)], dim=1)
+                        rn / (_group_mean(rn, sub_batch) + EPS)], dim=1)
     step = rho * (0.5 + 1.5 * layer.residual_scale_net(feat)).squeeze(1)
     return Z + step.reshape(-1, 1, 1) * R
 
@@ -159,14 +172,19 @@ def _peak_head(head, phi):
 
 
 def unrolled_forward(model, y: torch.Tensor, b: torch.Tensor, sigma: torch.Tensor,
-                     solver: Optional[Callable] = None, assembler=None):
+                     solver: Optional[Callable] = None, assembler=None, sub_batch: Optional[int] = None):
     """Differentiable K-layer forward on the device of ``y`` (admm_net.py:742-764 / 791-816).
+
+    ``sub_batch = g`` evaluates the consecutive groups of g signals as independent batches, each with its own mean
+    (``_FusedBase.sub_batch``); None: the call is one batch.
 
     ``solver(A) -> (w, V)`` defaults to the HIP eigensolver and ``assembler`` to the HIP contractions; the CPU unit
     tests pass stand-ins (``torch.linalg.eigh``, ``TorchAssembler``) to check the autograd wiring against the reference's
     gradients without a GPU.
     Returns phi, or (tau, f, confidences, phi) when the model has a PeakSearchLayer.
     """
+    if sub_batch is not None and sub_batch < 1:
+        raise ValueError(f"sub_batch must be None or >= 1, got {sub_batch}")
     solver = ops.eigh if solver is None else solver
     asm = Assembler if assembler is None else assembler
     K, D = model.num_layers, model.M * model.N
@@ -185,7 +203,7 @@ def unrolled_forward(model, y: torch.Tensor, b: torch.Tensor, sigma: torch.Tenso
             break
         h = _h_layer(model.hLayers[k], G, Z, sigma)
         G = _g_layer(model.gLayers[k], phi, h, Z, solver, asm)
-        Z = _z_layer(model.zLayers[k], k, phi, h, G, Z)
+        Z = _z_layer(model.zLayers[k], k, phi, h, G, Z, sub_batch)
     if getattr(model, "_HAS_HEAD", False):
         tau, f, conf = _peak_head(model.peakSearchLayer, phi)
         return tau, f, conf, phi

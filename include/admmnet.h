@@ -50,9 +50,15 @@ typedef struct admmnet_cfg {
     int32_t chunk;      /* signals per eigensolver work chunk (0 = auto); a
                            work split only: the bits of a signal depend on its
                            inputs, the weights, the batch mean and the batch
-                           size B of the call, never on chunk (a rank of a
-                           sharded forward is one call)                       */
-    int32_t reserved[2];
+                           size B of the call (of its sub-batch, below), never
+                           on chunk (a rank of a sharded forward is one call) */
+    int32_t sub_batch;  /* 0: the call is one batch (admm_net.py:459 takes its
+                           mean over all B signals).  g >= 1: the signals
+                           [j g, min((j + 1) g, B)) form sub-batch j, of
+                           ngroups = ceil(B / g), each with its own mean; every
+                           sub-batch gets the bits a separate call on it alone
+                           returns (g >= B: one sub-batch).  < 0: ADMMNET_E_ARG */
+    int32_t reserved[1];
 } admmnet_cfg;
 
 int         admmnet_abi_version(void);
@@ -92,12 +98,13 @@ int     admmnet_pack_weights(const admmnet_cfg *cfg, const float *raw_host,
                              float *packed_host);
 
 /* ---- workspace -------------------------------------------------------------*/
+/* (with cfg->sub_batch > 0 it includes one (sum, count) pair and one mean per sub-batch) */
 int64_t admmnet_workspace_bytes(const admmnet_cfg *cfg, int64_t B);
 
 /* ---- whole forward ----------------------------------------------------------
  * Replaces PhiEstADMMNet.forward (admm_net.py:742-764) and ADMMNet.forward
  * (admm_net.py:791-816) with the batch mean of ZLayer (admm_net.py:459) taken
- * over the B signals of this call.
+ * over the B signals of this call, or over each sub-batch of cfg->sub_batch signals.
  *   y, b      device complex64 [B][D]
  *   sigma     device float32   [B]
  *   phi_out   device complex64 [B][D]
@@ -119,9 +126,11 @@ int admmnet_forward_f32(const admmnet_cfg *cfg, const float *weights_dev,
  * layer_front(k): lazy Z update with the step of layer k-1, phi/H/G of layer k
  *   (admm_net.py:806-810) and r_b = ||G_b - C_b||_F; writes the LOCAL sum of
  *   r_b to sum_out[0] and the local count B to sum_out[1] (device float64 [2]).
- *   For k == K-1 only phi is produced.
+ *   With cfg->sub_batch > 0: sum_out is device float64 [ngroups][2], the
+ *   (sum, count) pair of every sub-batch.  For k == K-1 only phi is produced.
  * layer_back(k): ZLayer step (admm_net.py:443-474) from a caller-supplied
- *   batch mean (device float, e.g. all-reduced sum / global B).
+ *   batch mean (device float, e.g. all-reduced sum / global B); with
+ *   cfg->sub_batch > 0, mean_dev is device float [ngroups], one per sub-batch.
  * begin() zeroes the per-forward state; finish() writes phi_out (+ head).
  */
 int admmnet_begin(const admmnet_cfg *cfg, int64_t B, void *workspace,
@@ -132,7 +141,8 @@ int admmnet_layer_front(const admmnet_cfg *cfg, const float *weights_dev, int32_
 int admmnet_layer_back(const admmnet_cfg *cfg, const float *weights_dev, int32_t k,
                        int64_t B, void *workspace, const float *mean_dev, void *stream);
 /* The same from the (all-reduced) pair the protocol carries: sum_count_dev = device float64 [2] = (sum of r_b, number of
- * signals) over all ranks -- the mean of admm_net.py:459 is formed on the device, no host arithmetic between the calls. */
+ * signals) over all ranks -- the mean of admm_net.py:459 is formed on the device, no host arithmetic between the calls.
+ * With cfg->sub_batch > 0: device float64 [ngroups][2], the pairs layer_front wrote (sub-batches need no all-reduce). */
 int admmnet_layer_back_pair(const admmnet_cfg *cfg, const float *weights_dev, int32_t k,
                             int64_t B, void *workspace, const double *sum_count_dev, void *stream);
 int admmnet_finish(const admmnet_cfg *cfg, const float *weights_dev, int64_t B,
