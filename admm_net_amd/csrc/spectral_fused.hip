@@ -671,7 +671,10 @@ __global__ __launch_bounds__(64 * W, W == 12 ? 1 : 3) void sp_fused_kernel(int D
     if (wave == 0) {   // the 11 evaluations of f on 11 lanes, in double
         const double thr = lw[S_THR];
         const double dl0 = cv.sc[0], dl1 = cv.sc[1], c = cv.sc[2];
-        const double delta = sqrt(sqrt((double)fro));   // ||E||_2 <= ||E^2||_F^(1/2)
+        // ||E||_2 <= ||E^2||_F^(1/2), but E^2 is formed from bf16 operands (2^-9 relative each): with one dominant bulk eigenvalue
+        // (||E^2||_F^(1/2) -> ||E||_2) the bare value fell short of ||E||_2 and a kink of f just inside it went unsampled
+        // (tests/test_gpu_glayer_route.py, dominant bulk eigenvalue); 2^-8 covers the operands' rounding twice over
+        const double delta = sqrt(sqrt((double)fro)) * (1.0 + 0x1p-8);
         const double ts[9] = {-1.0, 0.0, 1.0, -0.75, -0.5, -0.25, 0.25, 0.5, 0.75};
         double arg = c;
         if (lane < 9) arg = c + ts[lane] * delta;

@@ -1,6 +1,7 @@
 """Generate golden vectors by IMPORTING the reference (build container only).
 
 Run:  PYTHONDONTWRITEBYTECODE=1 python tests/golden/make_golden.py
+      (--trained-only [name ...]: only the trained-weight fixtures, ~6 minutes on 8 CPU threads)
 Needs /root/reference (read-only, never copied).  Writes small .npz fixtures
 next to this file: inputs, the reference's own state_dict (as arrays) and the
 outputs of the reference's forward.  Only data is stored -- no reference code.
@@ -108,7 +109,77 @@ def depth_cases():
     run_case("phiest_16x16_K32_default", "PhiEstADMMNet", 16, 16, 32, 1, 24, False, False, False, store_weights=False)
 
 
+TRAIN_THREADS = 8
+
+
+def _noise_free_label(truth, Nb, Nd):
+    """The scene's noise-free signal Psi = kr(S, conj(D)) C of make_batch (its truth), the training label."""
+    from admm_net_amd.synth import steering
+    S, Dm = steering(truth["f"].astype(np.float64), Nb), steering(truth["tau"].astype(np.float64), Nd)
+    psi = np.einsum("bl,bli,blj->bij", truth["C"].astype(np.complex128), S, np.conj(Dm))
+    return psi.reshape(psi.shape[0], Nb * Nd).astype(np.complex64)
+
+
+def trained_case(name, Nb, Nd, K, steps, batch, B, seed, lr=5e-3):
+    """The reference's PhiEstADMMNet trained on the CPU with the recipe of trainPhi.py:99-178 (PhiAlignmentLoss; AdamW,
+    lr 5e-3 with the ADMM-layer group at 0.5 lr, weight decay 1e-3; gradient norm clipped at 1.0), one fresh make_batch per
+    step.  Labels: the noise-free signal of make_batch's truth (the classical solver's phi costs minutes per signal here).
+    Stores the trained state_dict (w:), a held-out batch with the reference's eval-mode phi, and
+    train = [seed, steps, batch, lr, first loss, final loss, label kind (0 = noise-free signal), threads] + the loss curve."""
+    import time
+    import loss as ref_loss   # the reference's loss module (imported, not copied)
+    torch.set_num_threads(TRAIN_THREADS)
+    torch.manual_seed(seed)
+    model = ref.PhiEstADMMNet(M=Nb, N=Nd, L=3, num_layers=K)
+    crit = ref_loss.PhiAlignmentLoss()
+    admm = [p for n, p in model.named_parameters() if any(s in n for s in ("phiLayers", "hLayers", "gLayers", "zLayers"))]
+    assert len(admm) == len(list(model.parameters()))
+    opt = torch.optim.AdamW([{"params": admm, "lr": lr * 0.5}], lr=lr, weight_decay=1e-3)
+    model.train()
+    t0 = time.perf_counter()
+    losses = []
+    for step in range(steps):
+        y, b, sigma, truth = make_batch(batch, Nb, Nd, seed=seed * 100003 + step)
+        label = torch.from_numpy(_noise_free_label(truth, Nb, Nd))
+        opt.zero_grad()
+        phi = model(torch.from_numpy(y), torch.from_numpy(b), torch.from_numpy(sigma))
+        total, _ = crit(phi, label)
+        total.backward()
+        torch.nn.utils.clip_grad_norm_(model.parameters(), max_norm=1.0)
+        opt.step()
+        losses.append(float(total.item()))
+        if step % 10 == 0 or step == steps - 1:
+            print(f"{name} step {step}: loss {losses[-1]:.5f} ({time.perf_counter() - t0:.0f} s)", flush=True)
+    model.eval()
+    y, b, sigma, _ = make_batch(B, Nb, Nd, seed=seed + 7)
+    with torch.no_grad():
+        out = model(torch.from_numpy(y), torch.from_numpy(b), torch.from_numpy(sigma))
+    rec = dict(y=y, b=b, sigma=sigma, phi=out.numpy(), meta=np.array([Nb, Nd, K, B, 3, 0, 0]),
+               train=np.array([seed, steps, batch, lr, losses[0], losses[-1], 0, TRAIN_THREADS], dtype=np.float64),
+               train_loss=np.array(losses, dtype=np.float32))
+    rec.update(sd_arrays(model))
+    path = os.path.join(HERE, name + ".npz")
+    np.savez_compressed(path, **rec)
+    print(f"{name}: {os.path.getsize(path) / 1024:.0f} KiB, {steps} steps in {time.perf_counter() - t0:.0f} s, "
+          f"loss {losses[0]:.5f} -> {losses[-1]:.5f}")
+
+
+def trained_cases(only=None):
+    """Weights a user has trained (VERDICT 'What's missing' #2): value_net, threshold, rho and the H-layer MLPs moved together.
+    10x10 K=10 is trainPhi.py's own config; 8x16 K=8 is cfg2 (D = 128, both kernel shapes); 16x16 K=4 is D = 256 (K=4 keeps the
+    file under 1 MB)."""
+    for args in (("phiest_10x10_K10_trained", 10, 10, 10, 120, 32, 16, 31),
+                 ("phiest_8x16_K8_trained", 8, 16, 8, 100, 32, 16, 32),
+                 ("phiest_16x16_K4_trained", 16, 16, 4, 300, 16, 8, 33)):
+        if only is None or args[0] in only:
+            trained_case(*args)
+
+
 if __name__ == "__main__":
+    if "--trained-only" in sys.argv:
+        sys.path.insert(0, REF)
+        trained_cases([a for a in sys.argv[1:] if not a.startswith("--")] or None)
+        sys.exit(0)
     if "--depth-only" in sys.argv:
         depth_cases()
         sys.exit(0)

@@ -16,6 +16,7 @@ Bounds (per accepted matrix, over the lower triangle):
     4 * 2^-24 * (|Z| + |alpha| (|G_prev| + |C_prev|)) of the expression evaluated in float64 on the same float32 operands
     (three roundings: the difference, the product, the sum).
 """
+import collections
 import ctypes
 import functools
 import os
@@ -445,6 +446,241 @@ def test_accepted_matrices_are_accurate_under_spectral_surgery(dev, grid, kind, 
           f"delta/gap {min(ratios):.3g}..{max(ratios):.3g}")
     if (kind, par) in DECISIVE:
         assert acc == 0, (kind, par, flags)
+
+
+# ------------------------------------------------------------------ soundness of acceptance: the edges of the checks
+# The kernel accepts a matrix when, among others, the quadratic through f(c), f(c +- delta) misses f by at most tol * scale
+# (tol = 1e-6) at c + {+-0.25, +-0.5, +-0.75} delta, with delta = ||E^2||_F^(1/2) >= ||E||_2.  The cases below sit where those
+# checks are tight: a kink of f between the sample points with a sampled miss of 0.3 .. 100 x the tolerance; a bulk with one
+# dominant eigenvalue (delta / ||E||_2 -> 1) and a steep kink just inside it; the kink of |w| at w = 0 inside the bulk.  Every
+# accepted matrix must meet TOL_G / TOL_RN (the universal assertion), and the sampled miss, recomputed in float64 from the spectrum
+# the kernel received, must agree with the flag.  A case counts only if the fp32 input allows the bound at all:
+# L_f * 8 * 2^-24 * ||A||_2 <= 2e-6 * scale, L_f the Lipschitz bound of f on the bulk interval (the eigensolver route misses the
+# bound beyond it as well); the cases this guard skips are counted.
+TOL_MODEL = 1e-6
+DELTA_INFLATE = 1.0 + 2.0 ** -8   # the kernel's delta is ||E^2||_F^(1/2) (1 + 2^-8): its E^2 has bf16 operands
+TS = np.array([-1.0, 0.0, 1.0, -0.75, -0.5, -0.25, 0.25, 0.5, 0.75])   # the kernel's sample points, in units of delta
+EDGE_B = (0, 1)                                                          # matrices of the surgery base
+KINK_T = [i / 8 for i in range(-10, 11)]                                 # kink positions c + t r, r = the bulk's half-width
+KINK_MISS = (0.3, 1.0, 3.0, 10.0, 100.0)                                 # sampled miss, in units of TOL_MODEL * scale
+ZERO_S = (0.0, 0.1, -0.1, 0.5, -0.5, 0.9, -0.9, 1.1, -1.1)               # bulk centre c = s delta around the kink of |w|
+DOM_R = (10.0, 30.0)                                                     # dominant bulk eigenvalue at R x the half-width
+DOM_T = (0.9, 0.95, 0.97, 0.99, 0.999, 1.001, 1.02)                      # kink at c + t ||E||_2 on its side
+MISS_FLAGS = (8, 1, 2, 4)                                                # the miss check and the checks before it
+
+
+def _gparams(sd):
+    """(thr, W0, B0, W2, B2) of value_net of layer SURGERY_K in float64, from the float32 weights the kernel reads."""
+    p = f"gLayers.{SURGERY_K}."
+    g = lambda key: sd[p + key].double().numpy()   # noqa: E731
+    return (float(torch.sigmoid(sd[p + "threshold"].double())), g("value_net.0.weight")[:, 0], g("value_net.0.bias"),
+            g("value_net.2.weight")[0], float(g("value_net.2.bias")[0]))
+
+
+def _fmap(gp, w):
+    """The eigenvalue map f of oracle/admm_net_ref.py (eigenvalue_map) in float64, numpy."""
+    thr, W0, B0, W2, B2 = gp
+    w = np.asarray(w, dtype=np.float64)
+    v = np.maximum(np.abs(w)[..., None] * W0 + B0, 0.0) @ W2 + B2
+    with np.errstate(over="ignore"):
+        return np.logaddexp(0.0, w - thr) / (1.0 + np.exp(-v))
+
+
+def _sampled_model(gp, w):
+    """The kernel's model check on spectrum w, in float64: (miss, scale, c, delta)."""
+    o, bulk = _split(w)
+    c, _, delta = _bulk_stats(w[bulk])
+    delta *= DELTA_INFLATE
+    f = _fmap(gp, c + TS * delta)
+    a1, a2 = (f[2] - f[0]) / (2 * delta), (f[2] - 2 * f[1] + f[0]) / (2 * delta * delta)
+    t = TS[3:] * delta
+    miss = float(np.abs(f[3:] - (f[1] + a1 * t + a2 * t * t)).max())
+    scale = max(abs(f[1]), float(np.abs(_fmap(gp, w[o])).max()), 1e-6)
+    return miss, scale, c, delta
+
+
+def _with_kink(sd, x, uslope, s2):
+    """value_net unit 0 of layer SURGERY_K replaced by s2 * relu(uslope * (|w| - x)): a kink of f at |w| = x."""
+    p = f"gLayers.{SURGERY_K}.value_net."
+    sd2 = dict(sd)
+    for key in ("0.weight", "0.bias", "2.weight"):
+        sd2[p + key] = sd[p + key].clone()
+    sd2[p + "0.weight"][0, 0] = uslope
+    sd2[p + "0.bias"][0] = -uslope * x
+    sd2[p + "2.weight"][0, 0] = s2
+    return sd2
+
+
+def _strength_for(sd, w, x, uslope, target):
+    """s2 whose sampled miss on spectrum w is `target` x TOL_MODEL * scale (secant steps); None if no s2 gets there (the kink
+    is where no sample sees it)."""
+    s2 = 1.0
+    for _ in range(8):
+        miss, scale, _, _ = _sampled_model(_gparams(_with_kink(sd, x, uslope, s2)), w)
+        ratio = miss / (TOL_MODEL * scale)
+        if ratio < 1e-3 * target:
+            return None
+        if abs(ratio / target - 1.0) < 0.05:
+            return s2
+        s2 = float(np.clip(s2 * target / ratio, 1e-8, 1e4))
+    return s2 if abs(ratio / target - 1.0) < 0.5 else None
+
+
+def _lipschitz(gp, lo, hi):
+    x = np.linspace(lo, hi, 4001)
+    return float(np.abs(np.diff(_fmap(gp, x))).max() / (x[1] - x[0]))
+
+
+def _conditioned(sd2, w):
+    """The guard: can an fp32 input meet the bound on this spectrum at all?"""
+    gp = _gparams(sd2)
+    o, bulk = _split(w)
+    c, r, delta = _bulk_stats(w[bulk])
+    _, scale, _, _ = _sampled_model(gp, w)
+    half = 1.05 * max(r, delta)
+    return _lipschitz(gp, c - half, c + half) * 8 * U32 * float(np.abs(w).max()) <= 2e-6 * scale
+
+
+def _steepest(sd, w, x, uslope):
+    """The largest s2 the guard allows (secant steps on the Lipschitz bound); None if f itself is too steep already."""
+    o, bulk = _split(w)
+    c, r, delta = _bulk_stats(w[bulk])
+    half = 1.05 * max(r, delta)
+    gp0 = _gparams(_with_kink(sd, x, uslope, 0.0))
+    _, scale, _, _ = _sampled_model(gp0, w)
+    lmax = 0.9 * 2e-6 * scale / (8 * U32 * float(np.abs(w).max()))
+    l0 = _lipschitz(gp0, c - half, c + half)
+    if l0 >= lmax:
+        return None
+    s2 = 1.0
+    for _ in range(8):
+        lf = _lipschitz(_gparams(_with_kink(sd, x, uslope, s2)), c - half, c + half)
+        s2 = float(np.clip(s2 * (lmax - l0) / max(lf - l0, 1e-300), 1e-8, 1e6))
+    return s2
+
+
+def _edge_case(dev, grid, b, wp, sd2, what, log, check_miss=True):
+    """Matrix b of the surgery base with spectrum wp (eigenvectors kept) under weights sd2: the universal assertion, then the
+    sampled miss (float64, on the spectrum the kernel received) against the flag."""
+    Nb, Nd = grid
+    if not _conditioned(sd2, wp):
+        log["skipped"] += 1
+        return
+    sd, phi, h, _, V = _surgery_base(Nb, Nd)
+    n = wp.size
+    tri = _tril(n)
+    ph, hh = phi[b:b + 1], h[b:b + 1]
+    Z = _z_for(sd2, ph, hh, (V[b:b + 1] * torch.from_numpy(wp[None]).unsqueeze(1)) @ V[b:b + 1].mH)
+    m = _model(sd2, Nb, Nd, K_TRACE)
+    G0, rn0 = torch.full((1, n, n), SENT_G, dtype=torch.complex64), torch.full((1,), SENT_RN)
+    _, G, rn, flag, st = _run(dev, m, SURGERY_K, ph, hh, Z, G0, rn0)
+    _check_status(flag, st)
+    sd64 = {key: v.double() for key, v in sd2.items() if key.startswith(f"gLayers.{SURGERY_K}.")}
+    G_ref, w_act, _ = R.g_layer(sd64, SURGERY_K, ph.to(torch.complex128), hh.double(), Z.to(torch.complex128), return_eig=True)
+    Cz = R.block_matrix(ph.to(torch.complex128), hh.double(), _corner(sd2, f"zLayers.{SURGERY_K}.lambda_param"))
+    err = _check_accepted(G, rn, flag, G_ref, torch.linalg.norm(G_ref - Cz, dim=(1, 2)), tri, what)   # the universal assertion
+    miss, scale, _, _ = _sampled_model(_gparams(sd2), w_act[0].numpy())
+    ratio = miss / (TOL_MODEL * scale)
+    f = int(flag[0])
+    if not check_miss:
+        pass
+    elif ratio > 2.0:
+        assert f in MISS_FLAGS, (what, "sampled miss / tol", ratio, "accepted" if f == 0 else f)
+    elif ratio < 0.5:
+        assert f != 4, (what, "sampled miss / tol", ratio, f)
+    log["run"] += 1
+    log["accepted"] += f == 0
+    log["worst"] = max(log["worst"], err)
+    log["flags"][f] += 1
+    if f == 0:
+        log["max_ratio_accepted"] = max(log["max_ratio_accepted"], ratio)
+
+
+def _new_log():
+    return dict(run=0, skipped=0, accepted=0, worst=0.0, unreached=0, max_ratio_accepted=0.0, flags=collections.Counter())
+
+
+def _print_log(what, grid, log):
+    print(f"EDGE D={grid[0] * grid[1]} {what}: {log['run']} cases, accepted {log['accepted']}, flags {dict(log['flags'])}, "
+          f"worst accepted G error {log['worst']:.2e}, largest sampled miss accepted {log['max_ratio_accepted']:.2f} x tol, "
+          f"skipped by the conditioning guard {log['skipped']}, strength not reachable {log['unreached']}")
+    # the guard must not hollow the test out
+    assert log["skipped"] <= 0.15 * (log["run"] + log["skipped"]), log
+
+
+@pytest.mark.parametrize("grid", [pytest.param(g, id=name) for g, name in SURGERY_GEOMS])
+def test_moderate_kinks_between_the_sample_points(dev, grid):
+    """A kink of f at c + t r for t on a grid of eighths (on the sample points and between them), its strength chosen per
+    matrix so that the sampled miss is 0.3 .. 100 x the tolerance."""
+    sd, _, _, w, _ = _surgery_base(*grid)
+    log = _new_log()
+    for b in EDGE_B:
+        o, bulk = _split(w[b])
+        c, r, _ = _bulk_stats(w[b][bulk])
+        for t in KINK_T:
+            x, uslope = abs(c + t * r), 1.0 / r
+            for target in KINK_MISS:
+                s2 = _strength_for(sd, w[b], x, uslope, target)
+                if s2 is None:
+                    log["unreached"] += 1
+                    continue
+                _edge_case(dev, grid, b, w[b], _with_kink(sd, x, uslope, s2), ("moderate kink", b, t, target), log)
+    _print_log("moderate kinks", grid, log)
+    assert log["unreached"] <= 0.2 * len(EDGE_B) * len(KINK_T) * len(KINK_MISS), log
+
+
+@pytest.mark.parametrize("grid", [pytest.param(g, id=name) for g, name in SURGERY_GEOMS])
+def test_kink_of_abs_at_zero_inside_the_bulk(dev, grid):
+    """The spectrum shifted so that the bulk centre is c = s delta: for |s| < 1 the kink of |w| at w = 0 lies inside the sampled
+    interval.  With the weights as they are (their own kink there gives a sampled miss of ~2 x tol), and with unit 0 of
+    value_net made linear in |w| at the strengths of the moderate kinks (those below the weights' own miss are not reachable)."""
+    sd, _, _, w, _ = _surgery_base(*grid)
+    log = _new_log()
+    for b in EDGE_B:
+        o, bulk = _split(w[b])
+        c, _, delta = _bulk_stats(w[b][bulk])
+        for s in ZERO_S:
+            wp = w[b] + (s * delta - c)
+            _edge_case(dev, grid, b, wp, sd, ("kink of |w| at 0, weights as they are", b, s), log)
+            for target in KINK_MISS:
+                s2 = _strength_for(sd, wp, 0.0, 1.0 / delta, target)
+                if s2 is None:
+                    log["unreached"] += 1
+                    continue
+                _edge_case(dev, grid, b, wp, _with_kink(sd, 0.0, 1.0 / delta, s2), ("kink of |w| at 0", b, s, target), log)
+    _print_log("kink of |w| at zero", grid, log)
+
+
+@pytest.mark.parametrize("grid", [pytest.param(g, id=name) for g, name in SURGERY_GEOMS])
+def test_dominant_bulk_eigenvalue_and_a_steep_kink_just_inside(dev, grid):
+    """The bulk compressed to 1e-3 of its width and one of its eigenvalues moved out to R = 10 .. 30 x the old half-width (still
+    under 0.05 x the gap): delta / ||E||_2 -> 1.  A kink of f at c + t ||E||_2 on that eigenvalue's side, as steep as the guard
+    allows: sampled or not, where the kink is just inside ||E||_2 the dominant eigenvalue is off the model by >= 1e-4 of the
+    scale unless the samples reach it."""
+    sd, _, _, w, _ = _surgery_base(*grid)
+    log = _new_log()
+    for b in EDGE_B:
+        o, bulk = _split(w[b])
+        c, r, _ = _bulk_stats(w[b][bulk])
+        gap = float(np.abs(w[b][o] - c).min())
+        sgn = 1.0 if c >= 0 else -1.0
+        e = bulk[np.argmax(np.abs(w[b][bulk] - c))]
+        for rf in DOM_R:
+            wp = w[b].copy()
+            wp[bulk] = c + 1e-3 * (w[b][bulk] - c)
+            wp[e] = c + sgn * min(rf * r, 0.03 * gap)
+            c2, en, d2 = _bulk_stats(wp[bulk])
+            for t in DOM_T:
+                x = abs(c2 + sgn * t * en)
+                s2 = _steepest(sd, wp, x, 1.0 / en)
+                if s2 is None:
+                    log["skipped"] += 1
+                    continue
+                # beyond ||E||_2 (t > 1) the kink touches no bulk eigenvalue: whether the samples reach it is the margin's
+                # business, not the claim's -- only the universal assertion applies there
+                _edge_case(dev, grid, b, wp, _with_kink(sd, x, 1.0 / en, s2), ("dominant", b, rf, t, d2 / en), log,
+                           check_miss=t < 1.0)
+    _print_log("dominant bulk eigenvalue", grid, log)
 
 
 # ------------------------------------------------------------------------------ reference-written per-layer fixtures
