@@ -54,6 +54,20 @@ SYMBOLS = {
                                    c_void_p, c_void_p]),
     "admmnet_vdvh_c64": (c_int32, [c_int32, c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
     "admmnet_vhsv_f32": (c_int32, [c_int32, c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "admmnet_train_partials": (c_int64, [c_int32, c_int64]),
+    "admmnet_train_matrix_f32": (c_int32, [c_int32, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_void_p]),
+    "admmnet_train_matrix_bwd_f32": (c_int32, [c_int32, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                               c_void_p, c_void_p, c_void_p]),
+    "admmnet_train_resnorm_f32": (c_int32, [c_int32, c_int64, c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_void_p]),
+    "admmnet_train_resnorm_bwd_f32": (c_int32, [c_int32, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float,
+                                                c_void_p, c_void_p, c_void_p, c_void_p]),
+    "admmnet_train_zupdate_c64": (c_int32, [c_int32, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float,
+                                            c_void_p, c_void_p]),
+    "admmnet_train_zupdate_bwd_c64": (c_int32, [c_int32, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float,
+                                                c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "admmnet_train_gather_c64": (c_int32, [c_int32, c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "admmnet_train_scatter_c64": (c_int32, [c_int32, c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "admmnet_train_herm_c64": (c_int32, [c_int32, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "admmnet_spectrum_workspace_bytes": (c_int64, [c_int32, c_int32, c_int32, c_int32]),
     "admmnet_spectrum_f64": (c_int32, [c_void_p, c_int64, c_int32, c_int32, c_void_p, c_int32, c_void_p,
                                        c_int32, c_void_p, c_void_p, c_int64, c_void_p]),

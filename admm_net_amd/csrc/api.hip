@@ -783,6 +783,76 @@ int admmnet_vhsv_f32(int32_t n, int64_t B, const void *V, const void *S, float *
     return launch_vhsv(n, B, (const float2 *)V, (const float2 *)S, q, (hipStream_t)stream);
 }
 
+// ---- training route: the n^2-sized steps of a layer (train_layer.hip) ------------------------------------------------------
+// n as admmnet_eigh_c64 takes it; the tile-pair grid B * pairs(n) must fit a 31-bit grid
+static int train_args_ok(const char *what, int32_t n, int64_t B, bool ptrs) {
+    if (n < 2 || n - 1 > kMaxD || B < 1 || B * (int64_t)train_tile_pairs(n) > 0x7fffffffLL || !ptrs) {
+        set_error("%s: bad argument (n=%d, B=%lld)", what, n, (long long)B);
+        return ADMMNET_E_ARG;
+    }
+    return ADMMNET_OK;
+}
+
+int64_t admmnet_train_partials(int32_t n, int64_t B) {
+    if (n < 2 || n - 1 > kMaxD || B < 1) return -1;
+    return B * (int64_t)train_tile_pairs(n);
+}
+
+int admmnet_train_matrix_f32(int32_t n, int64_t B, const void *phi, const float *h, const void *Z, const float *r, float corner,
+                             void *A, void *stream) {
+    if (int rc = train_args_ok("train_matrix", n, B, phi && h && Z && r && A)) return rc;
+    return launch_train_matrix(n, B, (const float2 *)phi, h, (const float2 *)Z, r, corner, (float2 *)A, (hipStream_t)stream);
+}
+
+int admmnet_train_matrix_bwd_f32(int32_t n, int64_t B, const void *gA, const void *Z, const float *r, void *gZ, void *g_phi,
+                                 float *g_h, float *g_r, float *partials, void *stream) {
+    if (int rc = train_args_ok("train_matrix_bwd", n, B, gA && Z && r && gZ && g_phi && g_h && g_r && partials)) return rc;
+    return launch_train_matrix_bwd(n, B, (const float2 *)gA, (const float2 *)Z, r, (float2 *)gZ, (float2 *)g_phi, g_h, g_r,
+                                   partials, (hipStream_t)stream);
+}
+
+int admmnet_train_resnorm_f32(int32_t n, int64_t B, const void *G, const void *phi, const float *h, float corner, float *rn,
+                              void *stream) {
+    if (int rc = train_args_ok("train_resnorm", n, B, G && phi && h && rn)) return rc;
+    return launch_train_resnorm(n, B, (const float2 *)G, (const float2 *)phi, h, corner, rn, (hipStream_t)stream);
+}
+
+int admmnet_train_resnorm_bwd_f32(int32_t n, int64_t B, const float *g_rn, const float *rn, const void *G, const void *phi,
+                                  const float *h, float corner, void *gG, void *g_phi, float *g_h, void *stream) {
+    if (int rc = train_args_ok("train_resnorm_bwd", n, B, g_rn && rn && G && phi && h && gG && g_phi && g_h)) return rc;
+    return launch_train_resnorm_bwd(n, B, g_rn, rn, (const float2 *)G, (const float2 *)phi, h, corner, (float2 *)gG,
+                                    (float2 *)g_phi, g_h, (hipStream_t)stream);
+}
+
+int admmnet_train_zupdate_c64(int32_t n, int64_t B, const void *Z, const void *G, const void *phi, const float *h,
+                              const float *s, float corner, void *Z_new, void *stream) {
+    if (int rc = train_args_ok("train_zupdate", n, B, Z && G && phi && h && s && Z_new)) return rc;
+    return launch_train_zupdate(n, B, (const float2 *)Z, (const float2 *)G, (const float2 *)phi, h, s, corner, (float2 *)Z_new,
+                                (hipStream_t)stream);
+}
+
+int admmnet_train_zupdate_bwd_c64(int32_t n, int64_t B, const void *g, const void *G, const void *phi, const float *h,
+                                  const float *s, float corner, void *gG, void *g_phi, float *g_h, float *g_s, void *stream) {
+    if (int rc = train_args_ok("train_zupdate_bwd", n, B, g && G && phi && h && s && gG && g_phi && g_h && g_s)) return rc;
+    return launch_train_zupdate_bwd(n, B, (const float2 *)g, (const float2 *)G, (const float2 *)phi, h, s, corner, (float2 *)gG,
+                                    (float2 *)g_phi, g_h, g_s, (hipStream_t)stream);
+}
+
+int admmnet_train_gather_c64(int32_t n, int64_t B, const void *X, void *col, float *diag, void *stream) {
+    if (int rc = train_args_ok("train_gather", n, B, X && col && diag)) return rc;
+    return launch_train_gather(n, B, (const float2 *)X, (float2 *)col, diag, (hipStream_t)stream);
+}
+
+int admmnet_train_scatter_c64(int32_t n, int64_t B, const void *g_col, const float *g_diag, void *gX, void *stream) {
+    if (int rc = train_args_ok("train_scatter", n, B, g_col && g_diag && gX)) return rc;
+    return launch_train_scatter(n, B, (const float2 *)g_col, g_diag, (float2 *)gX, (hipStream_t)stream);
+}
+
+int admmnet_train_herm_c64(int32_t n, int64_t B, const void *g, const void *g_col, const float *g_diag, void *S, void *stream) {
+    if (int rc = train_args_ok("train_herm", n, B, g && S && (!g_col == !g_diag))) return rc;
+    return launch_train_herm(n, B, (const float2 *)g, (const float2 *)g_col, g_diag, (float2 *)S, (hipStream_t)stream);
+}
+
 int admmnet_profile_enable(int32_t on) {
     ProfState &p = prof();
     std::lock_guard<std::mutex> lk(p.mu);

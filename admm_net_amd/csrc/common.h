@@ -218,6 +218,23 @@ int launch_spectral(int D, int64_t nb, const float *lw, const float2 *phi, const
 // vdvh.hip (training route)
 int launch_vdvh(int n, int64_t nb, const float2 *V, const float *d, float2 *out, hipStream_t st);
 int launch_vhsv(int n, int64_t nb, const float2 *V, const float2 *S, float *q, hipStream_t st);
+// train_layer.hip (training route, the n^2-sized layer steps; r, s: device values)
+int train_tile_pairs(int n);
+int launch_train_matrix(int n, int64_t B, const float2 *phi, const float *h, const float2 *Z, const float *r, float corner,
+                        float2 *A, hipStream_t st);
+int launch_train_matrix_bwd(int n, int64_t B, const float2 *gA, const float2 *Z, const float *r, float2 *gZ, float2 *gphi,
+                            float *gh, float *gr, float *part, hipStream_t st);
+int launch_train_resnorm(int n, int64_t B, const float2 *G, const float2 *phi, const float *h, float corner, float *rn,
+                         hipStream_t st);
+int launch_train_resnorm_bwd(int n, int64_t B, const float *grn, const float *rn, const float2 *G, const float2 *phi,
+                             const float *h, float corner, float2 *gG, float2 *gphi, float *gh, hipStream_t st);
+int launch_train_zupdate(int n, int64_t B, const float2 *Z, const float2 *G, const float2 *phi, const float *h, const float *s,
+                         float corner, float2 *Zn, hipStream_t st);
+int launch_train_gather(int n, int64_t B, const float2 *X, float2 *col, float *dg, hipStream_t st);
+int launch_train_scatter(int n, int64_t B, const float2 *gcol, const float *gdg, float2 *gX, hipStream_t st);
+int launch_train_herm(int n, int64_t B, const float2 *g, const float2 *gcol, const float *gdg, float2 *S, hipStream_t st);
+int launch_train_zupdate_bwd(int n, int64_t B, const float2 *g, const float2 *G, const float2 *phi, const float *h,
+                             const float *s, float corner, float2 *gG, float2 *gphi, float *gh, float *gs, hipStream_t st);
 
 // synth.hip
 int launch_synth(int64_t B, int Nb, int Nd, int L, unsigned long long seed, double snr_lo, double snr_hi, double snr_e,

@@ -10,7 +10,7 @@
 
 CLI:  python -m admm_net_amd.harness time-net  --layers 5 --runs 1000 --out time_net_5.txt [--checkpoint best_model.pth]
       python -m admm_net_amd.harness time-admm --runs 1000 --out time.txt
-      python -m admm_net_amd.harness train-step --layers 10 --batch 256 --steps 20     (one JSON line)
+      python -m admm_net_amd.harness train-step --layers 10 --batch 256 --steps 20 [--route fused] [--grid 16x16]   (one JSON line)
 """
 from __future__ import annotations
 
@@ -139,20 +139,23 @@ def load_checkpoint(path, model, optimizer=None, scheduler=None, map_location="c
     return ckpt
 
 
-def time_train_step(layers=10, batch=256, steps=20, warmup=3, seed=0, device="cuda:0"):
+def time_train_step(layers=10, batch=256, steps=20, warmup=3, seed=0, device="cuda:0", route="tensor", grid=(NB, ND)):
     """Wall time of one optimisation step at the reference's own training configuration (trainPhi.py:16-38: 10 x 10 grid,
     num_layers = 10, batch_size = 256, AdamW lr 1e-3 / weight decay 1e-3, gradient clipping at 1.0, :179-190): forward in
     train mode (the differentiable route of admm_net_amd.training: HIP eigensolver + HIP contractions), a phi-alignment
     loss against the classical solver's phi labels (generated on the device, csrc/synth.hip), backward, clip, step.
     The loss is a plain normalised squared error: the reference's loss.py is user code outside this path.
-    Returns a dict (seconds per step, signals per second)."""
+    ``route``: ``model.train_route`` ("tensor" | "fused"); ``grid`` = (M, N) of another geometry, same recipe.
+    Returns a dict (seconds per step, signals per second, route, geometry)."""
     from . import PhiEstADMMNet, synth
     dev = torch.device(device)
     torch.manual_seed(seed)
-    model = PhiEstADMMNet(num_layers=layers, M=NB, N=ND, L=3).to(dev)
+    M, N = grid
+    model = PhiEstADMMNet(num_layers=layers, M=M, N=N, L=3).to(dev)
+    model.train_route = route
     model.train()
     opt = torch.optim.AdamW(model.parameters(), lr=1e-3, weight_decay=1e-3)
-    y, b, sigma, extra = synth.make_batch_device(batch, NB, ND, seed=20260104 + seed, device=dev, labels=True)
+    y, b, sigma, extra = synth.make_batch_device(batch, M, N, seed=20260104 + seed, device=dev, labels=True)
     label = extra["phi"].to(torch.complex64)
     scale = label.abs().pow(2).mean()
 
@@ -175,7 +178,8 @@ def time_train_step(layers=10, batch=256, steps=20, warmup=3, seed=0, device="cu
     torch.cuda.synchronize(dev)
     dt = (time.perf_counter() - t0) / steps
     losses.append(float(last.item()))
-    return {"config": f"PhiEstADMMNet 10x10 K={layers}, batch {batch}, AdamW + clip 1.0 (trainPhi.py:16-38, 179-190)",
+    return {"config": f"PhiEstADMMNet {M}x{N} K={layers}, batch {batch}, AdamW + clip 1.0 (trainPhi.py:16-38, 179-190)",
+            "route": route, "grid": [M, N], "layers": layers, "batch": batch,
             "seconds_per_step": round(dt, 6), "signals_per_second": round(batch / dt, 1), "steps": steps,
             "loss_first": round(losses[0], 6), "loss_last": round(losses[-1], 6)}
 
@@ -197,10 +201,17 @@ def main(argv=None):
     c.add_argument("--layers", type=int, default=10)
     c.add_argument("--batch", type=int, default=256)
     c.add_argument("--steps", type=int, default=20)
+    c.add_argument("--route", choices=("tensor", "fused"), default="tensor")
+    c.add_argument("--grid", default=f"{NB}x{ND}", help="MxN")
     args = ap.parse_args(argv)
     if args.cmd == "train-step":
         import json
-        print(json.dumps(time_train_step(args.layers, args.batch, args.steps)))
+        try:
+            grid = tuple(int(v) for v in args.grid.lower().split("x"))
+            assert len(grid) == 2 and min(grid) >= 1
+        except (ValueError, AssertionError):
+            ap.error(f"--grid must be MxN, got {args.grid!r}")
+        print(json.dumps(time_train_step(args.layers, args.batch, args.steps, route=args.route, grid=grid)))
         return
     if args.cmd == "time-net":
         from . import PhiEstADMMNet

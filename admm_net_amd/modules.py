@@ -11,7 +11,8 @@ weights); all arithmetic happens in the fused HIP path behind the C ABI of
 
 Inference (``.eval()`` or ``torch.no_grad()``) runs the fused forward.  In train mode with gradients
 enabled the call goes through ``training.unrolled_forward`` instead: differentiable tensor operations
-around the HIP eigensolver, with the reference's eigenvalue-only gradient.
+around the HIP eigensolver, with the reference's eigenvalue-only gradient (SURVEY.md section 8f rank 2);
+``model.train_route = "fused"`` moves the n^2-sized layer steps of that route onto HIP kernels too.
 """
 from __future__ import annotations
 
@@ -137,6 +138,7 @@ class _FusedBase(nn.Module):
         # execution knobs (not part of the reference API)
         self._chunk = 0                # signals per eigensolver chunk (0 = library default); see the `chunk` property
         self._sub_batch = None         # signals per independent sub-batch (None = the call is one batch); see `sub_batch`
+        self._train_route = "tensor"   # how the differentiable forward evaluates the n^2-sized layer steps; see `train_route`
         self.check_status = True       # one D2H read per forward: raise if the eigensolver failed
         self._wcache = None
         self._ws = None
@@ -175,6 +177,20 @@ class _FusedBase(nn.Module):
         if value != self._sub_batch:
             self._sub_batch = value
             self._ws = None
+
+    @property
+    def train_route(self) -> str:
+        """How the differentiable forward (train mode, ``forward_autograd``) evaluates the n^2-sized steps of a layer:
+        ``"tensor"`` (default) as framework tensor operations, ``"fused"`` through the streaming HIP kernels of
+        csrc/train_layer.hip with hand-written backwards (``training.LayerKernels``).  Both use the HIP eigensolver and
+        contractions; inference is not affected.  Not part of the state_dict."""
+        return self._train_route
+
+    @train_route.setter
+    def train_route(self, value: str):
+        if value not in ("tensor", "fused"):
+            raise ValueError(f"train_route must be 'tensor' or 'fused', got {value!r}")
+        self._train_route = value
 
     # ---- weights -----------------------------------------------------------
     def cfg(self) -> Cfg:
@@ -298,7 +314,8 @@ class _FusedBase(nn.Module):
         if pdev != dev:
             raise _lib.AdmmNetError(f"training runs on the GPU: parameters are on {pdev}, expected {dev} "
                                     "(move the model with .to(device) as train.py / trainPhi.py do)")
-        out = training.unrolled_forward(self, y.to(dev), b.to(dev), sigma.to(dev), sub_batch=self.sub_batch)
+        out = training.unrolled_forward(self, y.to(dev), b.to(dev), sigma.to(dev), sub_batch=self.sub_batch,
+                                        fused=self.train_route == "fused")
         if isinstance(out, tuple):
             return tuple(o.to(y.device) for o in out)
         return out.to(y.device)

@@ -86,6 +86,157 @@ def vhsv(V: torch.Tensor, S: torch.Tensor) -> torch.Tensor:
     return q
 
 
+# ---- training route: the n^2-sized steps of one layer (csrc/train_layer.hip) --------------------------------------------------
+# C(phi, h, c) = [[diag h, phi], [phi^H, c]], herm(X) = (X + X^H) / 2.  Matrices [B, n, n] complex64, phi [B, D] complex64,
+# h [B, D] float32 (D = n - 1); r (0-dim) and s [B] are float32 DEVICE tensors, corner a Python float.
+def _c64(t, dev, shape, name):
+    t = t.detach().to(device=dev, dtype=torch.complex64).resolve_conj().contiguous()
+    if tuple(t.shape) != tuple(shape):
+        raise ValueError(f"{name} must be {tuple(shape)}, got {tuple(t.shape)}")
+    return t
+
+
+def _f32(t, dev, shape, name):
+    t = t.detach().to(device=dev, dtype=torch.float32).contiguous()
+    if tuple(t.shape) != tuple(shape):
+        raise ValueError(f"{name} must be {tuple(shape)}, got {tuple(t.shape)}")
+    return t
+
+
+def _train_args(M, name):
+    """(lib, device, B, n) of a [B, n, n] matrix batch."""
+    _need_cuda(M, name)
+    if M.dim() != 3 or M.shape[1] != M.shape[2]:
+        raise ValueError(f"{name} must be [B, n, n], got {tuple(M.shape)}")
+    return _lib.load(), M.device, M.shape[0], M.shape[1]
+
+
+def train_matrix(phi, h, Z, r, corner: float) -> torch.Tensor:
+    """A = herm(C(phi, h, corner) - r Z), exactly Hermitian: GLayer's block matrix, ``- Z / rho`` and symmetrisation
+    (admm_net.py:262-300)."""
+    lib, dev, B, n = _train_args(Z, "Z")
+    with torch.cuda.device(dev):
+        Z, phi, h, r = _c64(Z, dev, (B, n, n), "Z"), _c64(phi, dev, (B, n - 1), "phi"), _f32(h, dev, (B, n - 1), "h"), _f32(r, dev, (), "r")
+        A = torch.empty_like(Z)
+        _lib.check(lib.admmnet_train_matrix_f32(n, B, _ptr(phi), _ptr(h), _ptr(Z), _ptr(r), float(corner), _ptr(A), _stream(dev)),
+                   "admmnet_train_matrix_f32")
+    return A
+
+
+def train_matrix_bwd(gA, Z, r):
+    """Backward of ``train_matrix`` with S = herm(gA): returns (g_phi = 2 S[:, :D, D], g_h = Re diag S, gZ = -r S,
+    g_r = -sum_b <S_b, Z_b> as a 0-dim tensor)."""
+    lib, dev, B, n = _train_args(gA, "gA")
+    with torch.cuda.device(dev):
+        gA, Z, r = _c64(gA, dev, (B, n, n), "gA"), _c64(Z, dev, (B, n, n), "Z"), _f32(r, dev, (), "r")
+        gZ = torch.empty_like(gA)
+        g_phi = torch.empty(B, n - 1, dtype=torch.complex64, device=dev)
+        g_h = torch.empty(B, n - 1, dtype=torch.float32, device=dev)
+        g_r = torch.empty((), dtype=torch.float32, device=dev)
+        part = torch.empty(lib.admmnet_train_partials(n, B), dtype=torch.float32, device=dev)
+        _lib.check(lib.admmnet_train_matrix_bwd_f32(n, B, _ptr(gA), _ptr(Z), _ptr(r), _ptr(gZ), _ptr(g_phi), _ptr(g_h), _ptr(g_r),
+                                                    _ptr(part), _stream(dev)), "admmnet_train_matrix_bwd_f32")
+    return g_phi, g_h, gZ, g_r
+
+
+def train_resnorm(G, phi, h, corner: float) -> torch.Tensor:
+    """rn[b] = ||G_b - C(phi, h, corner)||_F without storing the residual (admm_net.py:428-459).  Returns [B] float32."""
+    lib, dev, B, n = _train_args(G, "G")
+    with torch.cuda.device(dev):
+        G, phi, h = _c64(G, dev, (B, n, n), "G"), _c64(phi, dev, (B, n - 1), "phi"), _f32(h, dev, (B, n - 1), "h")
+        rn = torch.empty(B, dtype=torch.float32, device=dev)
+        _lib.check(lib.admmnet_train_resnorm_f32(n, B, _ptr(G), _ptr(phi), _ptr(h), float(corner), _ptr(rn), _stream(dev)),
+                   "admmnet_train_resnorm_f32")
+    return rn
+
+
+def train_resnorm_bwd(g_rn, rn, G, phi, h, corner: float):
+    """Backward of ``train_resnorm`` with q = g_rn / rn, R = G - C: returns (gG = q R, g_phi = -q (R[:, :D, D] +
+    conj R[:, D, :D]), g_h = -q Re diag R)."""
+    lib, dev, B, n = _train_args(G, "G")
+    with torch.cuda.device(dev):
+        G, phi, h = _c64(G, dev, (B, n, n), "G"), _c64(phi, dev, (B, n - 1), "phi"), _f32(h, dev, (B, n - 1), "h")
+        g_rn, rn = _f32(g_rn, dev, (B,), "g_rn"), _f32(rn, dev, (B,), "rn")
+        gG = torch.empty_like(G)
+        g_phi = torch.empty(B, n - 1, dtype=torch.complex64, device=dev)
+        g_h = torch.empty(B, n - 1, dtype=torch.float32, device=dev)
+        _lib.check(lib.admmnet_train_resnorm_bwd_f32(n, B, _ptr(g_rn), _ptr(rn), _ptr(G), _ptr(phi), _ptr(h), float(corner),
+                                                     _ptr(gG), _ptr(g_phi), _ptr(g_h), _stream(dev)),
+                   "admmnet_train_resnorm_bwd_f32")
+    return gG, g_phi, g_h
+
+
+def train_zupdate(Z, G, phi, h, s, corner: float) -> torch.Tensor:
+    """Z + s_b (G - C(phi, h, corner)): the dual update (admm_net.py:460-474)."""
+    lib, dev, B, n = _train_args(Z, "Z")
+    with torch.cuda.device(dev):
+        Z, G = _c64(Z, dev, (B, n, n), "Z"), _c64(G, dev, (B, n, n), "G")
+        phi, h, s = _c64(phi, dev, (B, n - 1), "phi"), _f32(h, dev, (B, n - 1), "h"), _f32(s, dev, (B,), "s")
+        Zn = torch.empty_like(Z)
+        _lib.check(lib.admmnet_train_zupdate_c64(n, B, _ptr(Z), _ptr(G), _ptr(phi), _ptr(h), _ptr(s), float(corner), _ptr(Zn),
+                                                 _stream(dev)), "admmnet_train_zupdate_c64")
+    return Zn
+
+
+def train_zupdate_bwd(g, G, phi, h, s, corner: float):
+    """Backward of ``train_zupdate`` from g (the gradient of Z is g itself): returns (gG = s g, g_phi = -s (g[:, :D, D] +
+    conj g[:, D, :D]), g_h = -s Re diag g, g_s[b] = <R_b, g_b>)."""
+    lib, dev, B, n = _train_args(g, "g")
+    with torch.cuda.device(dev):
+        g, G = _c64(g, dev, (B, n, n), "g"), _c64(G, dev, (B, n, n), "G")
+        phi, h, s = _c64(phi, dev, (B, n - 1), "phi"), _f32(h, dev, (B, n - 1), "h"), _f32(s, dev, (B,), "s")
+        gG = torch.empty_like(G)
+        g_phi = torch.empty(B, n - 1, dtype=torch.complex64, device=dev)
+        g_h = torch.empty(B, n - 1, dtype=torch.float32, device=dev)
+        g_s = torch.empty(B, dtype=torch.float32, device=dev)
+        _lib.check(lib.admmnet_train_zupdate_bwd_c64(n, B, _ptr(g), _ptr(G), _ptr(phi), _ptr(h), _ptr(s), float(corner), _ptr(gG),
+                                                     _ptr(g_phi), _ptr(g_h), _ptr(g_s), _stream(dev)),
+                   "admmnet_train_zupdate_bwd_c64")
+    return gG, g_phi, g_h, g_s
+
+
+def train_gather(X):
+    """(X[:, :D, D], Re diag X[:, :D]): all that the phi layer (admm_net.py:98-99) and the H layer (:150-152) read of G and
+    Z.  Returns ([B, D] complex64, [B, D] float32)."""
+    lib, dev, B, n = _train_args(X, "X")
+    with torch.cuda.device(dev):
+        X = _c64(X, dev, (B, n, n), "X")
+        col = torch.empty(B, n - 1, dtype=torch.complex64, device=dev)
+        dg = torch.empty(B, n - 1, dtype=torch.float32, device=dev)
+        _lib.check(lib.admmnet_train_gather_c64(n, B, _ptr(X), _ptr(col), _ptr(dg), _stream(dev)), "admmnet_train_gather_c64")
+    return col, dg
+
+
+def train_scatter(g_col, g_dg) -> torch.Tensor:
+    """Backward of ``train_gather``: the [B, n, n] matrix with g_col in the border column, g_dg on the diagonal (rows < D)
+    and zeros elsewhere."""
+    _need_cuda(g_col, "g_col")
+    lib, dev = _lib.load(), g_col.device
+    B, D = g_col.shape
+    with torch.cuda.device(dev):
+        g_col, g_dg = _c64(g_col, dev, (B, D), "g_col"), _f32(g_dg, dev, (B, D), "g_dg")
+        gX = torch.empty(B, D + 1, D + 1, dtype=torch.complex64, device=dev)
+        _lib.check(lib.admmnet_train_scatter_c64(D + 1, B, _ptr(g_col), _ptr(g_dg), _ptr(gX), _stream(dev)),
+                   "admmnet_train_scatter_c64")
+    return gX
+
+
+def train_herm(g, g_col=None, g_dg=None) -> torch.Tensor:
+    """herm(g + E) with E = ``train_scatter(g_col, g_dg)`` (E = 0 when both are None), exactly Hermitian: the symmetrisation
+    in the backward of the rebuild (admm_net.py:354) with the gather's gradient folded in."""
+    lib, dev, B, n = _train_args(g, "g")
+    if (g_col is None) != (g_dg is None):
+        raise ValueError("g_col and g_dg go together")
+    with torch.cuda.device(dev):
+        g = _c64(g, dev, (B, n, n), "g")
+        if g_col is not None:
+            g_col, g_dg = _c64(g_col, dev, (B, n - 1), "g_col"), _f32(g_dg, dev, (B, n - 1), "g_dg")
+        S = torch.empty_like(g)
+        _lib.check(lib.admmnet_train_herm_c64(n, B, _ptr(g), _ptr(g_col), _ptr(g_dg), _ptr(S), _stream(dev)),
+                   "admmnet_train_herm_c64")
+    return S
+
+
 def glayer(model, k: int, phi: torch.Tensor, h: torch.Tensor, Z=None):
     """GLayer.forward (admm_net.py:237-354) of layer k of ``model`` plus the Z-layer residual norm.
 

@@ -207,6 +207,49 @@ int admmnet_eigh_c64(int32_t n, int64_t B, const void *A, float *w, void *V,
 int admmnet_vdvh_c64(int32_t n, int64_t B, const void *V, const float *d, void *out, void *stream);
 int admmnet_vhsv_f32(int32_t n, int64_t B, const void *V, const void *S, float *q, void *stream);
 
+/* Training route, the n^2-sized steps of one layer and their backwards as streaming kernels (csrc/train_layer.hip).
+ * C(phi, h, c) = [[diag h, phi], [phi^H, c]] is never stored; herm(X) = (X + X^H) / 2; <X, Y> = Re sum conj(X_ij) Y_ij per
+ * signal; D = n - 1 is the border index; n as for admmnet_eigh_c64 (2 ... 257), any B >= 1 with B * ceil(n/32)(ceil(n/32)+1)/2
+ * below 2^31.  Matrices are device complex64 [B][n][n] with 16-byte aligned bases (otherwise the stream kernels move 8 bytes
+ * per lane instead of 16), phi / g_phi complex64 [B][D], h / g_h float [B][D]; r (one float) and s [B] are DEVICE values;
+ * corner is the host number the reference takes with .item().  Gradients follow torch's convention for complex tensors.
+ * Every sum runs in a fixed order without atomics: two runs on the same inputs give the same bits.
+ *   admmnet_train_matrix_f32      A = herm(C(phi, h, corner) - r Z), exactly Hermitian -- GLayer's block matrix, "- Z / rho"
+ *                                 and symmetrisation, admm_net.py:262-300.
+ *   admmnet_train_matrix_bwd_f32  from gA, with S = herm(gA): gZ = -r S, g_phi[i] = 2 S[i, D], g_h[i] = Re S[i, i],
+ *                                 g_r[0] = -sum_b <S_b, Z_b> (float64 over the batch).  partials: float scratch of
+ *                                 admmnet_train_partials(n, B) entries.
+ *   admmnet_train_resnorm_f32     rn[b] = ||G_b - C(phi, h, corner)||_F -- ZLayer's block matrix, residual and norm,
+ *                                 admm_net.py:428-459.
+ *   admmnet_train_resnorm_bwd_f32 from g_rn [B], with q = g_rn / rn and R = G - C: gG = q R,
+ *                                 g_phi[i] = -q (R[i, D] + conj R[D, i]), g_h[i] = -q Re R[i, i].
+ *   admmnet_train_zupdate_c64     Z_new = Z + s_b (G - C(phi, h, corner)) -- the dual update, admm_net.py:460-474.
+ *   admmnet_train_zupdate_bwd_c64 from g (which is also the gradient of Z, unchanged): gG = s g, g_s[b] = <R_b, g_b>,
+ *                                 g_phi[i] = -s (g[i, D] + conj g[D, i]), g_h[i] = -s Re g[i, i].
+ * The border column and the diagonal are all that PhiLayer (admm_net.py:98-99) and HLayer (:150-152) read of G and Z:
+ *   admmnet_train_gather_c64      col[b][i] = X[b][i][D], diag[b][i] = Re X[b][i][i], i < D.
+ *   admmnet_train_scatter_c64     its backward: gX = E(g_col, g_diag), the matrix with g_col in the border column, g_diag on
+ *                                 the diagonal (rows < D) and zeros elsewhere, written in one pass.
+ *   admmnet_train_herm_c64        S = herm(g + E(g_col, g_diag)), exactly Hermitian: the symmetrisation in the backward of the
+ *                                 rebuild (admm_net.py:354) with the gather's gradient folded in; g_col and g_diag may both
+ *                                 be null (S = herm(g)). */
+int64_t admmnet_train_partials(int32_t n, int64_t B);
+int admmnet_train_matrix_f32(int32_t n, int64_t B, const void *phi, const float *h, const void *Z, const float *r, float corner,
+                             void *A, void *stream);
+int admmnet_train_matrix_bwd_f32(int32_t n, int64_t B, const void *gA, const void *Z, const float *r, void *gZ, void *g_phi,
+                                 float *g_h, float *g_r, float *partials, void *stream);
+int admmnet_train_resnorm_f32(int32_t n, int64_t B, const void *G, const void *phi, const float *h, float corner, float *rn,
+                              void *stream);
+int admmnet_train_resnorm_bwd_f32(int32_t n, int64_t B, const float *g_rn, const float *rn, const void *G, const void *phi,
+                                  const float *h, float corner, void *gG, void *g_phi, float *g_h, void *stream);
+int admmnet_train_zupdate_c64(int32_t n, int64_t B, const void *Z, const void *G, const void *phi, const float *h,
+                              const float *s, float corner, void *Z_new, void *stream);
+int admmnet_train_zupdate_bwd_c64(int32_t n, int64_t B, const void *g, const void *G, const void *phi, const float *h,
+                                  const float *s, float corner, void *gG, void *g_phi, float *g_h, float *g_s, void *stream);
+int admmnet_train_gather_c64(int32_t n, int64_t B, const void *X, void *col, float *diag, void *stream);
+int admmnet_train_scatter_c64(int32_t n, int64_t B, const void *g_col, const float *g_diag, void *gX, void *stream);
+int admmnet_train_herm_c64(int32_t n, int64_t B, const void *g, const void *g_col, const float *g_diag, void *S, void *stream);
+
 /* Spectrum |phi^H kron(s(f), conj d(tau))|^2 on a (tau, f) grid:
  * peak_search_func / peak_search, utils/peakSearchUtils.py:9-60, evaluated in
  * float64 like the reference.
