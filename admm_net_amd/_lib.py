@@ -75,6 +75,10 @@ SYMBOLS = {
     "admmnet_peak_search_f64": (c_int32, [c_void_p, c_int64, c_int32, c_int32, c_void_p, c_int32, c_void_p, c_int32,
                                           c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_int64,
                                           c_void_p]),
+    "admmnet_peak_top_workspace_bytes": (c_int64, [c_int32, c_int32, c_int32, c_int32]),
+    "admmnet_peak_top_f64": (c_int32, [c_void_p, c_int64, c_int32, c_int32, c_void_p, c_int32, c_void_p, c_int32,
+                                       c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_int64,
+                                       c_void_p]),
     "admmnet_regional_maxima_f64": (c_int32, [c_void_p, c_int64, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p]),
     "admmnet_synth_batch": (c_int32, [c_int64, c_int32, c_int32, c_int32, ctypes.c_uint64, c_double, c_double, c_double,
                                       c_double, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,

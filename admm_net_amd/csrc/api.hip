@@ -941,6 +941,39 @@ int admmnet_peak_search_f64(const void *phi, int64_t B, int32_t xbase, int32_t y
                         peaks, counts, st);
 }
 
+int64_t admmnet_peak_top_workspace_bytes(int32_t xbase, int32_t ybase, int32_t nx, int32_t ny) {
+    return admmnet_spectrum_workspace_bytes(xbase, ybase, nx, ny);   // the two steering tables
+}
+
+int admmnet_peak_top_f64(const void *phi, int64_t B, int32_t xbase, int32_t ybase, const double *axis_x, int32_t nx,
+                         const double *axis_y, int32_t ny, const double *opts7, int32_t iters, int32_t L,
+                         const int32_t *top_n, double *top, int32_t *counts, void *workspace, int64_t workspace_bytes,
+                         void *stream) {
+    const int64_t need = admmnet_peak_top_workspace_bytes(xbase, ybase, nx, ny);
+    if (need < 0 || B < 0 || !phi || !axis_x || !axis_y || !opts7 || !top || !counts || !workspace || nx < 1 || ny < 1 ||
+        iters < 0 || L < 1 || L > 64) {
+        set_error("peak top: bad argument");
+        return ADMMNET_E_ARG;
+    }
+    if (workspace_bytes < need) {
+        set_error("peak top: workspace too small");
+        return ADMMNET_E_WORKSPACE;
+    }
+    // image + phi in double must fit one workgroup's LDS (checked here in 64 bits, exactly in launch_estimate)
+    if ((int64_t)nx * ny + 2 * (int64_t)xbase * ybase > 160 * 1024 / 8) {
+        set_error("peak top: grid %d x %d (phi %d x %d) does not fit the LDS", nx, ny, xbase, ybase);
+        return ADMMNET_E_ARG;
+    }
+    if (B == 0) return ADMMNET_OK;
+    hipStream_t st = (hipStream_t)stream;
+    double2 *tabD = (double2 *)workspace;
+    double2 *tabS = (double2 *)((char *)workspace + align_up(sizeof(double2) * (int64_t)nx * xbase, 256));
+    int rc;
+    if ((rc = launch_spectrum_tables(axis_x, nx, xbase, axis_y, ny, ybase, tabD, tabS, st))) return rc;
+    return launch_estimate((const float2 *)phi, B, xbase, ybase, tabD, nx, tabS, ny, axis_x, axis_y, opts7, iters, L,
+                           top_n, top, counts, st);
+}
+
 int admmnet_regional_maxima_f64(const double *Z, int64_t B, int32_t nx, int32_t ny, int32_t max_peaks,
                                 double *peaks, int32_t *counts, void *stream) {
     if (!Z || B < 1 || nx < 1 || ny < 1 || max_peaks < 1 || !peaks || !counts) {

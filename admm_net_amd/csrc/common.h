@@ -162,6 +162,9 @@ int launch_vgemm_big(int D, int64_t nb, const Ws &ws, hipStream_t st);          
 int launch_peaks(const float2 *phi, int64_t B, int xbase, int ybase, const double *Z, int nx, int ny,
                  const double *axis_x, const double *axis_y, const double *opt7, int iters, int max_peaks,
                  double *peaks, int32_t *counts, hipStream_t st);                          // peaks.hip
+int launch_estimate(const float2 *phi, int64_t B, int xbase, int ybase, const double2 *tabD, int nx,
+                    const double2 *tabS, int ny, const double *axis_x, const double *axis_y, const double *opt7,
+                    int iters, int L, const int32_t *top_n, double *top, int32_t *counts, hipStream_t st);   // estimate.hip
 bool arrow_rebuild_supported(int D);                                                       // arrow.hip
 int launch_arrow_rebuild(int D, int64_t nb, const float *lw, const float2 *phi, const float *h, float2 *G, float *rn,
                          float *w_out, int32_t *status, const Ws &ws, hipStream_t st, bool lower_only = false);   // arrow.hip

@@ -9,6 +9,7 @@
 // grid values.  Cost is O(D nx + ny ybase nx) per signal -- negligible next to
 // the eigensolver; VALU fp64 code, tables L2 resident.
 #include "common.h"
+#include "peak_core.h"
 
 namespace admmnet {
 
@@ -26,9 +27,7 @@ __global__ void steer_table_kernel(const double *__restrict__ freqs, int nf, int
     tab[idx] = make_double2(c, s);
 }
 
-constexpr int SP_THREADS = 256;
-constexpr int SP_XCHUNK = 64;
-
+// one workgroup per signal; the body is sp_image (peak_core.h), shared with estimate.hip
 __global__ __launch_bounds__(SP_THREADS) void spectrum_kernel(const float2 *__restrict__ phi, int xbase,
                                                               int ybase, const double2 *__restrict__ tabD,
                                                               int nx, const double2 *__restrict__ tabS,
@@ -43,34 +42,7 @@ __global__ __launch_bounds__(SP_THREADS) void spectrum_kernel(const float2 *__re
         ph[i] = make_double2((double)p.x, (double)p.y);
     }
     __syncthreads();
-    for (int x0 = 0; x0 < nx; x0 += SP_XCHUNK) {
-        const int xw = min(SP_XCHUNK, nx - x0);
-        for (int p = threadIdx.x; p < ybase * xw; p += SP_THREADS) {
-            const int ks = p / xw, xl = p - ks * xw;
-            const double2 *d = tabD + (int64_t)(x0 + xl) * xbase;
-            double ur = 0.0, ui = 0.0;
-            for (int kd = 0; kd < xbase; ++kd) {
-                // conj(phi) * conj(d) = conj(phi * d)
-                const double2 a = ph[ks * xbase + kd], e = d[kd];
-                ur += a.x * e.x - a.y * e.y;
-                ui -= a.x * e.y + a.y * e.x;
-            }
-            U[ks * SP_XCHUNK + xl] = make_double2(ur, ui);
-        }
-        __syncthreads();
-        for (int p = threadIdx.x; p < ny * xw; p += SP_THREADS) {
-            const int iy = p / xw, xl = p - iy * xw;
-            const double2 *s = tabS + (int64_t)iy * ybase;
-            double zr = 0.0, zi = 0.0;
-            for (int ks = 0; ks < ybase; ++ks) {
-                const double2 a = s[ks], u = U[ks * SP_XCHUNK + xl];
-                zr += a.x * u.x - a.y * u.y;
-                zi += a.x * u.y + a.y * u.x;
-            }
-            out[(b * ny + iy) * (int64_t)nx + x0 + xl] = zr * zr + zi * zi;
-        }
-        __syncthreads();
-    }
+    sp_image(ph, xbase, ybase, tabD, nx, tabS, ny, U, out + b * ny * (int64_t)nx);
 }
 
 int launch_spectrum_tables(const double *taus, int nx, int xbase, const double *fs, int ny, int ybase,

@@ -266,7 +266,7 @@ class _FusedBase(nn.Module):
             raise _lib.AdmmNetError("no HIP device: the ADMM-Net forward runs only on the GPU (no CPU fallback)")
         return torch.device("cuda", torch.cuda.current_device())
 
-    def _run(self, y, b, sigma):
+    def _run(self, y, b, sigma, to_caller=True):
         lib = _lib.load()
         dev = self._compute_device(y)
         D = self.M * self.N
@@ -296,12 +296,39 @@ class _FusedBase(nn.Module):
                 bad = int(self.last_status[0])
                 if bad:
                     raise _lib.AdmmNetError(f"eigensolver failed to converge on {bad} matrices")
+        if not to_caller:
+            return phi, head   # still on the compute device
         out_dev = y.device
         phi = phi.to(out_dev)
         if head is not None:
             head = head.to(out_dev)
         return phi, head
 
+    # ---- estimation ----------------------------------------------------------
+    def estimate(self, y, b, sigma, top=None, top_n=None, opts=None, xbase=None, ybase=None):
+        """The inference flow of main_for_net.py:99-126 / test/test_model_peaksearch.py:79-96 in one call: the forward,
+        alt_peak_search on its phi, the rows sorted by refined height and cut -- all on the device (``ops.peak_top``);
+        only the results below go back to ``y.device``.
+
+        Runs the inference forward under ``torch.no_grad()`` whatever the training flag (``chunk``, ``sub_batch`` and
+        ``check_status`` act as in ``forward``).  Defaults are main_for_net.py:107-116 read literally: ``top = self.L``,
+        ``xbase = self.M``, ``ybase = self.N``, ``opts = {'xstep': 1 / (10 * N), 'ystep': 1 / (10 * M), 'iter': 3}``.
+        ``top_n``: optional [B] integers, rows wanted per signal (the sample's L_true).
+
+        Returns (tau [B, top], f [B, top], height [B, top] float64, rank order, NaN where a signal has fewer peaks;
+        counts [B] int32, the number of regional maxima; phi [B, M*N] complex64)."""
+        from . import ops
+        top = self.L if top is None else top
+        xbase = self.M if xbase is None else xbase
+        ybase = self.N if ybase is None else ybase
+        if opts is None:
+            opts = {"xstep": 1 / (10 * self.N), "ystep": 1 / (10 * self.M), "iter": 3}
+        with torch.no_grad():
+            phi, _ = self._run(y, b, sigma, to_caller=False)
+            rows, counts = ops.peak_top(phi, xbase, ybase, opts, top=top, top_n=top_n)
+            out = y.device
+            return (rows[:, :, 0].contiguous().to(out), rows[:, :, 1].contiguous().to(out),
+                    rows[:, :, 2].contiguous().to(out), counts.to(out), phi.to(out))
 
     # ---- training ----------------------------------------------------------
     def forward_autograd(self, y, b, sigma):

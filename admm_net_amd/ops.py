@@ -373,6 +373,54 @@ def peak_search(phi: torch.Tensor, xbase: int, ybase: int, opts=None, max_peaks:
     return peaks, counts
 
 
+def peak_top(phi: torch.Tensor, xbase: int, ybase: int, opts=None, top: int = 3, top_n=None):
+    """The ``top`` highest peaks of every signal on the device in one kernel (csrc/estimate.hip): ``peak_search``
+    followed by the two lines both inference callers of the reference add, sort by refined height (descending, stable)
+    and cut (main_for_net.py:117-126, test/test_model_peaksearch.py:85-96).  Every regional maximum takes part: there
+    is no ``max_peaks``, and the coarse spectrum never leaves the chip.
+
+    phi [B, ybase*xbase] complex64; opts as for ``peak_search``; top: 1 .. 64; top_n: None, or [B] integers, the
+    number of rows wanted per signal (clamped to 0 .. top; test_model_peaksearch.py:91 cuts at the sample's L_true).
+    Returns (rows [B, top, 3] float64 = (tau, f, height) in rank order, ``peak_search.top_rows`` of the signal's peak
+    list bit for bit; rows beyond min(counts[b], top_n[b]) are NaN, counts [B] int32 = number of regional maxima).
+    """
+    from . import peak_search as ps
+    _need_cuda(phi, "phi")
+    lib = _lib.load()
+    dev = phi.device
+    B, D = phi.shape
+    if D != xbase * ybase:
+        raise ValueError(f"phi has {D} entries, expected xbase*ybase = {xbase * ybase}")
+    if isinstance(top, bool) or int(top) != top or not 1 <= int(top) <= 64:
+        raise ValueError(f"top must be an int in 1 .. 64, got {top!r}")
+    top = int(top)
+    so = {**ps.DEFAULT_OPTS, **(opts or {})}
+    ax, ay = ps.coarse_axes(opts)
+    nx, ny = len(ax), len(ay)
+    with torch.cuda.device(dev):
+        rows = torch.full((B, top, 3), float("nan"), dtype=torch.float64, device=dev)
+        counts = torch.zeros(B, dtype=torch.int32, device=dev)
+        if top_n is not None:
+            top_n = torch.as_tensor(top_n).to(device=dev, dtype=torch.int32).contiguous()
+            if tuple(top_n.shape) != (B,):
+                raise ValueError(f"top_n must be [{B}], got {tuple(top_n.shape)}")
+        if nx == 0 or ny == 0:
+            return rows, counts
+        tx = torch.from_numpy(ax).to(dev)
+        ty = torch.from_numpy(ay).to(dev)
+        need = lib.admmnet_peak_top_workspace_bytes(xbase, ybase, nx, ny)
+        if need < 0:
+            _lib.check(-1, "admmnet_peak_top_workspace_bytes")
+        ws = torch.empty(need, dtype=torch.uint8, device=dev)
+        o7 = (ctypes.c_double * 7)(so["xmin"], so["xmax"], so["xstep"], so["ymin"], so["ymax"], so["ystep"],
+                                   so["reducefactor"])
+        phi = phi.detach().to(torch.complex64).contiguous()
+        _lib.check(lib.admmnet_peak_top_f64(_ptr(phi), B, xbase, ybase, _ptr(tx), nx, _ptr(ty), ny, o7, int(so["iter"]),
+                                            top, _ptr(top_n), _ptr(rows), _ptr(counts), _ptr(ws), need, _stream(dev)),
+                   "admmnet_peak_top_f64")
+    return rows, counts
+
+
 def regional_maxima(Z: torch.Tensor):
     """skimage.morphology.local_maxima(connectivity=2) (utils/peakSearchUtils.py:118) of a batch of images on the
     device (the maxima stage of the peak-search kernel).  Z [B, ny, nx] float64 -> bool mask [B, ny, nx]."""

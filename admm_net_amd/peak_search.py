@@ -133,6 +133,17 @@ def coarse_axes(opts=None):
             np.arange(so["ymin"], so["ymax"] - so["xstep"], so["ystep"]))
 
 
+def top_rows(rows, top):
+    """The ``top`` highest peaks of ONE signal's list ``rows`` ([num, 3] = (x, y, height), e.g. from
+    ``alt_peak_search``), as both inference callers of the reference select them (main_for_net.py:119,126,
+    test/test_model_peaksearch.py:88,91): sort by height, descending -- Python's sort is stable, also with
+    ``reverse=True``, so equal heights keep their list order -- and keep the first ``top``.  The host definition of
+    what ``ops.peak_top`` computes on the device.  Returns a [min(num, top), 3] array."""
+    best = sorted(rows, key=lambda row: row[2], reverse=True)
+    best = best[:top]
+    return np.asarray(best, dtype=np.float64).reshape(-1, 3)
+
+
 def batched_peak_search(phi, xbase, ybase, opts=None, top=None, max_peaks=256, host_refine=False):
     """Peak search for a batch phi [B, D] (torch tensor on the HIP device).
 

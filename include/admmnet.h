@@ -277,6 +277,28 @@ int admmnet_peak_search_f64(const void *phi, int64_t B, int32_t xbase, int32_t y
                             const double *opts7, int32_t iters, int32_t max_peaks, double *peaks,
                             int32_t *counts, void *workspace, int64_t workspace_bytes, void *stream);
 
+/* Top-L target estimation: that peak search followed by the two lines both inference callers of the reference add,
+ * res = sorted(res, key=lambda x: x[2], reverse=True); res = res[:L]  (main_for_net.py:117-126,
+ * test/test_model_peaksearch.py:85-96), in one kernel, one signal per workgroup (csrc/estimate.hip).  The coarse
+ * spectrum stays on the chip and no peak list is kept: every regional maximum takes part, whatever their number.
+ *   phi, axis_x, axis_y, opts7, iters: as for admmnet_peak_search_f64, whose rows these are bit for bit;
+ *   L: 1 .. 64;  top_n: device int32 [B], the number of rows wanted of signal b (clamped to 0 .. L; the sample's own
+ *     L_true at test_model_peaksearch.py:91), or NULL for L rows of every signal;
+ *   top device float64 [B][L][3] = (x = tau, y = f, height), row r = the peak of rank r, where peak k (np.where order)
+ *     has rank #{j : h_j > h_k} + #{j < k : h_j == h_k} (Python's stable sort, reverse=True) and h is the height after
+ *     the last refinement round that ran for the peak, 0.0 if none did (:136-171 leave res[k, 2] untouched);
+ *     rows r >= min(counts[b], top_n[b]) are NaN;
+ *   counts device int32 [B]: number of regional maxima, the value admmnet_peak_search_f64 reports;
+ *   workspace: device scratch of admmnet_peak_top_workspace_bytes() bytes (the steering tables: independent of B).
+ * B >= 0.  A grid whose image does not fit one workgroup's LDS is ADMMNET_E_ARG. */
+int64_t admmnet_peak_top_workspace_bytes(int32_t xbase, int32_t ybase, int32_t nx, int32_t ny);
+int admmnet_peak_top_f64(const void *phi, int64_t B, int32_t xbase, int32_t ybase,
+                         const double *axis_x, int32_t nx, const double *axis_y, int32_t ny,
+                         const double *opts7, int32_t iters,
+                         int32_t L, const int32_t *top_n,
+                         double *top, int32_t *counts,
+                         void *workspace, int64_t workspace_bytes, void *stream);
+
 /* The regional-maxima stage of that kernel alone, on caller-supplied images: skimage.morphology.local_maxima(
  * connectivity=2) as used at utils/peakSearchUtils.py:118 (8-connected, plateau aware, borders allowed, a constant
  * image has none; the reference's own example input is the plateau matrix at :427-432).
