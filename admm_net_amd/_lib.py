@@ -68,6 +68,17 @@ SYMBOLS = {
     "admmnet_train_gather_c64": (c_int32, [c_int32, c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
     "admmnet_train_scatter_c64": (c_int32, [c_int32, c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
     "admmnet_train_herm_c64": (c_int32, [c_int32, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "admmnet_train_small_partials": (c_int64, [c_int32, c_int64, c_int64]),
+    "admmnet_train_phi_c64": (c_int32, [c_int32, c_int64] + [c_void_p] * 7),
+    "admmnet_train_phi_bwd_c64": (c_int32, [c_int32, c_int64] + [c_void_p] * 11),
+    "admmnet_train_hinput_f32": (c_int32, [c_int32, c_int64] + [c_void_p] * 5),
+    "admmnet_train_hinput_bwd_f32": (c_int32, [c_int32, c_int64] + [c_void_p] * 8),
+    "admmnet_train_hproject_f32": (c_int32, [c_int32, c_int64] + [c_void_p] * 6),
+    "admmnet_train_hproject_bwd_f32": (c_int32, [c_int32, c_int64] + [c_void_p] * 10),
+    "admmnet_train_eigmap_f32": (c_int32, [c_int32, c_int64] + [c_void_p] * 8),
+    "admmnet_train_eigmap_bwd_f32": (c_int32, [c_int32, c_int64] + [c_void_p] * 11),
+    "admmnet_train_stepsize_f32": (c_int32, [c_int64, c_int64, c_float] + [c_void_p] * 8),
+    "admmnet_train_stepsize_bwd_f32": (c_int32, [c_int64, c_int64, c_float] + [c_void_p] * 11),
     "admmnet_spectrum_workspace_bytes": (c_int64, [c_int32, c_int32, c_int32, c_int32]),
     "admmnet_spectrum_f64": (c_int32, [c_void_p, c_int64, c_int32, c_int32, c_void_p, c_int32, c_void_p,
                                        c_int32, c_void_p, c_void_p, c_int64, c_void_p]),

@@ -853,6 +853,113 @@ int admmnet_train_herm_c64(int32_t n, int64_t B, const void *g, const void *g_co
     return launch_train_herm(n, B, (const float2 *)g, (const float2 *)g_col, g_diag, (float2 *)S, (hipStream_t)stream);
 }
 
+// ---- training route "full": the O(B D)-sized steps of a layer (train_small.hip) -----------------------------------------------
+// D = M N for phi / hinput / hproject, n = D + 1 for eigmap; the slab grid must fit 31 bits
+static int train_small_args_ok(const char *what, int32_t d, int32_t dmin, int32_t dmax, int64_t B, bool ptrs) {
+    if (d < dmin || d > dmax || B < 1 || train_small_rows(B) > 0x7fffffffLL || !ptrs) {
+        set_error("%s: bad argument (size=%d, B=%lld)", what, d, (long long)B);
+        return ADMMNET_E_ARG;
+    }
+    return ADMMNET_OK;
+}
+
+static int train_step_args_ok(const char *what, int64_t B, int64_t g, bool ptrs) {
+    if (B < 1 || g < 0 || train_small_groups(B, g) > 0x7fffffffLL || !ptrs) {
+        set_error("%s: bad argument (B=%lld, sub_batch=%lld)", what, (long long)B, (long long)g);
+        return ADMMNET_E_ARG;
+    }
+    return ADMMNET_OK;
+}
+
+int64_t admmnet_train_small_partials(int32_t step, int64_t B, int64_t sub_batch) {
+    if (B < 1 || sub_batch < 0) return -1;
+    switch (step) {
+    case ADMMNET_TRAIN_PHI:
+    case ADMMNET_TRAIN_HINPUT:
+    case ADMMNET_TRAIN_HPROJECT: return train_small_rows(B);
+    case ADMMNET_TRAIN_EIGMAP: return train_small_rows(B) * ADMMNET_TRAIN_EIGMAP_GRADS;
+    case ADMMNET_TRAIN_STEPSIZE: return train_small_groups(B, sub_batch) * ADMMNET_TRAIN_STEPSIZE_GRADS + B;
+    }
+    return -1;
+}
+
+int admmnet_train_phi_c64(int32_t D, int64_t B, const void *y, const void *b, const void *g_col, const void *z_col,
+                          const float *rho, void *phi, void *stream) {
+    if (int rc = train_small_args_ok("train_phi", D, 1, kMaxD, B, y && b && g_col && z_col && rho && phi)) return rc;
+    return launch_train_phi(D, B, (const float2 *)y, (const float2 *)b, (const float2 *)g_col, (const float2 *)z_col, rho,
+                            (float2 *)phi, (hipStream_t)stream);
+}
+
+int admmnet_train_phi_bwd_c64(int32_t D, int64_t B, const void *g_phi, const void *y, const void *b, const void *g_col,
+                              const void *z_col, const float *rho, void *g_gcol, void *g_zcol, float *g_rho, float *partials,
+                              void *stream) {
+    if (int rc = train_small_args_ok("train_phi_bwd", D, 1, kMaxD, B,
+                                     g_phi && y && b && g_col && z_col && rho && g_gcol && g_zcol && g_rho && partials))
+        return rc;
+    return launch_train_phi_bwd(D, B, (const float2 *)g_phi, (const float2 *)y, (const float2 *)b, (const float2 *)g_col,
+                                (const float2 *)z_col, rho, (float2 *)g_gcol, (float2 *)g_zcol, g_rho, partials,
+                                (hipStream_t)stream);
+}
+
+int admmnet_train_hinput_f32(int32_t D, int64_t B, const float *g_dg, const float *z_dg, const float *rho, float *t,
+                             void *stream) {
+    if (int rc = train_small_args_ok("train_hinput", D, 1, kMaxD, B, g_dg && z_dg && rho && t)) return rc;
+    return launch_train_hinput(D, B, g_dg, z_dg, rho, t, (hipStream_t)stream);
+}
+
+int admmnet_train_hinput_bwd_f32(int32_t D, int64_t B, const float *g_t, const float *z_dg, const float *rho, float *g_gdg,
+                                 float *g_zdg, float *g_rho, float *partials, void *stream) {
+    if (int rc = train_small_args_ok("train_hinput_bwd", D, 1, kMaxD, B, g_t && z_dg && rho && g_gdg && g_zdg && g_rho && partials))
+        return rc;
+    return launch_train_hinput_bwd(D, B, g_t, z_dg, rho, g_gdg, g_zdg, g_rho, partials, (hipStream_t)stream);
+}
+
+int admmnet_train_hproject_f32(int32_t D, int64_t B, const float *t, const float *m, const float *sigma,
+                               const float *projection_weight, float *h, void *stream) {
+    if (int rc = train_small_args_ok("train_hproject", D, 1, kMaxD, B, t && m && sigma && projection_weight && h)) return rc;
+    return launch_train_hproject(D, B, t, m, sigma, projection_weight, h, (hipStream_t)stream);
+}
+
+int admmnet_train_hproject_bwd_f32(int32_t D, int64_t B, const float *g_h, const float *t, const float *m, const float *sigma,
+                                   const float *projection_weight, float *g_t, float *g_m, float *g_pw, float *partials,
+                                   void *stream) {
+    if (int rc = train_small_args_ok("train_hproject_bwd", D, 1, kMaxD, B,
+                                     g_h && t && m && sigma && projection_weight && g_t && g_m && g_pw && partials))
+        return rc;
+    return launch_train_hproject_bwd(D, B, g_h, t, m, sigma, projection_weight, g_t, g_m, g_pw, partials, (hipStream_t)stream);
+}
+
+int admmnet_train_eigmap_f32(int32_t n, int64_t B, const float *w, const float *threshold, const float *W1, const float *b1,
+                             const float *W2, const float *b2, float *wp, void *stream) {
+    if (int rc = train_small_args_ok("train_eigmap", n, 2, kMaxD + 1, B, w && threshold && W1 && b1 && W2 && b2 && wp)) return rc;
+    return launch_train_eigmap(n, B, w, threshold, W1, b1, W2, b2, wp, (hipStream_t)stream);
+}
+
+int admmnet_train_eigmap_bwd_f32(int32_t n, int64_t B, const float *g_wp, const float *w, const float *threshold, const float *W1,
+                                 const float *b1, const float *W2, const float *b2, float *g_w, float *g_params, float *partials,
+                                 void *stream) {
+    if (int rc = train_small_args_ok("train_eigmap_bwd", n, 2, kMaxD + 1, B,
+                                     g_wp && w && threshold && W1 && b1 && W2 && b2 && g_w && g_params && partials))
+        return rc;
+    return launch_train_eigmap_bwd(n, B, g_wp, w, threshold, W1, b1, W2, b2, g_w, g_params, partials, (hipStream_t)stream);
+}
+
+int admmnet_train_stepsize_f32(int64_t B, int64_t sub_batch, float knorm, const float *rn, const float *rho, const float *W1,
+                               const float *b1, const float *W2, const float *b2, float *step, void *stream) {
+    if (int rc = train_step_args_ok("train_stepsize", B, sub_batch, rn && rho && W1 && b1 && W2 && b2 && step)) return rc;
+    return launch_train_stepsize(B, sub_batch, knorm, rn, rho, W1, b1, W2, b2, step, (hipStream_t)stream);
+}
+
+int admmnet_train_stepsize_bwd_f32(int64_t B, int64_t sub_batch, float knorm, const float *g_step, const float *rn,
+                                   const float *rho, const float *W1, const float *b1, const float *W2, const float *b2,
+                                   float *g_rn, float *g_params, float *partials, void *stream) {
+    if (int rc = train_step_args_ok("train_stepsize_bwd", B, sub_batch,
+                                    g_step && rn && rho && W1 && b1 && W2 && b2 && g_rn && g_params && partials))
+        return rc;
+    return launch_train_stepsize_bwd(B, sub_batch, knorm, g_step, rn, rho, W1, b1, W2, b2, g_rn, g_params, partials,
+                                     (hipStream_t)stream);
+}
+
 int admmnet_profile_enable(int32_t on) {
     ProfState &p = prof();
     std::lock_guard<std::mutex> lk(p.mu);

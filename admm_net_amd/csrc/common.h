@@ -239,6 +239,31 @@ int launch_train_herm(int n, int64_t B, const float2 *g, const float2 *gcol, con
 int launch_train_zupdate_bwd(int n, int64_t B, const float2 *g, const float2 *G, const float2 *phi, const float *h,
                              const float *s, float corner, float2 *gG, float2 *gphi, float *gh, float *gs, hipStream_t st);
 
+// train_small.hip (training route "full", the O(B D)-sized layer steps; every parameter pointer is the RAW device value)
+int64_t train_small_rows(int64_t B);                  // partial rows of the per-signal kernels: one per slab of signals
+int64_t train_small_groups(int64_t B, int64_t g);     // groups of the step-size kernels (g = 0: one)
+int launch_train_phi(int D, int64_t B, const float2 *y, const float2 *b, const float2 *gcol, const float2 *zcol,
+                     const float *rho_raw, float2 *phi, hipStream_t st);
+int launch_train_phi_bwd(int D, int64_t B, const float2 *gphi, const float2 *y, const float2 *b, const float2 *gcol,
+                         const float2 *zcol, const float *rho_raw, float2 *ggcol, float2 *gzcol, float *grho, float *part,
+                         hipStream_t st);
+int launch_train_hinput(int D, int64_t B, const float *gdg, const float *zdg, const float *rho_raw, float *t, hipStream_t st);
+int launch_train_hinput_bwd(int D, int64_t B, const float *gt, const float *zdg, const float *rho_raw, float *ggdg, float *gzdg,
+                            float *grho, float *part, hipStream_t st);
+int launch_train_hproject(int D, int64_t B, const float *t, const float *m, const float *sigma, const float *pw_raw, float *h,
+                          hipStream_t st);
+int launch_train_hproject_bwd(int D, int64_t B, const float *gh, const float *t, const float *m, const float *sigma,
+                              const float *pw_raw, float *gt, float *gm, float *gpw, float *part, hipStream_t st);
+int launch_train_eigmap(int n, int64_t B, const float *w, const float *thr, const float *W1, const float *b1, const float *W2,
+                        const float *b2, float *wp, hipStream_t st);
+int launch_train_eigmap_bwd(int n, int64_t B, const float *gwp, const float *w, const float *thr, const float *W1, const float *b1,
+                            const float *W2, const float *b2, float *gw, float *gpar, float *part, hipStream_t st);
+int launch_train_stepsize(int64_t B, int64_t g, float knorm, const float *rn, const float *rho_raw, const float *W1,
+                          const float *b1, const float *W2, const float *b2, float *step, hipStream_t st);
+int launch_train_stepsize_bwd(int64_t B, int64_t g, float knorm, const float *gstep, const float *rn, const float *rho_raw,
+                              const float *W1, const float *b1, const float *W2, const float *b2, float *grn, float *gpar,
+                              float *part, hipStream_t st);
+
 // synth.hip
 int launch_synth(int64_t B, int Nb, int Nd, int L, unsigned long long seed, double snr_lo, double snr_hi, double snr_e,
                  double rho, int label_iters, float2 *y, float2 *b, float *sigma, float *tau, float *f, float2 *C,

@@ -1,0 +1,537 @@
+// train_small.hip -- the O(B D)-sized steps of one TRAINING layer, one forward and one hand-written backward kernel each, for
+// train_route = "full" of admm_net_amd/training.py (the n^2-sized steps are train_layer.hip's).  Every kernel reads the RAW
+// parameters from device memory and applies softplus / sigmoid itself; every backward returns gradients for the raw parameters.
+//   phi       phi = bs / (1 + rho bs) (y / (b + eps) + rho g_col + z_col), rho = softplus(rho_raw), bs = |b|^2 + eps   admm_net.py:79-105
+//   hinput    t = g_dg + z_dg / (softplus(rho_raw) + eps)                                                               :150-152
+//   hproject  tc = t + 0.1 m, c = A max|tc| + sum tc, A = 2 sqrt(D) sigma + sigma^2, s = min(sigmoid(pw) / (c + eps), 1),
+//             h = tc s (m = correction_net(t), a framework module call between hinput and hproject)                     :160-194
+//   eigmap    wp = softplus(w - sigmoid(thr)) sigmoid(W2 relu(W1 |w| + b1) + b2), one 1 -> 16 -> 1 network per eigenvalue :310-334
+//   stepsize  u_b = rn_b / (mean_g rn + eps), step_b = rho (0.5 + 1.5 sigmoid(W2 relu(W1 [k/10, rho, u_b] + b1) + b2));
+//             the rho FEATURE is a constant (the reference's .item()), the leading rho is not                           :440-474
+// Conventions (torch's): relu'(0) = 0, d|x|/dx = 0 at 0, clamp(max = 1) passes the gradient where its argument is <= 1, the
+// gradient of max|tc| goes to the lowest index among ties, softplus has beta = 1 and is linear above 20.
+//
+// Launch shapes.  D <= 256 is at most four elements per lane of one wave, so phi / hinput / hproject / eigmap give every signal
+// ONE WAVE and a workgroup a slab of four consecutive signals: the per-signal reductions (max, sum, dot products) are xor-shuffle
+// butterflies and need neither LDS nor a barrier.  stepsize couples the signals of a group through their mean: one 256-thread
+// workgroup per group (one for the whole call without sub-batches).
+// Sums over the batch (the parameter gradients) run in a fixed order without atomics: per lane serially, across the wave by
+// the butterfly, across the slab's four waves serially from LDS into one row of `partials` per workgroup; ts_colsum_kernel (one
+// workgroup) then adds the rows in float64, as tl_negsum_kernel / rn_sum_kernel do.  Two runs give the same bits.
+// Every access is a 4-byte (float) or 8-byte (float2) one: the [B, D] tensors need no more than their natural alignment.
+#include "common.h"
+
+namespace admmnet {
+
+constexpr int TS_THREADS = 256;
+constexpr int TS_SLAB = TS_THREADS / 64;   // signals per workgroup, one per wave
+constexpr int TS_PER_LANE = 5;             // ceil((kMaxD + 1) / 64): elements of one row a lane visits
+constexpr int TS_EIG_PAR = 50;             // g_thr, gW1[16], gb1[16], gW2[16], gb2
+constexpr int TS_STEP_PAR = 162;           // g_rho, gW1[32][3], gb1[32], gW2[32], gb2
+static_assert(TS_PER_LANE * 64 >= kMaxD + 1, "a wave must cover one row");
+
+__device__ __forceinline__ float ts_softplus(float x) { return x > 20.f ? x : log1pf(expf(x)); }
+__device__ __forceinline__ float ts_sigmoid(float x) { return 1.f / (1.f + expf(-x)); }
+// d softplus(x) / dx
+__device__ __forceinline__ float ts_dsoftplus(float x) { return x > 20.f ? 1.f : ts_sigmoid(x); }
+// d sigmoid(x) / dx = s (1 - s), from e = exp(-|x|) as e / (1 + e)^2: 1 - s itself loses every digit as s nears 1
+__device__ __forceinline__ float ts_dsigmoid(float x) {
+    const float e = expf(-fabsf(x)), d = 1.f + e;
+    return e / (d * d);
+}
+
+// v[0 .. COUNT) hold wave sums (the same value in every lane): adds the slab's waves in wave order into row blockIdx.x of part.
+// Every thread of the workgroup must call it.
+template <int COUNT>
+__device__ __forceinline__ void ts_slab_partials(const float (&v)[COUNT], float *sh, float *__restrict__ part) {
+    const int wave = threadIdx.x >> 6;
+    if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+        for (int c = 0; c < COUNT; ++c) sh[wave * COUNT + c] = v[c];
+    }
+    __syncthreads();
+    if ((int)threadIdx.x < COUNT) {
+        float s = 0.f;
+        for (int w = 0; w < TS_SLAB; ++w) s += sh[w * COUNT + threadIdx.x];
+        part[(int64_t)blockIdx.x * COUNT + threadIdx.x] = s;
+    }
+}
+
+// out[c] = sum over rows of part[row][c] in float64, fixed order: thread (c, s) adds the rows s, s + ns, ..., a tree halves
+// the ns slices (count <= 256; one workgroup)
+__global__ __launch_bounds__(TS_THREADS) void ts_colsum_kernel(int count, int ns, int64_t rows, const float *__restrict__ part,
+                                                               float *__restrict__ out) {
+    __shared__ double sh[TS_THREADS];
+    const int c = threadIdx.x % count, s = threadIdx.x / count;
+    const bool live = s < ns;
+    double a = 0.0;
+    if (live)
+        for (int64_t r = s; r < rows; r += ns) a += (double)part[r * count + c];
+    if (live) sh[s * count + c] = a;
+    __syncthreads();
+    for (int o = ns >> 1; o > 0; o >>= 1) {
+        if (live && s < o) sh[s * count + c] += sh[(s + o) * count + c];
+        __syncthreads();
+    }
+    if (live && s == 0) out[c] = (float)sh[c];
+}
+
+static int ts_colsum(int count, int64_t rows, const float *part, float *out, hipStream_t st) {
+    int ns = 1;
+    while (2 * ns * count <= TS_THREADS) ns *= 2;
+    hipLaunchKernelGGL(ts_colsum_kernel, dim3(1), dim3(TS_THREADS), 0, st, count, ns, rows, part, out);
+    ADMM_HIP(hipGetLastError());
+    return ADMMNET_OK;
+}
+
+// ---- phi ---------------------------------------------------------------------------------------------------------------------
+struct TsPhi {
+    float coef, dcoef;   // bs / (1 + rho bs) and its derivative by rho, -coef^2
+    float2 inner;        // y / (b + eps) + rho g + z
+};
+__device__ __forceinline__ TsPhi ts_phi_at(float2 y, float2 b, float2 g, float2 z, float rho) {
+    TsPhi p;
+    const float bs = b.x * b.x + b.y * b.y + kEpsRef;
+    p.coef = bs / (1.f + rho * bs);
+    p.dcoef = -p.coef * p.coef;
+    const float dx = b.x + kEpsRef, dy = b.y, dd = dx * dx + dy * dy;
+    const float qx = (y.x * dx + y.y * dy) / dd, qy = (y.y * dx - y.x * dy) / dd;
+    p.inner = make_float2(qx + rho * g.x + z.x, qy + rho * g.y + z.y);
+    return p;
+}
+
+__global__ __launch_bounds__(TS_THREADS) void ts_phi_kernel(int D, int64_t B, const float2 *__restrict__ y,
+                                                            const float2 *__restrict__ b, const float2 *__restrict__ gcol,
+                                                            const float2 *__restrict__ zcol, const float *__restrict__ rho_raw,
+                                                            float2 *__restrict__ phi) {
+    const int64_t sig = (int64_t)blockIdx.x * TS_SLAB + (threadIdx.x >> 6);
+    if (sig >= B) return;
+    const float rho = ts_softplus(rho_raw[0]);
+    for (int i = threadIdx.x & 63; i < D; i += 64) {
+        const int64_t e = sig * D + i;
+        const TsPhi p = ts_phi_at(y[e], b[e], gcol[e], zcol[e], rho);
+        phi[e] = make_float2(p.coef * p.inner.x, p.coef * p.inner.y);
+    }
+}
+
+// g_gcol = coef rho g_phi, g_zcol = coef g_phi, g_rho_raw = softplus'(rho_raw) sum Re(conj(g_phi) (coef g + dcoef inner))
+__global__ __launch_bounds__(TS_THREADS) void ts_phi_bwd_kernel(int D, int64_t B, const float2 *__restrict__ gphi,
+                                                                const float2 *__restrict__ y, const float2 *__restrict__ b,
+                                                                const float2 *__restrict__ gcol, const float2 *__restrict__ zcol,
+                                                                const float *__restrict__ rho_raw, float2 *__restrict__ ggcol,
+                                                                float2 *__restrict__ gzcol, float *__restrict__ part) {
+    __shared__ float sh[TS_SLAB];
+    const int64_t sig = (int64_t)blockIdx.x * TS_SLAB + (threadIdx.x >> 6);
+    const float raw = rho_raw[0], rho = ts_softplus(raw);
+    float acc = 0.f;
+    if (sig < B)
+        for (int i = threadIdx.x & 63; i < D; i += 64) {
+            const int64_t e = sig * D + i;
+            const float2 g = gcol[e], u = gphi[e];
+            const TsPhi p = ts_phi_at(y[e], b[e], g, zcol[e], rho);
+            ggcol[e] = make_float2(p.coef * rho * u.x, p.coef * rho * u.y);
+            gzcol[e] = make_float2(p.coef * u.x, p.coef * u.y);
+            const float dx = p.coef * g.x + p.dcoef * p.inner.x, dy = p.coef * g.y + p.dcoef * p.inner.y;
+            acc = fmaf(u.x, dx, fmaf(u.y, dy, acc));
+        }
+    const float v[1] = {wave_sum(acc) * ts_dsoftplus(raw)};
+    ts_slab_partials<1>(v, sh, part);
+}
+
+// ---- H input -----------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(TS_THREADS) void ts_hinput_kernel(int D, int64_t B, const float *__restrict__ gdg,
+                                                               const float *__restrict__ zdg, const float *__restrict__ rho_raw,
+                                                               float *__restrict__ t) {
+    const int64_t sig = (int64_t)blockIdx.x * TS_SLAB + (threadIdx.x >> 6);
+    if (sig >= B) return;
+    const float den = ts_softplus(rho_raw[0]) + kEpsRef;
+    for (int i = threadIdx.x & 63; i < D; i += 64) {
+        const int64_t e = sig * D + i;
+        t[e] = gdg[e] + zdg[e] / den;
+    }
+}
+
+// g_gdg = g_t, g_zdg = g_t / den, g_rho_raw = -softplus'(rho_raw) / den^2 sum g_t z_dg, den = softplus(rho_raw) + eps
+__global__ __launch_bounds__(TS_THREADS) void ts_hinput_bwd_kernel(int D, int64_t B, const float *__restrict__ gt,
+                                                                   const float *__restrict__ zdg, const float *__restrict__ rho_raw,
+                                                                   float *__restrict__ ggdg, float *__restrict__ gzdg,
+                                                                   float *__restrict__ part) {
+    __shared__ float sh[TS_SLAB];
+    const int64_t sig = (int64_t)blockIdx.x * TS_SLAB + (threadIdx.x >> 6);
+    const float raw = rho_raw[0], den = ts_softplus(raw) + kEpsRef;
+    float acc = 0.f;
+    if (sig < B)
+        for (int i = threadIdx.x & 63; i < D; i += 64) {
+            const int64_t e = sig * D + i;
+            const float u = gt[e];
+            ggdg[e] = u;
+            gzdg[e] = u / den;
+            acc = fmaf(u, zdg[e], acc);
+        }
+    const float v[1] = {-wave_sum(acc) * ts_dsoftplus(raw) / (den * den)};
+    ts_slab_partials<1>(v, sh, part);
+}
+
+// ---- H projection ------------------------------------------------------------------------------------------------------------
+// One wave's view of a signal: its tc values, c and the place of max|tc| (lowest index among ties)
+struct TsProj {
+    float tc[TS_PER_LANE - 1];
+    float A, c;
+    int imax;
+};
+__device__ __forceinline__ TsProj ts_project(int D, const float *__restrict__ t, const float *__restrict__ m, float sigma) {
+    TsProj p;
+    const int lane = threadIdx.x & 63;
+    float mx = -1.f, sm = 0.f;
+    int im = 0x7fffffff;
+#pragma unroll
+    for (int k = 0; k < TS_PER_LANE - 1; ++k) {
+        const int i = lane + 64 * k;
+        p.tc[k] = i < D ? t[i] + 0.1f * m[i] : 0.f;
+        sm += p.tc[k];
+        if (i < D && fabsf(p.tc[k]) > mx) mx = fabsf(p.tc[k]), im = i;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const float omx = __shfl_xor(mx, o, 64);
+        const int oim = __shfl_xor(im, o, 64);
+        if (omx > mx || (omx == mx && oim < im)) mx = omx, im = oim;
+    }
+    sm = wave_sum(sm);
+    p.A = 2.f * sqrtf((float)D) * sigma + sigma * sigma;
+    p.c = p.A * mx + sm;
+    p.imax = im;
+    return p;
+}
+
+__global__ __launch_bounds__(TS_THREADS) void ts_hproject_kernel(int D, int64_t B, const float *__restrict__ t,
+                                                                 const float *__restrict__ m, const float *__restrict__ sigma,
+                                                                 const float *__restrict__ pw_raw, float *__restrict__ h) {
+    const int64_t sig = (int64_t)blockIdx.x * TS_SLAB + (threadIdx.x >> 6);
+    if (sig >= B) return;
+    const TsProj p = ts_project(D, t + sig * D, m + sig * D, sigma[sig]);
+    const float s = fminf(ts_sigmoid(pw_raw[0]) / (p.c + kEpsRef), 1.f);
+#pragma unroll
+    for (int k = 0; k < TS_PER_LANE - 1; ++k) {
+        const int i = (threadIdx.x & 63) + 64 * k;
+        if (i < D) h[sig * D + i] = p.tc[k] * s;
+    }
+}
+
+// with sp = sigmoid(pw), q = sp / (c + eps), g_s = sum_i g_h[i] tc[i]:
+//   q <= 1:  g_c = -g_s sp / (c + eps)^2,  g_tc[i] = g_h[i] q + g_c (1 + [i = imax] A sign(tc[i])),  g_pw += g_s sp (1 - sp) / (c + eps)
+//   q >  1:  g_tc = g_h (the clamp holds s at 1 and passes nothing)
+// g_t = g_tc, g_m = 0.1 g_tc
+__global__ __launch_bounds__(TS_THREADS) void ts_hproject_bwd_kernel(int D, int64_t B, const float *__restrict__ gh,
+                                                                     const float *__restrict__ t, const float *__restrict__ m,
+                                                                     const float *__restrict__ sigma,
+                                                                     const float *__restrict__ pw_raw, float *__restrict__ gt,
+                                                                     float *__restrict__ gm, float *__restrict__ part) {
+    __shared__ float sh[TS_SLAB];
+    const int64_t sig = (int64_t)blockIdx.x * TS_SLAB + (threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    float gpw = 0.f;
+    if (sig < B) {
+        const TsProj p = ts_project(D, t + sig * D, m + sig * D, sigma[sig]);
+        const float sp = ts_sigmoid(pw_raw[0]), den = p.c + kEpsRef, q = sp / den;
+        float u[TS_PER_LANE - 1], gs = 0.f;
+#pragma unroll
+        for (int k = 0; k < TS_PER_LANE - 1; ++k) {
+            const int i = lane + 64 * k;
+            u[k] = i < D ? gh[sig * D + i] : 0.f;
+            gs = fmaf(u[k], p.tc[k], gs);
+        }
+        gs = wave_sum(gs);
+        const bool open = q <= 1.f;
+        const float s = open ? q : 1.f, gc = open ? -gs * sp / (den * den) : 0.f;
+        if (open) gpw = gs * ts_dsigmoid(pw_raw[0]) / den;
+#pragma unroll
+        for (int k = 0; k < TS_PER_LANE - 1; ++k) {
+            const int i = lane + 64 * k;
+            if (i >= D) continue;
+            const float sgn = p.tc[k] > 0.f ? 1.f : (p.tc[k] < 0.f ? -1.f : 0.f);
+            const float gtc = fmaf(u[k], s, gc * (1.f + (i == p.imax ? p.A * sgn : 0.f)));
+            gt[sig * D + i] = gtc;
+            gm[sig * D + i] = 0.1f * gtc;
+        }
+    }
+    const float v[1] = {gpw};
+    ts_slab_partials<1>(v, sh, part);
+}
+
+// ---- eigenvalue map ----------------------------------------------------------------------------------------------------------
+struct TsValueNet {   // value_net: Linear(1, 16), ReLU, Linear(16, 1), Sigmoid
+    float W1[16], b1[16], W2[16], b2, st;   // st = sigmoid(threshold_raw)
+};
+__device__ __forceinline__ TsValueNet ts_load_value_net(const float *__restrict__ thr, const float *__restrict__ W1,
+                                                        const float *__restrict__ b1, const float *__restrict__ W2,
+                                                        const float *__restrict__ b2) {
+    TsValueNet p;
+#pragma unroll
+    for (int j = 0; j < 16; ++j) p.W1[j] = W1[j], p.b1[j] = b1[j], p.W2[j] = W2[j];
+    p.b2 = b2[0];
+    p.st = ts_sigmoid(thr[0]);
+    return p;
+}
+
+__global__ __launch_bounds__(TS_THREADS) void ts_eigmap_kernel(int n, int64_t B, const float *__restrict__ w,
+                                                               const float *__restrict__ thr, const float *__restrict__ W1,
+                                                               const float *__restrict__ b1, const float *__restrict__ W2,
+                                                               const float *__restrict__ b2, float *__restrict__ wp) {
+    const int64_t sig = (int64_t)blockIdx.x * TS_SLAB + (threadIdx.x >> 6);
+    if (sig >= B) return;
+    const TsValueNet p = ts_load_value_net(thr, W1, b1, W2, b2);
+    for (int i = threadIdx.x & 63; i < n; i += 64) {
+        const float x = w[sig * n + i], ax = fabsf(x);
+        float o = p.b2;
+#pragma unroll
+        for (int j = 0; j < 16; ++j) o = fmaf(p.W2[j], fmaxf(fmaf(p.W1[j], ax, p.b1[j]), 0.f), o);
+        wp[sig * n + i] = ts_softplus(x - p.st) * ts_sigmoid(o);
+    }
+}
+
+// with a = softplus(w - st), v = sigmoid(o), g_a = g v, g_o = g a v (1 - v), dh_j = g_o W2_j [pre_j > 0]:
+//   g_w = g_a sigmoid(w - st) + sign(w) sum_j dh_j W1_j
+//   g_thr_raw = -st (1 - st) sum g_a sigmoid(w - st);  gW1_j = sum dh_j |w|;  gb1_j = sum dh_j;  gW2_j = sum g_o relu(pre_j);  gb2 = sum g_o
+__global__ __launch_bounds__(TS_THREADS) void ts_eigmap_bwd_kernel(int n, int64_t B, const float *__restrict__ gwp,
+                                                                   const float *__restrict__ w, const float *__restrict__ thr,
+                                                                   const float *__restrict__ W1, const float *__restrict__ b1,
+                                                                   const float *__restrict__ W2, const float *__restrict__ b2,
+                                                                   float *__restrict__ gw, float *__restrict__ part) {
+    __shared__ float sh[TS_SLAB * TS_EIG_PAR];
+    const int64_t sig = (int64_t)blockIdx.x * TS_SLAB + (threadIdx.x >> 6);
+    const TsValueNet p = ts_load_value_net(thr, W1, b1, W2, b2);
+    float acc[TS_EIG_PAR];
+#pragma unroll
+    for (int c = 0; c < TS_EIG_PAR; ++c) acc[c] = 0.f;
+    if (sig < B)
+        for (int i = threadIdx.x & 63; i < n; i += 64) {
+            const float x = w[sig * n + i], ax = fabsf(x), g = gwp[sig * n + i];
+            float pre[16], o = p.b2;
+#pragma unroll
+            for (int j = 0; j < 16; ++j) {
+                pre[j] = fmaf(p.W1[j], ax, p.b1[j]);
+                o = fmaf(p.W2[j], fmaxf(pre[j], 0.f), o);
+            }
+            const float a = ts_softplus(x - p.st), da = ts_dsoftplus(x - p.st), v = ts_sigmoid(o);
+            const float ga = g * v, go = g * a * ts_dsigmoid(o);
+            float gax = 0.f;
+            acc[0] = fmaf(ga, da, acc[0]);
+#pragma unroll
+            for (int j = 0; j < 16; ++j) {
+                const float dh = pre[j] > 0.f ? go * p.W2[j] : 0.f;
+                acc[1 + j] = fmaf(dh, ax, acc[1 + j]);
+                acc[17 + j] += dh;
+                acc[33 + j] = fmaf(go, fmaxf(pre[j], 0.f), acc[33 + j]);
+                gax = fmaf(dh, p.W1[j], gax);
+            }
+            acc[49] += go;
+            const float sgn = x > 0.f ? 1.f : (x < 0.f ? -1.f : 0.f);
+            gw[sig * n + i] = fmaf(ga, da, sgn * gax);
+        }
+#pragma unroll
+    for (int c = 0; c < TS_EIG_PAR; ++c) acc[c] = wave_sum(acc[c]);
+    acc[0] *= -ts_dsigmoid(thr[0]);
+    ts_slab_partials<TS_EIG_PAR>(acc, sh, part);
+}
+
+// ---- step size ---------------------------------------------------------------------------------------------------------------
+// residual_scale_net: Linear(3, 32) (W1 [32][3] row-major), ReLU, Linear(32, 1), Sigmoid.  Group gi of a call with
+// sub_batch = g is the signals [gi g, min((gi + 1) g, B)); g = 0: the call is one group.
+__device__ __forceinline__ float ts_step_pre(const float *__restrict__ W1, const float *__restrict__ b1, int j, float f0, float f1,
+                                             float u) {
+    return fmaf(W1[3 * j + 2], u, fmaf(W1[3 * j + 1], f1, fmaf(W1[3 * j], f0, b1[j])));
+}
+
+// mean of the group's rn: float64, thread t adds rn[t], rn[t + 256], ..., a tree halves the 256 slots
+__device__ __forceinline__ float ts_group_mean(const float *__restrict__ rn, int64_t r, double *sh) {
+    double a = 0.0;
+    for (int64_t i = threadIdx.x; i < r; i += TS_THREADS) a += (double)rn[i];
+    sh[threadIdx.x] = a;
+    __syncthreads();
+    for (int o = TS_THREADS / 2; o > 0; o >>= 1) {
+        if ((int)threadIdx.x < o) sh[threadIdx.x] += sh[threadIdx.x + o];
+        __syncthreads();
+    }
+    return (float)(sh[0] / (double)r);
+}
+
+__global__ __launch_bounds__(TS_THREADS) void ts_stepsize_kernel(int64_t B, int64_t g, float knorm, const float *__restrict__ rng,
+                                                                 const float *__restrict__ rho_raw, const float *__restrict__ W1,
+                                                                 const float *__restrict__ b1, const float *__restrict__ W2,
+                                                                 const float *__restrict__ b2, float *__restrict__ stepg) {
+    __shared__ double shd[TS_THREADS];
+    const int64_t s0 = g ? (int64_t)blockIdx.x * g : 0, r = g ? (B - s0 < g ? B - s0 : g) : B;
+    const float *rn = rng + s0;
+    const float den = ts_group_mean(rn, r, shd) + kEpsRef, rho = ts_softplus(rho_raw[0]);
+    for (int64_t i = threadIdx.x; i < r; i += TS_THREADS) {
+        const float u = rn[i] / den;
+        float o = b2[0];
+#pragma unroll
+        for (int j = 0; j < 32; ++j) o = fmaf(W2[j], fmaxf(ts_step_pre(W1, b1, j, knorm, rho, u), 0.f), o);
+        stepg[s0 + i] = rho * (0.5f + 1.5f * ts_sigmoid(o));
+    }
+}
+
+// sum over the workgroup in a fixed order, returned to every thread
+__device__ __forceinline__ float ts_block_sum(float x, float *sh) {
+    x = wave_sum(x);
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = x;
+    __syncthreads();
+    float s = 0.f;
+    for (int w = 0; w < TS_SLAB; ++w) s += sh[w];
+    return s;
+}
+
+// from g_step [B], with sg_b = sigmoid(o_b), dy_b = g_step_b rho 1.5 sg_b (1 - sg_b), dh_bj = dy_b W2_j [pre_bj > 0],
+// g_u_b = sum_j dh_bj W1[j][2], den = mean + eps, r the group's size:
+//   g_rn_b = ((g_u_b mean - (sum_b' g_u_b' rn_b') / r) + g_u_b eps) / den^2                (= g_u_b / den - mean(g_u rn) / den^2, the
+//            coupling through the mean; in a group of ONE signal the two parts cancel to g_u eps / den^2, which this form keeps --
+//            the two products are rounded separately, so their difference is then an exact zero)
+//   g_rho_raw = softplus'(rho_raw) sum_b g_step_b (0.5 + 1.5 sg_b)                         (leading factor only)
+//   gW2_j = sum_b dy_b relu(pre_bj), gb2 = sum_b dy_b, gb1_j = sum_b dh_bj, gW1[j] = (k/10 gb1_j, rho gb1_j, sum_b dh_bj u_b)
+// Pass 1 gives a thread the signals t, t + 256, ... and leaves dy_b in tmp and g_u_b in g_rn; pass 2 gives thread (j, q) =
+// (t / 8, t % 8) the sums of hidden unit j over the signals q, q + 8, ..., joined over q by a butterfly; pass 3 finishes g_rn.
+// One row of TS_STEP_PAR partials per group.
+__global__ __launch_bounds__(TS_THREADS) void ts_stepsize_bwd_kernel(int64_t B, int64_t g, float knorm, const float *__restrict__ gstepg,
+                                                                     const float *__restrict__ rng, const float *__restrict__ rho_raw,
+                                                                     const float *__restrict__ W1, const float *__restrict__ b1,
+                                                                     const float *__restrict__ W2, const float *__restrict__ b2,
+                                                                     float *grng, float *tmpg, float *__restrict__ part) {
+    __shared__ double shd[TS_THREADS];
+    __shared__ float sh[TS_SLAB];
+    const int64_t s0 = g ? (int64_t)blockIdx.x * g : 0, r = g ? (B - s0 < g ? B - s0 : g) : B;
+    const float *rn = rng + s0, *gstep = gstepg + s0;
+    float *grn = grng + s0, *tmp = tmpg + s0;
+    const float mean = ts_group_mean(rn, r, shd), den = mean + kEpsRef, raw = rho_raw[0], rho = ts_softplus(raw);
+    float a_rho = 0.f, a_b2 = 0.f, a_gm = 0.f;
+    for (int64_t i = threadIdx.x; i < r; i += TS_THREADS) {
+        const float x = rn[i], u = x / den, gs = gstep[i];
+        float o = b2[0];
+#pragma unroll
+        for (int j = 0; j < 32; ++j) o = fmaf(W2[j], fmaxf(ts_step_pre(W1, b1, j, knorm, rho, u), 0.f), o);
+        const float sg = ts_sigmoid(o), dy = gs * rho * 1.5f * ts_dsigmoid(o);
+        float gu = 0.f;
+#pragma unroll
+        for (int j = 0; j < 32; ++j)
+            if (ts_step_pre(W1, b1, j, knorm, rho, u) > 0.f) gu = fmaf(dy * W2[j], W1[3 * j + 2], gu);
+        a_rho = fmaf(gs, 0.5f + 1.5f * sg, a_rho);
+        a_b2 += dy;
+        a_gm += __fmul_rn(gu, x);
+        tmp[i] = dy;
+        grn[i] = gu;
+    }
+    a_rho = ts_block_sum(a_rho, sh);
+    a_b2 = ts_block_sum(a_b2, sh);
+    a_gm = ts_block_sum(a_gm, sh);   // (its barriers also order the writes of tmp before pass 2)
+    float *row = part + (int64_t)blockIdx.x * TS_STEP_PAR;
+    {
+        const int j = threadIdx.x >> 3, q = threadIdx.x & 7;
+        const float w2 = W2[j];
+        float s1 = 0.f, s2 = 0.f, s3 = 0.f;
+        for (int64_t i = q; i < r; i += 8) {
+            const float dy = tmp[i], u = rn[i] / den, pre = ts_step_pre(W1, b1, j, knorm, rho, u);
+            const float dh = pre > 0.f ? dy * w2 : 0.f;
+            s1 += dh;
+            s2 = fmaf(dy, fmaxf(pre, 0.f), s2);
+            s3 = fmaf(dh, u, s3);
+        }
+#pragma unroll
+        for (int o = 4; o > 0; o >>= 1) {
+            s1 += __shfl_xor(s1, o, 64);
+            s2 += __shfl_xor(s2, o, 64);
+            s3 += __shfl_xor(s3, o, 64);
+        }
+        if (q == 0) {
+            row[1 + 3 * j] = knorm * s1;
+            row[2 + 3 * j] = rho * s1;
+            row[3 + 3 * j] = s3;
+            row[97 + j] = s1;
+            row[129 + j] = s2;
+        }
+    }
+    if (threadIdx.x == 0) {
+        row[0] = a_rho * ts_dsoftplus(raw);
+        row[161] = a_b2;
+    }
+    const float gmean = a_gm / (float)r;
+    for (int64_t i = threadIdx.x; i < r; i += TS_THREADS) {
+        const float gu = grn[i];
+        grn[i] = (__fsub_rn(__fmul_rn(gu, mean), gmean) + gu * kEpsRef) / (den * den);
+    }
+}
+
+// ---- launchers ---------------------------------------------------------------------------------------------------------------
+int64_t train_small_rows(int64_t B) { return (B + TS_SLAB - 1) / TS_SLAB; }
+int64_t train_small_groups(int64_t B, int64_t g) { return g > 0 ? (B + g - 1) / g : 1; }
+
+#define TS_LAUNCH(kernel, grid, ...)                                                                \
+    hipLaunchKernelGGL(kernel, dim3((unsigned)(grid)), dim3(TS_THREADS), 0, st, __VA_ARGS__);       \
+    ADMM_HIP(hipGetLastError())
+
+int launch_train_phi(int D, int64_t B, const float2 *y, const float2 *b, const float2 *gcol, const float2 *zcol,
+                     const float *rho_raw, float2 *phi, hipStream_t st) {
+    TS_LAUNCH(ts_phi_kernel, train_small_rows(B), D, B, y, b, gcol, zcol, rho_raw, phi);
+    return ADMMNET_OK;
+}
+
+int launch_train_phi_bwd(int D, int64_t B, const float2 *gphi, const float2 *y, const float2 *b, const float2 *gcol,
+                         const float2 *zcol, const float *rho_raw, float2 *ggcol, float2 *gzcol, float *grho, float *part,
+                         hipStream_t st) {
+    TS_LAUNCH(ts_phi_bwd_kernel, train_small_rows(B), D, B, gphi, y, b, gcol, zcol, rho_raw, ggcol, gzcol, part);
+    return ts_colsum(1, train_small_rows(B), part, grho, st);
+}
+
+int launch_train_hinput(int D, int64_t B, const float *gdg, const float *zdg, const float *rho_raw, float *t, hipStream_t st) {
+    TS_LAUNCH(ts_hinput_kernel, train_small_rows(B), D, B, gdg, zdg, rho_raw, t);
+    return ADMMNET_OK;
+}
+
+int launch_train_hinput_bwd(int D, int64_t B, const float *gt, const float *zdg, const float *rho_raw, float *ggdg, float *gzdg,
+                            float *grho, float *part, hipStream_t st) {
+    TS_LAUNCH(ts_hinput_bwd_kernel, train_small_rows(B), D, B, gt, zdg, rho_raw, ggdg, gzdg, part);
+    return ts_colsum(1, train_small_rows(B), part, grho, st);
+}
+
+int launch_train_hproject(int D, int64_t B, const float *t, const float *m, const float *sigma, const float *pw_raw, float *h,
+                          hipStream_t st) {
+    TS_LAUNCH(ts_hproject_kernel, train_small_rows(B), D, B, t, m, sigma, pw_raw, h);
+    return ADMMNET_OK;
+}
+
+int launch_train_hproject_bwd(int D, int64_t B, const float *gh, const float *t, const float *m, const float *sigma,
+                              const float *pw_raw, float *gt, float *gm, float *gpw, float *part, hipStream_t st) {
+    TS_LAUNCH(ts_hproject_bwd_kernel, train_small_rows(B), D, B, gh, t, m, sigma, pw_raw, gt, gm, part);
+    return ts_colsum(1, train_small_rows(B), part, gpw, st);
+}
+
+int launch_train_eigmap(int n, int64_t B, const float *w, const float *thr, const float *W1, const float *b1, const float *W2,
+                        const float *b2, float *wp, hipStream_t st) {
+    TS_LAUNCH(ts_eigmap_kernel, train_small_rows(B), n, B, w, thr, W1, b1, W2, b2, wp);
+    return ADMMNET_OK;
+}
+
+int launch_train_eigmap_bwd(int n, int64_t B, const float *gwp, const float *w, const float *thr, const float *W1, const float *b1,
+                            const float *W2, const float *b2, float *gw, float *gpar, float *part, hipStream_t st) {
+    TS_LAUNCH(ts_eigmap_bwd_kernel, train_small_rows(B), n, B, gwp, w, thr, W1, b1, W2, b2, gw, part);
+    return ts_colsum(TS_EIG_PAR, train_small_rows(B), part, gpar, st);
+}
+
+int launch_train_stepsize(int64_t B, int64_t g, float knorm, const float *rn, const float *rho_raw, const float *W1,
+                          const float *b1, const float *W2, const float *b2, float *step, hipStream_t st) {
+    TS_LAUNCH(ts_stepsize_kernel, train_small_groups(B, g), B, g, knorm, rn, rho_raw, W1, b1, W2, b2, step);
+    return ADMMNET_OK;
+}
+
+// part: [groups][TS_STEP_PAR] rows, then B floats for dy
+int launch_train_stepsize_bwd(int64_t B, int64_t g, float knorm, const float *gstep, const float *rn, const float *rho_raw,
+                              const float *W1, const float *b1, const float *W2, const float *b2, float *grn, float *gpar,
+                              float *part, hipStream_t st) {
+    const int64_t groups = train_small_groups(B, g);
+    TS_LAUNCH(ts_stepsize_bwd_kernel, groups, B, g, knorm, gstep, rn, rho_raw, W1, b1, W2, b2, grn, part + groups * TS_STEP_PAR,
+              part);
+    return ts_colsum(TS_STEP_PAR, groups, part, gpar, st);
+}
+
+}  // namespace admmnet

@@ -10,7 +10,7 @@
 
 CLI:  python -m admm_net_amd.harness time-net  --layers 5 --runs 1000 --out time_net_5.txt [--checkpoint best_model.pth]
       python -m admm_net_amd.harness time-admm --runs 1000 --out time.txt
-      python -m admm_net_amd.harness train-step --layers 10 --batch 256 --steps 20 [--route fused] [--grid 16x16]   (one JSON line)
+      python -m admm_net_amd.harness train-step --layers 10 --batch 256 --steps 20 [--route fused|full] [--grid 16x16]   (one JSON line)
 """
 from __future__ import annotations
 
@@ -145,7 +145,7 @@ def time_train_step(layers=10, batch=256, steps=20, warmup=3, seed=0, device="cu
     train mode (the differentiable route of admm_net_amd.training: HIP eigensolver + HIP contractions), a phi-alignment
     loss against the classical solver's phi labels (generated on the device, csrc/synth.hip), backward, clip, step.
     The loss is a plain normalised squared error: the reference's loss.py is user code outside this path.
-    ``route``: ``model.train_route`` ("tensor" | "fused"); ``grid`` = (M, N) of another geometry, same recipe.
+    ``route``: ``model.train_route`` ("tensor" | "fused" | "full"); ``grid`` = (M, N) of another geometry, same recipe.
     Returns a dict (seconds per step, signals per second, route, geometry)."""
     from . import PhiEstADMMNet, synth
     dev = torch.device(device)
@@ -201,7 +201,7 @@ def main(argv=None):
     c.add_argument("--layers", type=int, default=10)
     c.add_argument("--batch", type=int, default=256)
     c.add_argument("--steps", type=int, default=20)
-    c.add_argument("--route", choices=("tensor", "fused"), default="tensor")
+    c.add_argument("--route", choices=("tensor", "fused", "full"), default="tensor")
     c.add_argument("--grid", default=f"{NB}x{ND}", help="MxN")
     args = ap.parse_args(argv)
     if args.cmd == "train-step":

@@ -12,7 +12,8 @@ weights); all arithmetic happens in the fused HIP path behind the C ABI of
 Inference (``.eval()`` or ``torch.no_grad()``) runs the fused forward.  In train mode with gradients
 enabled the call goes through ``training.unrolled_forward`` instead: differentiable tensor operations
 around the HIP eigensolver, with the reference's eigenvalue-only gradient (SURVEY.md section 8f rank 2);
-``model.train_route = "fused"`` moves the n^2-sized layer steps of that route onto HIP kernels too.
+``model.train_route = "fused"`` moves the n^2-sized layer steps of that route onto HIP kernels too, ``"full"`` the
+O(B D)-sized ones as well.
 """
 from __future__ import annotations
 
@@ -182,14 +183,16 @@ class _FusedBase(nn.Module):
     def train_route(self) -> str:
         """How the differentiable forward (train mode, ``forward_autograd``) evaluates the n^2-sized steps of a layer:
         ``"tensor"`` (default) as framework tensor operations, ``"fused"`` through the streaming HIP kernels of
-        csrc/train_layer.hip with hand-written backwards (``training.LayerKernels``).  Both use the HIP eigensolver and
-        contractions; inference is not affected.  Not part of the state_dict."""
+        csrc/train_layer.hip with hand-written backwards (``training.LayerKernels``), ``"full"`` as ``"fused"`` and with the
+        O(B D)-sized steps -- phi layer, H layer around its correction_net, eigenvalue map, step-size network -- on the kernels
+        of csrc/train_small.hip too (``training.SmallKernels``).  All use the HIP eigensolver and contractions; inference is
+        not affected.  Not part of the state_dict."""
         return self._train_route
 
     @train_route.setter
     def train_route(self, value: str):
-        if value not in ("tensor", "fused"):
-            raise ValueError(f"train_route must be 'tensor' or 'fused', got {value!r}")
+        if not isinstance(value, str) or value not in ("tensor", "fused", "full"):
+            raise ValueError(f"train_route must be 'tensor', 'fused' or 'full', got {value!r}")
         self._train_route = value
 
     # ---- weights -----------------------------------------------------------
@@ -342,7 +345,7 @@ class _FusedBase(nn.Module):
             raise _lib.AdmmNetError(f"training runs on the GPU: parameters are on {pdev}, expected {dev} "
                                     "(move the model with .to(device) as train.py / trainPhi.py do)")
         out = training.unrolled_forward(self, y.to(dev), b.to(dev), sigma.to(dev), sub_batch=self.sub_batch,
-                                        fused=self.train_route == "fused")
+                                        fused=self.train_route != "tensor", small=self.train_route == "full")
         if isinstance(out, tuple):
             return tuple(o.to(y.device) for o in out)
         return out.to(y.device)

@@ -237,6 +237,170 @@ def train_herm(g, g_col=None, g_dg=None) -> torch.Tensor:
     return S
 
 
+# ---- training route "full": the O(B D)-sized steps of one layer (csrc/train_small.hip) ---------------------------------------
+# [B, D] tensors complex64 / float32; every parameter (rho, projection_weight, threshold, the two small networks) is handed
+# over as the RAW device tensor -- the kernels apply softplus / sigmoid and the ``_bwd`` forms return raw-parameter gradients.
+_TS_PHI, _TS_HINPUT, _TS_HPROJECT, _TS_EIGMAP, _TS_STEPSIZE = range(5)
+
+
+def _small_args(x, name):
+    """(lib, device, B, D) of a [B, D] tensor."""
+    _need_cuda(x, name)
+    if x.dim() != 2:
+        raise ValueError(f"{name} must be [B, D], got {tuple(x.shape)}")
+    return _lib.load(), x.device, x.shape[0], x.shape[1]
+
+
+def _small_partials(lib, step, B, dev, sub_batch=0):
+    need = lib.admmnet_train_small_partials(step, B, sub_batch)
+    if need < 0:
+        raise _lib.AdmmNetError(f"train_small: bad size (B={B}, sub_batch={sub_batch})")
+    return torch.empty(need, dtype=torch.float32, device=dev)
+
+
+def _net(dev, W1, b1, W2, b2, hidden, fan_in):
+    return (_f32(W1, dev, (hidden, fan_in), "W1"), _f32(b1, dev, (hidden,), "b1"), _f32(W2, dev, (1, hidden), "W2"),
+            _f32(b2, dev, (1,), "b2"))
+
+
+def train_phi(y, b, g_col, z_col, rho) -> torch.Tensor:
+    """phi = bs / (1 + r bs) (y / (b + eps) + r g_col + z_col) with r = softplus(rho), bs = |b|^2 + eps (admm_net.py:79-105)."""
+    lib, dev, B, D = _small_args(y, "y")
+    with torch.cuda.device(dev):
+        y, b, g_col, z_col = (_c64(t, dev, (B, D), nm) for t, nm in ((y, "y"), (b, "b"), (g_col, "g_col"), (z_col, "z_col")))
+        rho = _f32(rho, dev, (), "rho")
+        phi = torch.empty_like(y)
+        _lib.check(lib.admmnet_train_phi_c64(D, B, _ptr(y), _ptr(b), _ptr(g_col), _ptr(z_col), _ptr(rho), _ptr(phi), _stream(dev)),
+                   "admmnet_train_phi_c64")
+    return phi
+
+
+def train_phi_bwd(g_phi, y, b, g_col, z_col, rho):
+    """Backward of ``train_phi``: returns (g_gcol, g_zcol [B, D] complex64, g_rho 0-dim, for the raw rho)."""
+    lib, dev, B, D = _small_args(g_phi, "g_phi")
+    with torch.cuda.device(dev):
+        g_phi, y, b, g_col, z_col = (_c64(t, dev, (B, D), nm) for t, nm in ((g_phi, "g_phi"), (y, "y"), (b, "b"), (g_col, "g_col"),
+                                                                           (z_col, "z_col")))
+        rho = _f32(rho, dev, (), "rho")
+        g_gcol, g_zcol = torch.empty_like(y), torch.empty_like(y)
+        g_rho = torch.empty((), dtype=torch.float32, device=dev)
+        part = _small_partials(lib, _TS_PHI, B, dev)
+        _lib.check(lib.admmnet_train_phi_bwd_c64(D, B, _ptr(g_phi), _ptr(y), _ptr(b), _ptr(g_col), _ptr(z_col), _ptr(rho),
+                                                 _ptr(g_gcol), _ptr(g_zcol), _ptr(g_rho), _ptr(part), _stream(dev)),
+                   "admmnet_train_phi_bwd_c64")
+    return g_gcol, g_zcol, g_rho
+
+
+def train_hinput(g_dg, z_dg, rho) -> torch.Tensor:
+    """t = g_dg + z_dg / (softplus(rho) + eps): the H layer's input from the two real diagonals (admm_net.py:150-152)."""
+    lib, dev, B, D = _small_args(g_dg, "g_dg")
+    with torch.cuda.device(dev):
+        g_dg, z_dg, rho = _f32(g_dg, dev, (B, D), "g_dg"), _f32(z_dg, dev, (B, D), "z_dg"), _f32(rho, dev, (), "rho")
+        t = torch.empty_like(g_dg)
+        _lib.check(lib.admmnet_train_hinput_f32(D, B, _ptr(g_dg), _ptr(z_dg), _ptr(rho), _ptr(t), _stream(dev)),
+                   "admmnet_train_hinput_f32")
+    return t
+
+
+def train_hinput_bwd(g_t, z_dg, rho):
+    """Backward of ``train_hinput``: returns (g_gdg, g_zdg [B, D], g_rho 0-dim)."""
+    lib, dev, B, D = _small_args(g_t, "g_t")
+    with torch.cuda.device(dev):
+        g_t, z_dg, rho = _f32(g_t, dev, (B, D), "g_t"), _f32(z_dg, dev, (B, D), "z_dg"), _f32(rho, dev, (), "rho")
+        g_gdg, g_zdg = torch.empty_like(g_t), torch.empty_like(g_t)
+        g_rho = torch.empty((), dtype=torch.float32, device=dev)
+        part = _small_partials(lib, _TS_HINPUT, B, dev)
+        _lib.check(lib.admmnet_train_hinput_bwd_f32(D, B, _ptr(g_t), _ptr(z_dg), _ptr(rho), _ptr(g_gdg), _ptr(g_zdg), _ptr(g_rho),
+                                                    _ptr(part), _stream(dev)), "admmnet_train_hinput_bwd_f32")
+    return g_gdg, g_zdg, g_rho
+
+
+def train_hproject(t, m, sigma, pw) -> torch.Tensor:
+    """h = tc s with tc = t + 0.1 m, c = A max|tc| + sum tc, A = 2 sqrt(D) sigma + sigma^2, s = min(sigmoid(pw) / (c + eps), 1)
+    (admm_net.py:160-194); m = correction_net(t)."""
+    lib, dev, B, D = _small_args(t, "t")
+    with torch.cuda.device(dev):
+        t, m, sigma, pw = _f32(t, dev, (B, D), "t"), _f32(m, dev, (B, D), "m"), _f32(sigma, dev, (B,), "sigma"), _f32(pw, dev, (), "pw")
+        h = torch.empty_like(t)
+        _lib.check(lib.admmnet_train_hproject_f32(D, B, _ptr(t), _ptr(m), _ptr(sigma), _ptr(pw), _ptr(h), _stream(dev)),
+                   "admmnet_train_hproject_f32")
+    return h
+
+
+def train_hproject_bwd(g_h, t, m, sigma, pw):
+    """Backward of ``train_hproject``: returns (g_t, g_m [B, D], g_pw 0-dim)."""
+    lib, dev, B, D = _small_args(g_h, "g_h")
+    with torch.cuda.device(dev):
+        g_h, t, m = _f32(g_h, dev, (B, D), "g_h"), _f32(t, dev, (B, D), "t"), _f32(m, dev, (B, D), "m")
+        sigma, pw = _f32(sigma, dev, (B,), "sigma"), _f32(pw, dev, (), "pw")
+        g_t, g_m = torch.empty_like(t), torch.empty_like(t)
+        g_pw = torch.empty((), dtype=torch.float32, device=dev)
+        part = _small_partials(lib, _TS_HPROJECT, B, dev)
+        _lib.check(lib.admmnet_train_hproject_bwd_f32(D, B, _ptr(g_h), _ptr(t), _ptr(m), _ptr(sigma), _ptr(pw), _ptr(g_t), _ptr(g_m),
+                                                      _ptr(g_pw), _ptr(part), _stream(dev)), "admmnet_train_hproject_bwd_f32")
+    return g_t, g_m, g_pw
+
+
+def train_eigmap(w, thr, W1, b1, W2, b2) -> torch.Tensor:
+    """wp = softplus(w - sigmoid(thr)) sigmoid(W2 relu(W1 |w| + b1) + b2) over [B, n] (admm_net.py:310-334); W1 [16, 1],
+    b1 [16], W2 [1, 16], b2 [1] are value_net's parameters."""
+    lib, dev, B, n = _small_args(w, "w")
+    with torch.cuda.device(dev):
+        w, thr = _f32(w, dev, (B, n), "w"), _f32(thr, dev, (), "thr")
+        W1, b1, W2, b2 = _net(dev, W1, b1, W2, b2, 16, 1)
+        wp = torch.empty_like(w)
+        _lib.check(lib.admmnet_train_eigmap_f32(n, B, _ptr(w), _ptr(thr), _ptr(W1), _ptr(b1), _ptr(W2), _ptr(b2), _ptr(wp),
+                                                _stream(dev)), "admmnet_train_eigmap_f32")
+    return wp
+
+
+def train_eigmap_bwd(g_wp, w, thr, W1, b1, W2, b2):
+    """Backward of ``train_eigmap``: returns (g_w [B, n], g_thr 0-dim, gW1 [16, 1], gb1 [16], gW2 [1, 16], gb2 [1])."""
+    lib, dev, B, n = _small_args(g_wp, "g_wp")
+    with torch.cuda.device(dev):
+        g_wp, w, thr = _f32(g_wp, dev, (B, n), "g_wp"), _f32(w, dev, (B, n), "w"), _f32(thr, dev, (), "thr")
+        W1, b1, W2, b2 = _net(dev, W1, b1, W2, b2, 16, 1)
+        g_w = torch.empty_like(w)
+        g = torch.empty(50, dtype=torch.float32, device=dev)
+        part = _small_partials(lib, _TS_EIGMAP, B, dev)
+        _lib.check(lib.admmnet_train_eigmap_bwd_f32(n, B, _ptr(g_wp), _ptr(w), _ptr(thr), _ptr(W1), _ptr(b1), _ptr(W2), _ptr(b2),
+                                                    _ptr(g_w), _ptr(g), _ptr(part), _stream(dev)), "admmnet_train_eigmap_bwd_f32")
+    return g_w, g[0], g[1:17].reshape(16, 1), g[17:33], g[33:49].reshape(1, 16), g[49:50]
+
+
+def train_stepsize(rn, rho, W1, b1, W2, b2, knorm: float, sub_batch=None) -> torch.Tensor:
+    """step_b = r (0.5 + 1.5 sigmoid(W2 relu(W1 [knorm, r, u_b] + b1) + b2)) with r = softplus(rho), u_b = rn_b / (mean + eps)
+    (admm_net.py:440-474); the mean is over the call or over each group of ``sub_batch`` consecutive signals.  W1 [32, 3],
+    b1 [32], W2 [1, 32], b2 [1] are residual_scale_net's parameters."""
+    _need_cuda(rn, "rn")
+    lib, dev, B = _lib.load(), rn.device, rn.shape[0]
+    with torch.cuda.device(dev):
+        rn, rho = _f32(rn, dev, (B,), "rn"), _f32(rho, dev, (), "rho")
+        W1, b1, W2, b2 = _net(dev, W1, b1, W2, b2, 32, 3)
+        step = torch.empty_like(rn)
+        _lib.check(lib.admmnet_train_stepsize_f32(B, int(sub_batch or 0), float(knorm), _ptr(rn), _ptr(rho), _ptr(W1), _ptr(b1),
+                                                  _ptr(W2), _ptr(b2), _ptr(step), _stream(dev)), "admmnet_train_stepsize_f32")
+    return step
+
+
+def train_stepsize_bwd(g_step, rn, rho, W1, b1, W2, b2, knorm: float, sub_batch=None):
+    """Backward of ``train_stepsize``: returns (g_rn [B] with the coupling through the mean, g_rho 0-dim through the leading
+    factor only, gW1 [32, 3], gb1 [32], gW2 [1, 32], gb2 [1])."""
+    _need_cuda(g_step, "g_step")
+    lib, dev, B = _lib.load(), g_step.device, g_step.shape[0]
+    g = int(sub_batch or 0)
+    with torch.cuda.device(dev):
+        g_step, rn, rho = _f32(g_step, dev, (B,), "g_step"), _f32(rn, dev, (B,), "rn"), _f32(rho, dev, (), "rho")
+        W1, b1, W2, b2 = _net(dev, W1, b1, W2, b2, 32, 3)
+        g_rn = torch.empty_like(rn)
+        out = torch.empty(162, dtype=torch.float32, device=dev)
+        part = _small_partials(lib, _TS_STEPSIZE, B, dev, g)
+        _lib.check(lib.admmnet_train_stepsize_bwd_f32(B, g, float(knorm), _ptr(g_step), _ptr(rn), _ptr(rho), _ptr(W1), _ptr(b1),
+                                                      _ptr(W2), _ptr(b2), _ptr(g_rn), _ptr(out), _ptr(part), _stream(dev)),
+                   "admmnet_train_stepsize_bwd_f32")
+    return g_rn, out[0], out[1:97].reshape(32, 3), out[97:129], out[129:161].reshape(1, 32), out[161:162]
+
+
 def glayer(model, k: int, phi: torch.Tensor, h: torch.Tensor, Z=None):
     """GLayer.forward (admm_net.py:237-354) of layer k of ``model`` plus the Z-layer residual norm.
 

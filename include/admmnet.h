@@ -250,6 +250,68 @@ int admmnet_train_gather_c64(int32_t n, int64_t B, const void *X, void *col, flo
 int admmnet_train_scatter_c64(int32_t n, int64_t B, const void *g_col, const float *g_diag, void *gX, void *stream);
 int admmnet_train_herm_c64(int32_t n, int64_t B, const void *g, const void *g_col, const float *g_diag, void *S, void *stream);
 
+/* Training route "full", the O(B D)-sized steps of one layer and their backwards (csrc/train_small.hip): one kernel per
+ * forward, one (plus a float64 sum over the batch) per backward.  D = M N <= 256, n = D + 1, B >= 1.  [B][D] tensors are dense
+ * and need only their natural alignment (4 bytes float, 8 bytes complex64).  Every PARAMETER pointer (rho, projection_weight,
+ * threshold, W1, b1, W2, b2) is the RAW device value: the kernels apply softplus (beta 1, linear above 20) / sigmoid
+ * themselves, and the backwards return the gradients of the raw values.  eps = 1e-8.  relu'(0) = 0, d|x|/dx = 0 at 0,
+ * the clamp passes the gradient where its argument is <= 1, the gradient of max|.| goes to the lowest index among ties.
+ * Sums over the batch run in a fixed order without atomics (float64 across workgroups): two runs give the same bits.
+ * `partials` is float scratch of admmnet_train_small_partials(step, B, sub_batch) entries (sub_batch read for STEPSIZE only).
+ *   admmnet_train_phi_c64          phi = bs / (1 + rho bs) (y / (b + eps) + rho g_col + z_col), rho = softplus(*rho),
+ *                                  bs = |b|^2 + eps; all tensors complex64 [B][D] -- PhiLayer, admm_net.py:79-105.
+ *   admmnet_train_phi_bwd_c64      from g_phi: g_gcol, g_zcol [B][D] complex64 (torch's convention), g_rho[0].
+ *   admmnet_train_hinput_f32       t = g_dg + z_dg / (softplus(*rho) + eps) -- HLayer's input, :150-152.
+ *   admmnet_train_hinput_bwd_f32   from g_t: g_gdg, g_zdg [B][D], g_rho[0].
+ *   admmnet_train_hproject_f32     tc = t + 0.1 m, c = A max|tc| + sum tc with A = 2 sqrt(D) sigma_b + sigma_b^2,
+ *                                  s = min(sigmoid(*projection_weight) / (c + eps), 1), h = tc s -- :160-194; m is
+ *                                  correction_net(t), evaluated by the caller.
+ *   admmnet_train_hproject_bwd_f32 from g_h: g_t, g_m [B][D], g_pw[0].
+ *   admmnet_train_eigmap_f32       wp = softplus(w - sigmoid(*threshold)) sigmoid(W2 relu(W1 |w| + b1) + b2) over [B][n], the
+ *                                  1 -> 16 -> 1 value_net (W1, b1, W2 [16], b2 [1]) -- GLayer, :310-334.
+ *   admmnet_train_eigmap_bwd_f32   from g_wp: g_w [B][n]; g_params[50] = g_threshold, gW1[16], gb1[16], gW2[16], gb2.
+ *   admmnet_train_stepsize_f32     u_b = rn_b / (mean rn + eps), step_b = rho (0.5 + 1.5 sigmoid(W2 relu(W1 [knorm, rho, u_b]
+ *                                  + b1) + b2)), rho = softplus(*rho), the 3 -> 32 -> 1 residual_scale_net (W1 [32][3], b1,
+ *                                  W2 [32], b2 [1]) -- ZLayer, :440-474.  The mean (float64) is over the call (sub_batch = 0)
+ *                                  or over each group of sub_batch consecutive signals, the last one possibly shorter.
+ *   admmnet_train_stepsize_bwd_f32 from g_step: g_rn [B] including the coupling through the mean; g_params[162] = g_rho
+ *                                  (through the leading factor only: the rho feature is a constant, the reference's .item()),
+ *                                  gW1[32][3], gb1[32], gW2[32], gb2. */
+enum {
+    ADMMNET_TRAIN_PHI = 0,
+    ADMMNET_TRAIN_HINPUT = 1,
+    ADMMNET_TRAIN_HPROJECT = 2,
+    ADMMNET_TRAIN_EIGMAP = 3,
+    ADMMNET_TRAIN_STEPSIZE = 4,
+    ADMMNET_TRAIN_EIGMAP_GRADS = 50,
+    ADMMNET_TRAIN_STEPSIZE_GRADS = 162
+};
+int64_t admmnet_train_small_partials(int32_t step, int64_t B, int64_t sub_batch);
+int admmnet_train_phi_c64(int32_t D, int64_t B, const void *y, const void *b, const void *g_col, const void *z_col,
+                          const float *rho, void *phi, void *stream);
+int admmnet_train_phi_bwd_c64(int32_t D, int64_t B, const void *g_phi, const void *y, const void *b, const void *g_col,
+                              const void *z_col, const float *rho, void *g_gcol, void *g_zcol, float *g_rho, float *partials,
+                              void *stream);
+int admmnet_train_hinput_f32(int32_t D, int64_t B, const float *g_dg, const float *z_dg, const float *rho, float *t,
+                             void *stream);
+int admmnet_train_hinput_bwd_f32(int32_t D, int64_t B, const float *g_t, const float *z_dg, const float *rho, float *g_gdg,
+                                 float *g_zdg, float *g_rho, float *partials, void *stream);
+int admmnet_train_hproject_f32(int32_t D, int64_t B, const float *t, const float *m, const float *sigma,
+                               const float *projection_weight, float *h, void *stream);
+int admmnet_train_hproject_bwd_f32(int32_t D, int64_t B, const float *g_h, const float *t, const float *m, const float *sigma,
+                                   const float *projection_weight, float *g_t, float *g_m, float *g_pw, float *partials,
+                                   void *stream);
+int admmnet_train_eigmap_f32(int32_t n, int64_t B, const float *w, const float *threshold, const float *W1, const float *b1,
+                             const float *W2, const float *b2, float *wp, void *stream);
+int admmnet_train_eigmap_bwd_f32(int32_t n, int64_t B, const float *g_wp, const float *w, const float *threshold, const float *W1,
+                                 const float *b1, const float *W2, const float *b2, float *g_w, float *g_params, float *partials,
+                                 void *stream);
+int admmnet_train_stepsize_f32(int64_t B, int64_t sub_batch, float knorm, const float *rn, const float *rho, const float *W1,
+                               const float *b1, const float *W2, const float *b2, float *step, void *stream);
+int admmnet_train_stepsize_bwd_f32(int64_t B, int64_t sub_batch, float knorm, const float *g_step, const float *rn,
+                                   const float *rho, const float *W1, const float *b1, const float *W2, const float *b2,
+                                   float *g_rn, float *g_params, float *partials, void *stream);
+
 /* Spectrum |phi^H kron(s(f), conj d(tau))|^2 on a (tau, f) grid:
  * peak_search_func / peak_search, utils/peakSearchUtils.py:9-60, evaluated in
  * float64 like the reference.

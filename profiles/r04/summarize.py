@@ -3,8 +3,8 @@
 
 Writes one row per kernel (calls, total / average / min / max ns, share of the GPU kernel time, class) and prints one JSON
 line: dispatches per step and the share of kernel time per class.  Classes: `eig` = the library's eigensolver kernels,
-`contract` = vdvh_kernel / vhsv_kernel, `train_layer` = the fused layer kernels of csrc/train_layer.hip, `framework` =
-everything else (ATen elementwise / copy / reduce / cat kernels, rocBLAS GEMMs of the MLPs, the optimiser).
+`contract` = vdvh_kernel / vhsv_kernel, `train_layer` = the fused layer kernels of csrc/train_layer.hip, `train_small` = the
+O(B D)-sized step kernels of csrc/train_small.hip (route "full"), `framework` = everything else (ATen elementwise / copy / reduce / cat kernels, rocBLAS GEMMs of the MLPs, the optimiser).
 """
 import csv
 import json
@@ -36,6 +36,8 @@ def klass(name):
         return "contract"
     if "admmnet::tl_" in name:
         return "train_layer"
+    if "admmnet::ts_" in name:
+        return "train_small"
     return "eig"      # every other library kernel on this path belongs to admmnet_eigh_c64
 
 
