@@ -10,6 +10,13 @@
 //   P4 secular roots, one thread per root                P7 eigenvectors written straight into LDS as VT[c][rho]
 //   P8 deflation rotations undone, phases applied        then rebuild_from_lds (shared with backrebuild.hip)
 // V never exists in memory; the only HBM traffic is phi, h in and G out.
+//
+// 128 < D <= 256 (AR_FUSED): the image does not fit the LDS, and it is not needed.  With p_i = phi_i / |phi_i| every
+// eigenvector is V[i][c] = p_i X[c][i] with X REAL, so G_ij = p_i conj(p_j) S_ij with S = X^T diag(f) X real symmetric.
+// After P6 the kernel generates X in slabs of AF_KS eigenvectors straight into LDS (one fast division per entry, from
+// O(n) data already there), accumulates all 36 lower 32 x 32 tiles of S as resident f32 matrix-core accumulators and
+// applies the phases in the epilogue (arrow_fused_tail below).  ADMMNET_ARROW_FUSED=0 keeps the former pair: this kernel
+// writing the image to the global VT buffer (AR_GLOBAL), then rebuild.hip's kernel.
 #include <cstdio>
 #include <cstdlib>
 
@@ -21,6 +28,10 @@
 namespace admmnet {
 
 constexpr int AR_THREADS = 256;
+enum ArMode { AR_LDS = 0, AR_GLOBAL = 1, AR_FUSED = 2 };   // where the eigenvectors go: LDS image, global image, slabs
+constexpr int AF_KS = 16;     // eigenvectors per slab of the fused form
+constexpr int AF_W = kMaxD;   // slab row: one float per original index
+static_assert(AR_THREADS == AF_W, "the fused tail gives every thread one column of X");
 
 struct ArShared {
     int k, nrot, conf;
@@ -35,13 +46,202 @@ __host__ __device__ inline size_t ar_lds_bytes(const BrGeom &g) {
     return sizeof(float) * (g.vt_floats() + g.small_floats() + 12 * NP) + sizeof(int) * 5 * NP + sizeof(DcRot) * NP;
 }
 
-// BIG (128 < D <= 256): the eigenvector image does not fit the LDS; it is built in the global VT buffer of the
-// dense path (rows c, planes at 0 / D, pitch 2 D) together with w and w0, and rebuild.hip's kernel consumes it.
-template <bool BIG>
-__global__ __launch_bounds__(AR_THREADS, 1) void arrow_rebuild_kernel(
+// ---- fused tail (AR_FUSED, 128 < D <= 256): S = X^T diag(f) X on the matrix cores, X generated slab by slab in LDS ----
+// In: the solver's LDS arrays after P6 -- fs / w0f / z0s / lamc / tauc in FINAL eigenvalue order c, zh / dl per surviving
+// pole, kidx / perm / rnk / rot of the deflation.  Thread t owns column t of X (original index): entry [c][t] is
+// arrow_vec_entry for a surviving pole, a unit entry in row rnk[slot] for a deflated one.  Rotations (rare) are undone
+// row by row in the slab.  Four waves; wave w holds block rows 7 - w and w of the lower triangle: slot q <= 7 - w is
+// tile (7 - w, q), slot q > 7 - w is tile (w, 8 - q) -- nine 32 x 32 accumulators, the column block of every slot static.
+using f32x16 = __attribute__((ext_vector_type(16))) float;
+
+template <class Mark>
+__device__ __forceinline__ void arrow_fused_tail(int D, int nrot, int64_t b, const float *__restrict__ lw, float *slab,
+                                                 const float *fs, const float *w0f, const float *z0s, const float *lamc,
+                                                 const float *tauc, const float *phr, const float *phim, const float *zh,
+                                                 const float *dl, const int *kidx, int *ipos, const int *perm,
+                                                 const int *rnk, const DcRot *rot, float *redb,
+                                                 const float2 *__restrict__ phi, const float *__restrict__ h,
+                                                 float2 *__restrict__ G, float *__restrict__ rn, int lower_only, Mark mark) {
+    const int n = D + 1, NT = (D + 31) >> 5;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int r32 = lane & 31, kh = lane >> 5;
+    const int Ihi = 7 - wave, Ilo = wave;
+    for (int p = tid; p < D; p += AR_THREADS) ipos[perm[p]] = p;   // inverse permutation
+    __syncthreads();
+    float zi = 0.f, di = 0.f;
+    int cdef = -1;   // deflated pole: the row of its unit entry
+    bool surv = false;
+    if (tid < D) {
+        const int kd = kidx[ipos[tid]];
+        if (kd >= 0) {
+            surv = true;
+            zi = zh[kd];
+            di = dl[kd];
+        } else {
+            cdef = rnk[-kd - 1];
+        }
+    }
+    auto gen = [&](int sl, int buf) {   // rows beyond n and columns beyond D: zeros
+        float *dst = slab + buf * (AF_KS * AF_W) + tid;
+        const int c0 = sl * AF_KS;
+#pragma unroll
+        for (int r = 0; r < AF_KS; ++r) {
+            const int c = c0 + r, cc = min(c, n - 1);
+            const float v = surv ? arrow_vec_entry(zi, di, lamc[cc], tauc[cc], z0s[cc]) : (c == cdef ? 1.f : 0.f);
+            dst[r * AF_W] = (c < n) ? v : 0.f;
+        }
+    };
+    // deflation rotations undone (reverse order, v = G^T v'), one thread per row of the slab -- arrow.hip P8
+    auto unrotate = [&](int sl, int buf) {
+        const int r = tid >> 4;
+        if ((tid & 15) == 0 && sl * AF_KS + r < n) {
+            float *row = slab + (buf * AF_KS + r) * AF_W;
+            for (int q = nrot - 1; q >= 0; --q) {
+                const DcRot rr = rot[q];
+                const int ia = perm[rr.pa], ib = perm[rr.pb];
+                const float a = row[ia], bb = row[ib];
+                row[ia] = rr.c * a - rr.s * bb;
+                row[ib] = rr.s * a + rr.c * bb;
+            }
+        }
+    };
+    // slot -> tile.  Slots 0 .. 4 are always (Ihi, q) and slot 8 is (Ilo, 0); slots 5 .. 7 depend on the wave.
+    const bool hi5 = 5 <= Ihi, hi6 = 6 <= Ihi, hi7 = 7 <= Ihi;
+    const int J5 = hi5 ? 5 : 3, J6 = hi6 ? 6 : 2, J7 = hi7 ? 7 : 1;
+    // D < 256: block rows >= NT are not computed (their slab columns hold zeros)
+    const bool en_hi = Ihi < NT, en_lo = Ilo < NT;
+    const bool en5 = hi5 ? en_hi : en_lo, en6 = hi6 ? en_hi : en_lo, en7 = hi7 ? en_hi : en_lo;
+    f32x16 acc[9];
+#pragma unroll
+    for (int q = 0; q < 9; ++q) acc[q] = f32x16{0};
+    float arow = 0.f;   // sum_c f_c x0_c X[c][tid]
+    const int nslab = (n + AF_KS - 1) / AF_KS;
+    gen(0, 0);
+    __syncthreads();
+    if (nrot > 0) {   // (uniform; the usual case has none)
+        unrotate(0, 0);
+        __syncthreads();
+    }
+    mark(3);
+    // one slab: arrow row, then k-steps of two eigenvectors (lane half kh takes eigenvector c0 + kk + kh)
+    auto consume = [&](int sl) {
+        const int c0 = sl * AF_KS;
+        const float *sb = slab + (sl & 1) * (AF_KS * AF_W);
+#pragma unroll
+        for (int r = 0; r < AF_KS; ++r) arow = fmaf(w0f[min(c0 + r, n)], sb[r * AF_W + tid], arow);   // (w0f[n] = 0)
+        // operands of one k-step, read one step ahead of the MFMAs that use them (sched_barrier pins that order: left
+        // alone, the scheduler hoists every read of the slab to the top and spills the accumulators)
+        struct Step { float x0, x1, x2, x3, x4, x5, x6, x7, ahi, alo; };
+        auto load = [&](int kk) {
+            const float fc = fs[min(c0 + kk + kh, n)];   // (fs[n] = 0; rows beyond n hold zeros)
+            const float *row = sb + (kk + kh) * AF_W + r32;
+            return Step{row[0], row[32], row[64], row[96], row[128], row[32 * J5], row[32 * J6], row[32 * J7],
+                        row[32 * Ihi] * fc, row[32 * Ilo] * fc};
+        };
+        Step cur = load(0);
+#pragma unroll
+        for (int kk = 0; kk < AF_KS; kk += 2) {
+            Step nxt = cur;
+            if (kk + 2 < AF_KS) nxt = load(kk + 2);
+            __builtin_amdgcn_sched_barrier(0);
+            if (c0 + kk < n) {   // (uniform) the last slab is short
+                const float a5 = hi5 ? cur.ahi : cur.alo, a6 = hi6 ? cur.ahi : cur.alo, a7 = hi7 ? cur.ahi : cur.alo;
+                if (en_hi) {
+                    acc[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(cur.ahi, cur.x0, acc[0], 0, 0, 0);
+                    acc[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(cur.ahi, cur.x1, acc[1], 0, 0, 0);
+                    acc[2] = __builtin_amdgcn_mfma_f32_32x32x2f32(cur.ahi, cur.x2, acc[2], 0, 0, 0);
+                    acc[3] = __builtin_amdgcn_mfma_f32_32x32x2f32(cur.ahi, cur.x3, acc[3], 0, 0, 0);
+                    acc[4] = __builtin_amdgcn_mfma_f32_32x32x2f32(cur.ahi, cur.x4, acc[4], 0, 0, 0);
+                }
+                if (en5) acc[5] = __builtin_amdgcn_mfma_f32_32x32x2f32(a5, cur.x5, acc[5], 0, 0, 0);
+                if (en6) acc[6] = __builtin_amdgcn_mfma_f32_32x32x2f32(a6, cur.x6, acc[6], 0, 0, 0);
+                if (en7) acc[7] = __builtin_amdgcn_mfma_f32_32x32x2f32(a7, cur.x7, acc[7], 0, 0, 0);
+                if (en_lo) acc[8] = __builtin_amdgcn_mfma_f32_32x32x2f32(cur.alo, cur.x0, acc[8], 0, 0, 0);
+            }
+            __builtin_amdgcn_sched_barrier(0);
+            cur = nxt;
+        }
+    };
+    for (int sl = 0; sl < nslab; ++sl) {
+        if (sl + 1 < nslab) gen(sl + 1, (sl & 1) ^ 1);
+        consume(sl);
+        __syncthreads();
+        if (nrot > 0 && sl + 1 < nslab) {
+            unrotate(sl + 1, (sl & 1) ^ 1);
+            __syncthreads();
+        }
+    }
+    mark(4);
+    // ---- epilogue: C/D layout col = lane & 31, row = (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5)
+    float2 *Gb = G + b * (int64_t)n * n;
+    float acc2 = 0.f;
+#pragma unroll
+    for (int q = 0; q < 9; ++q) {
+        const bool hi = q <= 4 || (q == 5 && hi5) || (q == 6 && hi6) || (q == 7 && hi7);
+        const int I = hi ? Ihi : Ilo, J = hi ? q : 8 - q;
+        if (I < NT) {
+            const int gj = 32 * J + r32;
+            const float prj = phr[min(gj, D - 1)], pij = phim[min(gj, D - 1)];
+#pragma unroll
+            for (int e = 0; e < 16; ++e) {
+                const int gi = 32 * I + (e & 3) + 8 * (e >> 2) + 4 * kh;
+                if (gi >= gj && gi < D) {
+                    const float S = acc[q][e];
+                    if (gi == gj) {
+                        Gb[(int64_t)gi * n + gj] = make_float2(S, 0.f);
+                        const float d = S - h[b * D + gi];
+                        acc2 += d * d;
+                    } else {
+                        float re, im;
+                        arrow_phase_entry(S, phr[gi], phim[gi], prj, pij, re, im);
+                        Gb[(int64_t)gi * n + gj] = make_float2(re, im);
+                        if (!lower_only) Gb[(int64_t)gj * n + gi] = make_float2(re, -im);
+                        acc2 += 2.f * (re * re + im * im);
+                    }
+                }
+            }
+        }
+    }
+    if (tid < D) {   // arrow row G[D][o] = arow conj(p_o)
+        const int o = tid;
+        const float gr = arow * phr[o], gim = -(arow * phim[o]);
+        Gb[(int64_t)D * n + o] = make_float2(gr, gim);
+        if (!lower_only) Gb[(int64_t)o * n + D] = make_float2(gr, -gim);
+        const float2 p = phi[b * D + o];                   // C[D][o] = conj(phi_o)
+        const float dr = gr - p.x, dm = gim + p.y;
+        acc2 += 2.f * (dr * dr + dm * dm);
+    }
+    if (wave == 0) {   // corner: G[D][D] = sum_c f_c x0_c^2
+        float g00 = 0.f;
+        for (int c = lane; c < n; c += 64) g00 = fmaf(w0f[c], z0s[c], g00);
+        g00 = wave_sum(g00);
+        if (lane == 0) {
+            Gb[(int64_t)D * n + D] = make_float2(g00, 0.f);
+            const float d = g00 - lw[S_CORNER_Z];
+            acc2 += d * d;
+        }
+    }
+    acc2 = wave_sum(acc2);
+    if (lane == 0) redb[wave] = acc2;
+    __syncthreads();
+    if (tid == 0) {
+        float s = 0.f;
+        for (int i = 0; i < AR_THREADS / 64; ++i) s += redb[i];
+        rn[b] = sqrtf(s);
+    }
+    mark(5);
+}
+
+// BIG (AR_GLOBAL, 128 < D <= 256 with ADMMNET_ARROW_FUSED=0): the eigenvector image does not fit the LDS; it is built
+// in the global VT buffer of the dense path (rows c, planes at 0 / D, pitch 2 D) together with w and w0, and rebuild.hip's
+// kernel consumes it.
+template <int MODE>
+__global__ __launch_bounds__(AR_THREADS, MODE == AR_FUSED ? 2 : 1) void arrow_rebuild_kernel(
     int D, const float *__restrict__ lw, const float2 *__restrict__ phi, const float *__restrict__ h,
     float2 *__restrict__ G, float *__restrict__ rn, float *__restrict__ w_out, int32_t *__restrict__ status,
     unsigned long long *__restrict__ ptime, int lower_only, float *VTg, float *__restrict__ w0g) {
+    constexpr bool BIG = MODE == AR_GLOBAL, FUSED = MODE == AR_FUSED;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     __shared__ ArShared sh;
     // developer phase timer (ADMMNET_AR_TIMING=1): cycles of thread 0 between marks
@@ -61,7 +261,7 @@ __global__ __launch_bounds__(AR_THREADS, 1) void arrow_rebuild_kernel(
     const int64_t b = blockIdx.x;
     const float alpha = lw[S_CORNER_G];   // corner of C = 1 / (lambda^2 + eps), admm_net.py:271
     float *VTl = BIG ? VTg + b * ((int64_t)n * 2 * D) : reinterpret_cast<float *>(smem);
-    float *fs = reinterpret_cast<float *>(smem) + (BIG ? 0 : g.vt_floats());
+    float *fs = reinterpret_cast<float *>(smem) + (BIG || FUSED ? 0 : g.vt_floats());
     float *w0f = fs + ((n + 4) & ~3);
     float *z0s = w0f + ((n + 4) & ~3);
     float *rowb = z0s + ((n + 4) & ~3);
@@ -85,6 +285,7 @@ __global__ __launch_bounds__(AR_THREADS, 1) void arrow_rebuild_kernel(
     int *rnk = org + NP;
     int *kidx = rnk + NP;
     DcRot *rot = reinterpret_cast<DcRot *>(kidx + NP);
+    float *lamc = ds, *tauc = zl;   // (FUSED, after P6) origin pole value and tau of the root in final position c
 
     // ---- P0: load, moduli and phases
     if (tid == 0) {
@@ -268,6 +469,11 @@ __global__ __launch_bounds__(AR_THREADS, 1) void arrow_rebuild_kernel(
             z0s[c] = xa;
             if (w_out) w_out[b * n + c] = lam;
             if (BIG) w0g[b * n + c] = xa;
+            if (FUSED) {   // (deflated slots: a divisor no pole value reaches; their x0 = 0 makes the entry an exact zero)
+                const bool root = s <= k && k > 0;
+                lamc[c] = root ? lamd[s] : 3.0e38f;
+                tauc[c] = root ? tau[s] : 0.f;
+            }
         }
         if (tid == 0) {
             fs[n] = 0.f;
@@ -277,6 +483,13 @@ __global__ __launch_bounds__(AR_THREADS, 1) void arrow_rebuild_kernel(
     }
     __syncthreads();
     mark(2);
+    if constexpr (FUSED) {
+        if (__syncthreads_or(bad) && tid == 0 && status) atomicAdd(status, 1);
+        arrow_fused_tail(D, nrot, b, lw, reinterpret_cast<float *>(rot + NP), fs, w0f, z0s, lamc, tauc, phr, phim, zh, dl,
+                         kidx, reinterpret_cast<int *>(hraw), perm, rnk, rot, redb, phi, h, G, rn, lower_only,
+                         [&](int id) { mark(id); });
+        return;
+    }
     // ---- P7: eigenvectors in the rotated real basis, straight into VT[c][column of ORIGINAL index]
     //      thread = original index i (both planes' padding columns are zeroed as well)
     int *ipos = reinterpret_cast<int *>(hraw);   // inverse permutation (hraw is dead since P1)
@@ -347,6 +560,28 @@ __global__ __launch_bounds__(AR_THREADS, 1) void arrow_rebuild_kernel(
 
 bool arrow_rebuild_supported(int D) { return D >= 1 && D <= 256; }
 
+// developer phase timer (ADMMNET_AR_TIMING=1): mean cycles of thread 0 per phase, printed after the launch
+struct ArTiming {
+    unsigned long long *d = nullptr;
+    int begin(hipStream_t st) {
+        static const bool on = getenv("ADMMNET_AR_TIMING") != nullptr;   // developer aid, never on by default
+        if (!on) return ADMMNET_OK;
+        ADMM_HIP(hipMalloc(&d, 16 * sizeof(unsigned long long)));
+        ADMM_HIP(hipMemsetAsync(d, 0, 16 * sizeof(unsigned long long), st));
+        return ADMMNET_OK;
+    }
+    int end(hipStream_t st, int D, int64_t nb, const char *const (&nm)[6]) {
+        if (!d) return ADMMNET_OK;
+        unsigned long long hb[16];
+        ADMM_HIP(hipMemcpyAsync(hb, d, sizeof(hb), hipMemcpyDeviceToHost, st));
+        ADMM_HIP(hipStreamSynchronize(st));
+        ADMM_HIP(hipFree(d));
+        fprintf(stderr, "[arrow_rebuild timing] D=%d nb=%lld  mean cycles per workgroup:\n", D, (long long)nb);
+        for (int i = 0; i < 6; ++i) fprintf(stderr, "   %-14s %10.0f\n", nm[i], (double)hb[i] / (double)nb);
+        return ADMMNET_OK;
+    }
+};
+
 int launch_arrow_rebuild(int D, int64_t nb, const float *lw, const float2 *phi, const float *h, float2 *G, float *rn,
                          float *w_out, int32_t *status, const Ws &ws, hipStream_t st, bool lower_only) {
     if (nb <= 0) return ADMMNET_OK;
@@ -355,13 +590,29 @@ int launch_arrow_rebuild(int D, int64_t nb, const float *lw, const float2 *phi, 
         return ADMMNET_E_ARG;
     }
     const BrGeom g(D);
+    int rc;
+    // D > 128: one kernel, X in LDS slabs and real S on the matrix cores; ADMMNET_ARROW_FUSED=0 keeps the two-kernel form
+    static const bool fused_env = !(getenv("ADMMNET_ARROW_FUSED") && atoi(getenv("ADMMNET_ARROW_FUSED")) == 0);
+    if (D > 128 && fused_env && !ws.skip) {
+        ProfScope _prof(KC_REBUILD, st);
+        const size_t lds = ar_lds_bytes(g) - sizeof(float) * g.vt_floats() + sizeof(float) * 2 * AF_KS * AF_W;
+        ADMM_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(arrow_rebuild_kernel<AR_FUSED>),
+                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        ArTiming tm;
+        if ((rc = tm.begin(st))) return rc;
+        hipLaunchKernelGGL(arrow_rebuild_kernel<AR_FUSED>, dim3((unsigned)nb), dim3(AR_THREADS), lds, st, D, lw, phi, h, G,
+                           rn, w_out, status, tm.d, lower_only ? 1 : 0, (float *)nullptr, (float *)nullptr);
+        ADMM_HIP(hipGetLastError());
+        static const char *const nm[6] = {"sort+deflate", "roots", "zhat+rank+norm", "first slab", "slabs + S", "epilogue"};
+        return tm.end(st, D, nb, nm);
+    }
     if (D > 128) {   // eigenvectors to the global image, then the dense path's rebuild kernel
         {
             ProfScope _prof(KC_REBUILD, st);
             const size_t lds = ar_lds_bytes(g) - sizeof(float) * g.vt_floats();
-            ADMM_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(arrow_rebuild_kernel<true>),
+            ADMM_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(arrow_rebuild_kernel<AR_GLOBAL>),
                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            hipLaunchKernelGGL(arrow_rebuild_kernel<true>, dim3((unsigned)nb), dim3(AR_THREADS), lds, st, D, lw, phi, h,
+            hipLaunchKernelGGL(arrow_rebuild_kernel<AR_GLOBAL>, dim3((unsigned)nb), dim3(AR_THREADS), lds, st, D, lw, phi, h,
                                G, rn, ws.w, status, (unsigned long long *)nullptr, lower_only ? 1 : 0, ws.VT, ws.w0);
             ADMM_HIP(hipGetLastError());
         }
@@ -369,27 +620,15 @@ int launch_arrow_rebuild(int D, int64_t nb, const float *lw, const float2 *phi, 
     }
     ProfScope _prof(KC_REBUILD, st);
     const size_t lds = ar_lds_bytes(g);
-    ADMM_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(arrow_rebuild_kernel<false>),
+    ADMM_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(arrow_rebuild_kernel<AR_LDS>),
                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    static const bool timing = getenv("ADMMNET_AR_TIMING") != nullptr;   // developer aid, never on by default
-    unsigned long long *ptime = nullptr;
-    if (timing) {
-        ADMM_HIP(hipMalloc(&ptime, 16 * sizeof(unsigned long long)));
-        ADMM_HIP(hipMemsetAsync(ptime, 0, 16 * sizeof(unsigned long long), st));
-    }
-    hipLaunchKernelGGL(arrow_rebuild_kernel<false>, dim3((unsigned)nb), dim3(AR_THREADS), lds, st, D, lw, phi, h, G, rn,
-                       w_out, status, ptime, lower_only ? 1 : 0, (float *)nullptr, (float *)nullptr);
+    ArTiming tm;
+    if ((rc = tm.begin(st))) return rc;
+    hipLaunchKernelGGL(arrow_rebuild_kernel<AR_LDS>, dim3((unsigned)nb), dim3(AR_THREADS), lds, st, D, lw, phi, h, G, rn,
+                       w_out, status, tm.d, lower_only ? 1 : 0, (float *)nullptr, (float *)nullptr);
     ADMM_HIP(hipGetLastError());
-    if (timing) {
-        unsigned long long hb[16];
-        ADMM_HIP(hipMemcpyAsync(hb, ptime, sizeof(hb), hipMemcpyDeviceToHost, st));
-        ADMM_HIP(hipStreamSynchronize(st));
-        ADMM_HIP(hipFree(ptime));
-        static const char *nm[6] = {"sort+deflate", "roots", "zhat+rank+norm", "vectors", "G tiles", "arrow+norm"};
-        fprintf(stderr, "[arrow_rebuild timing] D=%d nb=%lld  mean cycles per workgroup:\n", D, (long long)nb);
-        for (int i = 0; i < 6; ++i) fprintf(stderr, "   %-14s %10.0f\n", nm[i], (double)hb[i] / (double)nb);
-    }
-    return ADMMNET_OK;
+    static const char *const nm[6] = {"sort+deflate", "roots", "zhat+rank+norm", "vectors", "G tiles", "arrow+norm"};
+    return tm.end(st, D, nb, nm);
 }
 
 }  // namespace admmnet

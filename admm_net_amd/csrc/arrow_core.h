@@ -196,4 +196,18 @@ HD float arrow_zhat(int k, int i, FA d, FA lamd, FA tau, int sub = 0, int G = 1,
     return sqrtf(fabsf(red(w)));
 }
 
+// ---- the eigenvectors as a REAL matrix X times phases (first G-layer at D > 128, arrow.hip: arrow_fused_tail) ----------
+// Component of surviving pole (zeta-hat zi, value di) in the normalised eigenvector of the root lam = lamd + tau whose
+// arrow component is x0.  A deflated slot is passed as (lamd = 3e38, tau = 0, x0 = 0): an exact zero.
+HD float arrow_vec_entry(float zi, float di, float lamd, float tau, float x0) {
+    return fdiv_fast(zi, (lamd - di) + tau) * x0;
+}
+
+// G_ij = p_i conj(p_j) S_ij for i != j (p = unit phases, S real symmetric); the mirrored entry is its exact conjugate
+HD void arrow_phase_entry(float S, float pri, float pii, float prj, float pij, float &re, float &im) {
+    const float cr = pri * prj + pii * pij, ci = pii * prj - pri * pij;
+    re = S * cr;
+    im = S * ci;
+}
+
 }  // namespace admmnet
