@@ -52,8 +52,6 @@ __host__ __device__ inline size_t ar_lds_bytes(const BrGeom &g) {
 // arrow_vec_entry for a surviving pole, a unit entry in row rnk[slot] for a deflated one.  Rotations (rare) are undone
 // row by row in the slab.  Four waves; wave w holds block rows 7 - w and w of the lower triangle: slot q <= 7 - w is
 // tile (7 - w, q), slot q > 7 - w is tile (w, 8 - q) -- nine 32 x 32 accumulators, the column block of every slot static.
-using f32x16 = __attribute__((ext_vector_type(16))) float;
-
 template <class Mark>
 __device__ __forceinline__ void arrow_fused_tail(int D, int nrot, int64_t b, const float *__restrict__ lw, float *slab,
                                                  const float *fs, const float *w0f, const float *z0s, const float *lamc,
@@ -203,33 +201,12 @@ __device__ __forceinline__ void arrow_fused_tail(int D, int nrot, int64_t b, con
             }
         }
     }
-    if (tid < D) {   // arrow row G[D][o] = arow conj(p_o)
-        const int o = tid;
-        const float gr = arow * phr[o], gim = -(arow * phim[o]);
-        Gb[(int64_t)D * n + o] = make_float2(gr, gim);
-        if (!lower_only) Gb[(int64_t)o * n + D] = make_float2(gr, -gim);
-        const float2 p = phi[b * D + o];                   // C[D][o] = conj(phi_o)
-        const float dr = gr - p.x, dm = gim + p.y;
-        acc2 += 2.f * (dr * dr + dm * dm);
-    }
-    if (wave == 0) {   // corner: G[D][D] = sum_c f_c x0_c^2
-        float g00 = 0.f;
-        for (int c = lane; c < n; c += 64) g00 = fmaf(w0f[c], z0s[c], g00);
-        g00 = wave_sum(g00);
-        if (lane == 0) {
-            Gb[(int64_t)D * n + D] = make_float2(g00, 0.f);
-            const float d = g00 - lw[S_CORNER_Z];
-            acc2 += d * d;
-        }
-    }
-    acc2 = wave_sum(acc2);
-    if (lane == 0) redb[wave] = acc2;
-    __syncthreads();
-    if (tid == 0) {
-        float s = 0.f;
-        for (int i = 0; i < AR_THREADS / 64; ++i) s += redb[i];
-        rn[b] = sqrtf(s);
-    }
+    // arrow row G[D][o] = arow conj(p_o): thread o holds its own arow (D <= AR_THREADS)
+    rebuild_tail<AR_THREADS / 64>(acc2, 0, n, D, Gb, phi + b * D, lw[S_CORNER_Z], w0f, z0s, redb, rn + b, lower_only,
+                                  [&](int o, float &gr, float &gim) {
+                                      gr = arow * phr[o];
+                                      gim = -(arow * phim[o]);
+                                  });
     mark(5);
 }
 
@@ -463,7 +440,7 @@ __global__ __launch_bounds__(AR_THREADS, MODE == AR_FUSED ? 2 : 1) void arrow_re
             x0[s] = xa;
             const int c = rnk[s];
             const float lam = vals[s];
-            const float f = br_eig_map(lam, thr, vn);
+            const float f = eig_map(lam, thr, vn);
             fs[c] = f;
             w0f[c] = xa * f;
             z0s[c] = xa;

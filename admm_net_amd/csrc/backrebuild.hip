@@ -24,8 +24,6 @@
 
 namespace admmnet {
 
-using f32x16 = __attribute__((ext_vector_type(16))) float;
-
 constexpr int BR_THREADS = 256;
 constexpr int BR_KS = 16;          // K rows per slab
 constexpr int BR_NCT = 5;          // eigenvector tiles: n <= 129 + padding
@@ -80,18 +78,7 @@ __global__ __launch_bounds__(BR_THREADS, 1) void back_rebuild_kernel(
 
     {   // eigenvalue map (independent of phase A: overlaps its first loads)
         const LayerLayout L{D};
-        const float thr = lw[S_THR];
-        const float *vn = lw + L.off_vn();
-        for (int c = tid; c <= n; c += BR_THREADS) {
-            float f = 0.f, z0 = 0.f;
-            if (c < n) {
-                f = br_eig_map(wv[b * n + c], thr, vn);
-                z0 = w0v[b * n + c];
-            }
-            fs[c] = f;
-            w0f[c] = z0 * f;
-            z0s[c] = z0;
-        }
+        rebuild_fill_f<BR_THREADS>(n, n + 1, wv + b * n, w0v + b * n, lw[S_THR], lw + L.off_vn(), fs, w0f, z0s);
     }
 
     // ---------------- phase A: VT = W^T-rows x QT on the matrix cores, K streamed through LDS ------

@@ -19,21 +19,11 @@
 #include <string.h>
 
 #include "common.h"
+#include "rebuild_core.h"
 
 namespace admmnet {
 
-using f32x16 = __attribute__((ext_vector_type(16))) float;
 constexpr int RB_THREADS = 256;
-
-__device__ __forceinline__ float eig_map(float w, float thr, const float *vn) {
-    // vn: w1[16] b1[16] w2[16] b2[1]
-    const float base = softplus_f(w - thr);
-    const float a = fabsf(w);
-    float acc = vn[48];
-#pragma unroll
-    for (int j = 0; j < 16; ++j) acc = fmaf(vn[32 + j], fmaxf(fmaf(vn[j], a, vn[16 + j]), 0.f), acc);
-    return base * sigmoid_f(acc);
-}
 
 __global__ __launch_bounds__(RB_THREADS) void rebuild_kernel(int D, const float *__restrict__ lw,
                                                              const float *__restrict__ QV,
@@ -53,18 +43,7 @@ __global__ __launch_bounds__(RB_THREADS) void rebuild_kernel(int D, const float 
     float *rowb = z0s + ((n + 4) & ~3);            // [2D] last-row staging
     float *redb = rowb + 2 * D;                    // [8]
     const LayerLayout L{D};
-    const float thr = lw[S_THR];
-    const float *vn = lw + L.off_vn();
-    for (int c = tid; c <= n; c += RB_THREADS) {
-        float f = 0.f, z0 = 0.f;
-        if (c < n) {
-            f = eig_map(wv[b * n + c], thr, vn);
-            z0 = w0v[b * n + c];
-        }
-        fs[c] = f;
-        w0f[c] = z0 * f;
-        z0s[c] = z0;
-    }
+    rebuild_fill_f<RB_THREADS>(n, n + 1, wv + b * n, w0v + b * n, lw[S_THR], lw + L.off_vn(), fs, w0f, z0s);
     __syncthreads();
 
     const float *VT = QV + b * ((int64_t)n * 2 * D);
@@ -77,10 +56,8 @@ __global__ __launch_bounds__(RB_THREADS) void rebuild_kernel(int D, const float 
     const int ntiles = NT * (NT + 1) / 2;
     const int r = lane & 31, kh = lane >> 5;
     for (int t = wave; t < ntiles; t += RB_THREADS / 64) {
-        // decode lower-triangular tile index t -> (I, J), I >= J
-        int I = 0;
-        while ((I + 1) * (I + 2) / 2 <= t) ++I;
-        const int J = t - I * (I + 1) / 2;
+        int I, J;
+        tri_tile(t, I, J);
         const int i0 = 32 * I, j0 = 32 * J;
         const bool iv = (i0 + r) < D, jv = (j0 + r) < D;
         const int xo = iv ? (i0 + r) : 0, yo = jv ? (j0 + r) : 0;
@@ -103,25 +80,7 @@ __global__ __launch_bounds__(RB_THREADS) void rebuild_kernel(int D, const float 
             aIm = __builtin_amdgcn_mfma_f32_32x32x2f32(xi, yr, aIm, 0, 0, 0);
             aIm = __builtin_amdgcn_mfma_f32_32x32x2f32(-xr, yi, aIm, 0, 0, 0);
         }
-        // epilogue: C/D layout col = lane&31, row = (reg&3) + 8*(reg>>2) + 4*(lane>>5)
-#pragma unroll
-        for (int q = 0; q < 16; ++q) {
-            const int gi = i0 + (q & 3) + 8 * (q >> 2) + 4 * kh;
-            const int gj = j0 + r;
-            if (gi < D && gj < D && gi >= gj) {
-                float re = aRe[q], im = aIm[q];
-                if (gi == gj) {
-                    im = 0.f;
-                    Gb[(int64_t)gi * n + gj] = make_float2(re, 0.f);
-                    const float d = re - h[b * D + gi];
-                    acc2 += d * d;
-                } else {
-                    Gb[(int64_t)gi * n + gj] = make_float2(re, im);
-                    if (!lower_only) Gb[(int64_t)gj * n + gi] = make_float2(re, -im);
-                    acc2 += 2.f * (re * re + im * im);
-                }
-            }
-        }
+        acc2 = rebuild_tile_store(aRe, aIm, i0, j0, D, n, Gb, h + b * D, lower_only, acc2);
     }
 
     // ---- arrow row (perm row 0 = original row D): G'[0][j] = sum_c w0_c f_c conj(V[j][c])
@@ -132,32 +91,11 @@ __global__ __launch_bounds__(RB_THREADS) void rebuild_kernel(int D, const float 
         rowb[rho] = a;
     }
     __syncthreads();
-    for (int o = tid; o < D; o += RB_THREADS) {
-        const float gr = rowb[o], gim = -rowb[D + o];     // G[D][o]
-        Gb[(int64_t)D * n + o] = make_float2(gr, gim);
-        if (!lower_only) Gb[(int64_t)o * n + D] = make_float2(gr, -gim);
-        const float2 p = phi[b * D + o];                  // C[D][o] = conj(phi_o)
-        const float dr = gr - p.x, di = gim + p.y;
-        acc2 += 2.f * (dr * dr + di * di);
-    }
-    if (wave == 0) {   // corner: G'[0][0] = sum_c f_c w0_c^2
-        float g00 = 0.f;
-        for (int c = lane; c < n; c += 64) g00 = fmaf(w0f[c], z0s[c], g00);
-        g00 = wave_sum(g00);
-        if (lane == 0) {
-            Gb[(int64_t)D * n + D] = make_float2(g00, 0.f);
-            const float d = g00 - lw[S_CORNER_Z];
-            acc2 += d * d;
-        }
-    }
-    acc2 = wave_sum(acc2);
-    if (lane == 0) redb[wave] = acc2;
-    __syncthreads();
-    if (tid == 0) {
-        float s = 0.f;
-        for (int i = 0; i < RB_THREADS / 64; ++i) s += redb[i];
-        rn[b] = sqrtf(s);
-    }
+    rebuild_tail<RB_THREADS / 64>(acc2, 0, n, D, Gb, phi + b * D, lw[S_CORNER_Z], w0f, z0s, redb, rn + b, lower_only,
+                                  [&](int o, float &gr, float &gim) {   // G[D][o]
+                                      gr = rowb[o];
+                                      gim = -rowb[D + o];
+                                  });
 }
 
 // Generic eigh output: V[b][row][col] row-major complex from VT / w0; used by admmnet_eigh_c64.

@@ -9,10 +9,9 @@
 // image = 16 KB) is staged through LDS once and feeds every tile, so V^T is read exactly once and G written once.
 // The arrow row (sum_c w0_c f_c conj(V[j][c])) rides along on the staged slabs.
 #include "common.h"
+#include "rebuild_core.h"
 
 namespace admmnet {
-
-using f32x16 = __attribute__((ext_vector_type(16))) float;
 
 constexpr int RG_D = 256;
 constexpr int RG_THREADS = 512;
@@ -20,15 +19,6 @@ constexpr int RG_KS = 8;                    // eigenvectors per slab
 constexpr int RG_PITCH = 2 * RG_D + 32;     // floats per staged row: the two k-halves of a wave read rows 32 banks apart
 constexpr int RG_NT = 8;                    // 32-blocks per dimension
 constexpr int RG_TILES = RG_NT * (RG_NT + 1) / 2;   // 36
-
-__device__ __forceinline__ float rg_eig_map(float w, float thr, const float *vn) {   // rebuild.hip: eig_map
-    const float base = softplus_f(w - thr);
-    const float a = fabsf(w);
-    float acc = vn[48];
-#pragma unroll
-    for (int j = 0; j < 16; ++j) acc = fmaf(vn[32 + j], fmaxf(fmaf(vn[j], a, vn[16 + j]), 0.f), acc);
-    return base * sigmoid_f(acc);
-}
 
 __global__ __launch_bounds__(RG_THREADS, 2) void rebuild_big_kernel(const float *__restrict__ lw,
                                                                     const float *__restrict__ VTg,
@@ -52,18 +42,7 @@ __global__ __launch_bounds__(RG_THREADS, 2) void rebuild_big_kernel(const float 
     const int64_t b = blockIdx.x;
     if (skip && skip[b] == 0) return;   // (uniform) this matrix' G is already there: spectral.hip
     const LayerLayout L{Da};
-    const float thr = lw[S_THR];
-    const float *vn = lw + L.off_vn();
-    for (int c = tid; c < 264; c += RG_THREADS) {
-        float f = 0.f, z0 = 0.f;
-        if (c < n) {
-            f = rg_eig_map(wv[b * n + c], thr, vn);
-            z0 = w0v[b * n + c];
-        }
-        fs[c] = f;
-        w0f[c] = z0 * f;
-        z0s[c] = z0;
-    }
+    rebuild_fill_f<RG_THREADS>(n, 264, wv + b * n, w0v + b * n, lw[S_THR], lw + L.off_vn(), fs, w0f, z0s);
     const float *VT = VTg + b * ((int64_t)n * 2 * D);
     float2 *Gb = G + b * (int64_t)na * na;
 
@@ -72,10 +51,10 @@ __global__ __launch_bounds__(RG_THREADS, 2) void rebuild_big_kernel(const float 
 #pragma unroll
     for (int s = 0; s < 5; ++s) {
         const int t = wave + 8 * s;
-        int I = 0;
-        while ((I + 1) * (I + 2) / 2 <= t) ++I;
+        int I, J;
+        tri_tile(t, I, J);
         tI[s] = (t < RG_TILES) ? I : 0;
-        tJ[s] = (t < RG_TILES) ? t - I * (I + 1) / 2 : 0;
+        tJ[s] = (t < RG_TILES) ? J : 0;
     }
     const int nmine = (wave + 32 < RG_TILES) ? 5 : 4;   // (uniform) waves 0 .. 3 own five tiles
     f32x16 aRe[5], aIm[5];
@@ -136,61 +115,20 @@ __global__ __launch_bounds__(RG_THREADS, 2) void rebuild_big_kernel(const float 
         if (sl + 1 < NSLAB) lstore(buf ^ 1);
         __syncthreads();
     }
-    // ---- epilogue: C/D layout col = lane & 31, row = (q & 3) + 8 (q >> 2) + 4 (lane >> 5)
     float acc2 = 0.f;
 #pragma unroll
-    for (int s = 0; s < 5; ++s) {
-        if (s < nmine) {
-            const int i0 = 32 * tI[s], j0 = 32 * tJ[s];
-#pragma unroll
-            for (int q = 0; q < 16; ++q) {
-                const int gi = i0 + (q & 3) + 8 * (q >> 2) + 4 * kh, gj = j0 + r32;
-                if (gi >= gj && gi < Da) {
-                    const float re = aRe[s][q], im = aIm[s][q];
-                    if (gi == gj) {
-                        Gb[(int64_t)gi * na + gj] = make_float2(re, 0.f);
-                        const float d = re - h[b * Da + gi];
-                        acc2 += d * d;
-                    } else {
-                        Gb[(int64_t)gi * na + gj] = make_float2(re, im);
-                        if (!lower_only) Gb[(int64_t)gj * na + gi] = make_float2(re, -im);
-                        acc2 += 2.f * (re * re + im * im);
-                    }
-                }
-            }
-        }
-    }
+    for (int s = 0; s < 5; ++s)
+        if (s < nmine) acc2 = rebuild_tile_store(aRe[s], aIm[s], 32 * tI[s], 32 * tJ[s], Da, na, Gb, h + b * Da, lower_only, acc2);
     // arrow row G[D][o] = (arow[o], -arow[D + o]): exchange the two planes through LDS
     float *rowb = &slab[0][0][0];
     rowb[tid] = arow;
     __syncthreads();
-    if (tid < Da) {
-        const int o = tid;
-        const float gr = rowb[o], gim = -rowb[D + o];
-        Gb[(int64_t)Da * na + o] = make_float2(gr, gim);
-        if (!lower_only) Gb[(int64_t)o * na + Da] = make_float2(gr, -gim);
-        const float2 p = phi[b * Da + o];                 // C[D][o] = conj(phi_o)
-        const float dr = gr - p.x, di = gim + p.y;
-        acc2 += 2.f * (dr * dr + di * di);
-    }
-    if (wave == 7) {   // corner: G[D][D] = sum_c f_c w0_c^2
-        float g00 = 0.f;
-        for (int c = lane; c < n; c += 64) g00 = fmaf(w0f[c], z0s[c], g00);
-        g00 = wave_sum(g00);
-        if (lane == 0) {
-            Gb[(int64_t)Da * na + Da] = make_float2(g00, 0.f);
-            const float d = g00 - lw[S_CORNER_Z];
-            acc2 += d * d;
-        }
-    }
-    acc2 = wave_sum(acc2);
-    if (lane == 0) redb[wave] = acc2;
-    __syncthreads();
-    if (tid == 0) {
-        float s = 0.f;
-        for (int i = 0; i < 8; ++i) s += redb[i];
-        rn[b] = sqrtf(s);
-    }
+    // (the corner in wave 7: waves 0 .. 3 hold five tiles)
+    rebuild_tail<RG_THREADS / 64>(acc2, 7, n, Da, Gb, phi + b * Da, lw[S_CORNER_Z], w0f, z0s, redb, rn + b, lower_only,
+                                  [&](int o, float &gr, float &gim) {
+                                      gr = rowb[o];
+                                      gim = -rowb[D + o];
+                                  });
 }
 
 bool rebuild_big_supported(int image_dim) { return image_dim == RG_D; }

@@ -8,6 +8,7 @@
 //   fs[c] = f(lambda_c) with fs[n] = 0, w0f[c] = w0_c f_c, z0s[c] = w0_c (w0 = arrow-row entries of V)
 #pragma once
 #include "common.h"
+#include "rebuild_core.h"
 
 namespace admmnet {
 
@@ -22,17 +23,6 @@ struct BrGeom {
     __host__ __device__ size_t small_floats() const { return (size_t)3 * ((n + 4) & ~3) + 2 * Dp + 8; }
 };
 
-// learned eigenvalue map  f(lambda) = softplus(lambda - sigmoid(thr)) * value_net(|lambda|)
-// (/root/reference/admm_net.py:310-334); vn: w1[16] b1[16] w2[16] b2[1], thr already sigmoid-ed
-__device__ __forceinline__ float br_eig_map(float w, float thr, const float *vn) {
-    const float base = softplus_f(w - thr);
-    const float a = fabsf(w);
-    float acc = vn[48];
-#pragma unroll
-    for (int j = 0; j < 16; ++j) acc = fmaf(vn[32 + j], fmaxf(fmaf(vn[j], a, vn[16 + j]), 0.f), acc);
-    return base * sigmoid_f(acc);
-}
-
 template <class Mark>
 __device__ __forceinline__ void rebuild_from_lds(const BrGeom &g, int64_t b, const float *__restrict__ lw,
                                                  const float *VTl, const float *fs, const float *w0f,
@@ -40,7 +30,6 @@ __device__ __forceinline__ void rebuild_from_lds(const BrGeom &g, int64_t b, con
                                                  const float2 *__restrict__ phi, const float *__restrict__ h,
                                                  float2 *__restrict__ G, float *__restrict__ rn, Mark mark,
                                                  int lower_only = 0) {
-    using f32x16 = __attribute__((ext_vector_type(16))) float;
     constexpr int BR_THREADS = 256;
     const int D = g.D, n = g.n, NT = g.NT, Dp = g.Dp, VP = g.VP;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -50,9 +39,8 @@ __device__ __forceinline__ void rebuild_from_lds(const BrGeom &g, int64_t b, con
     float acc2 = 0.f;
     const int ntiles = NT * (NT + 1) / 2;
     for (int t = wave; t < ntiles; t += BR_THREADS / 64) {
-        int I = 0;
-        while ((I + 1) * (I + 2) / 2 <= t) ++I;
-        const int J = t - I * (I + 1) / 2;
+        int I, J;
+        tri_tile(t, I, J);
         const int i0 = 32 * I, j0 = 32 * J;
         f32x16 aRe = {0}, aIm = {0};
         // K-steps in groups of 4, software pipelined: the 20 LDS reads of group g + 1 are issued before
@@ -115,24 +103,7 @@ __device__ __forceinline__ void rebuild_from_lds(const BrGeom &g, int64_t b, con
             __builtin_amdgcn_sched_barrier(0);
         }
         if (gq < ngrp) mfma_part(0, U, fx, xr, xi, yr, yi);
-        // epilogue: C/D layout col = lane&31, row = (reg&3) + 8*(reg>>2) + 4*(lane>>5)
-#pragma unroll
-        for (int q = 0; q < 16; ++q) {
-            const int gi = i0 + (q & 3) + 8 * (q >> 2) + 4 * kh;
-            const int gj = j0 + l32;
-            if (gi < D && gj < D && gi >= gj) {
-                const float re = aRe[q], im = aIm[q];
-                if (gi == gj) {
-                    Gb[(int64_t)gi * n + gj] = make_float2(re, 0.f);
-                    const float d = re - h[b * D + gi];
-                    acc2 += d * d;
-                } else {
-                    Gb[(int64_t)gi * n + gj] = make_float2(re, im);
-                    if (!lower_only) Gb[(int64_t)gj * n + gi] = make_float2(re, -im);   // (state kept as lower triangle)
-                    acc2 += 2.f * (re * re + im * im);
-                }
-            }
-        }
+        acc2 = rebuild_tile_store(aRe, aIm, i0, j0, D, n, Gb, h + b * D, lower_only, acc2);
     }
 
     mark(4);
@@ -152,33 +123,12 @@ __device__ __forceinline__ void rebuild_from_lds(const BrGeom &g, int64_t b, con
         }
     }
     __syncthreads();
-    for (int o = tid; o < D; o += BR_THREADS) {
-        const float gr = rowb[o], gim = -rowb[Dp + o];     // G[D][o]
-        Gb[(int64_t)D * n + o] = make_float2(gr, gim);
-        if (!lower_only) Gb[(int64_t)o * n + D] = make_float2(gr, -gim);
-        const float2 p = phi[b * D + o];                   // C[D][o] = conj(phi_o)
-        const float dr = gr - p.x, di = gim + p.y;
-        acc2 += 2.f * (dr * dr + di * di);
-    }
-    if (wave == 0) {   // corner: G'[0][0] = sum_c f_c w0_c^2
-        float g00 = 0.f;
-        for (int c = lane; c < n; c += 64) g00 = fmaf(w0f[c], z0s[c], g00);
-        g00 = wave_sum(g00);
-        if (lane == 0) {
-            Gb[(int64_t)D * n + D] = make_float2(g00, 0.f);
-            const float d = g00 - lw[S_CORNER_Z];
-            acc2 += d * d;
-        }
-    }
-    acc2 = wave_sum(acc2);
-    if (lane == 0) redb[wave] = acc2;
-    __syncthreads();
+    rebuild_tail<BR_THREADS / 64>(acc2, 0, n, D, Gb, phi + b * D, lw[S_CORNER_Z], w0f, z0s, redb, rn + b, lower_only,
+                                  [&](int o, float &gr, float &gim) {   // G[D][o]
+                                      gr = rowb[o];
+                                      gim = -rowb[Dp + o];
+                                  });
     mark(5);
-    if (tid == 0) {
-        float s = 0.f;
-        for (int i = 0; i < BR_THREADS / 64; ++i) s += redb[i];
-        rn[b] = sqrtf(s);
-    }
 }
 
 }  // namespace admmnet

@@ -27,6 +27,7 @@
 #include <stdlib.h>
 
 #include "common.h"
+#include "rebuild_core.h"
 
 namespace admmnet {
 
@@ -289,9 +290,8 @@ __global__ __launch_bounds__(SP_THREADS) void sp_square_kernel(int n, const floa
     const int nt = (n + 31) >> 5, ntri = nt * (nt + 1) / 2;
     float fro = 0.f;
     for (int t = wave; t < ntri; t += SP_THREADS / 64) {
-        int I = 0;
-        while ((I + 1) * (I + 2) / 2 <= t) ++I;
-        const int J = t - I * (I + 1) / 2;
+        int I, J;
+        tri_tile(t, I, J);
         const int i = 32 * I + r32, j = 32 * J + r32;
         const bool iv = i < n, jv = j < n;
         f32x16 aRe = {0}, aIm = {0};
@@ -325,18 +325,6 @@ __global__ __launch_bounds__(SP_THREADS) void sp_square_kernel(int n, const floa
 }
 
 // ---- F5: checks, then G = a0 I + a1 E + a2 E^2 + sum_k (f(lam_k) - a0) v_k v_k^H and ||G - C_z||_F ------------------------
-__device__ inline double sp_eig_map(double w, double thr, const float *vn) {   // rebuild_lds.h: br_eig_map, in double
-    const double x = w - thr;
-    const double base = x > 20.0 ? x : log1p(exp(x));
-    const double a = fabs(w);
-    double acc = vn[48];
-    for (int j = 0; j < 16; ++j) {
-        const double pre = (double)vn[j] * a + (double)vn[16 + j];
-        acc += (double)vn[32 + j] * (pre > 0.0 ? pre : 0.0);
-    }
-    return base / (1.0 + exp(-acc));
-}
-
 __global__ __launch_bounds__(SP_THREADS) void sp_assemble_kernel(int D, const float *__restrict__ lw, const float2 *__restrict__ Eg,
                                                                  const float2 *__restrict__ E2g, const float2 *__restrict__ vecs,
                                                                  const double *__restrict__ vals, const float2 *__restrict__ phi,
@@ -371,12 +359,12 @@ __global__ __launch_bounds__(SP_THREADS) void sp_assemble_kernel(int D, const fl
         if (good && !(delta < 0.05 * fmin(g0, g1))) good = false, why = 2;
         double a0 = 0, a1 = 0, a2 = 0, f0k = 0, f1k = 0;
         if (good) {
-            const double fm = sp_eig_map(c - delta, thr, vn), fc = sp_eig_map(c, thr, vn), fp = sp_eig_map(c + delta, thr, vn);
+            const double fm = eig_map_f64(c - delta, thr, vn), fc = eig_map_f64(c, thr, vn), fp = eig_map_f64(c + delta, thr, vn);
             a0 = fc;
             a1 = (fp - fm) / (2.0 * delta);
             a2 = (fp - 2.0 * fc + fm) / (2.0 * delta * delta);
-            f0k = sp_eig_map(l0, thr, vn);
-            f1k = sp_eig_map(l1, thr, vn);
+            f0k = eig_map_f64(l0, thr, vn);
+            f1k = eig_map_f64(l1, thr, vn);
             // the quadratic through (c - d, c, c + d) against f at interior points: a smooth f misses it by ~ f''' d^3 / 16 there
             // (the truncation error of the series on the bulk is of that size); a kink of f (|lam| = 0, a ReLU of value_net)
             // or a bulk too wide for two terms shows as a miss
@@ -385,7 +373,7 @@ __global__ __launch_bounds__(SP_THREADS) void sp_assemble_kernel(int D, const fl
             const double ts[6] = {-0.75, -0.5, -0.25, 0.25, 0.5, 0.75};
             for (int q = 0; q < 6; ++q) {
                 const double t = ts[q] * delta;
-                miss = fmax(miss, fabs(sp_eig_map(c + t, thr, vn) - (a0 + a1 * t + a2 * t * t)));
+                miss = fmax(miss, fabs(eig_map_f64(c + t, thr, vn) - (a0 + a1 * t + a2 * t * t)));
             }
             if (!(miss <= (double)tol * scale)) good = false, why = 4;
         }

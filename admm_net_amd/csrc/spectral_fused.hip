@@ -23,6 +23,7 @@
 #include <type_traits>
 
 #include "common.h"
+#include "rebuild_core.h"
 #include "lane_reduce.h"
 
 namespace admmnet {
@@ -95,18 +96,6 @@ __device__ __forceinline__ void sf_block_sum8(float &a, float &b, float &c, floa
         s[q] = v;
     }
     a = s[0]; b = s[1]; c = s[2]; d = s[3]; e = s[4]; f = s[5];
-}
-
-__device__ inline double sf_eig_map(double w, double thr, const float *vn) {   // rebuild_lds.h: br_eig_map, in double
-    const double x = w - thr;
-    const double base = x > 20.0 ? x : log1p(exp(x));
-    const double a = fabs(w);
-    double acc = vn[48];
-    for (int j = 0; j < 16; ++j) {
-        const double pre = (double)vn[j] * a + (double)vn[16 + j];
-        acc += (double)vn[32 + j] * (pre > 0.0 ? pre : 0.0);
-    }
-    return base / (1.0 + exp(-acc));
 }
 
 struct SfCarve {
@@ -447,13 +436,7 @@ __global__ __launch_bounds__(64 * W, W == 12 ? 1 : 3) void sp_fused_kernel(int D
     // ---- P2 + P3: E in bf16 slabs through LDS, E^H E on the matrix cores ------------------------------------------------------
     int tI[TPW], tJ[TPW];
 #pragma unroll
-    for (int s = 0; s < TPW; ++s) {
-        const int t = wave * TPW + s;
-        int I = 0;
-        while ((I + 1) * (I + 2) / 2 <= t) ++I;
-        tI[s] = I;
-        tJ[s] = t - I * (I + 1) / 2;
-    }
+    for (int s = 0; s < TPW; ++s) tri_tile(wave * TPW + s, tI[s], tJ[s]);
     f32x16 accRe[TPW], accIm[TPW];
 #pragma unroll
     for (int s = 0; s < TPW; ++s) {
@@ -680,7 +663,7 @@ __global__ __launch_bounds__(64 * W, W == 12 ? 1 : 3) void sp_fused_kernel(int D
         if (lane < 9) arg = c + ts[lane] * delta;
         else if (lane == 9) arg = dl0;
         else if (lane == 10) arg = dl1;
-        const double fv = sf_eig_map(arg, thr, vn);
+        const double fv = eig_map_f64(arg, thr, vn);
         auto bcast = [&](int src) {
             const long long bits = __builtin_bit_cast(long long, fv);
             const int lo = __builtin_amdgcn_readlane((int)(bits & 0xffffffffll), src);

@@ -21,6 +21,7 @@
 // Every sum runs in a fixed order -- per thread serially, across a wave by xor-shuffles, across the waves serially from
 // LDS -- and the sum over the batch (g_r) in float64 by one workgroup, as rn_sum_kernel (zstep.hip) does.  No atomics.
 #include "common.h"
+#include "rebuild_core.h"
 
 namespace admmnet {
 
@@ -38,12 +39,6 @@ __device__ __forceinline__ float2 tl_c(int i, int j, int D, const float2 *__rest
         return make_float2(p.x, -p.y);
     }
     return make_float2(0.f, 0.f);
-}
-
-__device__ __forceinline__ void tl_tile_of_pair(int t, int &I, int &J) {
-    I = 0;
-    while ((I + 1) * (I + 2) / 2 <= t) ++I;
-    J = t - I * (I + 1) / 2;
 }
 
 // sum over the workgroup in a fixed order; every thread must call it; the result is valid in thread 0
@@ -87,7 +82,7 @@ __global__ __launch_bounds__(TL_PAIR_THREADS) void tl_matrix_kernel(int n, int n
     __shared__ TlTiles T;
     const int64_t b = blockIdx.x / npairs;
     int I, J;
-    tl_tile_of_pair((int)(blockIdx.x - b * npairs), I, J);
+    tri_tile((int)(blockIdx.x - b * npairs), I, J);
     const int D = n - 1;
     const float2 *phi = phig + b * D, *Z = Zg + b * (int64_t)n * n;
     const float *h = hg + b * D;
@@ -124,7 +119,7 @@ __global__ __launch_bounds__(TL_PAIR_THREADS) void tl_matrix_bwd_kernel(int n, i
     __shared__ float sh[TL_PAIR_THREADS / 64];
     const int64_t b = blockIdx.x / npairs;
     int I, J;
-    tl_tile_of_pair((int)(blockIdx.x - b * npairs), I, J);
+    tri_tile((int)(blockIdx.x - b * npairs), I, J);
     const int D = n - 1;
     const float2 *gA = gAg + b * (int64_t)n * n, *Z = Zg + b * (int64_t)n * n;
     float2 *gZ = gZg + b * (int64_t)n * n, *gphi = gphig + b * D;
@@ -375,7 +370,7 @@ __global__ __launch_bounds__(TL_PAIR_THREADS) void tl_herm_kernel(int n, int npa
     __shared__ TlTiles T;
     const int64_t b = blockIdx.x / npairs;
     int I, J;
-    tl_tile_of_pair((int)(blockIdx.x - b * npairs), I, J);
+    tri_tile((int)(blockIdx.x - b * npairs), I, J);
     const int D = n - 1;
     const bool sc = gcolg != nullptr;
     const float2 *g = gg + b * (int64_t)n * n, *gcol = sc ? gcolg + b * D : nullptr;

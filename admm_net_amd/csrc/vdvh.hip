@@ -13,6 +13,7 @@
 // tile, lane half -> k).  V of one matrix is 82 KB at the reference's n = 101 and 528 KB at n = 257: it stays in the L2
 // across the tiles of its workgroup.
 #include "common.h"
+#include "rebuild_core.h"
 
 namespace admmnet {
 
@@ -30,9 +31,8 @@ __global__ __launch_bounds__(VD_THREADS) void vdvh_kernel(int n, const float2 *_
     const int r32 = lane & 31, kh = lane >> 5;
     const int nt = (n + 31) >> 5, ntri = nt * (nt + 1) / 2;
     for (int t = wave; t < ntri; t += VD_THREADS / 64) {
-        int I = 0;
-        while ((I + 1) * (I + 2) / 2 <= t) ++I;
-        const int J = t - I * (I + 1) / 2;
+        int I, J;
+        tri_tile(t, I, J);
         const int i = 32 * I + r32, j = 32 * J + r32;
         const bool iv = i < n, jv = j < n;
         const float2 *xi_p = V + (int64_t)(iv ? i : 0) * n, *yj_p = V + (int64_t)(jv ? j : 0) * n;

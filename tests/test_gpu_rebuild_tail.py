@@ -1,0 +1,133 @@
+"""GPU: the tail every G-layer route ends in (csrc/rebuild_core.h: f-table, tile store, arrow row, corner, ||G - C||_F),
+one case per kernel that carries it, at the smallest geometry where its tile bookkeeping can still go wrong.
+
+ops.glayer runs layer 0 (Z = None: the arrowhead routes of arrow.hip) and layer 1 (the dense eigen-pipeline:
+backrebuild.hip at D <= 128, rebuild_big.hip above) on phi, h, Z of the float64 oracle trace.  Bounds are those of
+tests/test_gpu_parity.py for the same quantities: G within 2e-5 of max|G|, G exactly Hermitian with an exactly real
+diagonal, sorted eigenvalues within 1e-5; rn within 2e-5 of ||G_returned - C||_F recomputed in float64 from the returned
+G, which isolates the tail from the eigensolver.  Two child processes (the switches are read once per process) reach
+arrow_rebuild_kernel<AR_GLOBAL> + rebuild_big_kernel (ADMMNET_ARROW_FUSED=0) and rebuild_kernel
+(ADMMNET_SPECTRAL=0 ADMMNET_TRIDIAG_BIG=sweep).
+
+Seeds: the oracle's own float32 evaluation of these layers on the same inputs stays within half of each bound of its
+float64 evaluation (checked on the CPU when the seeds were chosen: G <= 1.4e-6, w <= 3.9e-7, rn <= 4.9e-6 over all
+six; at 16 x 16 the seeds 45 - 47 gave a float32 rn 3e-5 from its own G and were passed over)."""
+import functools
+import json
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+import torch
+import torch.nn.functional as F
+
+import admm_net_amd as A
+from admm_net_amd import ops, synth
+from oracle import admm_net_ref as R
+
+pytestmark = pytest.mark.gpu
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+B, K = 3, 3
+# (Nb, Nd): D = Nb * Nd
+GEOMS = {
+    "2x4": (2, 4),       # D = 8: one tile, three of four waves hold none
+    "5x8": (5, 8),       # D = 40: 3 tiles, heavy = 3, a single wave takes the arrow row in rebuild_from_lds
+    "10x10": (10, 10),   # D = 100: 10 tiles, heavy = 2, ragged last tile, D % 32 != 0
+    "8x16": (8, 16),     # D = 128: full tiles, the largest LDS-resident case
+    "10x13": (10, 13),   # D = 130: padded image, Da < D in rebuild_big_kernel, NT = 5 in arrow_fused_tail
+    "16x16": (16, 16),   # D = 256: all 36 tiles
+}
+BIG = ["10x13", "16x16"]
+SEED = {"2x4": 40, "5x8": 41, "10x10": 42, "8x16": 43, "10x13": 44, "16x16": 49}
+
+
+def rel(a, b):
+    return float(np.abs(a - b).max() / np.abs(b).max())
+
+
+@functools.lru_cache(maxsize=None)
+def case(name):
+    """Weights, model and the float64 oracle trace of one geometry (computed once, never modified)."""
+    Nb, Nd = GEOMS[name]
+    sd = R.make_weights(Nb, Nd, K, seed=SEED[name], head=False, perturb=0.3)
+    m = A.PhiEstADMMNet(M=Nb, N=Nd, num_layers=K).eval()
+    m.load_state_dict(sd)
+    y, b, s, _ = synth.make_batch(B, Nb, Nd, seed=SEED[name] + 100)
+    tr = []
+    R.forward(sd, torch.from_numpy(y), torch.from_numpy(b), torch.from_numpy(s), Nb, Nd, K, dtype="f64", trace=tr)
+    return sd, m, tr
+
+
+def layer_inputs(tr, k):
+    """phi, h, Z that layer k's G-layer reads, in the precision the kernels take them."""
+    Zin = None if k == 0 else tr[k - 1]["Z"].to(torch.complex64)
+    return tr[k]["phi"].to(torch.complex64), tr[k]["h"].float(), Zin
+
+
+def rn_from_G(sd, k, phi, h, G):
+    """||G - C||_F in float64 from a returned G; C = [[diag h, phi], [phi^H, corner_z]] of the Z-layer."""
+    corner = float(1.0 / (F.softplus(sd[f"zLayers.{k}.lambda_param"].double()) ** 2 + R.EPS))
+    C = R.block_matrix(phi.to(torch.complex128), h.double(), corner)
+    return torch.linalg.norm(torch.from_numpy(G).to(torch.complex128) - C, dim=(1, 2)).numpy()
+
+
+def measure(name):
+    """Layers 0 and 1 of one geometry through ops.glayer: the figures the assertions are about."""
+    sd, m, tr = case(name)
+    dev = torch.device("cuda:0")
+    out = {}
+    for k in (0, 1):
+        phi, h, Zin = layer_inputs(tr, k)
+        G, w, rn = ops.glayer(m, k, phi.to(dev), h.to(dev), None if Zin is None else Zin.to(dev))
+        G, w, rn = G.cpu().numpy(), w.cpu().numpy(), rn.cpu().numpy().astype(np.float64)
+        n = G.shape[1]
+        out[f"layer{k}"] = dict(
+            G=rel(G, tr[k]["G"].numpy()),
+            hermitian=bool(np.array_equal(G, G.conj().transpose(0, 2, 1))),
+            real_diag=bool(np.all(G[:, np.arange(n), np.arange(n)].imag == 0)),
+            w=rel(np.sort(w, 1), tr[k]["w"].numpy()),
+            rn=float(np.abs(rn / rn_from_G(sd, k, phi, h, G) - 1.0).max()))
+    return out
+
+
+def check(name, res, what):
+    for layer, r in res.items():
+        print(what, name, layer, r)
+        assert r["G"] < 2e-5, (what, name, layer, r)
+        assert r["hermitian"] and r["real_diag"], (what, name, layer, r)
+        assert r["w"] < 1e-5, (what, name, layer, r)
+        assert r["rn"] < 2e-5, (what, name, layer, r)
+
+
+@pytest.mark.parametrize("name", list(GEOMS))
+def test_rebuild_tail_default_routes(name):
+    assert torch.cuda.is_available(), "these tests need the MI355X"
+    check(name, measure(name), "default")
+
+
+CHILD = r"""
+import json, sys
+sys.path.insert(0, {root!r}); sys.path.insert(0, {tests!r})
+import test_gpu_rebuild_tail as T
+print("RESULT " + json.dumps({{name: T.measure(name) for name in T.BIG}}))
+"""
+
+SWITCHES = {
+    "arrow_unfused": {"ADMMNET_ARROW_FUSED": "0"},                                   # AR_GLOBAL + rebuild_big_kernel
+    "rebuild_tiles": {"ADMMNET_SPECTRAL": "0", "ADMMNET_TRIDIAG_BIG": "sweep"},      # rebuild_kernel
+}
+
+
+@pytest.mark.parametrize("switch", list(SWITCHES))
+def test_rebuild_tail_switched_routes(switch):
+    env = dict(os.environ, **SWITCHES[switch])
+    p = subprocess.run([sys.executable, "-c", CHILD.format(root=ROOT, tests=os.path.join(ROOT, "tests"))], env=env,
+                       capture_output=True, text=True, timeout=600)
+    assert p.returncode == 0, p.stderr[-2000:]
+    line = [ln for ln in p.stdout.splitlines() if ln.startswith("RESULT ")][-1]
+    res = json.loads(line[len("RESULT "):])
+    assert sorted(res) == sorted(BIG)
+    for name in BIG:
+        check(name, res[name], switch)

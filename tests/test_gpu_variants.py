@@ -48,6 +48,7 @@ VARIANTS = {
     "full_storage": dict(EIGEN, ADMMNET_LEAN="0"),
     # 128 < D <= 256: per-reflector register sweep + explicit Q + Q W; D = 192 runs at its own size instead of padded to 256
     "sweep_big": dict(EIGEN, ADMMNET_TRIDIAG_BIG="sweep"),
+    "rebuild_tiles": dict(EIGEN, ADMMNET_REBUILD="tiles"),      # D = 256: rebuild_kernel instead of rebuild_big_kernel
     "explicit_q": dict(EIGEN, ADMMNET_BACK="q"),               # D = 256: panel tridiagonalisation, explicit Q + Q W
     "panel_one_stage": dict(EIGEN, ADMMNET_PN_SPLIT="0"),      # D = 256: the whole panel reduction in the 8-wave kernel
     "panel_two_stages": dict(EIGEN, ADMMNET_PN_SPLIT="8"),     # D = 256: panels 0..7 | 8..15 (default: 0..7 | 8..11 | 12..15)
