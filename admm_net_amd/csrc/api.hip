@@ -105,17 +105,7 @@ static int64_t group_count(const admmnet_cfg *cfg, int64_t B) {
     return g > 0 ? (B + g - 1) / g : 1;
 }
 
-// Tridiagonal eigensolver: divide & conquer (default) or QL + rotation replay (ADMMNET_EIG=ql).
-bool use_dc() {
-    static int v = -1;
-    if (v < 0) {
-        const char *e = getenv("ADMMNET_EIG");
-        v = (e && !strcmp(e, "ql")) ? 0 : 1;
-    }
-    return v == 1;
-}
-
-int64_t pick_chunk(const admmnet_cfg *cfg, int64_t B) {
+static int64_t pick_chunk(const admmnet_cfg *cfg, int64_t B) {
     int64_t c = cfg->chunk > 0 ? cfg->chunk : 8192;
     if (c > B) c = B;
     if (c < 1) c = 1;
@@ -134,27 +124,10 @@ struct Carver {
     }
 };
 
-// 128 < D < 256 ("padded route"): the layer matrix is embedded in the D = 256 pipeline as A' = diag(A, 0) -- arrow-first
-// order puts the padding behind the last row of the D x D block.  The reflectors of A have exact zeros in the padded rows,
-// the padded columns reduce to identity reflectors (tau = 0), so T' = diag(T, 0) exactly; the padded poles deflate (z = 0)
-// with unit eigenvectors, the block reflectors leave those alone, and G' = V' f(L') V'^H = diag(G, f(0) I): the rebuild
-// stores the leading block.  Costs the D = 256 flops whatever D is, still several times faster than the per-reflector
-// sweep (tridiag_big.hip) it replaces as the default; any switch that leaves the panel / D&C / block-reflector route
-// (ADMMNET_TRIDIAG_BIG=sweep, ADMMNET_BACK=q, ADMMNET_TRIDIAG=lds, ADMMNET_EIG=ql) also leaves the padding.
-// Below kPadMin the sweep at the geometry's own size is faster than 256-sized work (measured on MI355X, K = 16, 4096
-// signals, padded vs sweep per forward: D = 160 306 vs 280 ms, D = 176 312 vs 368 ms, D = 192 319 vs 396 ms) -- ADMMNET_PAD_MIN
-// moves the switch.
-static int pad_min() {
-    // (with the matrix-function route on -- the default -- the eigen-pipeline only sees the matrices it rejects, and the route needs
-    //  the lower-triangle state of the padded pipeline: every 128 < D < 256 is then padded, the crossover no longer matters)
-    static const int v = getenv("ADMMNET_PAD_MIN") ? atoi(getenv("ADMMNET_PAD_MIN")) : (use_spectral() ? 129 : 176);
-    return v;
-}
-int eig_dim(int D) { return (D > 128 && D >= pad_min() && D < 256 && use_wy_back(256)) ? 256 : D; }
-
-static void carve_chunk(Carver &c, int Dact, int64_t chunk, Ws *ws) {
-    const int D = eig_dim(Dact);
-    const int64_t n = D + 1;
+// lays out exactly r.buffers behind the buffers every route has, all for r.eig_dim
+static void carve_chunk(Carver &c, const Route &r, int64_t chunk, Ws *ws) {
+    const int D = r.eig_dim;
+    const int64_t n = D + 1, na = r.D + 1;
     ws->chunk = chunk;
     ws->cap = ((int64_t)kLogCapMul * n * n + 64 * n + 64 + 7) & ~(int64_t)7;   // whole 64-byte groups
     ws->Mbuf = c.take<float2>(chunk * ((int64_t)D * D + D + 1));
@@ -165,44 +138,19 @@ static void carve_chunk(Carver &c, int Dact, int64_t chunk, Ws *ws) {
     ws->w = c.take<float>(chunk * n);
     ws->w0 = c.take<float>(chunk * n);
     ws->logn = c.take<int>(chunk * 2);
-    ws->Tfac = nullptr;
-    ws->Tail = nullptr;
-    ws->Wmap = nullptr;
-    if (use_dc()) {
-        ws->Wdc = c.take<float>(chunk * 3 * n * n);
-        ws->VT = c.take<float>(chunk * n * 2 * D);
-        if (tridiag_panel_supported(D)) {
-            ws->Tfac = c.take<float2>(chunk * 17 * 256);
-            ws->Tail = c.take<float2>(chunk * tridiag_panel_tail_elems());
-            ws->Wmap = c.take<int2>(chunk * n);
-        }
-        ws->log = nullptr;
-    } else {
-        ws->log = c.take<LogRec>(chunk * ws->cap);
-        ws->Wdc = nullptr;
-        ws->VT = ws->QV;   // the rotation replay works in place
-    }
-    ws->spec_mat = nullptr;
-    ws->spec_vec = nullptr;
-    ws->spec_val = nullptr;
-    ws->spec_flag = nullptr;
+    const auto has = [&](Buffer b) { return (r.buffers & b) != 0; };
+    ws->Wdc = has(BUF_WDC) ? c.take<float>(chunk * 3 * n * n) : nullptr;
+    ws->VT = has(BUF_WDC) ? c.take<float>(chunk * n * 2 * D) : ws->QV;   // (the rotation replay works in place)
+    ws->Tfac = has(BUF_PANEL) ? c.take<float2>(chunk * 17 * 256) : nullptr;
+    ws->Tail = has(BUF_PANEL) ? c.take<float2>(chunk * tridiag_panel_tail_elems()) : nullptr;
+    ws->Wmap = has(BUF_PANEL) ? c.take<int2>(chunk * n) : nullptr;
+    ws->log = has(BUF_LOG) ? c.take<LogRec>(chunk * ws->cap) : nullptr;
+    // (in the layer's own dimension: the fast path never sees the padded image; the multi-kernel form keeps A / E and E^2 in memory)
+    ws->spec_mat = has(BUF_SPEC_MAT) ? c.take<float2>(2 * chunk * na * na) : nullptr;
+    ws->spec_vec = has(BUF_SPEC_MAT) ? c.take<float2>(chunk * 2 * na) : nullptr;
+    ws->spec_val = has(BUF_SPEC_MAT) ? c.take<double>(chunk * 8) : nullptr;
+    ws->spec_flag = has(BUF_SPEC_FLAG) ? c.take<int>(chunk) : nullptr;
     ws->skip = nullptr;
-    if (use_spectral()) {   // (in the layer's own dimension: the fast path never sees the padded image)
-        const int64_t na = Dact + 1;
-        if (!use_spectral_fused()) {   // (the multi-kernel form keeps A / E and E^2 in memory)
-            ws->spec_mat = c.take<float2>(2 * chunk * na * na);
-            ws->spec_vec = c.take<float2>(chunk * 2 * na);
-            ws->spec_val = c.take<double>(chunk * 8);
-        }
-        ws->spec_flag = c.take<int>(chunk);
-    }
-}
-
-int64_t eig_chunk_bytes(int D, int64_t chunk) {
-    Carver c{nullptr};
-    Ws ws;
-    carve_chunk(c, D, chunk, &ws);
-    return c.off;
 }
 
 // Two chunks in flight (ADMMNET_STREAMS=2): the per-chunk kernel sequence prep -> tridiagonalisation -> D&C -> back-transform ->
@@ -210,11 +158,6 @@ int64_t eig_chunk_bytes(int D, int64_t chunk) {
 // vector-ALU-bound kernels of one chunk and the matrix-core-bound kernels of the other can share the CUs wherever their
 // registers and LDS admit both.  Only for batches of at least two chunks; the state (G, Z, phi, h, rn) is shared -- the
 // chunks touch disjoint slices of it.
-static bool two_streams() {
-    static const bool on = getenv("ADMMNET_STREAMS") && atoi(getenv("ADMMNET_STREAMS")) == 2;
-    return on;
-}
-
 struct ChunkStreams {   // per device, created on first use (non-blocking streams: they order against the caller's by events)
     std::mutex mu;
     hipStream_t s[2] = {nullptr, nullptr};
@@ -236,15 +179,7 @@ static int chunk_streams(hipStream_t out[2]) {
     return ADMMNET_OK;
 }
 
-static void carve_chunk(Carver &c, int Dact, int64_t chunk, Ws *ws);
-
-// the second set of chunk buffers (same layout as the first; state pointers copied from `ws`)
-static void carve_second_set(Carver &c, int D, const Ws &ws, Ws *ws2) {
-    *ws2 = ws;
-    carve_chunk(c, D, ws.chunk, ws2);
-}
-
-int carve_workspace(const admmnet_cfg *cfg, int64_t B, void *base, int64_t bytes, Ws *ws, bool state) {
+static int carve_workspace(const admmnet_cfg *cfg, int64_t B, void *base, int64_t bytes, Ws *ws, bool state) {
     const int D = cfg->M * cfg->N;
     const int64_t n = D + 1;
     Carver c{reinterpret_cast<char *>(base)};
@@ -261,12 +196,13 @@ int carve_workspace(const admmnet_cfg *cfg, int64_t B, void *base, int64_t bytes
         ws->mean = c.take<float>(ng > 4 ? ng : 4);
         ws->headkv = c.take<float>((int64_t)2 * D * 128);
     }
-    carve_chunk(c, D, pick_chunk(cfg, B), ws);
+    const Route r = route_for(D, switches());
+    carve_chunk(c, r, pick_chunk(cfg, B), ws);
     ws->set2_offset = 0;
-    if (state && two_streams() && B > ws->chunk) {   // room for a second chunk in flight
+    if (state && switches().two_streams && B > ws->chunk) {   // room for a second chunk in flight: a second set, same layout
         ws->set2_offset = c.off;
         Ws tmp;
-        carve_second_set(c, D, *ws, &tmp);
+        carve_chunk(c, r, ws->chunk, &tmp);
     }
     ws->total_bytes = c.off;
     if (base && bytes < c.off) {
@@ -276,53 +212,38 @@ int carve_workspace(const admmnet_cfg *cfg, int64_t B, void *base, int64_t bytes
     return ADMMNET_OK;
 }
 
-// The G-layer can take V = Q W inside its rebuild kernel (backrebuild.hip, D <= 128, D&C path):
-// then the eigen-solve stops at (Q, W) and V never goes through memory.  ADMMNET_FUSE_BACK=0 keeps
-// the separate kernels (tuning / debugging aid).
-static bool fuse_back(int D, const Ws &ws) {
-    static const bool on = !(getenv("ADMMNET_FUSE_BACK") && atoi(getenv("ADMMNET_FUSE_BACK")) == 0);
-    return on && ws.Wdc && back_rebuild_supported(D);
-}
+// What the G-layer of a chunk reads and writes (Zlow: the lower-triangle Z of ST_LEAN storage, for the tridiagonalisation's loader)
+struct GLayerIO {
+    const float *lw = nullptr;
+    const float2 *phi = nullptr;
+    const float *h = nullptr;
+    const float2 *Zlow = nullptr;
+    float2 *G = nullptr;
+    float *rn = nullptr, *w_out = nullptr;
+    bool lower_only = false;
+};
 
-// The first G-layer (Z = 0) sees a plain arrowhead matrix: arrow.hip solves it directly in O(n^2)
-// (fused with the rebuild for D <= 128, through the global eigenvector image above).  ADMMNET_ARROW=0 sends it
-// down the dense path like every other layer.
-static bool use_arrow(int D) {
-    static const bool on = !(getenv("ADMMNET_ARROW") && atoi(getenv("ADMMNET_ARROW")) == 0);
-    return on && arrow_rebuild_supported(D);
-}
-
-// "Lean" state (D <= 128, register-resident tridiagonalisation, arrowhead first layer): G and Z are kept as
-// lower triangles and the tridiagonalisation forms A = C - Z / rho itself, so the prep kernel only streams the
-// lazy Z update (no A image is written or read).  ADMMNET_LEAN=0 keeps full storage + the image.
-static bool use_lean(int D) {
-    static const bool on = !(getenv("ADMMNET_LEAN") && atoi(getenv("ADMMNET_LEAN")) == 0);
-    static const bool lds = getenv("ADMMNET_TRIDIAG") && !strcmp(getenv("ADMMNET_TRIDIAG"), "lds");
-    static const bool sweep = getenv("ADMMNET_TRIDIAG_BIG") && !strcmp(getenv("ADMMNET_TRIDIAG_BIG"), "sweep");
-    // D = 256 on the panel tridiagonalisation: the same idea in its "half image" form (prep.hip PM_HALF): lower-triangle
-    // G / Z, image of the lower 16-block triangle -- exactly the tiles tridiag_panel_kernel loads
-    if (D > 128) return on && !lds && !sweep && use_dc() && tridiag_panel_supported(eig_dim(D)) && use_arrow(D);
-    return on && !lds && use_arrow(D);
-}
-
-static int eig_chunk(int Dact, int64_t nb, const Ws &ws, int32_t *status, hipStream_t st, bool with_v = true,
-                     const float2 *Zlow = nullptr, const float2 *phi = nullptr, const float *h = nullptr,
-                     const float *lw = nullptr) {
-    const int D = eig_dim(Dact);   // (the image, T, W and the eigenvector image are all of this dimension)
+// The eigen-pipeline of a chunk whose image is built (ws.skip: its per-matrix filter), then the rebuild of G.  io == nullptr:
+// eigenvalues and the explicit eigenvector image only (admmnet_eigh_c64).
+static int eig_chunk(const Route &r, int64_t nb, const Ws &ws, int32_t *status, hipStream_t st, const GLayerIO *io) {
+    const int D = r.D, E = r.eig_dim;   // (the image, T, W and the eigenvector image are all of dimension E)
+    const Back back = io ? r.back : r.back_v();
+    const GLayerIO g = io ? *io : GLayerIO{};
     int rc;
-    if ((rc = launch_tridiag(D, nb, ws, st, Zlow, phi, h, lw))) return rc;
-    if (ws.Wdc) {   // divide & conquer + V = Q W on the matrix cores
-        // the fused consumer (backrebuild.hip) and the large back-transform read the transposed image WT themselves
-        const bool big = vgemm_big_supported(D);
-        // (the block-reflector back-transform reads the eigenvectors through the column map of the top-level merge)
-        const bool wy = big && use_wy_back(D) && with_v && ws.Wmap;
-        if ((rc = launch_dc(D + 1, nb, ws, status, st, with_v && !big, wy))) return rc;
-        if (!with_v) return ADMMNET_OK;
-        if (wy) return launch_wy_apply(D, nb, ws, st);   // block reflectors applied to W: no explicit Q
-        return big ? launch_vgemm_big(D, nb, ws, st) : launch_vgemm(D, nb, ws, st);
+    if ((rc = launch_tridiag(r, nb, ws, st, g.Zlow, g.phi, g.h, g.lw))) return rc;
+    if (r.dc) rc = launch_dc(E + 1, nb, ws, status, st, Route::dc_rowmajor(back), Route::dc_colmap(back));
+    else rc = launch_tql(E + 1, nb, ws, status, st);
+    if (rc) return rc;
+    switch (back) {
+        case BK_IN_REBUILD: break;
+        case BK_VGEMM: rc = launch_vgemm(E, nb, ws, st); break;            // V = Q W on the matrix cores
+        case BK_VGEMM_BIG: rc = launch_vgemm_big(E, nb, ws, st); break;
+        case BK_WY: rc = launch_wy_apply(E, nb, ws, st); break;            // block reflectors applied to W: no explicit Q
+        case BK_ROTATION: rc = launch_rotapply(E, nb, ws, st); break;
     }
-    if ((rc = launch_tql(D + 1, nb, ws, status, st))) return rc;
-    return launch_rotapply(D, nb, ws, st);
+    if (rc || !io) return rc;
+    if (r.rebuild == RB_BACK) return launch_back_rebuild(D, nb, g.lw, g.phi, g.h, g.G, g.rn, g.w_out, ws, st, g.lower_only);
+    return launch_rebuild(D, nb, g.lw, g.phi, g.h, g.G, g.rn, g.w_out, ws, st, g.lower_only, r.rebuild, E);
 }
 
 }  // namespace admmnet
@@ -497,16 +418,22 @@ int admmnet_layer_front(const admmnet_cfg *cfg, const float *W, int32_t k, const
     const int64_t n = D + 1;
     const LayerLayout L{D};
     const float2 *yy = (const float2 *)y, *bb = (const float2 *)b;
-    if (k == cfg->K - 1) return launch_prep(cfg, W, k, yy, bb, sigma, 0, B, ws, true, st);
+    const Route r = route_for(D, switches());
+    if (k == cfg->K - 1) return launch_prep(cfg, W, k, yy, bb, sigma, 0, B, ws, PM_PHI_ONLY, r.eig_dim, st);
+    const bool arrow = k == 0 && r.first != AR_NONE;   // Z = 0: arrowhead, no matrix is ever formed
+    if (!arrow && r.error != RE_NONE) {
+        set_error("%s", kRouteErrorText[r.error]);
+        return ADMMNET_E_ARG;
+    }
     const float *lw = W + (int64_t)k * L.size();
     const int cur = k & 1;
-    // chunk buffers and streams: one set on the caller's stream, or two sets on two internal streams (two_streams())
+    // chunk buffers and streams: one set on the caller's stream, or two sets on two internal streams (ADMMNET_STREAMS=2)
     Ws sets[2] = {ws, ws};
     hipStream_t ss[2] = {st, st};
     const bool dual = ws.set2_offset != 0;
     if (dual) {
         Carver c2{reinterpret_cast<char *>(workspace) + ws.set2_offset};
-        carve_second_set(c2, D, ws, &sets[1]);
+        carve_chunk(c2, r, ws.chunk, &sets[1]);
         if ((rc = chunk_streams(ss))) return rc;
         hipEvent_t e0;
         ADMM_HIP(hipEventCreateWithFlags(&e0, hipEventDisableTiming));
@@ -528,41 +455,36 @@ int admmnet_layer_front(const admmnet_cfg *cfg, const float *W, int32_t k, const
         const int waves = b0 >= last0 ? waves_last : waves_full;
         const Ws &wc = sets[ci & 1];
         hipStream_t sc = ss[ci & 1];
-        const bool lean = use_lean(D);
-        const float2 *phk = ws.phi[cur] + b0 * D;
-        const float *hk = ws.h[cur] + b0 * D;
-        float2 *Gk = ws.G + b0 * n * n;
-        if (k == 0 && use_arrow(D)) {   // Z = 0: arrowhead, no matrix is ever formed
-            if ((rc = launch_prep(cfg, W, k, yy, bb, sigma, b0, nb, wc, false, sc, true))) return rc;
-            if ((rc = launch_arrow_rebuild(D, nb, lw, phk, hk, Gk, ws.rn + b0, nullptr, status, wc, sc, lean))) return rc;
+        float2 *Zk = ws.Z + b0 * n * n;
+        GLayerIO io{lw, ws.phi[cur] + b0 * D, ws.h[cur] + b0 * D, r.storage == ST_LEAN ? Zk : nullptr, ws.G + b0 * n * n,
+                    ws.rn + b0, nullptr, r.lean()};
+        if (arrow) {
+            if ((rc = launch_prep(cfg, W, k, yy, bb, sigma, b0, nb, wc, PM_NO_MATRIX, r.eig_dim, sc))) return rc;
+            if ((rc = launch_arrow_rebuild(r, nb, io.lw, io.phi, io.h, io.G, io.rn, io.w_out, status, wc, sc, io.lower_only)))
+                return rc;
             continue;
         }
-        const bool fused = fuse_back(D, wc);
+        // the lazy Z update of the previous layer rides the first sweep of the fused kernel: prep then only computes phi and h
+        const bool fold = r.fold && k >= 1;
+        const int mode = (r.storage == ST_HALF ? PM_HALF : r.storage == ST_LEAN ? PM_LEAN : 0) | (r.late_image ? PM_NOIMG : 0) |
+                         (fold ? PM_SMALL : 0);
+        if ((rc = launch_prep(cfg, W, k, yy, bb, sigma, b0, nb, wc, mode, r.eig_dim, sc))) return rc;
+        Ws wf = wc;
         // G as a matrix function where the spectrum allows it (checked per matrix, spectral.hip); the eigen-pipeline below then
         // only runs the matrices it flagged
-        const bool spec = use_spectral() && wc.spec_flag && lean && D >= 8 && (D > 128 || fused);
-        const bool late_image = spec && D > 128 && use_spectral_fused();   // (the image only for the flagged matrices, afterwards)
-        // the lazy Z update of the previous layer rides the first sweep of the fused kernel: prep then only computes phi and h
-        static const bool fold_env = !(getenv("ADMMNET_SF_FOLD") && atoi(getenv("ADMMNET_SF_FOLD")) == 0);
-        const bool fold = spec && use_spectral_fused() && fold_env && k >= 1;
-        if ((rc = launch_prep(cfg, W, k, yy, bb, sigma, b0, nb, wc, false, sc, false, lean, late_image, fold))) return rc;
-        Ws wf = wc;
-        if (spec) {
+        if (r.matfun != MF_OFF) {
             const int prv = cur ^ 1;
             const float *lwp = k >= 1 ? W + (int64_t)(k - 1) * L.size() : lw;
-            if ((rc = launch_spectral(D, nb, lw, phk, hk, ws.Z + b0 * n * n, Gk, ws.rn + b0, wc, status, sc, true,
-                                      waves, fold ? ws.alpha + b0 : nullptr, fold ? ws.phi[prv] + b0 * D : nullptr,
+            if ((rc = launch_spectral(D, nb, lw, io.phi, io.h, Zk, io.G, io.rn, wc, status, sc, r.matfun, waves,
+                                      fold ? ws.alpha + b0 : nullptr, fold ? ws.phi[prv] + b0 * D : nullptr,
                                       fold ? ws.h[prv] + b0 * D : nullptr, fold ? lwp : nullptr, fold ? (k == 1 ? 2 : 1) : 0)))
                 return rc;
             wf.skip = wc.spec_flag;
-            if (late_image && (rc = launch_half_image(D, nb, lw, phk, hk, ws.Z + b0 * n * n, wf, sc))) return rc;
+            // (the image only for the flagged matrices, afterwards)
+            if (r.late_image && (rc = launch_half_image(D, nb, lw, io.phi, io.h, Zk, wf, r.eig_dim, sc))) return rc;
         }
-        // (D <= 128: the tridiagonalisation's own loader forms A from the lower triangle of Z; D = 256 reads the half image)
-        if ((rc = eig_chunk(D, nb, wf, status, sc, !fused, (lean && D <= 128) ? ws.Z + b0 * n * n : nullptr, phk, hk, lw)))
-            return rc;
-        rc = fused ? launch_back_rebuild(D, nb, lw, phk, hk, Gk, ws.rn + b0, nullptr, wf, sc, lean)
-                   : launch_rebuild(D, nb, lw, phk, hk, Gk, ws.rn + b0, nullptr, wf, sc, lean, eig_dim(D));
-        if (rc) return rc;
+        // (ST_LEAN: the tridiagonalisation's own loader forms A from the lower triangle of Z; ST_HALF reads the half image)
+        if ((rc = eig_chunk(r, nb, wf, status, sc, &io))) return rc;
     }
     if (dual) {   // the caller's stream continues behind both chunk streams
         for (int q = 0; q < 2; ++q) {
@@ -683,25 +605,19 @@ int admmnet_glayer_f32(const admmnet_cfg *cfg, const float *lw, const void *phi,
     if ((rc = carve_workspace(&c2, B, base + rn_bytes, workspace_bytes - rn_bytes, &ws, false))) return rc;
     float *rn_tmp = (float *)base;
     if (status) ADMM_HIP(hipMemsetAsync(status, 0, 4 * sizeof(int32_t), st));
+    const Route r = route_for(D, switches());
     for (int64_t b0 = 0; b0 < B; b0 += ws.chunk) {
         const int64_t nb = (B - b0 < ws.chunk) ? (B - b0) : ws.chunk;
-        const float2 *ph = (const float2 *)phi + b0 * D;
         const float2 *Zc = Z ? (const float2 *)Z + b0 * n * n : nullptr;
-        if (!Zc && use_arrow(D)) {
-            if ((rc = launch_arrow_rebuild(D, nb, lw, ph, h + b0 * D, (float2 *)G_out + b0 * n * n,
-                                           rn_out ? rn_out + b0 : rn_tmp + b0, w_out ? w_out + b0 * n : nullptr,
-                                           status, ws, st)))
+        const GLayerIO io{lw, (const float2 *)phi + b0 * D, h + b0 * D, nullptr, (float2 *)G_out + b0 * n * n,
+                          rn_out ? rn_out + b0 : rn_tmp + b0, w_out ? w_out + b0 * n : nullptr, false};
+        if (!Zc && r.first != AR_NONE) {
+            if ((rc = launch_arrow_rebuild(r, nb, io.lw, io.phi, io.h, io.G, io.rn, io.w_out, status, ws, st, io.lower_only)))
                 return rc;
             continue;
         }
-        if ((rc = launch_build_block(D, nb, sc[S_CORNER_G], sc[S_INV_RHO_G], ph, h + b0 * D, Zc, ws, st))) return rc;
-        const bool fused = fuse_back(D, ws);
-        if ((rc = eig_chunk(D, nb, ws, status, st, !fused))) return rc;
-        float2 *Go = (float2 *)G_out + b0 * n * n;
-        float *rno = rn_out ? rn_out + b0 : rn_tmp + b0, *wo = w_out ? w_out + b0 * n : nullptr;
-        rc = fused ? launch_back_rebuild(D, nb, lw, ph, h + b0 * D, Go, rno, wo, ws, st)
-                   : launch_rebuild(D, nb, lw, ph, h + b0 * D, Go, rno, wo, ws, st, false, eig_dim(D));
-        if (rc) return rc;
+        if ((rc = launch_build_block(D, nb, sc[S_CORNER_G], sc[S_INV_RHO_G], io.phi, io.h, Zc, ws, r.eig_dim, st))) return rc;
+        if ((rc = eig_chunk(r, nb, ws, status, st, &io))) return rc;
     }
     return ADMMNET_OK;
 }
@@ -725,7 +641,7 @@ int admmnet_glayer_spectral_f32(const admmnet_cfg *cfg, const float *layer_weigh
     hipStream_t st = (hipStream_t)stream;
     ADMM_HIP(hipMemsetAsync(status, 0, 4 * sizeof(int32_t), st));
     return launch_spectral_fused(D, B, layer_weights, (const float2 *)phi, h, (float2 *)Z, (float2 *)G, rn_out, flag, status,
-                                 spectral_tol(), mode ? alpha : nullptr, mode ? (const float2 *)phi_prev : nullptr,
+                                 switches().spectral_tol, mode ? alpha : nullptr, mode ? (const float2 *)phi_prev : nullptr,
                                  mode ? h_prev : nullptr, mode ? prev_layer_weights : nullptr, mode,
                                  waves ? waves : spectral_waves(D, B), st);
 }
@@ -758,11 +674,12 @@ int admmnet_eigh_c64(int32_t n, int64_t B, const void *A, float *w, void *V, voi
     if ((rc = carve_workspace(&cfg, B, workspace, workspace_bytes, &ws, false))) return rc;
     if (status) ADMM_HIP(hipMemsetAsync(status, 0, 4 * sizeof(int32_t), st));
     const int D = n - 1;
+    const Route r = route_for(D, switches());
     for (int64_t b0 = 0; b0 < B; b0 += ws.chunk) {
         const int64_t nb = (B - b0 < ws.chunk) ? (B - b0) : ws.chunk;
-        if ((rc = launch_build_generic(n, nb, (const float2 *)A + b0 * n * n, ws, st))) return rc;
-        if ((rc = eig_chunk(D, nb, ws, status, st))) return rc;
-        if ((rc = launch_vout(n, nb, (float2 *)V + b0 * (int64_t)n * n, w + b0 * n, ws, st))) return rc;
+        if ((rc = launch_build_generic(n, nb, (const float2 *)A + b0 * n * n, ws, r.eig_dim, st))) return rc;
+        if ((rc = eig_chunk(r, nb, ws, status, st, nullptr))) return rc;
+        if ((rc = launch_vout(n, nb, (float2 *)V + b0 * (int64_t)n * n, w + b0 * n, ws, r.eig_dim, st))) return rc;
     }
     return ADMMNET_OK;
 }

@@ -28,7 +28,7 @@
 namespace admmnet {
 
 constexpr int AR_THREADS = 256;
-enum ArMode { AR_LDS = 0, AR_GLOBAL = 1, AR_FUSED = 2 };   // where the eigenvectors go: LDS image, global image, slabs
+// (ArMode, route.h: where the eigenvectors go -- AR_LDS image in LDS, AR_GLOBAL image in global memory, AR_FUSED slabs)
 constexpr int AF_KS = 16;     // eigenvectors per slab of the fused form
 constexpr int AF_W = kMaxD;   // slab row: one float per original index
 static_assert(AR_THREADS == AF_W, "the fused tail gives every thread one column of X");
@@ -538,29 +538,18 @@ __global__ __launch_bounds__(AR_THREADS, MODE == AR_FUSED ? 2 : 1) void arrow_re
 bool arrow_rebuild_supported(int D) { return D >= 1 && D <= 256; }
 
 // developer phase timer (ADMMNET_AR_TIMING=1): mean cycles of thread 0 per phase, printed after the launch
-struct ArTiming {
-    unsigned long long *d = nullptr;
-    int begin(hipStream_t st) {
-        static const bool on = getenv("ADMMNET_AR_TIMING") != nullptr;   // developer aid, never on by default
-        if (!on) return ADMMNET_OK;
-        ADMM_HIP(hipMalloc(&d, 16 * sizeof(unsigned long long)));
-        ADMM_HIP(hipMemsetAsync(d, 0, 16 * sizeof(unsigned long long), st));
-        return ADMMNET_OK;
-    }
-    int end(hipStream_t st, int D, int64_t nb, const char *const (&nm)[6]) {
-        if (!d) return ADMMNET_OK;
-        unsigned long long hb[16];
-        ADMM_HIP(hipMemcpyAsync(hb, d, sizeof(hb), hipMemcpyDeviceToHost, st));
-        ADMM_HIP(hipStreamSynchronize(st));
-        ADMM_HIP(hipFree(d));
-        fprintf(stderr, "[arrow_rebuild timing] D=%d nb=%lld  mean cycles per workgroup:\n", D, (long long)nb);
-        for (int i = 0; i < 6; ++i) fprintf(stderr, "   %-14s %10.0f\n", nm[i], (double)hb[i] / (double)nb);
-        return ADMMNET_OK;
-    }
-};
+static int ar_timing_end(PhaseTimer &tm, hipStream_t st, int D, int64_t nb, const char *const (&nm)[6]) {
+    if (!tm.dev) return ADMMNET_OK;
+    unsigned long long hb[16];
+    if (int rc = tm.end(st, hb)) return rc;
+    fprintf(stderr, "[arrow_rebuild timing] D=%d nb=%lld  mean cycles per workgroup:\n", D, (long long)nb);
+    for (int i = 0; i < 6; ++i) fprintf(stderr, "   %-14s %10.0f\n", nm[i], (double)hb[i] / (double)nb);
+    return ADMMNET_OK;
+}
 
-int launch_arrow_rebuild(int D, int64_t nb, const float *lw, const float2 *phi, const float *h, float2 *G, float *rn,
+int launch_arrow_rebuild(const Route &r, int64_t nb, const float *lw, const float2 *phi, const float *h, float2 *G, float *rn,
                          float *w_out, int32_t *status, const Ws &ws, hipStream_t st, bool lower_only) {
+    const int D = r.D;
     if (nb <= 0) return ADMMNET_OK;
     if (!arrow_rebuild_supported(D)) {
         set_error("arrow_rebuild: D=%d unsupported", D);
@@ -568,22 +557,21 @@ int launch_arrow_rebuild(int D, int64_t nb, const float *lw, const float2 *phi, 
     }
     const BrGeom g(D);
     int rc;
-    // D > 128: one kernel, X in LDS slabs and real S on the matrix cores; ADMMNET_ARROW_FUSED=0 keeps the two-kernel form
-    static const bool fused_env = !(getenv("ADMMNET_ARROW_FUSED") && atoi(getenv("ADMMNET_ARROW_FUSED")) == 0);
-    if (D > 128 && fused_env && !ws.skip) {
+    // D > 128: one kernel, X in LDS slabs and real S on the matrix cores (AR_FUSED), or the two-kernel form (AR_GLOBAL)
+    if (r.first == AR_FUSED) {
         ProfScope _prof(KC_REBUILD, st);
         const size_t lds = ar_lds_bytes(g) - sizeof(float) * g.vt_floats() + sizeof(float) * 2 * AF_KS * AF_W;
         ADMM_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(arrow_rebuild_kernel<AR_FUSED>),
                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        ArTiming tm;
-        if ((rc = tm.begin(st))) return rc;
+        PhaseTimer tm;
+        if ((rc = tm.begin(switches().ar_timing, st, 16))) return rc;
         hipLaunchKernelGGL(arrow_rebuild_kernel<AR_FUSED>, dim3((unsigned)nb), dim3(AR_THREADS), lds, st, D, lw, phi, h, G,
-                           rn, w_out, status, tm.d, lower_only ? 1 : 0, (float *)nullptr, (float *)nullptr);
+                           rn, w_out, status, tm.dev, lower_only ? 1 : 0, (float *)nullptr, (float *)nullptr);
         ADMM_HIP(hipGetLastError());
         static const char *const nm[6] = {"sort+deflate", "roots", "zhat+rank+norm", "first slab", "slabs + S", "epilogue"};
-        return tm.end(st, D, nb, nm);
+        return ar_timing_end(tm, st, D, nb, nm);
     }
-    if (D > 128) {   // eigenvectors to the global image, then the dense path's rebuild kernel
+    if (r.first == AR_GLOBAL) {   // eigenvectors to the global image, then the dense path's rebuild kernel
         {
             ProfScope _prof(KC_REBUILD, st);
             const size_t lds = ar_lds_bytes(g) - sizeof(float) * g.vt_floats();
@@ -593,19 +581,19 @@ int launch_arrow_rebuild(int D, int64_t nb, const float *lw, const float2 *phi, 
                                G, rn, ws.w, status, (unsigned long long *)nullptr, lower_only ? 1 : 0, ws.VT, ws.w0);
             ADMM_HIP(hipGetLastError());
         }
-        return launch_rebuild(D, nb, lw, phi, h, G, rn, w_out, ws, st, lower_only, D);   // (image laid out for D itself)
+        return launch_rebuild(D, nb, lw, phi, h, G, rn, w_out, ws, st, lower_only, r.first_rebuild, D);   // (image laid out for D itself)
     }
     ProfScope _prof(KC_REBUILD, st);
     const size_t lds = ar_lds_bytes(g);
     ADMM_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(arrow_rebuild_kernel<AR_LDS>),
                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    ArTiming tm;
-    if ((rc = tm.begin(st))) return rc;
+    PhaseTimer tm;
+    if ((rc = tm.begin(switches().ar_timing, st, 16))) return rc;
     hipLaunchKernelGGL(arrow_rebuild_kernel<AR_LDS>, dim3((unsigned)nb), dim3(AR_THREADS), lds, st, D, lw, phi, h, G, rn,
-                       w_out, status, tm.d, lower_only ? 1 : 0, (float *)nullptr, (float *)nullptr);
+                       w_out, status, tm.dev, lower_only ? 1 : 0, (float *)nullptr, (float *)nullptr);
     ADMM_HIP(hipGetLastError());
     static const char *const nm[6] = {"sort+deflate", "roots", "zhat+rank+norm", "vectors", "G tiles", "arrow+norm"};
-    return tm.end(st, D, nb, nm);
+    return ar_timing_end(tm, st, D, nb, nm);
 }
 
 }  // namespace admmnet

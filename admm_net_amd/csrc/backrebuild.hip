@@ -247,20 +247,14 @@ int launch_back_rebuild(int D, int64_t nb, const float *lw, const float2 *phi, c
                            : (v4 ? back_rebuild_kernel<5, 0, true> : back_rebuild_kernel<5, 0, false>);
     ADMM_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
                                  (int)lds));
-    static const bool timing = getenv("ADMMNET_BR_TIMING") != nullptr;   // developer aid, never on by default
-    unsigned long long *ptime = nullptr;
-    if (timing) {
-        ADMM_HIP(hipMalloc(&ptime, 16 * sizeof(unsigned long long)));
-        ADMM_HIP(hipMemsetAsync(ptime, 0, 16 * sizeof(unsigned long long), st));
-    }
+    PhaseTimer tm;
+    if (int rc = tm.begin(switches().br_timing, st, 16)) return rc;
     hipLaunchKernelGGL(kern, dim3((unsigned)nb), dim3(BR_THREADS), lds, st, D, lw, ws.Wdc, ws.QV,
-                       ws.w, ws.w0, phi, h, G, rn, ptime, dc_final_offset(D + 1), lower_only ? 1 : 0, ws.skip);
+                       ws.w, ws.w0, phi, h, G, rn, tm.dev, dc_final_offset(D + 1), lower_only ? 1 : 0, ws.skip);
     ADMM_HIP(hipGetLastError());
-    if (timing) {
+    if (tm.dev) {
         unsigned long long hb[16];
-        ADMM_HIP(hipMemcpyAsync(hb, ptime, sizeof(hb), hipMemcpyDeviceToHost, st));
-        ADMM_HIP(hipStreamSynchronize(st));
-        ADMM_HIP(hipFree(ptime));
+        if (int rc = tm.end(st, hb)) return rc;
         static const char *nm[6] = {"eig map", "first slab", "phase A", "phase B", "phase C", "arrow+norm"};
         fprintf(stderr, "[back_rebuild timing] D=%d nb=%lld  mean cycles per workgroup:\n", D, (long long)nb);
         for (int i = 0; i < 6; ++i) fprintf(stderr, "   %-12s %10.0f\n", nm[i], (double)hb[i] / (double)nb);

@@ -5,6 +5,7 @@
 
 #include "../../include/admmnet.h"
 #include "eig_core.h"
+#include "route.h"
 
 namespace admmnet {
 
@@ -115,46 +116,47 @@ struct Ws {
                               // at once (null: every matrix runs)
 };
 
-int64_t eig_chunk_bytes(int D, int64_t chunk);
-int carve_workspace(const admmnet_cfg *cfg, int64_t B, void *base, int64_t bytes, Ws *ws, bool state);
-int64_t pick_chunk(const admmnet_cfg *cfg, int64_t B);
 
 // ---- kernel launchers (each enqueues on `st`, returns ADMMNET_* code) ----------
 // prep.hip
+// mode bits of prep_kernel; launch_prep adds PM_FIRST / PM_ZZERO from k, the caller states the rest from the route
+constexpr int PM_FIRST = 1;      // layer 0: G = Z = 0, nothing is read
+constexpr int PM_ZZERO = 2;      // layer 1: stored Z is still zero (never written)
+constexpr int PM_PHI_ONLY = 4;   // last layer: only phi is needed (admm_net.py:757-764)
+constexpr int PM_NO_MATRIX = 8;  // layer 0 on the arrowhead path (arrow.hip): phi and h only, A is never formed
+constexpr int PM_HALF = 32;      // D = 256 (tridiag_panel.hip): G / Z streamed as lower triangles, the image written for the lower
+                                 // 16-block triangle only (diagonal blocks in full) -- the tiles that kernel loads
+constexpr int PM_NOIMG = 64;     // with PM_HALF: only the lazy Z update streams, no image -- the G-layer is evaluated as a matrix function
+                                 // straight from Z (spectral_fused.hip); the matrices it rejects get their image from half_image_kernel
+constexpr int PM_SMALL = 128;    // phi and h only: the lazy Z update is folded into the first sweep of the matrix-function kernel
+constexpr int PM_LEAN = 16;      // G / Z kept as lower triangles, A built by the tridiagonalisation's own loader
+                                 // (tridiag_reg.hip): only the lazy Z update streams here, 24 n^2 / 2 bytes per signal
+// (eig_dim, here and below: Route::eig_dim -- the matrix lands in an eig_dim x eig_dim image, zero outside its own D x D block)
 int launch_prep(const admmnet_cfg *cfg, const float *lw, int k, const float2 *y, const float2 *b,
-                const float *sigma, int64_t b0, int64_t nb, const Ws &ws, bool phi_only, hipStream_t st,
-                bool no_matrix = false, bool lean = false, bool no_image = false, bool small = false);
-// (small: phi and h only -- the Z update of the previous layer is then the matrix-function kernel's, launch_spectral's `update`)
-// (no_image, D > 128 lean route: only the Z update streams; launch_half_image then builds the image of the matrices with
-//  ws.skip[s] != 0 from the updated Z)
+                const float *sigma, int64_t b0, int64_t nb, const Ws &ws, int mode, int eig_dim, hipStream_t st);
+// (the image of the matrices with ws.skip[s] != 0 from the updated Z, behind a PM_NOIMG prep)
 int launch_half_image(int D, int64_t nb, const float *lw, const float2 *phi, const float *h, const float2 *Z, const Ws &ws,
-                      hipStream_t st);
-// (image builders: the matrix lands in an eig_dim x eig_dim image, zero outside its own D x D block)
-int launch_build_generic(int n, int64_t nb, const float2 *A, const Ws &ws, hipStream_t st);
+                      int eig_dim, hipStream_t st);
+int launch_build_generic(int n, int64_t nb, const float2 *A, const Ws &ws, int eig_dim, hipStream_t st);
 int launch_build_block(int D, int64_t nb, float corner, float inv_rho, const float2 *phi, const float *h,
-                       const float2 *Z, const Ws &ws, hipStream_t st);
-// tridiag.hip
-int launch_tridiag(int D, int64_t nb, const Ws &ws, hipStream_t st, const float2 *Zlow = nullptr,
-                   const float2 *phi = nullptr, const float *h = nullptr, const float *lw = nullptr);
-int launch_tridiag_reg(int D, int64_t nb, const Ws &ws, hipStream_t st, const float2 *Zlow = nullptr,
-                       const float2 *phi = nullptr, const float *h = nullptr,
-                       const float *lw = nullptr);   // tridiag_reg.hip, D <= 128
-int launch_tridiag_big(int D, int64_t nb, const Ws &ws, hipStream_t st);   // tridiag_big.hip, 128 < D <= 256
+                       const float2 *Z, const Ws &ws, int eig_dim, hipStream_t st);
+// tridiag.hip: r.tridiag at r.eig_dim.  Zlow != nullptr (ST_LEAN): tridiag_reg's own loader forms A = C - Z / rho
+int launch_tridiag(const Route &r, int64_t nb, const Ws &ws, hipStream_t st, const float2 *Zlow, const float2 *phi,
+                   const float *h, const float *lw);
+int launch_tridiag_reg(int D, int64_t nb, const Ws &ws, hipStream_t st, const float2 *Zlow, const float2 *phi, const float *h,
+                       const float *lw);   // tridiag_reg.hip, D <= 128
+int launch_tridiag_big(int D, int64_t nb, const Ws &ws, hipStream_t st, bool panel, bool explicit_q);   // tridiag_big.hip, 128 < D <= 256
 bool tridiag_panel_supported(int D);                                      // tridiag_panel.hip, D == 256
-// Dimension the eigen-pipeline works in: D itself, or 256 for 128 < D < 256 -- those geometries are embedded in the
-// D = 256 pipeline as diag(A, 0) (api.hip, "padded route"); every chunk buffer is laid out for eig_dim(D).
-int eig_dim(int D);
-int launch_tridiag_panel(int D, int64_t nb, const Ws &ws, hipStream_t st);
+int launch_tridiag_panel(int D, int64_t nb, const Ws &ws, hipStream_t st, bool explicit_q);
 int64_t tridiag_panel_tail_elems();                                       // float2 per matrix of Ws::Tail
-bool use_wy_back(int D);                                                  // wy_apply.hip: V = Q W without forming Q
-int launch_wy_apply(int D, int64_t nb, const Ws &ws, hipStream_t st);     // wy_apply.hip
+int launch_wy_apply(int D, int64_t nb, const Ws &ws, hipStream_t st);     // wy_apply.hip: V = Q W without forming Q
 // tql.hip
 int launch_tql(int n, int64_t nb, const Ws &ws, int32_t *status, hipStream_t st);
 // rotapply.hip
 int launch_rotapply(int D, int64_t nb, const Ws &ws, hipStream_t st);
 // rebuild.hip
-int launch_dc(int n, int64_t nb, const Ws &ws, int32_t *status, hipStream_t st, bool rowmajor = true,
-              bool colmap = false);   // dc.hip (colmap: leave the top level's deflated columns in place, write Ws::Wmap)
+int launch_dc(int n, int64_t nb, const Ws &ws, int32_t *status, hipStream_t st, bool rowmajor,
+              bool colmap);   // dc.hip (colmap: leave the top level's deflated columns in place, write Ws::Wmap)
 int64_t dc_final_offset(int n);                                                            // dc.hip
 int launch_vgemm(int D, int64_t nb, const Ws &ws, hipStream_t st);                       // dc.hip
 bool vgemm_big_supported(int D);                                                          // vgemm_big.hip
@@ -166,19 +168,17 @@ int launch_estimate(const float2 *phi, int64_t B, int xbase, int ybase, const do
                     const double2 *tabS, int ny, const double *axis_x, const double *axis_y, const double *opt7,
                     int iters, int L, const int32_t *top_n, double *top, int32_t *counts, hipStream_t st);   // estimate.hip
 bool arrow_rebuild_supported(int D);                                                       // arrow.hip
-int launch_arrow_rebuild(int D, int64_t nb, const float *lw, const float2 *phi, const float *h, float2 *G, float *rn,
-                         float *w_out, int32_t *status, const Ws &ws, hipStream_t st, bool lower_only = false);   // arrow.hip
+int launch_arrow_rebuild(const Route &r, int64_t nb, const float *lw, const float2 *phi, const float *h, float2 *G, float *rn,
+                         float *w_out, int32_t *status, const Ws &ws, hipStream_t st, bool lower_only);   // arrow.hip: r.first
 bool back_rebuild_supported(int D);                                                        // backrebuild.hip
 int launch_back_rebuild(int D, int64_t nb, const float *lw, const float2 *phi, const float *h, float2 *G,
-                        float *rn, float *w_out, const Ws &ws, hipStream_t st,
-                        bool lower_only = false);                                        // backrebuild.hip
-bool use_dc();                                                                          // api.hip
-// image_dim: the dimension the eigenvector image ws.VT is laid out for (eig_dim(D) behind the dense pipeline, D itself
-// behind the arrowhead solver of the first layer)
+                        float *rn, float *w_out, const Ws &ws, hipStream_t st, bool lower_only);   // backrebuild.hip
+// form: RB_BIG or RB_TILES; image_dim: the dimension the eigenvector image ws.VT is laid out for (Route::eig_dim behind the
+// dense pipeline, D itself behind the arrowhead solver of the first layer)
 int launch_rebuild(int D, int64_t nb, const float *lw, const float2 *phi, const float *h,
-                   float2 *G, float *rn, float *w_out, const Ws &ws, hipStream_t st, bool lower_only = false,
-                   int image_dim = 0);
-int launch_vout(int n, int64_t nb, float2 *V, float *w, const Ws &ws, hipStream_t st);
+                   float2 *G, float *rn, float *w_out, const Ws &ws, hipStream_t st, bool lower_only, Rebuild form,
+                   int image_dim);
+int launch_vout(int n, int64_t nb, float2 *V, float *w, const Ws &ws, int eig_dim, hipStream_t st);
 bool rebuild_big_supported(int D);                                                        // rebuild_big.hip, image dimension 256
 int launch_rebuild_big(int D, int64_t nb, const float *lw, const float2 *phi, const float *h, float2 *G, float *rn,
                        const Ws &ws, hipStream_t st, bool lower_only);
@@ -202,22 +202,15 @@ int launch_spectrum_tables(const double *taus, int nx, int xbase, const double *
 int launch_spectrum_main(const float2 *phi, int64_t B, int xbase, int ybase, const double2 *tabD, int nx,
                          const double2 *tabS, int ny, double *out, hipStream_t st);
 
-// spectral.hip
-bool use_spectral();
-bool use_spectral_fused();   // spectral_fused.hip: the whole evaluation in one kernel (default when the path is on)
-float spectral_tol();          // the model tolerance of the matrix-function checks (one value for every caller)
-// The workgroup shape of the fused kernel (4 or 12 waves per matrix), chosen once per CALL from the call's batch size B --
-// never from a chunk's size: the two shapes sum in different orders, and the bits of a signal must not depend on cfg.chunk.
-int spectral_waves(int D, int64_t B);
+// spectral.hip (form: MF_KERNELS, the five kernels there) / spectral_fused.hip (MF_FUSED: the whole evaluation in one kernel)
 int launch_spectral_fused(int D, int64_t nb, const float *lw, const float2 *phi, const float *h, float2 *Z, float2 *G,
                           float *rn, int *flag, int32_t *status, float tol, const float *alpha, const float2 *phi_prev,
                           const float *h_prev, const float *lw_prev, int update_mode, int waves, hipStream_t st);
 // update_mode 0: Z is current; 1 / 2: the fused kernel applies Z <- Z + alpha (G - C_prev) in its first sweep (2: stored Z still zero)
 // waves: spectral_waves(D, B) of the call the chunk belongs to
 int launch_spectral(int D, int64_t nb, const float *lw, const float2 *phi, const float *h, float2 *Z, float2 *G,
-                    float *rn, const Ws &ws, int32_t *status, hipStream_t st, bool lower_only, int waves,
-                    const float *alpha = nullptr, const float2 *phi_prev = nullptr, const float *h_prev = nullptr,
-                    const float *lw_prev = nullptr, int update_mode = 0);
+                    float *rn, const Ws &ws, int32_t *status, hipStream_t st, MatFun form, int waves, const float *alpha,
+                    const float2 *phi_prev, const float *h_prev, const float *lw_prev, int update_mode);
 // vdvh.hip (training route)
 int launch_vdvh(int n, int64_t nb, const float2 *V, const float *d, float2 *out, hipStream_t st);
 int launch_vhsv(int n, int64_t nb, const float2 *V, const float2 *S, float *q, hipStream_t st);
@@ -276,6 +269,26 @@ struct ProfScope {   // records start/stop events on `st` around a launcher body
     hipStream_t st;
     ProfScope(int kclass, hipStream_t s);
     ~ProfScope();
+};
+
+// ---- developer phase timers (ADMMNET_*_TIMING) ----------------------------------
+// n zeroed device counters for one launch (dev stays null when off); end() copies them back, synchronises and frees
+struct PhaseTimer {
+    unsigned long long *dev = nullptr;
+    int n = 0;
+    int begin(bool on, hipStream_t st, int n_counters) {
+        if (!on) return ADMMNET_OK;
+        n = n_counters;
+        ADMM_HIP(hipMalloc(&dev, n * sizeof(unsigned long long)));
+        ADMM_HIP(hipMemsetAsync(dev, 0, n * sizeof(unsigned long long), st));
+        return ADMMNET_OK;
+    }
+    int end(hipStream_t st, unsigned long long *host) {
+        ADMM_HIP(hipMemcpyAsync(host, dev, n * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+        ADMM_HIP(hipStreamSynchronize(st));
+        ADMM_HIP(hipFree(dev));
+        return ADMMNET_OK;
+    }
 };
 
 // ---- small device helpers ---------------------------------------------------

@@ -904,29 +904,22 @@ int launch_dc(int n, int64_t nb, const Ws &ws, int32_t *status, hipStream_t st, 
         return ADMMNET_E_ARG;
     }
     const size_t lds = dc_lds_bytes(n);
-    static const int env_occ = getenv("ADMMNET_DC_OCC") ? atoi(getenv("ADMMNET_DC_OCC")) : 0;   // tuning knob
-    const bool blk = n > 129 && !(getenv("ADMMNET_DC_BLOCKS") && !strcmp(getenv("ADMMNET_DC_BLOCKS"), "0"));
-    const int occ = env_occ > 0 ? env_occ : (blk ? 4 : 5);
+    const Switches &sw = switches();
+    const bool blk = n > 129 && sw.dc_blocks;
+    const int occ = sw.dc_occ > 0 ? sw.dc_occ : (blk ? 4 : 5);
     auto kern = blk ? (occ >= 8 ? dc_kernel<8, true> : occ == 6 ? dc_kernel<6, true> : occ == 5 ? dc_kernel<5, true> : dc_kernel<4, true>)
                     : (occ >= 8 ? dc_kernel<8, false> : occ == 6 ? dc_kernel<6, false> : occ == 4 ? dc_kernel<4, false> : dc_kernel<5, false>);
     ADMM_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
                                  (int)lds));
-    static const bool timing = getenv("ADMMNET_DC_TIMING") != nullptr;   // developer aid, never on by default
-    static const bool poison = getenv("ADMMNET_DC_POISON") != nullptr;   // tests: NaN in every never-written element
-    unsigned long long *ptime = nullptr;
-    if (timing) {
-        ADMM_HIP(hipMalloc(&ptime, 96 * sizeof(unsigned long long)));
-        ADMM_HIP(hipMemsetAsync(ptime, 0, 96 * sizeof(unsigned long long), st));
-    }
+    PhaseTimer tm;
+    if (int rc = tm.begin(sw.dc_timing, st, 96)) return rc;
     hipLaunchKernelGGL(kern, dim3((unsigned)nb), dim3(DC_THREADS), lds, st, n, ws.dT, ws.eT, ws.Wdc, ws.w,
-                       ws.w0, ws.logn, status, ptime, rowmajor ? 1 : 0, poison ? 1 : 0,
+                       ws.w0, ws.logn, status, tm.dev, rowmajor ? 1 : 0, sw.dc_poison ? 1 : 0,
                        (colmap && ws.Wmap && dc_leaf_count(n) > 1) ? ws.Wmap : nullptr, ws.skip);
     ADMM_HIP(hipGetLastError());
-    if (timing) {
+    if (tm.dev) {
         unsigned long long h[96];
-        ADMM_HIP(hipMemcpyAsync(h, ptime, sizeof(h), hipMemcpyDeviceToHost, st));
-        ADMM_HIP(hipStreamSynchronize(st));
-        ADMM_HIP(hipFree(ptime));
+        if (int rc = tm.end(st, h)) return rc;
         static const char *nm[12] = {"init", "leaves", "P1 sort", "P2 scan", "P3 rot+secular", "P4 zhat+rank",
                                      "P5 U", "P6 barrier wait", "P7 commit", "final transpose", "P6 copy", "P6 gemm"};
         fprintf(stderr, "[dc timing] n=%d nb=%lld  mean cycles per workgroup:\n", n, (long long)nb);

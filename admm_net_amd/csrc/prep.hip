@@ -41,19 +41,6 @@ __device__ __forceinline__ float pr_block_reduce(float v, float *scr, bool is_ma
     return r;
 }
 
-// mode bits
-constexpr int PM_FIRST = 1;      // layer 0: G = Z = 0, nothing is read
-constexpr int PM_ZZERO = 2;      // layer 1: stored Z is still zero (never written)
-constexpr int PM_PHI_ONLY = 4;   // last layer: only phi is needed (admm_net.py:757-764)
-constexpr int PM_NO_MATRIX = 8;  // layer 0 on the arrowhead path (arrow.hip): phi and h only, A is never formed
-constexpr int PM_HALF = 32;      // D = 256 (tridiag_panel.hip): G / Z streamed as lower triangles, the image written for the lower
-                                 // 16-block triangle only (diagonal blocks in full) -- the tiles that kernel loads
-constexpr int PM_NOIMG = 64;     // with PM_HALF: only the lazy Z update streams, no image -- the G-layer is evaluated as a matrix function
-                                 // straight from Z (spectral_fused.hip); the matrices it rejects get their image from half_image_kernel
-constexpr int PM_SMALL = 128;    // phi and h only: the lazy Z update is folded into the first sweep of the matrix-function kernel
-constexpr int PM_LEAN = 16;      // G / Z kept as lower triangles, A built by the tridiagonalisation's own loader
-                                 // (tridiag_reg.hip): only the lazy Z update streams here, 24 n^2 / 2 bytes per signal
-
 // (TRI: the D = 256 triangle walk with its 16 loads in flight compiled in -- 98 VGPRs; the other instance keeps the 54
 //  registers and 8 waves per SIMD the lean D <= 128 stream wants)
 // Zero padding of an eig_dim x eig_dim image around its D x D matrix (full storage: both triangles), arrow included.
@@ -364,54 +351,47 @@ __global__ void build_block_kernel(int D, float corner, float inv_rho, const flo
 }
 
 int launch_build_block(int D, int64_t nb, float corner, float inv_rho, const float2 *phi, const float *h,
-                       const float2 *Z, const Ws &ws, hipStream_t st) {
+                       const float2 *Z, const Ws &ws, int eig_dim, hipStream_t st) {
     if (nb <= 0) return ADMMNET_OK;
     hipLaunchKernelGGL(build_block_kernel, dim3((unsigned)nb), dim3(256), 0, st, D, corner, inv_rho, phi, h, Z,
-                       ws.Mbuf, eig_dim(D));
+                       ws.Mbuf, eig_dim);
     ADMM_HIP(hipGetLastError());
     return ADMMNET_OK;
 }
 
 int launch_prep(const admmnet_cfg *cfg, const float *lw_all, int k, const float2 *y, const float2 *b,
-                const float *sigma, int64_t b0, int64_t nb, const Ws &ws, bool phi_only, hipStream_t st,
-                bool no_matrix, bool lean, bool no_image, bool small) {
+                const float *sigma, int64_t b0, int64_t nb, const Ws &ws, int mode, int eig_dim, hipStream_t st) {
     ProfScope _prof(KC_PREP, st);
     if (nb <= 0) return ADMMNET_OK;
     const int D = cfg->M * cfg->N, n = D + 1;
     const LayerLayout L{D};
     const float *lw = lw_all + (int64_t)k * L.size();
     const float *lwp = k > 0 ? lw_all + (int64_t)(k - 1) * L.size() : lw;
-    int mode = 0;
     if (k == 0) mode |= PM_FIRST;
     if (k == 1) mode |= PM_ZZERO;
-    if (phi_only) mode |= PM_PHI_ONLY;
-    if (no_matrix && k == 0) mode |= PM_NO_MATRIX;
-    if (lean) mode |= (D > 128) ? PM_HALF : PM_LEAN;
-    if (no_image && (mode & PM_HALF)) mode |= PM_NOIMG;
-    if (small) mode |= PM_SMALL;
     const int cur = k & 1, prv = cur ^ 1;
     const size_t lds = sizeof(float2) * 2 * D + sizeof(float) * (3 * D + kHid + 8);
     auto kern = (mode & PM_HALF) ? prep_kernel<true> : prep_kernel<false>;
     hipLaunchKernelGGL(kern, dim3((unsigned)nb), dim3(PR_THREADS), lds, st, D, mode, lw, lwp,
                        y + b0 * D, b + b0 * D, sigma + b0, ws.G + b0 * (int64_t)n * n,
                        ws.Z + b0 * (int64_t)n * n, ws.phi[prv] + b0 * D, ws.h[prv] + b0 * D, ws.alpha + b0,
-                       ws.phi[cur] + b0 * D, ws.h[cur] + b0 * D, ws.Mbuf, eig_dim(D));
+                       ws.phi[cur] + b0 * D, ws.h[cur] + b0 * D, ws.Mbuf, eig_dim);
     ADMM_HIP(hipGetLastError());
     return ADMMNET_OK;
 }
 
 int launch_half_image(int D, int64_t nb, const float *lw, const float2 *phi, const float *h, const float2 *Z, const Ws &ws,
-                      hipStream_t st) {
+                      int eig_dim, hipStream_t st) {
     ProfScope _prof(KC_PREP, st);
     if (nb <= 0) return ADMMNET_OK;
-    hipLaunchKernelGGL(half_image_kernel, dim3((unsigned)nb), dim3(PR_THREADS), 0, st, D, eig_dim(D), lw, phi, h, Z, ws.Mbuf, ws.skip);
+    hipLaunchKernelGGL(half_image_kernel, dim3((unsigned)nb), dim3(PR_THREADS), 0, st, D, eig_dim, lw, phi, h, Z, ws.Mbuf, ws.skip);
     ADMM_HIP(hipGetLastError());
     return ADMMNET_OK;
 }
 
-int launch_build_generic(int n, int64_t nb, const float2 *A, const Ws &ws, hipStream_t st) {
+int launch_build_generic(int n, int64_t nb, const float2 *A, const Ws &ws, int eig_dim, hipStream_t st) {
     if (nb <= 0) return ADMMNET_OK;
-    hipLaunchKernelGGL(build_generic_kernel, dim3((unsigned)nb), dim3(256), 0, st, n, A, ws.Mbuf, eig_dim(n - 1));
+    hipLaunchKernelGGL(build_generic_kernel, dim3((unsigned)nb), dim3(256), 0, st, n, A, ws.Mbuf, eig_dim);
     ADMM_HIP(hipGetLastError());
     return ADMMNET_OK;
 }

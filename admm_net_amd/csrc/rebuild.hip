@@ -155,14 +155,12 @@ __global__ void unpad_kernel(int Da, int Dimg, const float *__restrict__ VTg, co
 }
 
 int launch_rebuild(int D, int64_t nb, const float *lw, const float2 *phi, const float *h, float2 *G,
-                   float *rn, float *w_out, const Ws &ws, hipStream_t st, bool lower_only, int image_dim) {
+                   float *rn, float *w_out, const Ws &ws, hipStream_t st, bool lower_only, Rebuild form, int image_dim) {
     ProfScope _prof(KC_REBUILD, st);
     if (nb <= 0) return ADMMNET_OK;
     const int n = D + 1;
-    if (image_dim <= 0) image_dim = D;
-    // image of dimension 256: every tile resident, V^T read once (rebuild_big.hip); ADMMNET_REBUILD=tiles keeps the kernel below
-    static const bool tiles = getenv("ADMMNET_REBUILD") && !strcmp(getenv("ADMMNET_REBUILD"), "tiles");
-    if ((!tiles || image_dim != D) && rebuild_big_supported(image_dim)) {
+    // RB_BIG, image of dimension 256: every tile resident, V^T read once (rebuild_big.hip); RB_TILES: the kernel below
+    if (form == RB_BIG) {
         int rc = launch_rebuild_big(D, nb, lw, phi, h, G, rn, ws, st, lower_only);
         if (rc) return rc;
         if (w_out && image_dim == D) ADMM_HIP(hipMemcpyAsync(w_out, ws.w, sizeof(float) * nb * n, hipMemcpyDeviceToDevice, st));
@@ -177,10 +175,6 @@ int launch_rebuild(int D, int64_t nb, const float *lw, const float2 *phi, const 
         set_error("rebuild: no kernel for a %d-image holding D=%d", image_dim, D);
         return ADMMNET_E_ARG;
     }
-    if (ws.skip) {
-        set_error("rebuild: the per-tile kernel has no per-matrix filter (ADMMNET_SPECTRAL=1 with ADMMNET_REBUILD=tiles)");
-        return ADMMNET_E_ARG;
-    }
     const size_t lds = sizeof(float) * (3 * ((n + 4) & ~3) + 2 * D + 8);
     hipLaunchKernelGGL(rebuild_kernel, dim3((unsigned)nb), dim3(RB_THREADS), lds, st, D, lw, ws.VT, ws.w,
                        ws.w0, phi, h, G, rn, lower_only ? 1 : 0);
@@ -189,10 +183,10 @@ int launch_rebuild(int D, int64_t nb, const float *lw, const float2 *phi, const 
     return ADMMNET_OK;
 }
 
-int launch_vout(int n, int64_t nb, float2 *V, float *w, const Ws &ws, hipStream_t st) {
+int launch_vout(int n, int64_t nb, float2 *V, float *w, const Ws &ws, int eig_dim, hipStream_t st) {
     if (nb <= 0) return ADMMNET_OK;
-    if (eig_dim(n - 1) != n - 1) {   // padded route: drop the eigenpairs of the padding
-        hipLaunchKernelGGL(unpad_kernel, dim3((unsigned)nb), dim3(256), 0, st, n - 1, eig_dim(n - 1), ws.VT, ws.w, ws.w0, w, V);
+    if (eig_dim != n - 1) {   // padded route: drop the eigenpairs of the padding
+        hipLaunchKernelGGL(unpad_kernel, dim3((unsigned)nb), dim3(256), 0, st, n - 1, eig_dim, ws.VT, ws.w, ws.w0, w, V);
         ADMM_HIP(hipGetLastError());
         return ADMMNET_OK;
     }

@@ -34,11 +34,6 @@ namespace admmnet {
 constexpr int SP_THREADS = 256;
 constexpr int SP_ITERS = 4;        // matrix-vector passes of the subspace iteration (3 power steps + the final Rayleigh-Ritz)
 
-bool use_spectral() {   // on by default; ADMMNET_SPECTRAL=0 sends every matrix through the eigensolver pipeline
-    static const bool on = !(getenv("ADMMNET_SPECTRAL") && atoi(getenv("ADMMNET_SPECTRAL")) == 0);
-    return on;
-}
-
 // ---- F1: A = C_g - inv_rho Z as a full Hermitian n x n matrix (Z: lower triangle valid if `lower`, else full) ------------
 __global__ __launch_bounds__(SP_THREADS) void sp_build_kernel(int D, const float *__restrict__ lw, const float2 *__restrict__ phi,
                                                               const float *__restrict__ h, const float2 *__restrict__ Zg,
@@ -420,32 +415,20 @@ __global__ __launch_bounds__(SP_THREADS) void sp_assemble_kernel(int D, const fl
 
 // Scratch of its own (Ws::spec_*, carved only when the path is on).  Returns with flag[] filled; the caller runs the
 // eigen-pipeline with Ws::skip = flag.
-// model tolerance: the quadratic may miss f on the bulk by 1e-6 of the result's scale -- below the eigensolver route's own
-// rounding per layer (~2e-6) and without effect on the distance to the float64 oracle (3e-7, 1e-6 and 3e-6 measured the same:
-// tests/gpu_spectral_check.py); at K = 32 the tighter 3e-7 rejected 3.0 % of the matrix-layers, this one 0.4 %
-float spectral_tol() {
-    static const float tol = getenv("ADMMNET_SPECTRAL_TOL") ? (float)atof(getenv("ADMMNET_SPECTRAL_TOL")) : 1e-6f;
-    return tol;
-}
-
 int launch_spectral(int D, int64_t nb, const float *lw, const float2 *phi, const float *h, float2 *Z, float2 *G,
-                    float *rn, const Ws &ws, int32_t *status, hipStream_t st, bool lower_only, int waves, const float *alpha,
+                    float *rn, const Ws &ws, int32_t *status, hipStream_t st, MatFun form, int waves, const float *alpha,
                     const float2 *phi_prev, const float *h_prev, const float *lw_prev, int update_mode) {
     ProfScope _prof(KC_GFUNC, st);
     if (nb <= 0) return ADMMNET_OK;
     const int n = D + 1;
-    const float tol = spectral_tol();
-    if (use_spectral_fused()) {
-        if (!ws.spec_flag || !lower_only) {
+    const float tol = switches().spectral_tol;
+    if (form == MF_FUSED) {
+        if (!ws.spec_flag) {
             set_error("spectral: the fused kernel needs the flag buffer and the lower-triangle state");
             return ADMMNET_E_WORKSPACE;
         }
         return launch_spectral_fused(D, nb, lw, phi, h, Z, G, rn, ws.spec_flag, status, tol, alpha, phi_prev, h_prev, lw_prev,
                                      update_mode, waves, st);
-    }
-    if (update_mode) {
-        set_error("spectral: the multi-kernel form does not apply the Z update");
-        return ADMMNET_E_ARG;
     }
     if (!ws.spec_flag || !ws.spec_vec || !ws.spec_val || !ws.spec_mat) {
         set_error("spectral: workspace without the fast-path buffers");
@@ -465,7 +448,7 @@ int launch_spectral(int D, int64_t nb, const float *lw, const float2 *phi, const
     hipLaunchKernelGGL(sp_square_kernel, dim3((unsigned)nb), dim3(SP_THREADS), 0, st, n, A, E2, ws.spec_val);
     ADMM_HIP(hipGetLastError());
     hipLaunchKernelGGL(sp_assemble_kernel, dim3((unsigned)nb), dim3(SP_THREADS), sizeof(float2) * 2 * n, st, D, lw, A, E2,
-                       ws.spec_vec, ws.spec_val, phi, h, G, rn, ws.spec_flag, status, lower_only ? 1 : 0, tol);
+                       ws.spec_vec, ws.spec_val, phi, h, G, rn, ws.spec_flag, status, /* lower_only: lean state */ 1, tol);
     ADMM_HIP(hipGetLastError());
     return ADMMNET_OK;
 }

@@ -774,31 +774,20 @@ __global__ __launch_bounds__(64 * W, W == 12 ? 1 : 3) void sp_fused_kernel(int D
     mark(7);
 }
 
-bool use_spectral_fused() {
-    static const bool on = !(getenv("ADMMNET_SPECTRAL_FUSED") && atoi(getenv("ADMMNET_SPECTRAL_FUSED")) == 0);
-    return on;
-}
-
 template <int TPW, int W>
 static int sf_launch(int D, int64_t nb, const float *lw, const float2 *phi, const float *h, float2 *Z, float2 *G, float *rn,
                      int *flag, int32_t *status, float tol, int iters, const SfUpdate &up, hipStream_t st) {
     const size_t lds = SfCarve::bytes(D + 1, W);
     ADMM_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(sp_fused_kernel<TPW, W>), hipFuncAttributeMaxDynamicSharedMemorySize,
                                  (int)lds));
-    static const bool timing = getenv("ADMMNET_SF_TIMING") != nullptr;   // developer aid, never on by default
-    unsigned long long *ptime = nullptr;
-    if (timing) {
-        ADMM_HIP(hipMalloc(&ptime, 16 * sizeof(unsigned long long)));
-        ADMM_HIP(hipMemsetAsync(ptime, 0, 16 * sizeof(unsigned long long), st));
-    }
+    PhaseTimer tm;
+    if (int rc = tm.begin(switches().sf_timing, st, 16)) return rc;
     hipLaunchKernelGGL((sp_fused_kernel<TPW, W>), dim3((unsigned)nb), dim3(64 * W), lds, st, D, lw, phi, h, Z, G, rn, flag, status,
-                       tol, iters, ptime, up);
+                       tol, iters, tm.dev, up);
     ADMM_HIP(hipGetLastError());
-    if (timing) {
+    if (tm.dev) {
         unsigned long long hb[16];
-        ADMM_HIP(hipMemcpyAsync(hb, ptime, sizeof(hb), hipMemcpyDeviceToHost, st));
-        ADMM_HIP(hipStreamSynchronize(st));
-        ADMM_HIP(hipFree(ptime));
+        if (int rc = tm.end(st, hb)) return rc;
         fprintf(stderr, "[sf timing D=%d nb=%lld] cycles per workgroup: setup %.0f | matvec %.0f ritz %.0f (all passes) | stage %.0f "
                 "mfma %.0f border %.0f (all slabs) | model %.0f | assemble %.0f\n", D, (long long)nb, hb[0] / (double)nb,
                 hb[1] / (double)nb, hb[2] / (double)nb, (hb[3]) / (double)nb, hb[4] / (double)nb, hb[5] / (double)nb,
@@ -807,15 +796,7 @@ static int sf_launch(int D, int64_t nb, const float *lw, const float2 *phi, cons
     return ADMMNET_OK;
 }
 
-// 256 threads per matrix, three matrices per CU -- once there are more than two matrices per CU to overlap (measured at 10 x 10,
-// K = 10: 1024 signals 3.45 vs 3.63 ms per forward, 4096 signals 8.3 vs 10.4 ms; but 256 signals 2.42 vs 2.03 ms and a single
-// signal 0.64 vs 0.53 ms: a lone matrix is served faster by twelve waves).  B is the batch of the CALL (layer_front), not the
-// size of a chunk: the shapes split the mirrored mat-vec and the block sums differently, so a per-chunk choice made a signal's
-// bits depend on cfg.chunk and on whether it fell into a ragged last chunk.
-int spectral_waves(int D, int64_t B) {
-    static const bool small_wg = !(getenv("ADMMNET_SF_SMALLWG") && atoi(getenv("ADMMNET_SF_SMALLWG")) == 0);
-    return (D <= 128 && small_wg && B > 512) ? 4 : SF_WAVES;
-}
+static_assert(SF_WAVES == 12, "spectral_waves (route.h) names the shapes 4 and 12");
 
 int launch_spectral_fused(int D, int64_t nb, const float *lw, const float2 *phi, const float *h, float2 *Z, float2 *G,
                           float *rn, int *flag, int32_t *status, float tol, const float *alpha, const float2 *phi_prev,
@@ -829,7 +810,7 @@ int launch_spectral_fused(int D, int64_t nb, const float *lw, const float2 *phi,
         set_error("spectral: %d waves per matrix at D=%d (need 12, or 4 with D <= 128)", waves, D);
         return ADMMNET_E_ARG;
     }
-    static const int iters = getenv("ADMMNET_SPECTRAL_ITERS") ? atoi(getenv("ADMMNET_SPECTRAL_ITERS")) : 5;   // (upper bound)
+    const int iters = switches().spectral_iters;   // (upper bound)
     const int NT = (D + 31) >> 5, ntri = NT * (NT + 1) / 2;
     if (waves == 4) {
         switch ((ntri + 3) / 4) {

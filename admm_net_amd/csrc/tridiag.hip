@@ -247,30 +247,22 @@ static size_t td_lds_bytes(int D, bool ldsm) {
     return sz;
 }
 
-int launch_tridiag(int D, int64_t nb, const Ws &ws, hipStream_t st, const float2 *Zlow, const float2 *phi,
+int launch_tridiag(const Route &r, int64_t nb, const Ws &ws, hipStream_t st, const float2 *Zlow, const float2 *phi,
                    const float *h, const float *lw) {
     ProfScope _prof(KC_TRIDIAG, st);
+    const int D = r.eig_dim;
     if (D < 1 || D > kMaxD) {
         set_error("tridiag: D=%d unsupported (1..%d)", D, kMaxD);
         return ADMMNET_E_ARG;
     }
     if (nb <= 0) return ADMMNET_OK;
-    // D <= 128: register-resident kernel (tridiag_reg.hip).  ADMMNET_TRIDIAG=lds keeps the
-    // LDS-resident version below selectable for A/B runs; it also serves 128 < D <= 256 (global image).
+    // TD_REG, D <= 128: register-resident kernel (tridiag_reg.hip).  TD_LDS keeps the LDS-resident version below selectable
+    // for A/B runs; it also serves 128 < D <= 256 (global image).
     // (A 512-thread, 4-waves-per-SIMD variant of tridiag_reg was measured 1.6x SLOWER: the O(n) per-wave
     // work of every reflector -- norm, Householder scalars, vector set-up, reductions -- is replicated in
     // each wave, and with 8 waves per matrix it outweighs the better latency hiding.)
-    static int use_lds = -1;
-    if (use_lds < 0) {
-        const char *e = getenv("ADMMNET_TRIDIAG");
-        use_lds = (e && !strcmp(e, "lds")) ? 1 : 0;
-    }
-    if (D <= 128 && !use_lds) return launch_tridiag_reg(D, nb, ws, st, Zlow, phi, h, lw);
-    if (Zlow) {
-        set_error("tridiag: the lean loader exists for the register-resident kernel only (D <= 128)");
-        return ADMMNET_E_ARG;
-    }
-    if (D <= 256 && !use_lds) return launch_tridiag_big(D, nb, ws, st);
+    if (r.tridiag == TD_REG) return launch_tridiag_reg(D, nb, ws, st, Zlow, phi, h, lw);
+    if (r.tridiag != TD_LDS) return launch_tridiag_big(D, nb, ws, st, r.tridiag == TD_PANEL, r.explicit_q);
     const bool ldsm = td_lds_bytes(D, true) <= 160 * 1024;
     const size_t lds = td_lds_bytes(D, ldsm);
     if (ldsm) {

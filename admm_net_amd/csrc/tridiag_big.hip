@@ -399,17 +399,12 @@ __global__ __launch_bounds__(TB_THREADS) void ungtr_big_kernel(int D, const floa
         }
 }
 
-// D = 256: the panel-blocked kernel of tridiag_panel.hip (trailing updates on the matrix cores) produces the same
-// (d, e, reflector rows, taus); ADMMNET_TRIDIAG_BIG=sweep keeps the per-reflector register sweep below for A/B runs.
-static bool use_panel(int D) {
-    static const bool sweep = getenv("ADMMNET_TRIDIAG_BIG") && !strcmp(getenv("ADMMNET_TRIDIAG_BIG"), "sweep");
-    return !sweep && tridiag_panel_supported(D);
-}
-
+// panel (TD_PANEL, D = 256): the panel-blocked kernel of tridiag_panel.hip (trailing updates on the matrix cores) produces the
+// same (d, e, reflector rows, taus) as the per-reflector register sweep below (TD_SWEEP), kept for A/B runs.
 template <int NA>
-static int launch_tb(int D, int64_t nb, const Ws &ws, hipStream_t st) {
-    if (use_panel(D)) {
-        int rc = launch_tridiag_panel(D, nb, ws, st);
+static int launch_tb(int D, int64_t nb, const Ws &ws, hipStream_t st, bool panel, bool explicit_q) {
+    if (panel) {
+        int rc = launch_tridiag_panel(D, nb, ws, st, explicit_q);
         if (rc) return rc;
     } else {
         const size_t lds = sizeof(TbShared<NA>) + sizeof(float2) * (2 * NA - 1) * TB_THREADS;
@@ -419,20 +414,20 @@ static int launch_tb(int D, int64_t nb, const Ws &ws, hipStream_t st) {
                            ws.eT);
         ADMM_HIP(hipGetLastError());
     }
-    if (use_panel(D) && use_wy_back(D)) return ADMMNET_OK;   // the back-transform applies the block reflectors itself
+    if (!explicit_q) return ADMMNET_OK;   // the back-transform applies the block reflectors itself
     hipLaunchKernelGGL(ungtr_big_kernel<NA>, dim3((unsigned)nb, (unsigned)((D + 127) / 128)), dim3(TB_THREADS), 0, st,
                        D, ws.Mbuf, ws.QV);
     ADMM_HIP(hipGetLastError());
     return ADMMNET_OK;
 }
 
-int launch_tridiag_big(int D, int64_t nb, const Ws &ws, hipStream_t st) {
+int launch_tridiag_big(int D, int64_t nb, const Ws &ws, hipStream_t st, bool panel, bool explicit_q) {
     const int na = (D + 31) / 32;
     switch (na) {
-        case 5: return launch_tb<5>(D, nb, ws, st);
-        case 6: return launch_tb<6>(D, nb, ws, st);
-        case 7: return launch_tb<7>(D, nb, ws, st);
-        case 8: return launch_tb<8>(D, nb, ws, st);
+        case 5: return launch_tb<5>(D, nb, ws, st, panel, explicit_q);
+        case 6: return launch_tb<6>(D, nb, ws, st, panel, explicit_q);
+        case 7: return launch_tb<7>(D, nb, ws, st, panel, explicit_q);
+        case 8: return launch_tb<8>(D, nb, ws, st, panel, explicit_q);
         default:
             set_error("tridiag_big: D=%d unsupported (129..256)", D);
             return ADMMNET_E_ARG;

@@ -787,45 +787,35 @@ int64_t tridiag_panel_tail_elems() { return PN_TAIL_TILES * 256; }
 // Stage split: the first kernel (8 waves, one workgroup per CU: the register-resident half of the 256 x 256 matrix)
 // reduces panels 0 .. 7, the second (4 waves, 69 KB of LDS: two workgroups per CU) the trailing 128 x 128 matrix.  Every
 // reflector is a chain of five barrier-separated latency-bound phases, so two independent matrices per CU overlap where
-// one leaves the CU idle.  ADMMNET_PN_SPLIT=0 runs the whole reduction in the first kernel.
-static int pn_split() {
-    static int v = -1;
-    if (v < 0) {
-        const char *e = getenv("ADMMNET_PN_SPLIT");
-        v = (e && !strcmp(e, "0")) ? 0 : (e && !strcmp(e, "8")) ? 8 : 84;
-    }
-    return v;
-}
+// one leaves the CU idle.  ADMMNET_PN_SPLIT=0 (Switches::pn_split) runs the whole reduction in the first kernel.
 
 template <int NT, bool HEAD, bool TIMING>
-static int pn_launch_stage(int64_t nb, const Ws &ws, int pstop, unsigned long long *tdbg, hipStream_t st) {
+static int pn_launch_stage(int64_t nb, const Ws &ws, int pstop, bool explicit_q, unsigned long long *tdbg, hipStream_t st) {
     const size_t lds = sizeof(PnShared<NT>);
     ADMM_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(tridiag_panel_kernel<NT, HEAD, TIMING>),
                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     hipLaunchKernelGGL((tridiag_panel_kernel<NT, HEAD, TIMING>), dim3((unsigned)nb), dim3(32 * NT), lds, st, ws.Mbuf,
-                       ws.dT, ws.eT, ws.Tfac, ws.Tail, pstop, use_wy_back(PN_D) ? 0 : 1, tdbg, ws.skip);
+                       ws.dT, ws.eT, ws.Tfac, ws.Tail, pstop, explicit_q ? 1 : 0, tdbg, ws.skip);
     ADMM_HIP(hipGetLastError());
     return ADMMNET_OK;
 }
 
-int launch_tridiag_panel(int D, int64_t nb, const Ws &ws, hipStream_t st) {
+int launch_tridiag_panel(int D, int64_t nb, const Ws &ws, hipStream_t st, bool explicit_q) {
     if (!tridiag_panel_supported(D)) {
         set_error("tridiag_panel: D=%d unsupported (256 only)", D);
         return ADMMNET_E_ARG;
     }
-    const bool split = pn_split() != 0 && ws.Tail != nullptr, split3 = split && pn_split() == 84;
-    static const bool timing = getenv("ADMMNET_PN_TIMING") != nullptr;   // developer aid, never on by default
-    if (timing) {
-        unsigned long long *ptime = nullptr, hb[3 * 112];
-        ADMM_HIP(hipMalloc(&ptime, sizeof(hb)));
-        ADMM_HIP(hipMemsetAsync(ptime, 0, sizeof(hb), st));
-        int rc = pn_launch_stage<16, true, true>(nb, ws, split ? 8 : 16, ptime, st);
-        if (rc == ADMMNET_OK && split) rc = pn_launch_stage<8, false, true>(nb, ws, split3 ? 4 : 8, ptime + 112, st);
-        if (rc == ADMMNET_OK && split3) rc = pn_launch_stage<4, false, true>(nb, ws, 4, ptime + 224, st);
+    const Switches &sw = switches();
+    const bool split = sw.pn_split != 0 && ws.Tail != nullptr, split3 = split && sw.pn_split == 84;
+    if (sw.pn_timing) {
+        PhaseTimer tm;
+        unsigned long long hb[3 * 112];
+        int rc = tm.begin(true, st, 3 * 112);
+        if (rc == ADMMNET_OK) rc = pn_launch_stage<16, true, true>(nb, ws, split ? 8 : 16, explicit_q, tm.dev, st);
+        if (rc == ADMMNET_OK && split) rc = pn_launch_stage<8, false, true>(nb, ws, split3 ? 4 : 8, explicit_q, tm.dev + 112, st);
+        if (rc == ADMMNET_OK && split3) rc = pn_launch_stage<4, false, true>(nb, ws, 4, explicit_q, tm.dev + 224, st);
+        if (rc == ADMMNET_OK) rc = tm.end(st, hb);
         if (rc != ADMMNET_OK) return rc;
-        ADMM_HIP(hipMemcpyAsync(hb, ptime, sizeof(hb), hipMemcpyDeviceToHost, st));
-        ADMM_HIP(hipStreamSynchronize(st));
-        ADMM_HIP(hipFree(ptime));
         static const char *nm[14] = {"w | column+norm", "reflector+dots", "matvec tiles", "row flush", "dot fix-up", "E: dot | look-ahead+T", "E: assemble y", "panel end + mfma",
                                      "wait B2", "wait B3", "wait B4", "wait B5", "E: corrections", ""};
         static const int order[13] = {0, 8, 1, 9, 2, 3, 4, 10, 6, 12, 5, 11, 7};
@@ -843,9 +833,9 @@ int launch_tridiag_panel(int D, int64_t nb, const Ws &ws, hipStream_t st) {
         }
         return ADMMNET_OK;
     }
-    int rc = pn_launch_stage<16, true, false>(nb, ws, split ? 8 : 16, nullptr, st);
-    if (rc == ADMMNET_OK && split) rc = pn_launch_stage<8, false, false>(nb, ws, split3 ? 4 : 8, nullptr, st);
-    if (rc == ADMMNET_OK && split3) rc = pn_launch_stage<4, false, false>(nb, ws, 4, nullptr, st);
+    int rc = pn_launch_stage<16, true, false>(nb, ws, split ? 8 : 16, explicit_q, nullptr, st);
+    if (rc == ADMMNET_OK && split) rc = pn_launch_stage<8, false, false>(nb, ws, split3 ? 4 : 8, explicit_q, nullptr, st);
+    if (rc == ADMMNET_OK && split3) rc = pn_launch_stage<4, false, false>(nb, ws, 4, explicit_q, nullptr, st);
     return rc;
 }
 

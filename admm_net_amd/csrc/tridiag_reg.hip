@@ -522,7 +522,7 @@ static int launch_tr(int D, int64_t nb, const Ws &ws, hipStream_t st, const floa
                      const float *h, const float *lw) {
     // developer knob: ADMMNET_TR_PAD_LDS=<bytes> of unused dynamic LDS per workgroup (e.g. 100000 leaves one
     // workgroup per CU: tells latency-bound from issue-bound)
-    static const int pad = getenv("ADMMNET_TR_PAD_LDS") ? atoi(getenv("ADMMNET_TR_PAD_LDS")) : 0;
+    const int pad = switches().tr_pad_lds;
     if (pad > 0) {
         ADMM_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(tridiag_reg_kernel<NA, true>),
                                      hipFuncAttributeMaxDynamicSharedMemorySize, pad));
@@ -532,9 +532,8 @@ static int launch_tr(int D, int64_t nb, const Ws &ws, hipStream_t st, const floa
     // NA = 7 (97 <= D <= 112, the reference's 10 x 10 geometry): compiled for THREE workgroups per CU (168 registers, a few
     // values in scratch) -- the kernel is a latency chain per reflector and a third matrix per CU hides more of it than the
     // spills cost; ADMMNET_TR_OCC=2 keeps the two-workgroup build for A/B runs.
-    static const int occ3 = !(getenv("ADMMNET_TR_OCC") && atoi(getenv("ADMMNET_TR_OCC")) == 2);
     if constexpr (NA == 7) {
-        if (occ3 && pad == 0) {
+        if (switches().tr_occ3 && pad == 0) {
             if (Zlow)
                 hipLaunchKernelGGL((tridiag_reg_kernel<NA, true, 3>), dim3((unsigned)nb), dim3(TR_THREADS), 0, st, D, ws.Mbuf,
                                    ws.QV, ws.dT, ws.eT, Zlow, phi, h, lw, ws.skip);

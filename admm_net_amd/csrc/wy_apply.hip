@@ -246,16 +246,7 @@ __global__ __launch_bounds__(64) void wy_lastcol_kernel(const float2 *__restrict
     }
 }
 
-// The block-reflector back-transform needs the T factors the panel tridiagonalisation writes; ADMMNET_BACK=q keeps the
-// explicit Q (ungtr_big_kernel) + vgemm_big_kernel pair for A/B runs.
-bool use_wy_back(int D) {
-    // (every switch that takes the tridiagonalisation or the tridiagonal solver off the panel / D&C route turns it off)
-    static const bool off = (getenv("ADMMNET_BACK") && !strcmp(getenv("ADMMNET_BACK"), "q")) ||
-                            (getenv("ADMMNET_TRIDIAG_BIG") && !strcmp(getenv("ADMMNET_TRIDIAG_BIG"), "sweep")) ||
-                            (getenv("ADMMNET_TRIDIAG") && !strcmp(getenv("ADMMNET_TRIDIAG"), "lds"));
-    return !off && use_dc() && tridiag_panel_supported(D);
-}
-
+// The block-reflector back-transform needs the T factors the panel tridiagonalisation writes (route.h: BK_WY).
 int launch_wy_apply(int D, int64_t nb, const Ws &ws, hipStream_t st) {
     ProfScope _prof(KC_ROTAPPLY, st);
     if (nb <= 0) return ADMMNET_OK;
