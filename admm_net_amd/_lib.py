@@ -79,6 +79,11 @@ SYMBOLS = {
     "admmnet_train_eigmap_bwd_f32": (c_int32, [c_int32, c_int64] + [c_void_p] * 11),
     "admmnet_train_stepsize_f32": (c_int32, [c_int64, c_int64, c_float] + [c_void_p] * 8),
     "admmnet_train_stepsize_bwd_f32": (c_int32, [c_int64, c_int64, c_float] + [c_void_p] * 11),
+    "admmnet_loss_partials": (c_int64, [c_int32, c_int64]),
+    "admmnet_loss_anm_f32": (c_int32, [c_int32, c_int32, c_int64] + [c_void_p] * 7 + [c_float] + [c_void_p] * 5),
+    "admmnet_loss_anm_bwd_f32": (c_int32, [c_int32, c_int32, c_int64] + [c_void_p] * 9 + [c_float] + [c_void_p] * 5),
+    "admmnet_loss_phi_c64": (c_int32, [c_int32, c_int64, c_void_p, c_void_p, c_float, c_float, c_void_p, c_void_p, c_void_p]),
+    "admmnet_loss_phi_bwd_c64": (c_int32, [c_int32, c_int64, c_void_p, c_void_p, c_void_p, c_float, c_float, c_void_p, c_void_p]),
     "admmnet_spectrum_workspace_bytes": (c_int64, [c_int32, c_int32, c_int32, c_int32]),
     "admmnet_spectrum_f64": (c_int32, [c_void_p, c_int64, c_int32, c_int32, c_void_p, c_int32, c_void_p,
                                        c_int32, c_void_p, c_void_p, c_int64, c_void_p]),

@@ -877,6 +877,57 @@ int admmnet_train_stepsize_bwd_f32(int64_t B, int64_t sub_batch, float knorm, co
                                      (hipStream_t)stream);
 }
 
+// ---- the training losses (loss.hip) ------------------------------------------------------------------------------------------
+// one lane per target slot (Lmax <= 64); the slab grid must fit 31 bits
+static int loss_args_ok(const char *what, int32_t Lmax, int32_t D, int64_t B, bool ptrs) {
+    if (Lmax < 1 || Lmax > 64 || D < 1 || B < 1 || train_small_rows(B) > 0x7fffffffLL || !ptrs) {
+        set_error("%s: bad argument (Lmax=%d, D=%d, B=%lld)", what, Lmax, D, (long long)B);
+        return ADMMNET_E_ARG;
+    }
+    return ADMMNET_OK;
+}
+
+int64_t admmnet_loss_partials(int32_t loss, int64_t B) {
+    if (B < 1 || (loss != ADMMNET_LOSS_ANM && loss != ADMMNET_LOSS_PHI)) return -1;
+    return loss_partials(loss, B);
+}
+
+int admmnet_loss_anm_f32(int32_t Lmax, int32_t D, int64_t B, const float *tau, const float *f, const float *conf,
+                         const float *tau_true, const float *f_true, const int64_t *L_true, const void *phi, float lambda_reg,
+                         float *out, float *norms, int32_t *status, float *partials, void *stream) {
+    if (int rc = loss_args_ok("loss_anm", Lmax, D, B,
+                              tau && f && conf && tau_true && f_true && L_true && phi && out && norms && status && partials))
+        return rc;
+    return launch_loss_anm(Lmax, D, B, tau, f, conf, tau_true, f_true, L_true, (const float2 *)phi, lambda_reg, out, norms,
+                           status, partials, (hipStream_t)stream);
+}
+
+int admmnet_loss_anm_bwd_f32(int32_t Lmax, int32_t D, int64_t B, const float *g_out, const float *tau, const float *f,
+                             const float *conf, const float *tau_true, const float *f_true, const int64_t *L_true,
+                             const void *phi, const float *norms, float lambda_reg, float *g_tau, float *g_f, float *g_conf,
+                             void *g_phi, void *stream) {
+    if (int rc = loss_args_ok("loss_anm_bwd", Lmax, D, B,
+                              g_out && tau && f && conf && tau_true && f_true && L_true && phi && norms && g_tau && g_f &&
+                                  g_conf && g_phi))
+        return rc;
+    return launch_loss_anm_bwd(Lmax, D, B, g_out, tau, f, conf, tau_true, f_true, L_true, (const float2 *)phi, norms,
+                               lambda_reg, g_tau, g_f, g_conf, (float2 *)g_phi, (hipStream_t)stream);
+}
+
+int admmnet_loss_phi_c64(int32_t D, int64_t B, const void *phi, const void *phi_true, float amplitude_weight,
+                         float phase_weight, float *out, float *partials, void *stream) {
+    if (int rc = loss_args_ok("loss_phi", 1, D, B, phi && phi_true && out && partials)) return rc;
+    return launch_loss_phi(D, B, (const float2 *)phi, (const float2 *)phi_true, amplitude_weight, phase_weight, out, partials,
+                           (hipStream_t)stream);
+}
+
+int admmnet_loss_phi_bwd_c64(int32_t D, int64_t B, const float *g_out, const void *phi, const void *phi_true,
+                             float amplitude_weight, float phase_weight, void *g_phi, void *stream) {
+    if (int rc = loss_args_ok("loss_phi_bwd", 1, D, B, g_out && phi && phi_true && g_phi)) return rc;
+    return launch_loss_phi_bwd(D, B, g_out, (const float2 *)phi, (const float2 *)phi_true, amplitude_weight, phase_weight,
+                               (float2 *)g_phi, (hipStream_t)stream);
+}
+
 int admmnet_profile_enable(int32_t on) {
     ProfState &p = prof();
     std::lock_guard<std::mutex> lk(p.mu);

@@ -257,6 +257,19 @@ int launch_train_stepsize_bwd(int64_t B, int64_t g, float knorm, const float *gs
                               const float *W1, const float *b1, const float *W2, const float *b2, float *grn, float *gpar,
                               float *part, hipStream_t st);
 
+// loss.hip (the training losses; sums over the batch as in train_small.hip)
+int64_t loss_partials(int loss, int64_t B);           // floats of partial-sum scratch of the forward of ADMMNET_LOSS_*
+int launch_loss_anm(int Lmax, int D, int64_t B, const float *tau, const float *f, const float *conf, const float *tau_true,
+                    const float *f_true, const int64_t *L_true, const float2 *phi, float lambda_reg, float *out, float *norms,
+                    int32_t *status, float *part, hipStream_t st);
+int launch_loss_anm_bwd(int Lmax, int D, int64_t B, const float *g_out, const float *tau, const float *f, const float *conf,
+                        const float *tau_true, const float *f_true, const int64_t *L_true, const float2 *phi, const float *norms,
+                        float lambda_reg, float *g_tau, float *g_f, float *g_conf, float2 *g_phi, hipStream_t st);
+int launch_loss_phi(int D, int64_t B, const float2 *phi, const float2 *phi_true, float amplitude_weight, float phase_weight,
+                    float *out, float *part, hipStream_t st);
+int launch_loss_phi_bwd(int D, int64_t B, const float *g_out, const float2 *phi, const float2 *phi_true, float amplitude_weight,
+                        float phase_weight, float2 *g_phi, hipStream_t st);
+
 // synth.hip
 int launch_synth(int64_t B, int Nb, int Nd, int L, unsigned long long seed, double snr_lo, double snr_hi, double snr_e,
                  double rho, int label_iters, float2 *y, float2 *b, float *sigma, float *tau, float *f, float2 *C,

@@ -20,11 +20,10 @@
 // workgroup) then adds the rows in float64, as tl_negsum_kernel / rn_sum_kernel do.  Two runs give the same bits.
 // Every access is a 4-byte (float) or 8-byte (float2) one: the [B, D] tensors need no more than their natural alignment.
 #include "common.h"
+#include "slab_partials.h"
 
 namespace admmnet {
 
-constexpr int TS_THREADS = 256;
-constexpr int TS_SLAB = TS_THREADS / 64;   // signals per workgroup, one per wave
 constexpr int TS_PER_LANE = 5;             // ceil((kMaxD + 1) / 64): elements of one row a lane visits
 constexpr int TS_EIG_PAR = 50;             // g_thr, gW1[16], gb1[16], gW2[16], gb2
 constexpr int TS_STEP_PAR = 162;           // g_rho, gW1[32][3], gb1[32], gW2[32], gb2
@@ -38,23 +37,6 @@ __device__ __forceinline__ float ts_dsoftplus(float x) { return x > 20.f ? 1.f :
 __device__ __forceinline__ float ts_dsigmoid(float x) {
     const float e = expf(-fabsf(x)), d = 1.f + e;
     return e / (d * d);
-}
-
-// v[0 .. COUNT) hold wave sums (the same value in every lane): adds the slab's waves in wave order into row blockIdx.x of part.
-// Every thread of the workgroup must call it.
-template <int COUNT>
-__device__ __forceinline__ void ts_slab_partials(const float (&v)[COUNT], float *sh, float *__restrict__ part) {
-    const int wave = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-        for (int c = 0; c < COUNT; ++c) sh[wave * COUNT + c] = v[c];
-    }
-    __syncthreads();
-    if ((int)threadIdx.x < COUNT) {
-        float s = 0.f;
-        for (int w = 0; w < TS_SLAB; ++w) s += sh[w * COUNT + threadIdx.x];
-        part[(int64_t)blockIdx.x * COUNT + threadIdx.x] = s;
-    }
 }
 
 // out[c] = sum over rows of part[row][c] in float64, fixed order: thread (c, s) adds the rows s, s + ns, ..., a tree halves

@@ -1,9 +1,11 @@
-"""``python -m admm_net_amd.dropin script.py [args ...]``: run one of the reference's scripts (main_for_net.py,
+"""``python -m admm_net_amd.dropin [--hip-loss] script.py [args ...]``: run one of the reference's scripts (main_for_net.py,
 test/test_time_net.py, main.py, test/test_time_admm.py, trainPhi.py ...) unchanged on the MI355X path.
 
 The script runs as ``__main__`` with the import order  shims -> repo root -> the script's own directory -> the rest,
 exactly what ``python script.py`` gives except that the shims come first.  Nothing is exec'ed: the script runs
 inside this interpreter (runpy), so a GPU that is already initialised is not an issue.
+``--hip-loss`` (before the script name; everything after the script name goes to the script) also shims the reference's
+``loss`` module, which otherwise stays the script directory's own file.
 """
 import os
 import runpy
@@ -13,15 +15,19 @@ from . import activate
 
 
 def main():
-    if len(sys.argv) < 2:
-        sys.exit("usage: python -m admm_net_amd.dropin script.py [args ...]")
-    script = os.path.abspath(sys.argv[1])
-    sys.argv = [script] + sys.argv[2:]
+    args = sys.argv[1:]
+    hip_loss = bool(args) and args[0] == "--hip-loss"
+    if hip_loss:
+        args = args[1:]
+    if not args:
+        sys.exit("usage: python -m admm_net_amd.dropin [--hip-loss] script.py [args ...]")
+    script = os.path.abspath(args[0])
+    sys.argv = [script] + args[1:]
     here = os.path.dirname(script)
     if here in sys.path:
         sys.path.remove(here)
     sys.path.insert(0, here)            # what `python script.py` would have put first ...
-    activate()                          # ... and the shims in front of it
+    activate(loss=hip_loss)             # ... and the shims in front of it
     runpy.run_path(script, run_name="__main__")
 
 

@@ -1,0 +1,3 @@
+"""Opt-in drop-in for the reference's ``loss`` module: its three public names on the kernels of csrc/loss.hip.  This directory
+goes on ``sys.path`` only with ``dropin.activate(loss=True)`` / ``--hip-loss`` / ``import admm_net_amd.dropin.activate_loss``."""
+from admm_net_amd.losses import BasicANMLoss, PhiAlignmentLoss, basic_parameter_loss  # noqa: F401

@@ -11,6 +11,7 @@
 CLI:  python -m admm_net_amd.harness time-net  --layers 5 --runs 1000 --out time_net_5.txt [--checkpoint best_model.pth]
       python -m admm_net_amd.harness time-admm --runs 1000 --out time.txt
       python -m admm_net_amd.harness train-step --layers 10 --batch 256 --steps 20 [--route fused|full] [--grid 16x16]   (one JSON line)
+      python -m admm_net_amd.harness loss-step --batch 256 --targets 3 --dim 100 --steps 200                              (one JSON line)
 """
 from __future__ import annotations
 
@@ -184,6 +185,46 @@ def time_train_step(layers=10, batch=256, steps=20, warmup=3, seed=0, device="cu
             "loss_first": round(losses[0], 6), "loss_last": round(losses[-1], 6)}
 
 
+def time_loss_step(batch=256, targets=3, dim=100, steps=200, warmup=10, seed=0, device="cuda:0"):
+    """Median wall time of one forward + backward of each loss of admm_net_amd.losses (``BasicANMLoss``, ``PhiAlignmentLoss``)
+    on ``route = "hip"`` and ``route = "tensor"``, on synthetic device tensors: [batch, targets] head outputs and labels with
+    L_true cycling through 0 .. targets, [batch, dim] complex phi.  Each step is bracketed by a device synchronisation, so a
+    figure is the latency of the loss alone, as a training loop sees it between the model's forward and backward.
+    Returns a dict of milliseconds per loss and route."""
+    from . import losses
+    dev = torch.device(device)
+    g = torch.Generator().manual_seed(seed)
+    r = lambda *shape: torch.rand(*shape, generator=g).to(dev)
+    tau, f, conf = (r(batch, targets).requires_grad_(True) for _ in range(3))
+    truth = {"tau_true": r(batch, targets), "f_true": r(batch, targets) - 0.5,
+             "L_true": (torch.arange(batch) % (targets + 1)).to(dev)}
+    phi = torch.randn(batch, dim, dtype=torch.complex64, generator=g).to(dev).requires_grad_(True)
+    phi_true = torch.randn(batch, dim, dtype=torch.complex64, generator=g).to(dev)
+    leaves = (tau, f, conf, phi)
+
+    def median_ms(crit, call):
+        times = []
+        for i in range(warmup + steps):
+            for t in leaves:
+                t.grad = None
+            torch.cuda.synchronize(dev)
+            t0 = time.perf_counter()
+            total, _ = call(crit)
+            total.backward()
+            torch.cuda.synchronize(dev)
+            if i >= warmup:
+                times.append(time.perf_counter() - t0)
+        return round(float(np.median(times)) * 1e3, 4)
+
+    out = {"batch": batch, "targets": targets, "dim": dim, "steps": steps}
+    for route in losses.ROUTES:
+        anm, pal = losses.BasicANMLoss(), losses.PhiAlignmentLoss()
+        anm.route = pal.route = route
+        out[f"anm_{route}_ms"] = median_ms(anm, lambda c: c({"tau_est": tau, "f_est": f, "confidences": conf, "phi_final": phi}, truth))
+        out[f"phi_{route}_ms"] = median_ms(pal, lambda c: c(phi, phi_true))
+    return out
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     sub = ap.add_subparsers(dest="cmd", required=True)
@@ -203,7 +244,16 @@ def main(argv=None):
     c.add_argument("--steps", type=int, default=20)
     c.add_argument("--route", choices=("tensor", "fused", "full"), default="tensor")
     c.add_argument("--grid", default=f"{NB}x{ND}", help="MxN")
+    d = sub.add_parser("loss-step")
+    d.add_argument("--batch", type=int, default=256)
+    d.add_argument("--targets", type=int, default=3)
+    d.add_argument("--dim", type=int, default=100)
+    d.add_argument("--steps", type=int, default=200)
     args = ap.parse_args(argv)
+    if args.cmd == "loss-step":
+        import json
+        print(json.dumps(time_loss_step(args.batch, args.targets, args.dim, args.steps)))
+        return
     if args.cmd == "train-step":
         import json
         try:

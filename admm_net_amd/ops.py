@@ -401,6 +401,95 @@ def train_stepsize_bwd(g_step, rn, rho, W1, b1, W2, b2, knorm: float, sub_batch=
     return g_rn, out[0], out[1:97].reshape(32, 3), out[97:129], out[129:161].reshape(1, 32), out[161:162]
 
 
+# ---- the training losses (csrc/loss.hip) --------------------------------------------------------------------------------------
+# out [3] float32 = (total, first part, second part); g_out [3] = the gradients of those three, a device tensor.
+_LOSS_ANM, _LOSS_PHI = range(2)
+
+
+def _loss_partials(lib, loss, B, dev):
+    need = lib.admmnet_loss_partials(loss, B)
+    if need < 0:
+        raise _lib.AdmmNetError(f"loss: bad size (B={B})")
+    return torch.empty(need, dtype=torch.float32, device=dev)
+
+
+def _anm_args(tau, f, conf, tau_true, f_true, L_true, phi):
+    """(lib, device, B, Lmax, D, the seven tensors as the kernels read them)."""
+    for t, name in ((tau, "tau"), (f, "f"), (conf, "conf"), (tau_true, "tau_true"), (f_true, "f_true"), (L_true, "L_true"),
+                    (phi, "phi")):
+        _need_cuda(t, name)
+    if tau.dim() != 2 or phi.dim() != 2:
+        raise ValueError(f"tau must be [B, Lmax] and phi [B, D], got {tuple(tau.shape)} and {tuple(phi.shape)}")
+    if L_true.is_floating_point() or L_true.is_complex() or L_true.dtype == torch.bool:
+        raise ValueError(f"L_true must hold integers, got {L_true.dtype}")
+    dev, (B, Lmax), D = tau.device, tau.shape, phi.shape[1]
+    if not 1 <= Lmax <= 64 or D < 1 or B < 1:
+        raise ValueError(f"loss_anm needs 1 <= Lmax <= 64, D >= 1, B >= 1, got Lmax={Lmax}, D={D}, B={B}")
+    with torch.cuda.device(dev):
+        real = [_f32(t, dev, (B, Lmax), name) for t, name in ((tau, "tau"), (f, "f"), (conf, "conf"), (tau_true, "tau_true"),
+                                                              (f_true, "f_true"))]
+        L_true = L_true.detach().to(device=dev, dtype=torch.int64).contiguous()
+        if tuple(L_true.shape) != (B,):
+            raise ValueError(f"L_true must be ({B},), got {tuple(L_true.shape)}")
+        phi = _c64(phi, dev, (B, D), "phi")
+    return _lib.load(), dev, B, Lmax, D, (*real, L_true, phi)
+
+
+def loss_anm(tau, f, conf, tau_true, f_true, L_true, phi, lambda_reg: float):
+    """BasicANMLoss (loss.py:6-60): returns (out [3] = (total, param, reg), norms [B] = ||phi_b|| for ``loss_anm_bwd``,
+    status [1] int32 = the number of signals whose L_true lies outside [0, Lmax] -- they are evaluated with L held to it)."""
+    lib, dev, B, Lmax, D, t = _anm_args(tau, f, conf, tau_true, f_true, L_true, phi)
+    with torch.cuda.device(dev):
+        out = torch.empty(3, dtype=torch.float32, device=dev)
+        norms = torch.empty(B, dtype=torch.float32, device=dev)
+        status = torch.empty(1, dtype=torch.int32, device=dev)
+        part = _loss_partials(lib, _LOSS_ANM, B, dev)
+        _lib.check(lib.admmnet_loss_anm_f32(Lmax, D, B, *(_ptr(x) for x in t), float(lambda_reg), _ptr(out), _ptr(norms),
+                                            _ptr(status), _ptr(part), _stream(dev)), "admmnet_loss_anm_f32")
+    return out, norms, status
+
+
+def loss_anm_bwd(g_out, tau, f, conf, tau_true, f_true, L_true, phi, norms, lambda_reg: float):
+    """Backward of ``loss_anm`` from g_out [3]: returns (g_tau, g_f, g_conf [B, Lmax], g_phi [B, D] complex64)."""
+    lib, dev, B, Lmax, D, t = _anm_args(tau, f, conf, tau_true, f_true, L_true, phi)
+    _need_cuda(g_out, "g_out")
+    with torch.cuda.device(dev):
+        g_out, norms = _f32(g_out, dev, (3,), "g_out"), _f32(norms, dev, (B,), "norms")
+        g_tau, g_f, g_conf = (torch.empty(B, Lmax, dtype=torch.float32, device=dev) for _ in range(3))
+        g_phi = torch.empty(B, D, dtype=torch.complex64, device=dev)
+        _lib.check(lib.admmnet_loss_anm_bwd_f32(Lmax, D, B, _ptr(g_out), *(_ptr(x) for x in t), _ptr(norms), float(lambda_reg),
+                                                _ptr(g_tau), _ptr(g_f), _ptr(g_conf), _ptr(g_phi), _stream(dev)),
+                   "admmnet_loss_anm_bwd_f32")
+    return g_tau, g_f, g_conf, g_phi
+
+
+def loss_phi(phi, phi_true, amplitude_weight: float, phase_weight: float) -> torch.Tensor:
+    """PhiAlignmentLoss (loss.py:62-98): returns out [3] = (total, amplitude, phase)."""
+    _need_cuda(phi_true, "phi_true")
+    lib, dev, B, D = _small_args(phi, "phi")
+    with torch.cuda.device(dev):
+        phi, phi_true = _c64(phi, dev, (B, D), "phi"), _c64(phi_true, dev, (B, D), "phi_true")
+        out = torch.empty(3, dtype=torch.float32, device=dev)
+        part = _loss_partials(lib, _LOSS_PHI, B, dev)
+        _lib.check(lib.admmnet_loss_phi_c64(D, B, _ptr(phi), _ptr(phi_true), float(amplitude_weight), float(phase_weight),
+                                            _ptr(out), _ptr(part), _stream(dev)), "admmnet_loss_phi_c64")
+    return out
+
+
+def loss_phi_bwd(g_out, phi, phi_true, amplitude_weight: float, phase_weight: float) -> torch.Tensor:
+    """Backward of ``loss_phi`` from g_out [3]: returns g_phi [B, D] complex64."""
+    _need_cuda(phi_true, "phi_true")
+    _need_cuda(g_out, "g_out")
+    lib, dev, B, D = _small_args(phi, "phi")
+    with torch.cuda.device(dev):
+        g_out = _f32(g_out, dev, (3,), "g_out")
+        phi, phi_true = _c64(phi, dev, (B, D), "phi"), _c64(phi_true, dev, (B, D), "phi_true")
+        g_phi = torch.empty_like(phi)
+        _lib.check(lib.admmnet_loss_phi_bwd_c64(D, B, _ptr(g_out), _ptr(phi), _ptr(phi_true), float(amplitude_weight),
+                                                float(phase_weight), _ptr(g_phi), _stream(dev)), "admmnet_loss_phi_bwd_c64")
+    return g_phi
+
+
 def glayer(model, k: int, phi: torch.Tensor, h: torch.Tensor, Z=None):
     """GLayer.forward (admm_net.py:237-354) of layer k of ``model`` plus the Z-layer residual norm.
 

@@ -312,6 +312,48 @@ int admmnet_train_stepsize_bwd_f32(int64_t B, int64_t sub_batch, float knorm, co
                                    const float *rho, const float *W1, const float *b1, const float *W2, const float *b2,
                                    float *g_rn, float *g_params, float *partials, void *stream);
 
+/* The training losses of the reference's loss.py (csrc/loss.hip): one kernel per forward (plus a float64 sum over the batch
+ * that also forms the outputs) and one elementwise kernel per backward.  B >= 1, D >= 1 (any signal length), 1 <= Lmax <= 64.
+ * All tensors are dense and need only their natural alignment (4 bytes float, 8 bytes complex64 and int64).  Sums over the
+ * batch run in a fixed order without atomics (float64 across workgroups): two runs give the same bits.  `partials` is float
+ * scratch of admmnet_loss_partials(loss, B) entries.  `g_out` is a DEVICE float[3]: the gradients of out[0], out[1], out[2].
+ * Complex gradients follow torch's convention (dL/dRe + i dL/dIm); the targets (tau_true, f_true, L_true, phi_true) get none.
+ *   admmnet_loss_anm_f32      BasicANMLoss, loss.py:6-60.  tau, f, conf, tau_true, f_true float [B][Lmax], L_true int64 [B],
+ *                             phi complex64 [B][D].  With L = L_true[b]:
+ *                               L = 0:   loss_b = sum_j conf_j^2 over all Lmax slots;
+ *                               L >= 1:  loss_b = mean_{j<L} (tau_j - tau_true_j)^2 + mean_{j<L} (f_j - f_true_j)^2
+ *                                                 + 0.1 mean_{j<L} (conf_j - 1)^2.
+ *                             out[3] = {param + reg, param, reg}, param = sum_b loss_b / B, reg = lambda_reg mean_b ||phi_b||_2;
+ *                             norms [B] = ||phi_b||_2, kept for the backward; status[0] = the number of signals whose L_true
+ *                             lies outside [0, Lmax] (the reference raises for those; the kernel evaluates them with L held
+ *                             to that range and reads nothing out of bounds).
+ *   admmnet_loss_anm_bwd_f32  with cp = g_out[0] + g_out[1], cr = g_out[0] + g_out[2]: g_tau, g_f, g_conf [B][Lmax] =
+ *                             cp d loss_b / d(.) / B (zeros at j >= L when L >= 1; g_tau = g_f = 0 when L = 0),
+ *                             g_phi[b] = cr lambda_reg / B phi_b / ||phi_b||, exactly 0 where the norm is 0.
+ *   admmnet_loss_phi_c64      PhiAlignmentLoss, loss.py:62-98.  phi, phi_true complex64 [B][D].
+ *                             amplitude = mean (|phi| - |phi_true|)^2, phase = mean wrap(arg phi - arg phi_true)^2 over the
+ *                             B D entries, wrap(d) = ((d + pi) mod 2 pi) - pi with the floored mod (+pi maps to -pi);
+ *                             out[3] = {amplitude_weight amplitude + phase_weight phase, amplitude, phase}.
+ *   admmnet_loss_phi_bwd_c64  with ca = g_out[0] amplitude_weight + g_out[1], cp = g_out[0] phase_weight + g_out[2], phi = x + iy:
+ *                             g_phi = ca 2 (|phi| - |phi_true|) / (B D) phi / |phi| + cp 2 wrap(.) / (B D) (-y + ix) / |phi|^2,
+ *                             exactly 0 where phi = 0; the wrap has derivative 1. */
+enum {
+    ADMMNET_LOSS_ANM = 0,
+    ADMMNET_LOSS_PHI = 1
+};
+int64_t admmnet_loss_partials(int32_t loss, int64_t B);
+int admmnet_loss_anm_f32(int32_t Lmax, int32_t D, int64_t B, const float *tau, const float *f, const float *conf,
+                         const float *tau_true, const float *f_true, const int64_t *L_true, const void *phi, float lambda_reg,
+                         float *out, float *norms, int32_t *status, float *partials, void *stream);
+int admmnet_loss_anm_bwd_f32(int32_t Lmax, int32_t D, int64_t B, const float *g_out, const float *tau, const float *f,
+                             const float *conf, const float *tau_true, const float *f_true, const int64_t *L_true,
+                             const void *phi, const float *norms, float lambda_reg, float *g_tau, float *g_f, float *g_conf,
+                             void *g_phi, void *stream);
+int admmnet_loss_phi_c64(int32_t D, int64_t B, const void *phi, const void *phi_true, float amplitude_weight,
+                         float phase_weight, float *out, float *partials, void *stream);
+int admmnet_loss_phi_bwd_c64(int32_t D, int64_t B, const float *g_out, const void *phi, const void *phi_true,
+                             float amplitude_weight, float phase_weight, void *g_phi, void *stream);
+
 /* Spectrum |phi^H kron(s(f), conj d(tau))|^2 on a (tau, f) grid:
  * peak_search_func / peak_search, utils/peakSearchUtils.py:9-60, evaluated in
  * float64 like the reference.
