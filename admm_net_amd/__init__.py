@@ -4,6 +4,7 @@ Public surface mirrors the reference's admm_net.py for the forward hot path:
 ``ADMMNet`` and ``PhiEstADMMNet`` (same ctor / forward / state_dict keys).
 Importing this package never imports the CPU oracle.
 """
+from .options import Options  # noqa: F401
 from .modules import ADMMNet, PhiEstADMMNet, PeakSearchLayer, PhiLayer, HLayer, GLayer, ZLayer  # noqa: F401
 
-__all__ = ["ADMMNet", "PhiEstADMMNet"]
+__all__ = ["ADMMNet", "PhiEstADMMNet", "Options"]

@@ -15,8 +15,9 @@ LIB_PATH = os.path.join(_HERE, "libadmmnet_hip.so")
 
 
 class Cfg(ctypes.Structure):
-    """struct admmnet_cfg (include/admmnet.h).  ``reserved[0]`` is the C struct's ``sub_batch`` (0 = one batch), the field
-    list keeps the two-int ``reserved`` of ABI version 1."""
+    """struct admmnet_cfg (include/admmnet.h).  ``reserved[0]`` is the C struct's ``sub_batch`` (0 = one batch) and
+    ``reserved[1]`` its ``reserved[0]``, the option handle (0 = the process defaults; ``options.Options``): the field list
+    keeps the two-int ``reserved`` of ABI version 1."""
     _fields_ = [("M", c_int32), ("N", c_int32), ("L", c_int32), ("K", c_int32),
                 ("has_head", c_int32), ("chunk", c_int32), ("reserved", c_int32 * 2)]
 
@@ -31,6 +32,8 @@ _lib = None
 SYMBOLS = {
     "admmnet_abi_version": (c_int32, []),
     "admmnet_last_error": (c_char_p, []),
+    "admmnet_options_intern": (c_int32, [POINTER(c_char_p), POINTER(c_char_p), c_int32]),
+    "admmnet_options_describe": (c_int64, [c_int32, c_char_p, c_int64]),
     "admmnet_raw_weight_count": (c_int64, [POINTER(Cfg)]),
     "admmnet_packed_weight_count": (c_int64, [POINTER(Cfg)]),
     "admmnet_pack_weights": (c_int32, [POINTER(Cfg), c_void_p, c_void_p]),
@@ -52,6 +55,9 @@ SYMBOLS = {
     "admmnet_eigh_workspace_bytes": (c_int64, [c_int32, c_int64]),
     "admmnet_eigh_c64": (c_int32, [c_int32, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int64,
                                    c_void_p, c_void_p]),
+    "admmnet_eigh_workspace_bytes_o": (c_int64, [c_int32, c_int64, c_int32]),
+    "admmnet_eigh_c64_o": (c_int32, [c_int32, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int64,
+                                     c_void_p, c_void_p, c_int32]),
     "admmnet_vdvh_c64": (c_int32, [c_int32, c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
     "admmnet_vhsv_f32": (c_int32, [c_int32, c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
     "admmnet_train_partials": (c_int64, [c_int32, c_int64]),

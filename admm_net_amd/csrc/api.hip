@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "common.h"
+#include "options.h"
 
 namespace admmnet {
 
@@ -92,8 +93,16 @@ static int check_cfg(const admmnet_cfg *cfg) {
         set_error("sub_batch=%d (need 0 = one batch, or >= 1 signals per sub-batch)", cfg->sub_batch);
         return ADMMNET_E_ARG;
     }
+    if (!options_resolve(cfg->reserved[0])) {
+        set_error("cfg.reserved[0] = %d is not an option handle admmnet_options_intern has issued (0 = the process defaults)",
+                  cfg->reserved[0]);
+        return ADMMNET_E_ARG;
+    }
     return ADMMNET_OK;
 }
+
+// The Switches of a call: the option set its cfg names (options.h; handle 0 = the process defaults).  Behind check_cfg.
+static const Switches &cfg_switches(const admmnet_cfg *cfg) { return *options_resolve(cfg->reserved[0]); }
 
 // Sub-batches (cfg->sub_batch = g > 0): the signals [j g, min((j + 1) g, B)) form group j, which takes its own batch mean.
 // group_size() is g capped at B (g >= B is one group); without sub-batches the whole call is one group of B.
@@ -196,10 +205,11 @@ static int carve_workspace(const admmnet_cfg *cfg, int64_t B, void *base, int64_
         ws->mean = c.take<float>(ng > 4 ? ng : 4);
         ws->headkv = c.take<float>((int64_t)2 * D * 128);
     }
-    const Route r = route_for(D, switches());
+    const Switches &sw = cfg_switches(cfg);
+    const Route r = route_for(D, sw);
     carve_chunk(c, r, pick_chunk(cfg, B), ws);
     ws->set2_offset = 0;
-    if (state && switches().two_streams && B > ws->chunk) {   // room for a second chunk in flight: a second set, same layout
+    if (state && sw.two_streams && B > ws->chunk) {   // room for a second chunk in flight: a second set, same layout
         ws->set2_offset = c.off;
         Ws tmp;
         carve_chunk(c, r, ws->chunk, &tmp);
@@ -225,13 +235,14 @@ struct GLayerIO {
 
 // The eigen-pipeline of a chunk whose image is built (ws.skip: its per-matrix filter), then the rebuild of G.  io == nullptr:
 // eigenvalues and the explicit eigenvector image only (admmnet_eigh_c64).
-static int eig_chunk(const Route &r, int64_t nb, const Ws &ws, int32_t *status, hipStream_t st, const GLayerIO *io) {
+static int eig_chunk(const Route &r, const Switches &sw, int64_t nb, const Ws &ws, int32_t *status, hipStream_t st,
+                     const GLayerIO *io) {
     const int D = r.D, E = r.eig_dim;   // (the image, T, W and the eigenvector image are all of dimension E)
     const Back back = io ? r.back : r.back_v();
     const GLayerIO g = io ? *io : GLayerIO{};
     int rc;
-    if ((rc = launch_tridiag(r, nb, ws, st, g.Zlow, g.phi, g.h, g.lw))) return rc;
-    if (r.dc) rc = launch_dc(E + 1, nb, ws, status, st, Route::dc_rowmajor(back), Route::dc_colmap(back));
+    if ((rc = launch_tridiag(r, sw, nb, ws, st, g.Zlow, g.phi, g.h, g.lw))) return rc;
+    if (r.dc) rc = launch_dc(sw, E + 1, nb, ws, status, st, Route::dc_rowmajor(back), Route::dc_colmap(back));
     else rc = launch_tql(E + 1, nb, ws, status, st);
     if (rc) return rc;
     switch (back) {
@@ -242,7 +253,7 @@ static int eig_chunk(const Route &r, int64_t nb, const Ws &ws, int32_t *status, 
         case BK_ROTATION: rc = launch_rotapply(E, nb, ws, st); break;
     }
     if (rc || !io) return rc;
-    if (r.rebuild == RB_BACK) return launch_back_rebuild(D, nb, g.lw, g.phi, g.h, g.G, g.rn, g.w_out, ws, st, g.lower_only);
+    if (r.rebuild == RB_BACK) return launch_back_rebuild(sw, D, nb, g.lw, g.phi, g.h, g.G, g.rn, g.w_out, ws, st, g.lower_only);
     return launch_rebuild(D, nb, g.lw, g.phi, g.h, g.G, g.rn, g.w_out, ws, st, g.lower_only, r.rebuild, E);
 }
 
@@ -254,6 +265,23 @@ extern "C" {
 
 int admmnet_abi_version(void) { return ADMMNET_ABI_VERSION; }
 const char *admmnet_last_error(void) { return g_err; }
+
+int32_t admmnet_options_intern(const char *const *names, const char *const *values, int32_t count) {
+    char err[sizeof(g_err)];
+    const int32_t h = options_intern(names, values, count, err, sizeof(err));
+    if (h >= 0) return h;
+    set_error("%s", err);
+    return ADMMNET_E_ARG;
+}
+
+int64_t admmnet_options_describe(int32_t handle, char *buf, int64_t len) {
+    const Switches *sw = options_resolve(handle);
+    if (!sw || !buf || len < 1) {
+        set_error("options_describe: %s (handle %d)", sw ? "no buffer" : "not an option handle admmnet_options_intern has issued", handle);
+        return ADMMNET_E_ARG;
+    }
+    return options_describe(*sw, buf, (size_t)len);
+}
 
 int64_t admmnet_raw_weight_count(const admmnet_cfg *cfg) {
     if (check_cfg(cfg)) return -1;
@@ -396,6 +424,13 @@ int admmnet_begin(const admmnet_cfg *cfg, int64_t B, void *workspace, int64_t wo
         set_error("begin: bad B or workspace");
         return ADMMNET_E_ARG;
     }
+    // a combination no kernel serves is refused here, before the forward enqueues anything (admmnet_layer_front refuses it too):
+    // the dense G-layers are k = 1 .. K - 2, and k = 0 where the arrowhead solver is off
+    const Route r = route_for(cfg->M * cfg->N, cfg_switches(cfg));
+    if (r.error != RE_NONE && (cfg->K >= 3 || (cfg->K == 2 && r.first == AR_NONE))) {
+        set_error("%s", kRouteErrorText[r.error]);
+        return ADMMNET_E_ARG;
+    }
     Ws ws;
     if ((rc = carve_workspace(cfg, B, workspace, workspace_bytes, &ws, true))) return rc;
     if (status) ADMM_HIP(hipMemsetAsync(status, 0, 4 * sizeof(int32_t), (hipStream_t)stream));
@@ -418,12 +453,21 @@ int admmnet_layer_front(const admmnet_cfg *cfg, const float *W, int32_t k, const
     const int64_t n = D + 1;
     const LayerLayout L{D};
     const float2 *yy = (const float2 *)y, *bb = (const float2 *)b;
-    const Route r = route_for(D, switches());
+    const Switches &sw = cfg_switches(cfg);
+    const Route r = route_for(D, sw);
     if (k == cfg->K - 1) return launch_prep(cfg, W, k, yy, bb, sigma, 0, B, ws, PM_PHI_ONLY, r.eig_dim, st);
     const bool arrow = k == 0 && r.first != AR_NONE;   // Z = 0: arrowhead, no matrix is ever formed
     if (!arrow && r.error != RE_NONE) {
         set_error("%s", kRouteErrorText[r.error]);
         return ADMMNET_E_ARG;
+    }
+    // status[1] of a forward = the matrix-layers that went through the eigensolver (include/admmnet.h).  One writer per call:
+    // with the matrix-function route on (r.matfun), its kernel counts the matrices it hands over and nothing is written here;
+    // with the route off for this call every matrix of a dense layer goes there and no kernel counts, so the word is set here
+    // to the dense matrix-layers up to and including layer k (the arrowhead layer is not one of them), saturating at INT32_MAX
+    if (!arrow && r.matfun == MF_OFF && status) {
+        const int64_t dense = B * (int64_t)(k + 1 - (r.first != AR_NONE ? 1 : 0));
+        ADMM_HIP(hipMemsetD32Async((hipDeviceptr_t)(status + 1), (int)(dense > INT32_MAX ? INT32_MAX : dense), 1, st));
     }
     const float *lw = W + (int64_t)k * L.size();
     const int cur = k & 1;
@@ -446,7 +490,7 @@ int admmnet_layer_front(const admmnet_cfg *cfg, const float *W, int32_t k, const
     // choose it (spectral_waves).  Full groups of g and a short last group may take different shapes: no chunk then
     // straddles the start of the last group.  Without sub-batches both are spectral_waves(D, B) and nothing splits.
     const int64_t gsz = group_size(cfg, B), last0 = (group_count(cfg, B) - 1) * gsz;
-    const int waves_full = spectral_waves(D, gsz), waves_last = spectral_waves(D, B - last0);
+    const int waves_full = spectral_waves(D, gsz, sw), waves_last = spectral_waves(D, B - last0, sw);
     int ci = 0;
     int64_t nb = 0;
     for (int64_t b0 = 0; b0 < B; b0 += nb, ++ci) {
@@ -460,7 +504,7 @@ int admmnet_layer_front(const admmnet_cfg *cfg, const float *W, int32_t k, const
                     ws.rn + b0, nullptr, r.lean()};
         if (arrow) {
             if ((rc = launch_prep(cfg, W, k, yy, bb, sigma, b0, nb, wc, PM_NO_MATRIX, r.eig_dim, sc))) return rc;
-            if ((rc = launch_arrow_rebuild(r, nb, io.lw, io.phi, io.h, io.G, io.rn, io.w_out, status, wc, sc, io.lower_only)))
+            if ((rc = launch_arrow_rebuild(r, sw, nb, io.lw, io.phi, io.h, io.G, io.rn, io.w_out, status, wc, sc, io.lower_only)))
                 return rc;
             continue;
         }
@@ -475,7 +519,7 @@ int admmnet_layer_front(const admmnet_cfg *cfg, const float *W, int32_t k, const
         if (r.matfun != MF_OFF) {
             const int prv = cur ^ 1;
             const float *lwp = k >= 1 ? W + (int64_t)(k - 1) * L.size() : lw;
-            if ((rc = launch_spectral(D, nb, lw, io.phi, io.h, Zk, io.G, io.rn, wc, status, sc, r.matfun, waves,
+            if ((rc = launch_spectral(sw, D, nb, lw, io.phi, io.h, Zk, io.G, io.rn, wc, status, sc, r.matfun, waves,
                                       fold ? ws.alpha + b0 : nullptr, fold ? ws.phi[prv] + b0 * D : nullptr,
                                       fold ? ws.h[prv] + b0 * D : nullptr, fold ? lwp : nullptr, fold ? (k == 1 ? 2 : 1) : 0)))
                 return rc;
@@ -484,7 +528,7 @@ int admmnet_layer_front(const admmnet_cfg *cfg, const float *W, int32_t k, const
             if (r.late_image && (rc = launch_half_image(D, nb, lw, io.phi, io.h, Zk, wf, r.eig_dim, sc))) return rc;
         }
         // (ST_LEAN: the tridiagonalisation's own loader forms A from the lower triangle of Z; ST_HALF reads the half image)
-        if ((rc = eig_chunk(r, nb, wf, status, sc, &io))) return rc;
+        if ((rc = eig_chunk(r, sw, nb, wf, status, sc, &io))) return rc;
     }
     if (dual) {   // the caller's stream continues behind both chunk streams
         for (int q = 0; q < 2; ++q) {
@@ -605,19 +649,20 @@ int admmnet_glayer_f32(const admmnet_cfg *cfg, const float *lw, const void *phi,
     if ((rc = carve_workspace(&c2, B, base + rn_bytes, workspace_bytes - rn_bytes, &ws, false))) return rc;
     float *rn_tmp = (float *)base;
     if (status) ADMM_HIP(hipMemsetAsync(status, 0, 4 * sizeof(int32_t), st));
-    const Route r = route_for(D, switches());
+    const Switches &sw = cfg_switches(cfg);
+    const Route r = route_for(D, sw);
     for (int64_t b0 = 0; b0 < B; b0 += ws.chunk) {
         const int64_t nb = (B - b0 < ws.chunk) ? (B - b0) : ws.chunk;
         const float2 *Zc = Z ? (const float2 *)Z + b0 * n * n : nullptr;
         const GLayerIO io{lw, (const float2 *)phi + b0 * D, h + b0 * D, nullptr, (float2 *)G_out + b0 * n * n,
                           rn_out ? rn_out + b0 : rn_tmp + b0, w_out ? w_out + b0 * n : nullptr, false};
         if (!Zc && r.first != AR_NONE) {
-            if ((rc = launch_arrow_rebuild(r, nb, io.lw, io.phi, io.h, io.G, io.rn, io.w_out, status, ws, st, io.lower_only)))
+            if ((rc = launch_arrow_rebuild(r, sw, nb, io.lw, io.phi, io.h, io.G, io.rn, io.w_out, status, ws, st, io.lower_only)))
                 return rc;
             continue;
         }
         if ((rc = launch_build_block(D, nb, sc[S_CORNER_G], sc[S_INV_RHO_G], io.phi, io.h, Zc, ws, r.eig_dim, st))) return rc;
-        if ((rc = eig_chunk(r, nb, ws, status, st, &io))) return rc;
+        if ((rc = eig_chunk(r, sw, nb, ws, status, st, &io))) return rc;
     }
     return ADMMNET_OK;
 }
@@ -640,15 +685,19 @@ int admmnet_glayer_spectral_f32(const admmnet_cfg *cfg, const float *layer_weigh
     }
     hipStream_t st = (hipStream_t)stream;
     ADMM_HIP(hipMemsetAsync(status, 0, 4 * sizeof(int32_t), st));
-    return launch_spectral_fused(D, B, layer_weights, (const float2 *)phi, h, (float2 *)Z, (float2 *)G, rn_out, flag, status,
-                                 switches().spectral_tol, mode ? alpha : nullptr, mode ? (const float2 *)phi_prev : nullptr,
+    const Switches &sw = cfg_switches(cfg);
+    return launch_spectral_fused(sw, D, B, layer_weights, (const float2 *)phi, h, (float2 *)Z, (float2 *)G, rn_out, flag, status,
+                                 mode ? alpha : nullptr, mode ? (const float2 *)phi_prev : nullptr,
                                  mode ? h_prev : nullptr, mode ? prev_layer_weights : nullptr, mode,
-                                 waves ? waves : spectral_waves(D, B), st);
+                                 waves ? waves : spectral_waves(D, B, sw), st);
 }
 
-int64_t admmnet_eigh_workspace_bytes(int32_t n, int64_t B) {
+int64_t admmnet_eigh_workspace_bytes(int32_t n, int64_t B) { return admmnet_eigh_workspace_bytes_o(n, B, 0); }
+
+int64_t admmnet_eigh_workspace_bytes_o(int32_t n, int64_t B, int32_t options) {
     if (n < 2 || n - 1 > kMaxD || B < 1) return -1;
-    admmnet_cfg cfg = {n - 1, 1, 3, 1, 0, 0, 0, {0}};
+    admmnet_cfg cfg = {n - 1, 1, 3, 1, 0, 0, 0, {options}};
+    if (check_cfg(&cfg)) return -1;
     Ws ws;
     carve_workspace(&cfg, B, nullptr, 0, &ws, false);
     return ws.total_bytes;
@@ -663,22 +712,29 @@ int64_t admmnet_glayer_workspace_bytes(const admmnet_cfg *cfg, int64_t B) {
 
 int admmnet_eigh_c64(int32_t n, int64_t B, const void *A, float *w, void *V, void *workspace,
                      int64_t workspace_bytes, int32_t *status, void *stream) {
+    return admmnet_eigh_c64_o(n, B, A, w, V, workspace, workspace_bytes, status, stream, 0);
+}
+
+int admmnet_eigh_c64_o(int32_t n, int64_t B, const void *A, float *w, void *V, void *workspace,
+                       int64_t workspace_bytes, int32_t *status, void *stream, int32_t options) {
     if (n < 2 || n - 1 > kMaxD || B < 1 || !A || !w || !V || !workspace) {
         set_error("eigh: bad argument (n=%d)", n);
         return ADMMNET_E_ARG;
     }
     hipStream_t st = (hipStream_t)stream;
-    admmnet_cfg cfg = {n - 1, 1, 3, 1, 0, 0, 0, {0}};
+    admmnet_cfg cfg = {n - 1, 1, 3, 1, 0, 0, 0, {options}};
     Ws ws;
     int rc;
+    if ((rc = check_cfg(&cfg))) return rc;
     if ((rc = carve_workspace(&cfg, B, workspace, workspace_bytes, &ws, false))) return rc;
     if (status) ADMM_HIP(hipMemsetAsync(status, 0, 4 * sizeof(int32_t), st));
     const int D = n - 1;
-    const Route r = route_for(D, switches());
+    const Switches &sw = cfg_switches(&cfg);
+    const Route r = route_for(D, sw);
     for (int64_t b0 = 0; b0 < B; b0 += ws.chunk) {
         const int64_t nb = (B - b0 < ws.chunk) ? (B - b0) : ws.chunk;
         if ((rc = launch_build_generic(n, nb, (const float2 *)A + b0 * n * n, ws, r.eig_dim, st))) return rc;
-        if ((rc = eig_chunk(r, nb, ws, status, st, nullptr))) return rc;
+        if ((rc = eig_chunk(r, sw, nb, ws, status, st, nullptr))) return rc;
         if ((rc = launch_vout(n, nb, (float2 *)V + b0 * (int64_t)n * n, w + b0 * n, ws, r.eig_dim, st))) return rc;
     }
     return ADMMNET_OK;

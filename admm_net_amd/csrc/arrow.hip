@@ -547,7 +547,7 @@ static int ar_timing_end(PhaseTimer &tm, hipStream_t st, int D, int64_t nb, cons
     return ADMMNET_OK;
 }
 
-int launch_arrow_rebuild(const Route &r, int64_t nb, const float *lw, const float2 *phi, const float *h, float2 *G, float *rn,
+int launch_arrow_rebuild(const Route &r, const Switches &sw, int64_t nb, const float *lw, const float2 *phi, const float *h, float2 *G, float *rn,
                          float *w_out, int32_t *status, const Ws &ws, hipStream_t st, bool lower_only) {
     const int D = r.D;
     if (nb <= 0) return ADMMNET_OK;
@@ -564,7 +564,7 @@ int launch_arrow_rebuild(const Route &r, int64_t nb, const float *lw, const floa
         ADMM_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(arrow_rebuild_kernel<AR_FUSED>),
                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         PhaseTimer tm;
-        if ((rc = tm.begin(switches().ar_timing, st, 16))) return rc;
+        if ((rc = tm.begin(sw.ar_timing, st, 16))) return rc;
         hipLaunchKernelGGL(arrow_rebuild_kernel<AR_FUSED>, dim3((unsigned)nb), dim3(AR_THREADS), lds, st, D, lw, phi, h, G,
                            rn, w_out, status, tm.dev, lower_only ? 1 : 0, (float *)nullptr, (float *)nullptr);
         ADMM_HIP(hipGetLastError());
@@ -588,7 +588,7 @@ int launch_arrow_rebuild(const Route &r, int64_t nb, const float *lw, const floa
     ADMM_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(arrow_rebuild_kernel<AR_LDS>),
                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     PhaseTimer tm;
-    if ((rc = tm.begin(switches().ar_timing, st, 16))) return rc;
+    if ((rc = tm.begin(sw.ar_timing, st, 16))) return rc;
     hipLaunchKernelGGL(arrow_rebuild_kernel<AR_LDS>, dim3((unsigned)nb), dim3(AR_THREADS), lds, st, D, lw, phi, h, G, rn,
                        w_out, status, tm.dev, lower_only ? 1 : 0, (float *)nullptr, (float *)nullptr);
     ADMM_HIP(hipGetLastError());

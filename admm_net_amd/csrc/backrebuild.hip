@@ -226,7 +226,7 @@ __global__ __launch_bounds__(BR_THREADS, 1) void back_rebuild_kernel(
 
 bool back_rebuild_supported(int D) { return D >= 1 && D <= 128; }
 
-int launch_back_rebuild(int D, int64_t nb, const float *lw, const float2 *phi, const float *h, float2 *G,
+int launch_back_rebuild(const Switches &sw, int D, int64_t nb, const float *lw, const float2 *phi, const float *h, float2 *G,
                         float *rn, float *w_out, const Ws &ws, hipStream_t st, bool lower_only) {
     ProfScope _prof(KC_REBUILD, st);
     if (nb <= 0) return ADMMNET_OK;
@@ -248,7 +248,7 @@ int launch_back_rebuild(int D, int64_t nb, const float *lw, const float2 *phi, c
     ADMM_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
                                  (int)lds));
     PhaseTimer tm;
-    if (int rc = tm.begin(switches().br_timing, st, 16)) return rc;
+    if (int rc = tm.begin(sw.br_timing, st, 16)) return rc;
     hipLaunchKernelGGL(kern, dim3((unsigned)nb), dim3(BR_THREADS), lds, st, D, lw, ws.Wdc, ws.QV,
                        ws.w, ws.w0, phi, h, G, rn, tm.dev, dc_final_offset(D + 1), lower_only ? 1 : 0, ws.skip);
     ADMM_HIP(hipGetLastError());

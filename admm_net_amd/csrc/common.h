@@ -118,6 +118,7 @@ struct Ws {
 
 
 // ---- kernel launchers (each enqueues on `st`, returns ADMMNET_* code) ----------
+// (sw: the Switches of the call, resolved from its cfg by api.hip -- a launcher reads its own knobs from it, never the process's)
 // prep.hip
 // mode bits of prep_kernel; launch_prep adds PM_FIRST / PM_ZZERO from k, the caller states the rest from the route
 constexpr int PM_FIRST = 1;      // layer 0: G = Z = 0, nothing is read
@@ -141,13 +142,13 @@ int launch_build_generic(int n, int64_t nb, const float2 *A, const Ws &ws, int e
 int launch_build_block(int D, int64_t nb, float corner, float inv_rho, const float2 *phi, const float *h,
                        const float2 *Z, const Ws &ws, int eig_dim, hipStream_t st);
 // tridiag.hip: r.tridiag at r.eig_dim.  Zlow != nullptr (ST_LEAN): tridiag_reg's own loader forms A = C - Z / rho
-int launch_tridiag(const Route &r, int64_t nb, const Ws &ws, hipStream_t st, const float2 *Zlow, const float2 *phi,
+int launch_tridiag(const Route &r, const Switches &sw, int64_t nb, const Ws &ws, hipStream_t st, const float2 *Zlow, const float2 *phi,
                    const float *h, const float *lw);
-int launch_tridiag_reg(int D, int64_t nb, const Ws &ws, hipStream_t st, const float2 *Zlow, const float2 *phi, const float *h,
+int launch_tridiag_reg(const Switches &sw, int D, int64_t nb, const Ws &ws, hipStream_t st, const float2 *Zlow, const float2 *phi, const float *h,
                        const float *lw);   // tridiag_reg.hip, D <= 128
-int launch_tridiag_big(int D, int64_t nb, const Ws &ws, hipStream_t st, bool panel, bool explicit_q);   // tridiag_big.hip, 128 < D <= 256
+int launch_tridiag_big(const Switches &sw, int D, int64_t nb, const Ws &ws, hipStream_t st, bool panel, bool explicit_q);   // tridiag_big.hip, 128 < D <= 256
 bool tridiag_panel_supported(int D);                                      // tridiag_panel.hip, D == 256
-int launch_tridiag_panel(int D, int64_t nb, const Ws &ws, hipStream_t st, bool explicit_q);
+int launch_tridiag_panel(const Switches &sw, int D, int64_t nb, const Ws &ws, hipStream_t st, bool explicit_q);
 int64_t tridiag_panel_tail_elems();                                       // float2 per matrix of Ws::Tail
 int launch_wy_apply(int D, int64_t nb, const Ws &ws, hipStream_t st);     // wy_apply.hip: V = Q W without forming Q
 // tql.hip
@@ -155,7 +156,7 @@ int launch_tql(int n, int64_t nb, const Ws &ws, int32_t *status, hipStream_t st)
 // rotapply.hip
 int launch_rotapply(int D, int64_t nb, const Ws &ws, hipStream_t st);
 // rebuild.hip
-int launch_dc(int n, int64_t nb, const Ws &ws, int32_t *status, hipStream_t st, bool rowmajor,
+int launch_dc(const Switches &sw, int n, int64_t nb, const Ws &ws, int32_t *status, hipStream_t st, bool rowmajor,
               bool colmap);   // dc.hip (colmap: leave the top level's deflated columns in place, write Ws::Wmap)
 int64_t dc_final_offset(int n);                                                            // dc.hip
 int launch_vgemm(int D, int64_t nb, const Ws &ws, hipStream_t st);                       // dc.hip
@@ -168,10 +169,10 @@ int launch_estimate(const float2 *phi, int64_t B, int xbase, int ybase, const do
                     const double2 *tabS, int ny, const double *axis_x, const double *axis_y, const double *opt7,
                     int iters, int L, const int32_t *top_n, double *top, int32_t *counts, hipStream_t st);   // estimate.hip
 bool arrow_rebuild_supported(int D);                                                       // arrow.hip
-int launch_arrow_rebuild(const Route &r, int64_t nb, const float *lw, const float2 *phi, const float *h, float2 *G, float *rn,
+int launch_arrow_rebuild(const Route &r, const Switches &sw, int64_t nb, const float *lw, const float2 *phi, const float *h, float2 *G, float *rn,
                          float *w_out, int32_t *status, const Ws &ws, hipStream_t st, bool lower_only);   // arrow.hip: r.first
 bool back_rebuild_supported(int D);                                                        // backrebuild.hip
-int launch_back_rebuild(int D, int64_t nb, const float *lw, const float2 *phi, const float *h, float2 *G,
+int launch_back_rebuild(const Switches &sw, int D, int64_t nb, const float *lw, const float2 *phi, const float *h, float2 *G,
                         float *rn, float *w_out, const Ws &ws, hipStream_t st, bool lower_only);   // backrebuild.hip
 // form: RB_BIG or RB_TILES; image_dim: the dimension the eigenvector image ws.VT is laid out for (Route::eig_dim behind the
 // dense pipeline, D itself behind the arrowhead solver of the first layer)
@@ -203,12 +204,12 @@ int launch_spectrum_main(const float2 *phi, int64_t B, int xbase, int ybase, con
                          const double2 *tabS, int ny, double *out, hipStream_t st);
 
 // spectral.hip (form: MF_KERNELS, the five kernels there) / spectral_fused.hip (MF_FUSED: the whole evaluation in one kernel)
-int launch_spectral_fused(int D, int64_t nb, const float *lw, const float2 *phi, const float *h, float2 *Z, float2 *G,
-                          float *rn, int *flag, int32_t *status, float tol, const float *alpha, const float2 *phi_prev,
+int launch_spectral_fused(const Switches &sw, int D, int64_t nb, const float *lw, const float2 *phi, const float *h, float2 *Z,
+                          float2 *G, float *rn, int *flag, int32_t *status, const float *alpha, const float2 *phi_prev,
                           const float *h_prev, const float *lw_prev, int update_mode, int waves, hipStream_t st);
 // update_mode 0: Z is current; 1 / 2: the fused kernel applies Z <- Z + alpha (G - C_prev) in its first sweep (2: stored Z still zero)
-// waves: spectral_waves(D, B) of the call the chunk belongs to
-int launch_spectral(int D, int64_t nb, const float *lw, const float2 *phi, const float *h, float2 *Z, float2 *G,
+// waves: spectral_waves(D, B, sw) of the call the chunk belongs to; sw: the call's tolerance, pass cap and phase timer
+int launch_spectral(const Switches &sw, int D, int64_t nb, const float *lw, const float2 *phi, const float *h, float2 *Z, float2 *G,
                     float *rn, const Ws &ws, int32_t *status, hipStream_t st, MatFun form, int waves, const float *alpha,
                     const float2 *phi_prev, const float *h_prev, const float *lw_prev, int update_mode);
 // vdvh.hip (training route)

@@ -896,7 +896,7 @@ int64_t dc_final_offset(int n) {
     return (levels & 1) ? (int64_t)n * n : 0;
 }
 
-int launch_dc(int n, int64_t nb, const Ws &ws, int32_t *status, hipStream_t st, bool rowmajor, bool colmap) {
+int launch_dc(const Switches &sw, int n, int64_t nb, const Ws &ws, int32_t *status, hipStream_t st, bool rowmajor, bool colmap) {
     ProfScope _prof(KC_TQL, st);
     if (nb <= 0) return ADMMNET_OK;
     if (n / DC_LS > DC_MAXLEAF) {
@@ -904,7 +904,6 @@ int launch_dc(int n, int64_t nb, const Ws &ws, int32_t *status, hipStream_t st, 
         return ADMMNET_E_ARG;
     }
     const size_t lds = dc_lds_bytes(n);
-    const Switches &sw = switches();
     const bool blk = n > 129 && sw.dc_blocks;
     const int occ = sw.dc_occ > 0 ? sw.dc_occ : (blk ? 4 : 5);
     auto kern = blk ? (occ >= 8 ? dc_kernel<8, true> : occ == 6 ? dc_kernel<6, true> : occ == 5 ? dc_kernel<5, true> : dc_kernel<4, true>)

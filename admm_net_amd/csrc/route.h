@@ -1,5 +1,6 @@
-// route.h -- the one place that reads the ADMMNET_* switches (Switches) and decides which kernels run for a geometry (Route):
-// api.hip carves and enqueues from the Route, the launchers receive the chosen form and choose nothing.
+// route.h -- the one place that parses the ADMMNET_* switches (Switches: the environment gives the process defaults, an option
+// set of options.h overrides them per model) and decides which kernels run for a geometry (Route): api.hip resolves the Switches
+// of a call from its cfg, carves and enqueues from the Route, the launchers receive the chosen form and choose nothing.
 // Plain C++17 without a HIP include: tests/host_model/route_model.cpp compiles it with g++ (tests/test_route_host.py).
 #pragma once
 #include <stdint.h>
@@ -57,46 +58,73 @@ struct Switches {   // (INTEGRATION.md section 6 is the user-facing table of the
     bool dc_timing;        // ADMMNET_DC_TIMING: developer phase timer of dc_kernel
 };
 
-inline Switches switches_from_env() {   // the only reader of the environment in csrc/
-    const auto env = [](const char *name) -> const char * { return getenv(name); };
-    const auto is = [&](const char *name, const char *word) { return env(name) && !strcmp(env(name), word); };
-    const auto on = [&](const char *name) { return !(env(name) && atoi(env(name)) == 0); };   // "=0" (anything atoi reads as 0) turns off
-    const auto num = [&](const char *name, int unset) { return env(name) ? atoi(env(name)) : unset; };
+// the built-in defaults: what every switch is with nothing set anywhere
+inline Switches builtin_switches() {
     Switches s;
-    s.spectral = on("ADMMNET_SPECTRAL");
-    s.spectral_fused = on("ADMMNET_SPECTRAL_FUSED");
-    s.spectral_tol = env("ADMMNET_SPECTRAL_TOL") ? (float)atof(env("ADMMNET_SPECTRAL_TOL")) : 1e-6f;
-    s.spectral_iters = num("ADMMNET_SPECTRAL_ITERS", 5);
-    s.sf_fold = on("ADMMNET_SF_FOLD");
-    s.sf_smallwg = on("ADMMNET_SF_SMALLWG");
-    s.sf_timing = env("ADMMNET_SF_TIMING") != nullptr;
-    s.eig_ql = is("ADMMNET_EIG", "ql");
-    s.arrow = on("ADMMNET_ARROW");
-    s.arrow_fused = on("ADMMNET_ARROW_FUSED");
-    s.ar_timing = env("ADMMNET_AR_TIMING") != nullptr;
-    s.lean = on("ADMMNET_LEAN");
-    s.fuse_back = on("ADMMNET_FUSE_BACK");
-    s.br_timing = env("ADMMNET_BR_TIMING") != nullptr;
-    s.tridiag_lds = is("ADMMNET_TRIDIAG", "lds");
-    s.tridiag_sweep = is("ADMMNET_TRIDIAG_BIG", "sweep");
-    s.back_q = is("ADMMNET_BACK", "q");
-    s.rebuild_tiles = is("ADMMNET_REBUILD", "tiles");
-    s.pad_min_set = env("ADMMNET_PAD_MIN") != nullptr;
-    s.pad_min = num("ADMMNET_PAD_MIN", 0);
-    s.two_streams = num("ADMMNET_STREAMS", 0) == 2;
-    s.tr_occ3 = num("ADMMNET_TR_OCC", 0) != 2;
-    s.tr_pad_lds = num("ADMMNET_TR_PAD_LDS", 0);
-    s.pn_split = is("ADMMNET_PN_SPLIT", "0") ? 0 : is("ADMMNET_PN_SPLIT", "8") ? 8 : 84;
-    s.pn_timing = env("ADMMNET_PN_TIMING") != nullptr;
-    s.dc_occ = num("ADMMNET_DC_OCC", 0);
-    s.dc_blocks = !is("ADMMNET_DC_BLOCKS", "0");
-    s.dc_poison = env("ADMMNET_DC_POISON") != nullptr;
-    s.dc_timing = env("ADMMNET_DC_TIMING") != nullptr;
+    s.spectral = s.spectral_fused = s.sf_fold = s.sf_smallwg = s.arrow = s.arrow_fused = s.lean = s.fuse_back = true;
+    s.spectral_tol = 1e-6f;
+    s.spectral_iters = 5;
+    s.sf_timing = s.ar_timing = s.br_timing = s.pn_timing = s.dc_timing = s.dc_poison = false;
+    s.eig_ql = s.tridiag_lds = s.tridiag_sweep = s.back_q = s.rebuild_tiles = s.two_streams = false;
+    s.pad_min_set = false;
+    s.pad_min = 0;
+    s.tr_occ3 = true;
+    s.tr_pad_lds = 0;
+    s.pn_split = 84;
+    s.dc_occ = 0;
+    s.dc_blocks = true;
     return s;
 }
 
-// read once per process (the child-process tests rely on it)
-inline const Switches &switches() { static const Switches s = switches_from_env(); return s; }
+// The one parser: `base` with every name that `env` has a value for (env(name) -> its string, or nullptr: keep base's) read in
+// the environment's syntax.  The process defaults are the environment over builtin_switches() (switches()), an option set is
+// the caller's (name, value) pairs over the process defaults (options.h): the names and spellings of both are these lines.
+template <class Lookup>
+inline Switches switches_from_env(const Switches &base, const Lookup &env) {
+    const auto is = [&](const char *name, const char *word, bool b) { return env(name) ? !strcmp(env(name), word) : b; };
+    const auto on = [&](const char *name, bool b) { return env(name) ? atoi(env(name)) != 0 : b; };   // "=0" (anything atoi reads as 0) turns off
+    const auto set = [&](const char *name, bool b) { return env(name) != nullptr || b; };             // present, whatever the value
+    const auto num = [&](const char *name, int b) { return env(name) ? atoi(env(name)) : b; };
+    Switches s = base;
+    s.spectral = on("ADMMNET_SPECTRAL", base.spectral);
+    s.spectral_fused = on("ADMMNET_SPECTRAL_FUSED", base.spectral_fused);
+    s.spectral_tol = env("ADMMNET_SPECTRAL_TOL") ? (float)atof(env("ADMMNET_SPECTRAL_TOL")) : base.spectral_tol;
+    s.spectral_iters = num("ADMMNET_SPECTRAL_ITERS", base.spectral_iters);
+    s.sf_fold = on("ADMMNET_SF_FOLD", base.sf_fold);
+    s.sf_smallwg = on("ADMMNET_SF_SMALLWG", base.sf_smallwg);
+    s.sf_timing = set("ADMMNET_SF_TIMING", base.sf_timing);
+    s.eig_ql = is("ADMMNET_EIG", "ql", base.eig_ql);
+    s.arrow = on("ADMMNET_ARROW", base.arrow);
+    s.arrow_fused = on("ADMMNET_ARROW_FUSED", base.arrow_fused);
+    s.ar_timing = set("ADMMNET_AR_TIMING", base.ar_timing);
+    s.lean = on("ADMMNET_LEAN", base.lean);
+    s.fuse_back = on("ADMMNET_FUSE_BACK", base.fuse_back);
+    s.br_timing = set("ADMMNET_BR_TIMING", base.br_timing);
+    s.tridiag_lds = is("ADMMNET_TRIDIAG", "lds", base.tridiag_lds);
+    s.tridiag_sweep = is("ADMMNET_TRIDIAG_BIG", "sweep", base.tridiag_sweep);
+    s.back_q = is("ADMMNET_BACK", "q", base.back_q);
+    s.rebuild_tiles = is("ADMMNET_REBUILD", "tiles", base.rebuild_tiles);
+    s.pad_min_set = set("ADMMNET_PAD_MIN", base.pad_min_set);
+    s.pad_min = num("ADMMNET_PAD_MIN", base.pad_min);
+    s.two_streams = env("ADMMNET_STREAMS") ? atoi(env("ADMMNET_STREAMS")) == 2 : base.two_streams;
+    s.tr_occ3 = env("ADMMNET_TR_OCC") ? atoi(env("ADMMNET_TR_OCC")) != 2 : base.tr_occ3;
+    s.tr_pad_lds = num("ADMMNET_TR_PAD_LDS", base.tr_pad_lds);
+    s.pn_split = !env("ADMMNET_PN_SPLIT") ? base.pn_split : is("ADMMNET_PN_SPLIT", "0", false) ? 0 : is("ADMMNET_PN_SPLIT", "8", false) ? 8 : 84;
+    s.pn_timing = set("ADMMNET_PN_TIMING", base.pn_timing);
+    s.dc_occ = num("ADMMNET_DC_OCC", base.dc_occ);
+    s.dc_blocks = !is("ADMMNET_DC_BLOCKS", "0", !base.dc_blocks);
+    s.dc_poison = set("ADMMNET_DC_POISON", base.dc_poison);
+    s.dc_timing = set("ADMMNET_DC_TIMING", base.dc_timing);
+    return s;
+}
+
+// The process defaults: the environment over the built-in values, read once per process (the
+// child-process tests rely on it).  The only reader of the environment in csrc/, and referenced only where the option handle 0
+// is resolved (options.h): everything else receives the Switches of its call.
+inline const Switches &switches() {
+    static const Switches s = switches_from_env(builtin_switches(), [](const char *name) -> const char * { return getenv(name); });
+    return s;
+}
 
 // ---- the route of a geometry --------------------------------------------------------------------------------------------------
 enum Storage { ST_FULL, ST_LEAN, ST_HALF };   // G / Z: full | lower triangles, A from the tridiagonalisation's loader | lower triangles + half image
@@ -184,6 +212,6 @@ inline constexpr const char *kRouteErrorText[] = {   // by RouteError
 // cfg.chunk.  256 threads per matrix, three matrices per CU, once there are more than two matrices per CU to overlap (measured at
 // 10 x 10, K = 10: 1024 signals 3.45 vs 3.63 ms per forward, 4096 signals 8.3 vs 10.4 ms; but 256 signals 2.42 vs 2.03 ms and a
 // single signal 0.64 vs 0.53 ms: a lone matrix is served faster by twelve waves).
-inline int spectral_waves(int D, int64_t B, const Switches &s = switches()) { return (D <= 128 && s.sf_smallwg && B > 512) ? 4 : 12; }
+inline int spectral_waves(int D, int64_t B, const Switches &s) { return (D <= 128 && s.sf_smallwg && B > 512) ? 4 : 12; }
 
 }  // namespace admmnet

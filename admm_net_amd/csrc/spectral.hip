@@ -415,19 +415,19 @@ __global__ __launch_bounds__(SP_THREADS) void sp_assemble_kernel(int D, const fl
 
 // Scratch of its own (Ws::spec_*, carved only when the path is on).  Returns with flag[] filled; the caller runs the
 // eigen-pipeline with Ws::skip = flag.
-int launch_spectral(int D, int64_t nb, const float *lw, const float2 *phi, const float *h, float2 *Z, float2 *G,
+int launch_spectral(const Switches &sw, int D, int64_t nb, const float *lw, const float2 *phi, const float *h, float2 *Z, float2 *G,
                     float *rn, const Ws &ws, int32_t *status, hipStream_t st, MatFun form, int waves, const float *alpha,
                     const float2 *phi_prev, const float *h_prev, const float *lw_prev, int update_mode) {
     ProfScope _prof(KC_GFUNC, st);
     if (nb <= 0) return ADMMNET_OK;
     const int n = D + 1;
-    const float tol = switches().spectral_tol;
+    const float tol = sw.spectral_tol;
     if (form == MF_FUSED) {
         if (!ws.spec_flag) {
             set_error("spectral: the fused kernel needs the flag buffer and the lower-triangle state");
             return ADMMNET_E_WORKSPACE;
         }
-        return launch_spectral_fused(D, nb, lw, phi, h, Z, G, rn, ws.spec_flag, status, tol, alpha, phi_prev, h_prev, lw_prev,
+        return launch_spectral_fused(sw, D, nb, lw, phi, h, Z, G, rn, ws.spec_flag, status, alpha, phi_prev, h_prev, lw_prev,
                                      update_mode, waves, st);
     }
     if (!ws.spec_flag || !ws.spec_vec || !ws.spec_val || !ws.spec_mat) {

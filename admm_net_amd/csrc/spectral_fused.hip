@@ -776,12 +776,12 @@ __global__ __launch_bounds__(64 * W, W == 12 ? 1 : 3) void sp_fused_kernel(int D
 
 template <int TPW, int W>
 static int sf_launch(int D, int64_t nb, const float *lw, const float2 *phi, const float *h, float2 *Z, float2 *G, float *rn,
-                     int *flag, int32_t *status, float tol, int iters, const SfUpdate &up, hipStream_t st) {
+                     int *flag, int32_t *status, float tol, int iters, bool timing, const SfUpdate &up, hipStream_t st) {
     const size_t lds = SfCarve::bytes(D + 1, W);
     ADMM_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(sp_fused_kernel<TPW, W>), hipFuncAttributeMaxDynamicSharedMemorySize,
                                  (int)lds));
     PhaseTimer tm;
-    if (int rc = tm.begin(switches().sf_timing, st, 16)) return rc;
+    if (int rc = tm.begin(timing, st, 16)) return rc;
     hipLaunchKernelGGL((sp_fused_kernel<TPW, W>), dim3((unsigned)nb), dim3(64 * W), lds, st, D, lw, phi, h, Z, G, rn, flag, status,
                        tol, iters, tm.dev, up);
     ADMM_HIP(hipGetLastError());
@@ -798,8 +798,8 @@ static int sf_launch(int D, int64_t nb, const float *lw, const float2 *phi, cons
 
 static_assert(SF_WAVES == 12, "spectral_waves (route.h) names the shapes 4 and 12");
 
-int launch_spectral_fused(int D, int64_t nb, const float *lw, const float2 *phi, const float *h, float2 *Z, float2 *G,
-                          float *rn, int *flag, int32_t *status, float tol, const float *alpha, const float2 *phi_prev,
+int launch_spectral_fused(const Switches &sw, int D, int64_t nb, const float *lw, const float2 *phi, const float *h, float2 *Z,
+                          float2 *G, float *rn, int *flag, int32_t *status, const float *alpha, const float2 *phi_prev,
                           const float *h_prev, const float *lw_prev, int update_mode, int waves, hipStream_t st) {
     const SfUpdate up{alpha, phi_prev, h_prev, lw_prev, update_mode};
     if (D < 2 || D > 256) {
@@ -810,19 +810,21 @@ int launch_spectral_fused(int D, int64_t nb, const float *lw, const float2 *phi,
         set_error("spectral: %d waves per matrix at D=%d (need 12, or 4 with D <= 128)", waves, D);
         return ADMMNET_E_ARG;
     }
-    const int iters = switches().spectral_iters;   // (upper bound)
+    const float tol = sw.spectral_tol;
+    const int iters = sw.spectral_iters;   // (upper bound)
+    const bool timing = sw.sf_timing;
     const int NT = (D + 31) >> 5, ntri = NT * (NT + 1) / 2;
     if (waves == 4) {
         switch ((ntri + 3) / 4) {
-            case 1: return sf_launch<1, 4>(D, nb, lw, phi, h, Z, G, rn, flag, status, tol, iters, up, st);
-            case 2: return sf_launch<2, 4>(D, nb, lw, phi, h, Z, G, rn, flag, status, tol, iters, up, st);
-            default: return sf_launch<3, 4>(D, nb, lw, phi, h, Z, G, rn, flag, status, tol, iters, up, st);
+            case 1: return sf_launch<1, 4>(D, nb, lw, phi, h, Z, G, rn, flag, status, tol, iters, timing, up, st);
+            case 2: return sf_launch<2, 4>(D, nb, lw, phi, h, Z, G, rn, flag, status, tol, iters, timing, up, st);
+            default: return sf_launch<3, 4>(D, nb, lw, phi, h, Z, G, rn, flag, status, tol, iters, timing, up, st);
         }
     }
     switch ((ntri + SF_WAVES - 1) / SF_WAVES) {
-        case 1: return sf_launch<1, SF_WAVES>(D, nb, lw, phi, h, Z, G, rn, flag, status, tol, iters, up, st);
-        case 2: return sf_launch<2, SF_WAVES>(D, nb, lw, phi, h, Z, G, rn, flag, status, tol, iters, up, st);
-        default: return sf_launch<3, SF_WAVES>(D, nb, lw, phi, h, Z, G, rn, flag, status, tol, iters, up, st);
+        case 1: return sf_launch<1, SF_WAVES>(D, nb, lw, phi, h, Z, G, rn, flag, status, tol, iters, timing, up, st);
+        case 2: return sf_launch<2, SF_WAVES>(D, nb, lw, phi, h, Z, G, rn, flag, status, tol, iters, timing, up, st);
+        default: return sf_launch<3, SF_WAVES>(D, nb, lw, phi, h, Z, G, rn, flag, status, tol, iters, timing, up, st);
     }
 }
 

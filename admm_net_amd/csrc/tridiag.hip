@@ -247,7 +247,7 @@ static size_t td_lds_bytes(int D, bool ldsm) {
     return sz;
 }
 
-int launch_tridiag(const Route &r, int64_t nb, const Ws &ws, hipStream_t st, const float2 *Zlow, const float2 *phi,
+int launch_tridiag(const Route &r, const Switches &sw, int64_t nb, const Ws &ws, hipStream_t st, const float2 *Zlow, const float2 *phi,
                    const float *h, const float *lw) {
     ProfScope _prof(KC_TRIDIAG, st);
     const int D = r.eig_dim;
@@ -261,8 +261,8 @@ int launch_tridiag(const Route &r, int64_t nb, const Ws &ws, hipStream_t st, con
     // (A 512-thread, 4-waves-per-SIMD variant of tridiag_reg was measured 1.6x SLOWER: the O(n) per-wave
     // work of every reflector -- norm, Householder scalars, vector set-up, reductions -- is replicated in
     // each wave, and with 8 waves per matrix it outweighs the better latency hiding.)
-    if (r.tridiag == TD_REG) return launch_tridiag_reg(D, nb, ws, st, Zlow, phi, h, lw);
-    if (r.tridiag != TD_LDS) return launch_tridiag_big(D, nb, ws, st, r.tridiag == TD_PANEL, r.explicit_q);
+    if (r.tridiag == TD_REG) return launch_tridiag_reg(sw, D, nb, ws, st, Zlow, phi, h, lw);
+    if (r.tridiag != TD_LDS) return launch_tridiag_big(sw, D, nb, ws, st, r.tridiag == TD_PANEL, r.explicit_q);
     const bool ldsm = td_lds_bytes(D, true) <= 160 * 1024;
     const size_t lds = td_lds_bytes(D, ldsm);
     if (ldsm) {

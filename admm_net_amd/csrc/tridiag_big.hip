@@ -402,9 +402,9 @@ __global__ __launch_bounds__(TB_THREADS) void ungtr_big_kernel(int D, const floa
 // panel (TD_PANEL, D = 256): the panel-blocked kernel of tridiag_panel.hip (trailing updates on the matrix cores) produces the
 // same (d, e, reflector rows, taus) as the per-reflector register sweep below (TD_SWEEP), kept for A/B runs.
 template <int NA>
-static int launch_tb(int D, int64_t nb, const Ws &ws, hipStream_t st, bool panel, bool explicit_q) {
+static int launch_tb(const Switches &sw, int D, int64_t nb, const Ws &ws, hipStream_t st, bool panel, bool explicit_q) {
     if (panel) {
-        int rc = launch_tridiag_panel(D, nb, ws, st, explicit_q);
+        int rc = launch_tridiag_panel(sw, D, nb, ws, st, explicit_q);
         if (rc) return rc;
     } else {
         const size_t lds = sizeof(TbShared<NA>) + sizeof(float2) * (2 * NA - 1) * TB_THREADS;
@@ -421,13 +421,13 @@ static int launch_tb(int D, int64_t nb, const Ws &ws, hipStream_t st, bool panel
     return ADMMNET_OK;
 }
 
-int launch_tridiag_big(int D, int64_t nb, const Ws &ws, hipStream_t st, bool panel, bool explicit_q) {
+int launch_tridiag_big(const Switches &sw, int D, int64_t nb, const Ws &ws, hipStream_t st, bool panel, bool explicit_q) {
     const int na = (D + 31) / 32;
     switch (na) {
-        case 5: return launch_tb<5>(D, nb, ws, st, panel, explicit_q);
-        case 6: return launch_tb<6>(D, nb, ws, st, panel, explicit_q);
-        case 7: return launch_tb<7>(D, nb, ws, st, panel, explicit_q);
-        case 8: return launch_tb<8>(D, nb, ws, st, panel, explicit_q);
+        case 5: return launch_tb<5>(sw, D, nb, ws, st, panel, explicit_q);
+        case 6: return launch_tb<6>(sw, D, nb, ws, st, panel, explicit_q);
+        case 7: return launch_tb<7>(sw, D, nb, ws, st, panel, explicit_q);
+        case 8: return launch_tb<8>(sw, D, nb, ws, st, panel, explicit_q);
         default:
             set_error("tridiag_big: D=%d unsupported (129..256)", D);
             return ADMMNET_E_ARG;

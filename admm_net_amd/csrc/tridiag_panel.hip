@@ -800,12 +800,11 @@ static int pn_launch_stage(int64_t nb, const Ws &ws, int pstop, bool explicit_q,
     return ADMMNET_OK;
 }
 
-int launch_tridiag_panel(int D, int64_t nb, const Ws &ws, hipStream_t st, bool explicit_q) {
+int launch_tridiag_panel(const Switches &sw, int D, int64_t nb, const Ws &ws, hipStream_t st, bool explicit_q) {
     if (!tridiag_panel_supported(D)) {
         set_error("tridiag_panel: D=%d unsupported (256 only)", D);
         return ADMMNET_E_ARG;
     }
-    const Switches &sw = switches();
     const bool split = sw.pn_split != 0 && ws.Tail != nullptr, split3 = split && sw.pn_split == 84;
     if (sw.pn_timing) {
         PhaseTimer tm;

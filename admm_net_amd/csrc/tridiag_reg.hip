@@ -518,11 +518,11 @@ __global__ __launch_bounds__(TR_THREADS, OCC) void tridiag_reg_kernel(int D, flo
 }
 
 template <int NA>
-static int launch_tr(int D, int64_t nb, const Ws &ws, hipStream_t st, const float2 *Zlow, const float2 *phi,
+static int launch_tr(const Switches &sw, int D, int64_t nb, const Ws &ws, hipStream_t st, const float2 *Zlow, const float2 *phi,
                      const float *h, const float *lw) {
     // developer knob: ADMMNET_TR_PAD_LDS=<bytes> of unused dynamic LDS per workgroup (e.g. 100000 leaves one
     // workgroup per CU: tells latency-bound from issue-bound)
-    const int pad = switches().tr_pad_lds;
+    const int pad = sw.tr_pad_lds;
     if (pad > 0) {
         ADMM_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(tridiag_reg_kernel<NA, true>),
                                      hipFuncAttributeMaxDynamicSharedMemorySize, pad));
@@ -533,7 +533,7 @@ static int launch_tr(int D, int64_t nb, const Ws &ws, hipStream_t st, const floa
     // values in scratch) -- the kernel is a latency chain per reflector and a third matrix per CU hides more of it than the
     // spills cost; ADMMNET_TR_OCC=2 keeps the two-workgroup build for A/B runs.
     if constexpr (NA == 7) {
-        if (switches().tr_occ3 && pad == 0) {
+        if (sw.tr_occ3 && pad == 0) {
             if (Zlow)
                 hipLaunchKernelGGL((tridiag_reg_kernel<NA, true, 3>), dim3((unsigned)nb), dim3(TR_THREADS), 0, st, D, ws.Mbuf,
                                    ws.QV, ws.dT, ws.eT, Zlow, phi, h, lw, ws.skip);
@@ -555,18 +555,18 @@ static int launch_tr(int D, int64_t nb, const Ws &ws, hipStream_t st, const floa
 }
 
 // Zlow != nullptr: "lean" loader (the kernel forms A = C - Z / rho itself, see tridiag_reg_kernel)
-int launch_tridiag_reg(int D, int64_t nb, const Ws &ws, hipStream_t st, const float2 *Zlow, const float2 *phi,
+int launch_tridiag_reg(const Switches &sw, int D, int64_t nb, const Ws &ws, hipStream_t st, const float2 *Zlow, const float2 *phi,
                        const float *h, const float *lw) {
     const int na = (D + 15) / 16;
     switch (na) {
-        case 1: return launch_tr<1>(D, nb, ws, st, Zlow, phi, h, lw);
-        case 2: return launch_tr<2>(D, nb, ws, st, Zlow, phi, h, lw);
-        case 3: return launch_tr<3>(D, nb, ws, st, Zlow, phi, h, lw);
-        case 4: return launch_tr<4>(D, nb, ws, st, Zlow, phi, h, lw);
-        case 5: return launch_tr<5>(D, nb, ws, st, Zlow, phi, h, lw);
-        case 6: return launch_tr<6>(D, nb, ws, st, Zlow, phi, h, lw);
-        case 7: return launch_tr<7>(D, nb, ws, st, Zlow, phi, h, lw);
-        case 8: return launch_tr<8>(D, nb, ws, st, Zlow, phi, h, lw);
+        case 1: return launch_tr<1>(sw, D, nb, ws, st, Zlow, phi, h, lw);
+        case 2: return launch_tr<2>(sw, D, nb, ws, st, Zlow, phi, h, lw);
+        case 3: return launch_tr<3>(sw, D, nb, ws, st, Zlow, phi, h, lw);
+        case 4: return launch_tr<4>(sw, D, nb, ws, st, Zlow, phi, h, lw);
+        case 5: return launch_tr<5>(sw, D, nb, ws, st, Zlow, phi, h, lw);
+        case 6: return launch_tr<6>(sw, D, nb, ws, st, Zlow, phi, h, lw);
+        case 7: return launch_tr<7>(sw, D, nb, ws, st, Zlow, phi, h, lw);
+        case 8: return launch_tr<8>(sw, D, nb, ws, st, Zlow, phi, h, lw);
         default:
             set_error("tridiag_reg: D=%d unsupported", D);
             return ADMMNET_E_ARG;

@@ -25,6 +25,7 @@ import torch.nn as nn
 
 from . import _lib
 from ._lib import Cfg
+from .options import Options
 
 HIDDEN = 128   # PeakSearchLayer hidden_dim (admm_net.py:496)
 HEADS = 4
@@ -139,6 +140,7 @@ class _FusedBase(nn.Module):
         # execution knobs (not part of the reference API)
         self._chunk = 0                # signals per eigensolver chunk (0 = library default); see the `chunk` property
         self._sub_batch = None         # signals per independent sub-batch (None = the call is one batch); see `sub_batch`
+        self._options = None           # per-model kernel routes and tolerances (None = the process defaults); see `options`
         self._train_route = "tensor"   # how the differentiable forward evaluates the n^2-sized layer steps; see `train_route`
         self.check_status = True       # one D2H read per forward: raise if the eigensolver failed
         self._wcache = None
@@ -180,6 +182,23 @@ class _FusedBase(nn.Module):
             self._ws = None
 
     @property
+    def options(self) -> Optional[Options]:
+        """Kernel routes and tolerances of THIS model: an ``Options`` of overrides over the process defaults (the
+        ``ADMMNET_*`` environment), or None for the defaults themselves.  Everything that takes its ``cfg`` from the model
+        follows -- the fused forward, ``estimate``, ``ops.glayer``, ``ops.glayer_spectral``, ``sharded.HipLayerEngine`` and
+        ``ShardedForward`` -- and so does the eigensolver of ``forward_autograd``; other models of the process are not
+        affected.  Not part of the state_dict; pickled and deep-copied with the module (as its overrides: a new process
+        interns them again).  Setting it drops the cached workspace: its carve depends on the route."""
+        return getattr(self, "_options", None)
+
+    @options.setter
+    def options(self, value: Optional[Options]):
+        if value is not None and not isinstance(value, Options):
+            raise TypeError(f"options must be None or an admm_net_amd.Options, got {type(value).__name__}")
+        self._options = value
+        self._ws = None
+
+    @property
     def train_route(self) -> str:
         """How the differentiable forward (train mode, ``forward_autograd``) evaluates the n^2-sized steps of a layer:
         ``"tensor"`` (default) as framework tensor operations, ``"fused"`` through the streaming HIP kernels of
@@ -197,8 +216,9 @@ class _FusedBase(nn.Module):
 
     # ---- weights -----------------------------------------------------------
     def cfg(self) -> Cfg:
-        return Cfg(self.M, self.N, self.L, self.num_layers, int(self._HAS_HEAD), int(self.chunk),
-                   (ctypes.c_int32 * 2)(self.sub_batch or 0, 0))   # reserved[0] = admmnet_cfg.sub_batch
+        opt = self.options
+        return Cfg(self.M, self.N, self.L, self.num_layers, int(self._HAS_HEAD), int(self.chunk),   # reserved[0] = admmnet_cfg.sub_batch,
+                   (ctypes.c_int32 * 2)(self.sub_batch or 0, 0 if opt is None else opt.handle))    # [1] = its option handle
 
     def _raw_params(self):
         """Parameters in the raw order documented in include/admmnet.h."""

@@ -26,10 +26,11 @@ def _need_cuda(t: torch.Tensor, name: str):
         raise _lib.AdmmNetError(f"{name} must be a HIP device tensor (no CPU fallback)")
 
 
-def eigh(A: torch.Tensor):
+def eigh(A: torch.Tensor, options=None):
     """Batched Hermitian eigendecomposition (torch.linalg.eigh at admm_net.py:303).
 
     A: [B, n, n] complex64 (lower triangle read).  Returns (w [B, n] unsorted, V [B, n, n]).
+    options: an ``admm_net_amd.Options`` choosing the eigensolver variant for this call (None = the process defaults).
     """
     _need_cuda(A, "A")
     lib = _lib.load()
@@ -37,15 +38,16 @@ def eigh(A: torch.Tensor):
     B, n, _ = A.shape
     dev = A.device
     with torch.cuda.device(dev):
-        need = lib.admmnet_eigh_workspace_bytes(n, B)
+        handle = 0 if options is None else options.handle
+        need = lib.admmnet_eigh_workspace_bytes_o(n, B, handle)
         if need < 0:
             raise _lib.AdmmNetError(f"eigh: unsupported n={n}")
         ws = torch.empty(need, dtype=torch.uint8, device=dev)
         w = torch.empty(B, n, dtype=torch.float32, device=dev)
         V = torch.empty(B, n, n, dtype=torch.complex64, device=dev)
         status = torch.zeros(4, dtype=torch.int32, device=dev)
-        _lib.check(lib.admmnet_eigh_c64(n, B, _ptr(A), _ptr(w), _ptr(V), _ptr(ws), need, _ptr(status),
-                                        _stream(dev)), "admmnet_eigh_c64")
+        _lib.check(lib.admmnet_eigh_c64_o(n, B, _ptr(A), _ptr(w), _ptr(V), _ptr(ws), need, _ptr(status),
+                                          _stream(dev), handle), "admmnet_eigh_c64")
         bad = int(status[0].item())
         if bad:
             raise _lib.AdmmNetError(f"eigensolver failed on {bad} matrices")

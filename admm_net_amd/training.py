@@ -650,7 +650,7 @@ def unrolled_forward(model, y: torch.Tensor, b: torch.Tensor, sigma: torch.Tenso
     ``sub_batch = g`` evaluates the consecutive groups of g signals as independent batches, each with its own mean
     (``_FusedBase.sub_batch``); None: the call is one batch.
 
-    ``solver(A) -> (w, V)`` defaults to the HIP eigensolver and ``assembler`` to the HIP contractions; the CPU unit
+    ``solver(A) -> (w, V)`` defaults to the HIP eigensolver (under ``model.options``) and ``assembler`` to the HIP contractions; the CPU unit
     tests pass stand-ins (``torch.linalg.eigh``, ``TorchAssembler``) to check the autograd wiring against the reference's
     gradients without a GPU.
 
@@ -664,7 +664,9 @@ def unrolled_forward(model, y: torch.Tensor, b: torch.Tensor, sigma: torch.Tenso
     """
     if sub_batch is not None and sub_batch < 1:
         raise ValueError(f"sub_batch must be None or >= 1, got {sub_batch}")
-    solver = ops.eigh if solver is None else solver
+    if solver is None:   # the HIP eigensolver under the model's own option set (``model.options``; None = the process defaults)
+        opts = getattr(model, "options", None)
+        solver = ops.eigh if opts is None else (lambda A: ops.eigh(A, options=opts))
     asm = Assembler if assembler is None else assembler
     if layer_kernels is not None and not fused:
         raise ValueError("layer_kernels is only used with fused=True")

@@ -19,6 +19,13 @@
  *   - complex64 = interleaved (re, im) float pairs, as torch.complex64.
  *   - D = M*N (signal length), n = D + 1 (state dimension), B = batch,
  *     K = number of unrolled layers.
+ *   - which kernels serve a call, and with which tolerances, is decided per
+ *     call from an OPTION SET (the switches of INTEGRATION.md section 6).  The
+ *     environment gives the process defaults, read once; admmnet_options_intern
+ *     turns overrides of them into a handle that admmnet_cfg carries, so two
+ *     models of one process can run different routes.  Apart from that
+ *     append-only table of immutable entries and the defaults, the library
+ *     keeps no state between calls: every entry point is re-entrant.
  */
 #ifndef ADMMNET_H
 #define ADMMNET_H
@@ -58,11 +65,37 @@ typedef struct admmnet_cfg {
                            ngroups = ceil(B / g), each with its own mean; every
                            sub-batch gets the bits a separate call on it alone
                            returns (g >= B: one sub-batch).  < 0: ADMMNET_E_ARG */
-    int32_t reserved[1];
+    int32_t reserved[1]; /* [0]: option handle of admmnet_options_intern; 0 =
+                           the process defaults.  A handle never issued is
+                           ADMMNET_E_ARG, before anything is enqueued.  One
+                           forward uses ONE cfg, handle included, from
+                           admmnet_workspace_bytes through admmnet_finish:
+                           every call carves the workspace from the cfg it
+                           is given                                         */
 } admmnet_cfg;
 
 int         admmnet_abi_version(void);
 const char *admmnet_last_error(void);
+
+/* ---- option sets ------------------------------------------------------------
+ * admmnet_options_intern: the process defaults (environment over built-in values)
+ *   overridden by count (name, value) pairs in the environment's own names and
+ *   syntax, e.g. {"ADMMNET_SPECTRAL", "0"}; of two pairs with one name the later
+ *   wins.  Returns a handle >= 1 for admmnet_cfg.reserved[0], or 0 when count == 0
+ *   or nothing differs from the defaults; ADMMNET_E_ARG for a name that is no
+ *   switch, a NULL name or value, or a full table (4096 distinct sets), with the
+ *   name in admmnet_last_error().  Sets are compared by their RESOLVED settings:
+ *   the same settings always give the same handle, whatever the order or the
+ *   spelling ("0" and "00").  Handles are immutable and valid for the life of
+ *   the process; the call is thread-safe.  A combination that no kernel serves
+ *    still interns: the entry point that would run it
+ *   returns ADMMNET_E_ARG before it enqueues anything, for that cfg only.
+ * admmnet_options_describe: the resolved settings of a handle (0: the defaults)
+ *   as "NAME value" lines, one per switch, NUL-terminated into buf[len].  Returns
+ *   the length of the whole text (cut to len - 1 characters if buf is smaller),
+ *   ADMMNET_E_ARG for a handle never issued. */
+int32_t admmnet_options_intern(const char *const *names, const char *const *values, int32_t count);
+int64_t admmnet_options_describe(int32_t handle, char *buf, int64_t len);
 
 /* ---- weights -------------------------------------------------------------
  * Raw (host) order, all float32, concatenated:
@@ -112,8 +145,10 @@ int64_t admmnet_workspace_bytes(const admmnet_cfg *cfg, int64_t B);
  *   status    device int32     [4] or NULL, zeroed by the call: [0] = #matrices whose eigensolver
  *             failed (must be 0).  The G-layer (admm_net.py:237-354: eigh, eigenvalue map f, V f(L) V^H) is
  *             evaluated as a matrix function wherever the per-matrix checks of csrc/spectral.hip allow it
- *             (ADMMNET_SPECTRAL=0: never) and through the eigensolver otherwise; [1] = #matrix-layers that
- *             went through the eigensolver after a rejection, [2] = #matrix-layers evaluated as a matrix
+ *             (ADMMNET_SPECTRAL=0 in the environment or the option set: never) and through the eigensolver otherwise; [1] = #matrix-layers that
+ *             went through the eigensolver: those the matrix-function kernel rejected (it counts them), or, with that route
+ *             off for the call, every matrix of every dense layer -- all G-layers but an arrowhead first one -- set by
+ *             admmnet_layer_front, saturating at INT32_MAX (the building blocks below report word [0] only), [2] = #matrix-layers evaluated as a matrix
  *             function, [3] = of [1], those rejected because f is not a quadratic on the bulk of the spectrum.
  */
 int admmnet_forward_f32(const admmnet_cfg *cfg, const float *weights_dev,
@@ -197,6 +232,11 @@ int64_t admmnet_eigh_workspace_bytes(int32_t n, int64_t B);
 int admmnet_eigh_c64(int32_t n, int64_t B, const void *A, float *w, void *V,
                      void *workspace, int64_t workspace_bytes,
                      int32_t *status, void *stream);
+/* The same under an option set (admmnet_options_intern); the two above pass 0.  Size and call take the same handle. */
+int64_t admmnet_eigh_workspace_bytes_o(int32_t n, int64_t B, int32_t options);
+int admmnet_eigh_c64_o(int32_t n, int64_t B, const void *A, float *w, void *V,
+                       void *workspace, int64_t workspace_bytes,
+                       int32_t *status, void *stream, int32_t options);
 
 /* Training route (trainPhi.py / train.py call forward in train mode).
  * admmnet_vdvh_c64: out = V diag(d) V^H, exactly Hermitian -- GLayer._rebuild_definite_matrix (admm_net.py:336-354: two
