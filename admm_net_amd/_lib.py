@@ -38,6 +38,7 @@ SYMBOLS = {
     "admmnet_packed_weight_count": (c_int64, [POINTER(Cfg)]),
     "admmnet_pack_weights": (c_int32, [POINTER(Cfg), c_void_p, c_void_p]),
     "admmnet_workspace_bytes": (c_int64, [POINTER(Cfg), c_int64]),
+    "admmnet_state_layout": (c_int32, [POINTER(Cfg), c_int64, POINTER(c_int64), POINTER(c_int32)]),
     "admmnet_forward_f32": (c_int32, [POINTER(Cfg), c_void_p, c_void_p, c_void_p, c_void_p, c_int64,
                                       c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),
     "admmnet_begin": (c_int32, [POINTER(Cfg), c_int64, c_void_p, c_int64, c_void_p, c_void_p]),

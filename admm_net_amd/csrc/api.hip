@@ -416,6 +416,21 @@ int64_t admmnet_workspace_bytes(const admmnet_cfg *cfg, int64_t B) {
     return ws.total_bytes;
 }
 
+int admmnet_state_layout(const admmnet_cfg *cfg, int64_t B, int64_t offsets[ADMMNET_STATE_SPANS + 1], int32_t *lower_only) {
+    int rc = check_cfg(cfg);
+    if (rc) return rc;
+    if (B < 1 || !offsets) {
+        set_error("state_layout: bad B or offsets");
+        return ADMMNET_E_ARG;
+    }
+    Ws ws;
+    carve_workspace(cfg, B, nullptr, 0, &ws, true);   // null base: every pointer is its offset
+    const void *spans[ADMMNET_STATE_SPANS + 1] = {ws.G, ws.Z, ws.phi[0], ws.phi[1], ws.h[0], ws.h[1], ws.alpha, ws.rn, ws.sum};
+    for (int i = 0; i <= ADMMNET_STATE_SPANS; ++i) offsets[i] = (int64_t)reinterpret_cast<intptr_t>(spans[i]);
+    if (lower_only) *lower_only = route_for(cfg->M * cfg->N, cfg_switches(cfg)).lean() ? 1 : 0;
+    return ADMMNET_OK;
+}
+
 int admmnet_begin(const admmnet_cfg *cfg, int64_t B, void *workspace, int64_t workspace_bytes,
                   int32_t *status, void *stream) {
     int rc = check_cfg(cfg);

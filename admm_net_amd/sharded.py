@@ -33,6 +33,53 @@ def _ptr(t):
     return ctypes.c_void_p(0 if t is None else t.data_ptr())
 
 
+STATE_SPANS = ("G", "Z", "phi0", "phi1", "h0", "h1", "alpha", "rn")   # admmnet_state_layout's order (include/admmnet.h)
+
+
+def state_layout(cfg, B: int):
+    """admmnet_state_layout as ({name: (byte offset, byte size of the buffer)}, end of the last span, lower_only): where the
+    per-forward state of (cfg, B) lies in the workspace.  Host only; needs no GPU."""
+    lib = _lib.load()
+    off = (ctypes.c_int64 * (len(STATE_SPANS) + 1))()
+    low = ctypes.c_int32(0)
+    _lib.check(lib.admmnet_state_layout(ctypes.byref(cfg), B, off, ctypes.byref(low)), "admmnet_state_layout")
+    D = cfg.M * cfg.N
+    n = D + 1
+    size = dict(G=8 * B * n * n, Z=8 * B * n * n, phi0=8 * B * D, phi1=8 * B * D, h0=4 * B * D, h1=4 * B * D,
+                alpha=4 * B, rn=4 * B)
+    return {name: (int(off[i]), size[name]) for i, name in enumerate(STATE_SPANS)}, int(off[len(STATE_SPANS)]), bool(low.value)
+
+
+class LayerState:
+    """Writable views (no copies) of the per-forward state inside a workspace: ``G``, ``Z`` complex64 [B, n, n], ``alpha``,
+    ``rn`` float32 [B], ``phi(k)`` complex64 / ``h(k)`` float32 [B, D] of layer k (the buffer ``k & 1``: layer k + 1 reads
+    them and writes the other one).  ``lower_only``: G and Z hold the lower triangle (row >= column) only, the other
+    triangle is neither read nor written.  ``spans``: {name: (byte offset, byte size)} of every buffer, ``end`` the first
+    byte behind them."""
+
+    def __init__(self, ws: torch.Tensor, cfg, B: int):
+        self.spans, self.end, self.lower_only = state_layout(cfg, B)
+        D = cfg.M * cfg.N
+        n = D + 1
+
+        def view(name, dtype, *shape):
+            o, sz = self.spans[name]
+            return ws[o:o + sz].view(dtype).view(*shape)
+
+        self.G = view("G", torch.complex64, B, n, n)
+        self.Z = view("Z", torch.complex64, B, n, n)
+        self._phi = (view("phi0", torch.complex64, B, D), view("phi1", torch.complex64, B, D))
+        self._h = (view("h0", torch.float32, B, D), view("h1", torch.float32, B, D))
+        self.alpha = view("alpha", torch.float32, B)
+        self.rn = view("rn", torch.float32, B)
+
+    def phi(self, k: int) -> torch.Tensor:
+        return self._phi[k & 1]
+
+    def h(self, k: int) -> torch.Tensor:
+        return self._h[k & 1]
+
+
 class HipLayerEngine:
     """begin / front(k) / back(k, mean) / finish over admmnet_begin ... admmnet_finish."""
 
@@ -61,6 +108,11 @@ class HipLayerEngine:
 
     def _stream(self):
         return ctypes.c_void_p(torch.cuda.current_stream(self.dev).cuda_stream)
+
+    def state(self) -> LayerState:
+        """The per-forward state the layer calls keep in ``self.ws``, as writable views: read it, or overwrite it, between
+        any two of begin / front / back / finish (on the stream the calls run on)."""
+        return LayerState(self.ws, self.cfg, self.B)
 
     def begin(self):
         with torch.cuda.device(self.dev):

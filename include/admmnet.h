@@ -200,6 +200,21 @@ int admmnet_glayer_f32(const admmnet_cfg *cfg, const float *layer_weights,
                        void *workspace, int64_t workspace_bytes,
                        int32_t *status, void *stream);
 
+/* Where the per-forward state lies in the workspace of (cfg, B): byte offsets from the workspace base, in layout order
+ *   [0] G       complex64 [B][n][n]   (n = M N + 1)         [1] Z       complex64 [B][n][n]
+ *   [2] phi[0]  complex64 [B][D]      [3] phi[1]            (layer k reads phi[(k - 1) & 1] and writes phi[k & 1])
+ *   [4] h[0]    float32   [B][D]      [5] h[1]              (likewise)
+ *   [6] alpha   float32   [B]         (the Z step of the layer before)
+ *   [7] rn      float32   [B]         (the residual norms layer_front wrote)
+ *   [8] the first byte behind rn's span: nothing of the above lies at or behind it
+ * Every offset is a multiple of 256; a span ends at the next offset and holds its buffer from its start, the rest is padding.
+ * *lower_only (may be NULL) is set to 1 where G and Z hold their lower triangles (row >= column) only -- the other triangle is
+ * neither read nor written -- and to 0 where both triangles are stored; it follows the route of cfg's option set.
+ * Host only: touches no device and enqueues nothing.  The answer is the carve the layer calls themselves use, so a caller
+ * may read and write the state between admmnet_begin / layer_front / layer_back / finish through these offsets. */
+#define ADMMNET_STATE_SPANS 8
+int admmnet_state_layout(const admmnet_cfg *cfg, int64_t B, int64_t offsets[ADMMNET_STATE_SPANS + 1], int32_t *lower_only);
+
 /* The matrix-function G-layer (csrc/spectral_fused.hip, the route of the forward's dense layers) on caller-supplied state,
  * one matrix per signal, with the forward's own tolerance and pass cap; for tests and utilities, the forward does not
  * call it.  Layout as in the workspace: n x n buffers per signal, only the lower triangle is read or written.

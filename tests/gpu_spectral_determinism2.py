@@ -23,7 +23,7 @@ for r in range(int(os.environ.get('RUNS', '6'))):
     eng.back(0, sc[0] / sc[1])
     sc = eng.front(1)
     torch.cuda.synchronize()
-    G = eng.ws[: B * n * n * 8].view(torch.float32).view(B, n, n, 2).clone()
+    G = torch.view_as_real(eng.state().G).clone()
     snaps.append(G)
     print("run", r, eng.status.tolist(), flush=True)
 tril = torch.tril(torch.ones(n, n, dtype=torch.bool, device=dev))
