@@ -16,6 +16,14 @@ namespace admmnet {
 
 constexpr int SY_THREADS = 256;
 constexpr int SY_MAXL = 8;
+// LDS of one workgroup: three double2 [D] arrays and the 8 block-sum slots (dynamic), the targets and the label
+// recursion's sum of d (static).  48 D + 352 bytes <= 160 KiB of a gfx950 CU: D <= SY_MAX_D = 3406 (exactly 160 KiB).
+constexpr size_t SY_LDS_LIMIT = 160 * 1024;
+constexpr size_t SY_STATIC_LDS = sizeof(double) * (SY_MAXL * 4 + 4);
+constexpr size_t sy_dynamic_lds(int64_t D) { return sizeof(double2) * 3 * (size_t)D + sizeof(double) * 8; }
+constexpr int64_t SY_MAX_D = (int64_t)((SY_LDS_LIMIT - SY_STATIC_LDS - sizeof(double) * 8) / (sizeof(double2) * 3));
+static_assert(sy_dynamic_lds(SY_MAX_D) + SY_STATIC_LDS <= SY_LDS_LIMIT &&
+              sy_dynamic_lds(SY_MAX_D + 1) + SY_STATIC_LDS > SY_LDS_LIMIT, "SY_MAX_D is the largest D that fits");
 
 __device__ __forceinline__ unsigned long long sy_mix(unsigned long long x) {
     x += 0x9E3779B97F4A7C15ull;
@@ -27,7 +35,7 @@ __device__ __forceinline__ unsigned long long sy_bits(unsigned long long seed, l
     return sy_mix(sy_mix(sy_mix(seed ^ 0xA5A5A5A55A5A5A5Aull) + (unsigned long long)sample) ^
                   (((unsigned long long)stream << 40) | (unsigned int)idx));
 }
-__device__ __forceinline__ double sy_uniform(unsigned long long bits) {   // (0, 1)
+__device__ __forceinline__ double sy_uniform(unsigned long long bits) {   // (0, 1]: the largest draw, 2^53 - 1/2, rounds to 2^53
     return ((double)(bits >> 11) + 0.5) * (1.0 / 9007199254740992.0);
 }
 // two independent standard normals (Box-Muller) from one 64-bit draw + its successor
@@ -54,6 +62,7 @@ __global__ __launch_bounds__(SY_THREADS) void synth_kernel(int Nb, int Nd, int L
     double2 *ph = bv + D;                                // [D] label recursion
     double *red = reinterpret_cast<double *>(ph + D);    // [8]
     __shared__ double tgt[SY_MAXL][4];                   // tau, f, Re C, Im C
+    __shared__ double sdw[4];                            // label recursion: sum of d per wave  (both in SY_STATIC_LDS)
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const long long s = blockIdx.x;
     if (tid < L) {
@@ -146,7 +155,6 @@ __global__ __launch_bounds__(SY_THREADS) void synth_kernel(int Nb, int Nd, int L
             red[wave] = sr;
             red[4 + wave] = si;
         }
-        __shared__ double sdw[4];
         if (lane == 0) sdw[wave] = sd;
         __syncthreads();
         const double Sr = (red[0] + red[1]) + (red[2] + red[3]), Si = (red[4] + red[5]) + (red[6] + red[7]);
@@ -167,8 +175,16 @@ int launch_synth(int64_t B, int Nb, int Nd, int L, unsigned long long seed, doub
                  double rho, int label_iters, float2 *y, float2 *b, float *sigma, float *tau, float *f, float2 *C,
                  float2 *phi_label, hipStream_t st) {
     if (B <= 0) return ADMMNET_OK;
-    const int D = Nb * Nd;
-    const size_t lds = sizeof(double2) * 3 * D + sizeof(double) * 8;
+    const int64_t D64 = (int64_t)Nb * Nd;
+    if (D64 > SY_MAX_D) {
+        set_error("synth_batch: Nb * Nd = %lld needs %lld bytes of LDS, the device has %lld (Nb * Nd <= %lld)", (long long)D64,
+                  (long long)(sy_dynamic_lds(D64) + SY_STATIC_LDS), (long long)SY_LDS_LIMIT, (long long)SY_MAX_D);
+        return ADMMNET_E_ARG;
+    }
+    const size_t lds = sy_dynamic_lds(D64);
+    if (lds > 64 * 1024)
+        ADMM_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(synth_kernel),
+                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     hipLaunchKernelGGL(synth_kernel, dim3((unsigned)B), dim3(SY_THREADS), lds, st, Nb, Nd, L, seed, snr_lo, snr_hi, snr_e,
                        rho, label_iters, y, b, sigma, tau, f, C, phi_label);
     ADMM_HIP(hipGetLastError());

@@ -472,7 +472,10 @@ int admmnet_regional_maxima_f64(const double *Z, int64_t B, int32_t nx, int32_t 
  *   outputs (device): y, b complex64 [B][Nb*Nd]; sigma float [B]; tau, f float [B][L]; C complex64 [B][L];
  *   phi_label complex64 [B][Nb*Nd] or NULL.  snr_lo..snr_hi: range of the per-sample SNR in dB (equal = fixed);
  *   snr_e: demodulation SNR (7); rho, label_iters: the classical solver's rho (1) and its iteration count (5).
- *   Counter-based generator: (seed, sample index) fixes a sample regardless of B or launch geometry. */
+ *   Counter-based generator: (seed, sample index) fixes a sample regardless of B or launch geometry.
+ *   1 <= L <= 8, label_iters >= 0, B < 2^31.  One workgroup holds y, b and the label recursion of a sample in float64 in
+ *   LDS: 48 Nb Nd + 352 bytes, which must fit the 160 KiB of a CU, so Nb * Nd <= 3406.  Anything else returns
+ *   ADMMNET_E_ARG with a message, before anything is launched. */
 int admmnet_synth_batch(int64_t B, int32_t Nb, int32_t Nd, int32_t L, uint64_t seed, double snr_lo, double snr_hi,
                         double snr_e, double rho, int32_t label_iters, void *y, void *b, float *sigma, float *tau,
                         float *f, void *C, void *phi_label, void *stream);
