@@ -113,13 +113,17 @@ __global__ __launch_bounds__(WY_THREADS, 3) void wy_apply_kernel(const float2 *_
         for (int jj = 0; jj < 8; ++jj) sh.Y[tid][8 + jj] = ypre[jj];
         __syncthreads();
         // ---- Z = Y^H X  (16 reflectors x 16 columns):  Zr = Yr Xr + Yi Xi,  Zi = Yr Xi - Yi Xr
-        //      THREE real products per complex one (the "3M" form of cgemm3m) -- the kernel is bound by the matrix cores:
-        //          T1 = Yr Xr,  T2 = Yi Xi,  T3 = (Yr + Yi)(Xi - Xr)  ->  Zr = T1 + T2,  Zi = T3 + T1 - T2
-        //      (normwise the same error bound as the four-product form: |error| <= c eps |Y| |X|.)
-        //      (Splitting this 256-term accumulation into block-local sums added pairwise was tried for accuracy: the
-        //      distance of V to the float64 back-transform of the same reflectors moved from 9.3e-7 to 8.7e-7 only, for
-        //      +28 % time -- the chain length is not what separates this kernel from the explicit-Q pair's 3.8e-7.)
-        f32x4 t1 = f32x4{0.f, 0.f, 0.f, 0.f}, t2 = t1, t3 = t1;
+        //      FOUR real products per complex one, each pair accumulated in one chain.  The three-product form the update
+        //      below uses (T3 = (Yr + Yi)(Xi - Xr), Zi = T3 + T1 - T2) has the same normwise bound, but over this 256-term
+        //      reduction its parts cancel: with it V landed 9.3e-7 from the float64 back-transform of the same reflectors
+        //      (explicit Q + Q W: 3.8e-7), and on a matrix whose largest eigenvalue is 40 max|A| the residual of that
+        //      eigenvector was 5.16e-5 max|A| at D = 193 and 4.1e-5 at D = 256; with four products here 1.43e-5 and 3.5e-6
+        //      (the record is the docstring of tests/test_gpu_eigh_routes.py, which holds the eigensolver to 5e-5).  Cost
+        //      on 2048 matrices: this kernel + wy_lastcol_kernel 2.68 -> 2.90 ms, the eigen-solve 15.05 -> 15.15 ms.  Four
+        //      products in the 16-term update as well changed no figure, so it keeps three.
+        //      (Splitting this accumulation into block-local sums added pairwise was tried for accuracy under the
+        //      three-product form: 9.3e-7 -> 8.7e-7 only, for +28 % time -- the chain length was not what mattered.)
+        f32x4 zr = f32x4{0.f, 0.f, 0.f, 0.f}, zi = zr;
 #pragma unroll
         for (int I = 0; I < 16; ++I) {
             if (I >= I0) {   // (uniform)
@@ -128,13 +132,13 @@ __global__ __launch_bounds__(WY_THREADS, 3) void wy_apply_kernel(const float2 *_
 #pragma unroll
                 for (int q = 0; q < 4; ++q) {
                     const float2 y = sh.Y[16 * I + 4 * g + q][c16];
-                    t1 = __builtin_amdgcn_mfma_f32_16x16x4f32(y.x, xrq[q], t1, 0, 0, 0);
-                    t2 = __builtin_amdgcn_mfma_f32_16x16x4f32(y.y, xiq[q], t2, 0, 0, 0);
-                    t3 = __builtin_amdgcn_mfma_f32_16x16x4f32(y.x + y.y, xiq[q] - xrq[q], t3, 0, 0, 0);
+                    zr = __builtin_amdgcn_mfma_f32_16x16x4f32(y.x, xrq[q], zr, 0, 0, 0);
+                    zi = __builtin_amdgcn_mfma_f32_16x16x4f32(y.x, xiq[q], zi, 0, 0, 0);
+                    zr = __builtin_amdgcn_mfma_f32_16x16x4f32(y.y, xiq[q], zr, 0, 0, 0);
+                    zi = __builtin_amdgcn_mfma_f32_16x16x4f32(-y.y, xrq[q], zi, 0, 0, 0);
                 }
             }
         }
-        const f32x4 zr = t1 + t2, zi = t3 + t1 - t2;
         // ---- Zt = T Z:  step q: B = Z register q (k = g <-> reflector 4 g + q), A[m][k = g] = T[m][4 g + q]
         f32x4 tr = f32x4{0.f, 0.f, 0.f, 0.f}, ti = f32x4{0.f, 0.f, 0.f, 0.f};
         {
@@ -149,7 +153,8 @@ __global__ __launch_bounds__(WY_THREADS, 3) void wy_apply_kernel(const float2 *_
             }
         }
         // ---- X -= Y Zt:  step q: B = Zt register q (k = g <-> reflector 4 g + q), A[m = row][k = g] = Y[16 I + m][4 g + q]
-        //      3M again:  P1 = Yr Zr,  P2 = Yi Zi,  P3 = (Yr + Yi)(Zr + Zi)  ->  Xr -= P1 - P2,  Xi -= P3 - P1 - P2
+        //      three products ("3M", cgemm3m) -- the kernel is bound by the matrix cores:
+        //          P1 = Yr Zr,  P2 = Yi Zi,  P3 = (Yr + Yi)(Zr + Zi)  ->  Xr -= P1 - P2,  Xi -= P3 - P1 - P2
         {
             const float trq[4] = {tr.x, tr.y, tr.z, tr.w}, tiq[4] = {ti.x, ti.y, ti.z, ti.w};
 #pragma unroll

@@ -7,11 +7,15 @@ tests/test_gpu_parity.py for the same quantities: G within 2e-5 of max|G|, G exa
 diagonal, sorted eigenvalues within 1e-5; rn within 2e-5 of ||G_returned - C||_F recomputed in float64 from the returned
 G, which isolates the tail from the eigensolver.  Two child processes (the switches are read once per process) reach
 arrow_rebuild_kernel<AR_GLOBAL> + rebuild_big_kernel (ADMMNET_ARROW_FUSED=0) and rebuild_kernel
-(ADMMNET_SPECTRAL=0 ADMMNET_TRIDIAG_BIG=sweep).
+(ADMMNET_SPECTRAL=0 ADMMNET_TRIDIAG_BIG=sweep).  Every other route a model can select runs in this process through
+``model.options`` (ROUTES_SMALL at D <= 128, ROUTES_BIG above) under the same four assertions: the separate back-transform
+with the tile rebuild, QL with rotation replay, the LDS tridiagonalisation, the dense first layer, full storage, the sweep at
+the geometry's own size (13 x 16: its bucket 7, reached by nothing else), explicit Q, the one-stage panel, the plain D&C.
 
 Seeds: the oracle's own float32 evaluation of these layers on the same inputs stays within half of each bound of its
 float64 evaluation (checked on the CPU when the seeds were chosen: G <= 1.4e-6, w <= 3.9e-7, rn <= 4.9e-6 over all
-six; at 16 x 16 the seeds 45 - 47 gave a float32 rn 3e-5 from its own G and were passed over)."""
+seven; at 16 x 16 the seeds 45 - 47 gave a float32 rn 3e-5 from its own G and were passed over, at 13 x 16 the seed 50 gives
+G 1.0e-6, w 3.1e-7, rn 4.4e-6 and the seeds 51 and 52 an rn of 4e-5)."""
 import functools
 import json
 import os
@@ -26,6 +30,7 @@ import torch.nn.functional as F
 import admm_net_amd as A
 from admm_net_amd import ops, synth
 from oracle import admm_net_ref as R
+import eigh_cases as E
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -38,9 +43,10 @@ GEOMS = {
     "8x16": (8, 16),     # D = 128: full tiles, the largest LDS-resident case
     "10x13": (10, 13),   # D = 130: padded image, Da < D in rebuild_big_kernel, NT = 5 in arrow_fused_tail
     "16x16": (16, 16),   # D = 256: all 36 tiles
+    "13x16": (13, 16),   # D = 208: padded like 10 x 13 by default; at its own size launch_tb<7> of the sweep, 7 x 7 tiles
 }
 BIG = ["10x13", "16x16"]
-SEED = {"2x4": 40, "5x8": 41, "10x10": 42, "8x16": 43, "10x13": 44, "16x16": 49}
+SEED = {"2x4": 40, "5x8": 41, "10x10": 42, "8x16": 43, "10x13": 44, "16x16": 49, "13x16": 50}
 
 
 def rel(a, b):
@@ -73,9 +79,15 @@ def rn_from_G(sd, k, phi, h, G):
     return torch.linalg.norm(torch.from_numpy(G).to(torch.complex128) - C, dim=(1, 2)).numpy()
 
 
-def measure(name):
-    """Layers 0 and 1 of one geometry through ops.glayer: the figures the assertions are about."""
+def measure(name, options=None):
+    """Layers 0 and 1 of one geometry through ops.glayer: the figures the assertions are about.  With ``options`` a fresh
+    model carries them (the cached one of case() stays as it is)."""
     sd, m, tr = case(name)
+    if options is not None:
+        Nb, Nd = GEOMS[name]
+        m = A.PhiEstADMMNet(M=Nb, N=Nd, num_layers=K).eval()
+        m.load_state_dict(sd)
+        m.options = options
     dev = torch.device("cuda:0")
     out = {}
     for k in (0, 1):
@@ -105,6 +117,42 @@ def check(name, res, what):
 def test_rebuild_tail_default_routes(name):
     assert torch.cuda.is_available(), "these tests need the MI355X"
     check(name, measure(name), "default")
+
+
+# ---- the selectable routes, in this process ---------------------------------------------------------------------------------
+ROUTES_SMALL = {   # D <= 128
+    "unfused_back": dict(fuse_back=0),             # vgemm_kernel + rebuild_kernel instead of back_rebuild_kernel
+    "ql": dict(eig="ql"),                          # tql + rotation replay + rebuild_kernel
+    "lds": dict(tridiag="lds"),                    # tridiag_kernel<true>, full storage
+    "no_arrow": dict(arrow=0),                     # layer 0 down the dense path as well
+    "full_storage": dict(lean=0),
+}
+ROUTES_BIG = {     # D > 128
+    "eigen_only": dict(spectral=0),                # 10 x 13 at its own size (pad_min = 176), 13 x 16 padded
+    "sweep": dict(tridiag_big="sweep"),            # launch_tb<5>, <7>, <8> + vgemm_big + rebuild_kernel / rebuild_big_kernel
+    "explicit_q": dict(back="q"),
+    "lds": dict(tridiag="lds"),                    # 10 x 13: the LDS image, 13 x 16 and 16 x 16: the global image
+    "ql": dict(eig="ql"),
+    "pn0": dict(pn_split=0),
+    "dc_plain": dict(dc_blocks=0),
+    "no_arrow": dict(arrow=0),
+    "eigen_tiles": dict(spectral=0, rebuild="tiles"),   # rebuild_kernel at D = 256
+}
+SMALL_GEOMS = ["2x4", "5x8", "10x10", "8x16"]
+BIG_GEOMS = ["10x13", "13x16", "16x16"]
+OPTION_CASES = [(r, g) for r in ROUTES_SMALL for g in SMALL_GEOMS] + [(r, g) for r in ROUTES_BIG for g in BIG_GEOMS]
+GUARD = E.DeviceGuard()   # once an in-process route case meets a HIP error the remaining ones do not touch the device
+
+
+@pytest.mark.parametrize("route,name", OPTION_CASES, ids=["%s-%s" % c for c in OPTION_CASES])
+def test_rebuild_tail_option_sets(route, name):
+    kwargs = (ROUTES_SMALL if name in SMALL_GEOMS else ROUTES_BIG)[route]
+    opts = A.Options(**kwargs)
+    got = opts.resolved()
+    for key, value in kwargs.items():
+        assert got[key] == (1 if isinstance(value, str) else value), (route, key, got[key])
+    res = GUARD.run(lambda: measure(name, opts))
+    check(name, res, route)
 
 
 CHILD = r"""
