@@ -86,6 +86,12 @@ SYMBOLS = {
     "admmnet_train_eigmap_bwd_f32": (c_int32, [c_int32, c_int64] + [c_void_p] * 11),
     "admmnet_train_stepsize_f32": (c_int32, [c_int64, c_int64, c_float] + [c_void_p] * 8),
     "admmnet_train_stepsize_bwd_f32": (c_int32, [c_int64, c_int64, c_float] + [c_void_p] * 11),
+    "admmnet_train_hlayer_workspace": (c_int64, [c_int32, c_int64]),
+    "admmnet_train_hlayer_f32": (c_int32, [c_int32, c_int64] + [c_void_p] * 14),
+    "admmnet_train_hlayer_bwd_f32": (c_int32, [c_int32, c_int64] + [c_void_p] * 17),
+    "admmnet_train_head_workspace": (c_int64, [c_int32, c_int32, c_int64, c_int32]),
+    "admmnet_train_head_f32": (c_int32, [c_int32, c_int32, c_int64] + [c_void_p] * 3 + [c_float] + [c_void_p] * 5),
+    "admmnet_train_head_bwd_f32": (c_int32, [c_int32, c_int32, c_int64] + [c_void_p] * 6 + [c_float] + [c_void_p] * 8),
     "admmnet_loss_partials": (c_int64, [c_int32, c_int64]),
     "admmnet_loss_anm_f32": (c_int32, [c_int32, c_int32, c_int64] + [c_void_p] * 7 + [c_float] + [c_void_p] * 5),
     "admmnet_loss_anm_bwd_f32": (c_int32, [c_int32, c_int32, c_int64] + [c_void_p] * 9 + [c_float] + [c_void_p] * 5),

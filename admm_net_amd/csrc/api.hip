@@ -917,6 +917,86 @@ int admmnet_train_hproject_bwd_f32(int32_t D, int64_t B, const float *g_h, const
     return launch_train_hproject_bwd(D, B, g_h, t, m, sigma, projection_weight, g_t, g_m, g_pw, partials, (hipStream_t)stream);
 }
 
+// ---- training route "native": the H layer with correction_net inside (train_hlayer.hip) ------------------------------------------
+// the batch-slab grid of the weight-gradient product is the launch's y dimension
+static int train_hlayer_args_ok(const char *what, int32_t D, int64_t B, bool ptrs) {
+    if (int rc = train_small_args_ok(what, D, 1, kMaxD, B, ptrs)) return rc;
+    if (B > (int64_t)65535 * 128) {
+        set_error("%s: bad argument (B=%lld)", what, (long long)B);
+        return ADMMNET_E_ARG;
+    }
+    return ADMMNET_OK;
+}
+
+int64_t admmnet_train_hlayer_workspace(int32_t D, int64_t B) {
+    if (D < 1 || D > kMaxD || B < 1 || B > (int64_t)65535 * 128) return -1;
+    return train_hlayer_workspace_floats(D, B) * (int64_t)sizeof(float);
+}
+
+int admmnet_train_hlayer_f32(int32_t D, int64_t B, const float *g_dg, const float *z_dg, const float *sigma, const float *rho,
+                             const float *projection_weight, const float *W1, const float *b1, const float *W2, const float *b2,
+                             float *h, float *t, float *a1, float *m, void *stream) {
+    if (int rc = train_hlayer_args_ok("train_hlayer", D, B,
+                                      g_dg && z_dg && sigma && rho && projection_weight && W1 && b1 && W2 && b2 && h && t && a1 && m))
+        return rc;
+    return launch_train_hlayer(D, B, g_dg, z_dg, sigma, rho, projection_weight, W1, b1, W2, b2, h, t, a1, m, (hipStream_t)stream);
+}
+
+int admmnet_train_hlayer_bwd_f32(int32_t D, int64_t B, const float *g_h, const float *z_dg, const float *sigma, const float *rho,
+                                 const float *projection_weight, const float *W1, const float *W2, const float *t, const float *a1,
+                                 const float *m, float *g_gdg, float *g_zdg, float *delta1, float *delta2, float *g_params,
+                                 void *workspace, void *stream) {
+    if (int rc = train_hlayer_args_ok("train_hlayer_bwd", D, B,
+                                      g_h && z_dg && sigma && rho && projection_weight && W1 && W2 && t && a1 && m && g_gdg &&
+                                          g_zdg && delta1 && delta2 && g_params && workspace))
+        return rc;
+    return launch_train_hlayer_bwd(D, B, g_h, z_dg, sigma, rho, projection_weight, W1, W2, t, a1, m, g_gdg, g_zdg, delta1, delta2,
+                                   g_params, (float *)workspace, (hipStream_t)stream);
+}
+
+// ---- training route "native": the PeakSearchLayer head (train_head.hip) ---------------------------------------------------------
+// the slabs of the (signal, target) pairs are the product launch's y dimension
+static int train_head_args_ok(const char *what, int32_t D, int32_t L, int64_t B, const void *const *params, const void *keep, float p,
+                              bool ptrs) {
+    bool ok = D >= 1 && D <= kMaxD && L >= 1 && L <= 16 && B >= 1 && B * L <= (int64_t)65535 * 128 && ptrs && params;
+    ok = ok && (!keep || (p >= 0.f && p < 1.f));
+    for (int i = 0; ok && i < 21 + 8 * L; ++i) ok = params[i] != nullptr;
+    if (!ok) {
+        set_error("%s: bad argument (D=%d, L=%d, B=%lld, p=%g)", what, D, L, (long long)B, (double)p);
+        return ADMMNET_E_ARG;
+    }
+    return ADMMNET_OK;
+}
+
+int64_t admmnet_train_head_workspace(int32_t D, int32_t L, int64_t B, int32_t part) {
+    if (D < 1 || D > kMaxD || L < 1 || L > 16 || B < 1 || B * L > (int64_t)65535 * 128) return -1;
+    switch (part) {
+    case ADMMNET_TRAIN_HEAD_SAVED: return train_head_saved_floats(D, L, B) * (int64_t)sizeof(float);
+    case ADMMNET_TRAIN_HEAD_WORK: return train_head_work_floats(D, L, B) * (int64_t)sizeof(float);
+    case ADMMNET_TRAIN_HEAD_GRADS: return train_head_grad_floats(D, L) * (int64_t)sizeof(float);
+    }
+    return -1;
+}
+
+int admmnet_train_head_f32(int32_t D, int32_t L, int64_t B, const void *phi, const void *const *params, const uint8_t *keep, float p,
+                           float *tau, float *f, float *conf, void *saved, void *stream) {
+    if (int rc = train_head_args_ok("train_head", D, L, B, phi ? params : nullptr, keep, p, phi && tau && f && conf && saved))
+        return rc;
+    return launch_train_head(D, L, B, (const float2 *)phi, (const float *const *)params, keep, keep ? p : 0.f, tau, f, conf,
+                             (float *)saved, (hipStream_t)stream);
+}
+
+int admmnet_train_head_bwd_f32(int32_t D, int32_t L, int64_t B, const float *g_tau, const float *g_f, const float *g_conf,
+                               const void *phi, const void *const *params, const uint8_t *keep, float p, const float *tau,
+                               const float *f, const float *conf, void *saved, void *g_phi, float *g_params, void *workspace,
+                               void *stream) {
+    const bool ptrs = g_tau && g_f && g_conf && phi && tau && f && conf && saved && g_phi && g_params && workspace;
+    if (int rc = train_head_args_ok("train_head_bwd", D, L, B, ptrs ? params : nullptr, keep, p, ptrs)) return rc;
+    return launch_train_head_bwd(D, L, B, g_tau, g_f, g_conf, (const float2 *)phi, (const float *const *)params, keep,
+                                 keep ? p : 0.f, tau, f, conf, (float *)saved, (float2 *)g_phi, g_params, (float *)workspace,
+                                 (hipStream_t)stream);
+}
+
 int admmnet_train_eigmap_f32(int32_t n, int64_t B, const float *w, const float *threshold, const float *W1, const float *b1,
                              const float *W2, const float *b2, float *wp, void *stream) {
     if (int rc = train_small_args_ok("train_eigmap", n, 2, kMaxD + 1, B, w && threshold && W1 && b1 && W2 && b2 && wp)) return rc;

@@ -258,6 +258,26 @@ int launch_train_stepsize_bwd(int64_t B, int64_t g, float knorm, const float *gs
                               const float *W1, const float *b1, const float *W2, const float *b2, float *grn, float *gpar,
                               float *part, hipStream_t st);
 
+// train_hlayer.hip (training route "native": the H layer with its correction_net inside; parameters RAW as in train_small.hip)
+int64_t train_hlayer_workspace_floats(int D, int64_t B);   // float scratch of the backward: slab rows, then the batch-slab partials
+int launch_train_hlayer(int D, int64_t B, const float *gdg, const float *zdg, const float *sigma, const float *rho_raw,
+                        const float *pw_raw, const float *W1, const float *b1, const float *W2, const float *b2, float *h, float *t,
+                        float *a1, float *m, hipStream_t st);
+int launch_train_hlayer_bwd(int D, int64_t B, const float *gh, const float *zdg, const float *sigma, const float *rho_raw,
+                            const float *pw_raw, const float *W1, const float *W2, const float *t, const float *a1, const float *m,
+                            float *ggdg, float *gzdg, float *d1, float *d2, float *gpar, float *work, hipStream_t st);
+
+// train_head.hip (training route "native": the PeakSearchLayer head; `params` is a HOST array of the 21 + 8 L device pointers to the
+// RAW parameters in the order of training._head_params)
+int64_t train_head_saved_floats(int D, int L, int64_t B);   // the forward's saved activations
+int64_t train_head_work_floats(int D, int L, int64_t B);    // the backward's deltas and slab partials
+int64_t train_head_grad_floats(int D, int L);               // the backward's gradient buffer
+int launch_train_head(int D, int L, int64_t B, const float2 *phi, const float *const *params, const unsigned char *keep, float p,
+                      float *tau, float *f, float *conf, float *saved, hipStream_t st);
+int launch_train_head_bwd(int D, int L, int64_t B, const float *gtau, const float *gf, const float *gconf, const float2 *phi,
+                          const float *const *params, const unsigned char *keep, float p, const float *tau, const float *f,
+                          const float *conf, float *saved, float2 *gphi, float *g, float *work, hipStream_t st);
+
 // loss.hip (the training losses; sums over the batch as in train_small.hip)
 int64_t loss_partials(int loss, int64_t B);           // floats of partial-sum scratch of the forward of ADMMNET_LOSS_*
 int launch_loss_anm(int Lmax, int D, int64_t B, const float *tau, const float *f, const float *conf, const float *tau_true,

@@ -140,19 +140,21 @@ def load_checkpoint(path, model, optimizer=None, scheduler=None, map_location="c
     return ckpt
 
 
-def time_train_step(layers=10, batch=256, steps=20, warmup=3, seed=0, device="cuda:0", route="tensor", grid=(NB, ND)):
+def time_train_step(layers=10, batch=256, steps=20, warmup=3, seed=0, device="cuda:0", route="tensor", grid=(NB, ND), head=False):
     """Wall time of one optimisation step at the reference's own training configuration (trainPhi.py:16-38: 10 x 10 grid,
     num_layers = 10, batch_size = 256, AdamW lr 1e-3 / weight decay 1e-3, gradient clipping at 1.0, :179-190): forward in
     train mode (the differentiable route of admm_net_amd.training: HIP eigensolver + HIP contractions), a phi-alignment
     loss against the classical solver's phi labels (generated on the device, csrc/synth.hip), backward, clip, step.
     The loss is a plain normalised squared error: the reference's loss.py is user code outside this path.
-    ``route``: ``model.train_route`` ("tensor" | "fused" | "full"); ``grid`` = (M, N) of another geometry, same recipe.
+    ``route``: ``model.train_route`` ("tensor" | "fused" | "full" | "native"); ``grid`` = (M, N) of another geometry, same recipe.
+    ``head = True`` times ``ADMMNet`` (the model of train.py) instead: the loss is then that phi error plus the plain squared
+    error of tau and f against the generator's labels.
     Returns a dict (seconds per step, signals per second, route, geometry)."""
-    from . import PhiEstADMMNet, synth
+    from . import ADMMNet, PhiEstADMMNet, synth
     dev = torch.device(device)
     torch.manual_seed(seed)
     M, N = grid
-    model = PhiEstADMMNet(num_layers=layers, M=M, N=N, L=3).to(dev)
+    model = (ADMMNet if head else PhiEstADMMNet)(num_layers=layers, M=M, N=N, L=3).to(dev)
     model.train_route = route
     model.train()
     opt = torch.optim.AdamW(model.parameters(), lr=1e-3, weight_decay=1e-3)
@@ -162,8 +164,12 @@ def time_train_step(layers=10, batch=256, steps=20, warmup=3, seed=0, device="cu
 
     def step():
         opt.zero_grad(set_to_none=True)
-        phi = model(y, b, sigma)
-        loss = (phi - label).abs().pow(2).mean() / scale
+        if head:
+            tau, f, _, phi = model(y, b, sigma)
+            loss = (phi - label).abs().pow(2).mean() / scale + (tau - extra["tau"]).pow(2).mean() + (f - extra["f"]).pow(2).mean()
+        else:
+            phi = model(y, b, sigma)
+            loss = (phi - label).abs().pow(2).mean() / scale
         loss.backward()
         torch.nn.utils.clip_grad_norm_(model.parameters(), 1.0)
         opt.step()
@@ -179,8 +185,8 @@ def time_train_step(layers=10, batch=256, steps=20, warmup=3, seed=0, device="cu
     torch.cuda.synchronize(dev)
     dt = (time.perf_counter() - t0) / steps
     losses.append(float(last.item()))
-    return {"config": f"PhiEstADMMNet {M}x{N} K={layers}, batch {batch}, AdamW + clip 1.0 (trainPhi.py:16-38, 179-190)",
-            "route": route, "grid": [M, N], "layers": layers, "batch": batch,
+    return {"config": f"{type(model).__name__} {M}x{N} K={layers}, batch {batch}, AdamW + clip 1.0 (trainPhi.py:16-38, 179-190)",
+            "route": route, "head": bool(head), "grid": [M, N], "layers": layers, "batch": batch,
             "seconds_per_step": round(dt, 6), "signals_per_second": round(batch / dt, 1), "steps": steps,
             "loss_first": round(losses[0], 6), "loss_last": round(losses[-1], 6)}
 
@@ -242,8 +248,10 @@ def main(argv=None):
     c.add_argument("--layers", type=int, default=10)
     c.add_argument("--batch", type=int, default=256)
     c.add_argument("--steps", type=int, default=20)
-    c.add_argument("--route", choices=("tensor", "fused", "full"), default="tensor")
+    c.add_argument("--route", choices=("tensor", "fused", "full", "native"), default="tensor")
     c.add_argument("--grid", default=f"{NB}x{ND}", help="MxN")
+    c.add_argument("--head", action="store_true", help="time ADMMNet (phi + tau + f loss) instead of PhiEstADMMNet")
+    c.add_argument("--warmup", type=int, default=3)
     d = sub.add_parser("loss-step")
     d.add_argument("--batch", type=int, default=256)
     d.add_argument("--targets", type=int, default=3)
@@ -261,7 +269,7 @@ def main(argv=None):
             assert len(grid) == 2 and min(grid) >= 1
         except (ValueError, AssertionError):
             ap.error(f"--grid must be MxN, got {args.grid!r}")
-        print(json.dumps(time_train_step(args.layers, args.batch, args.steps, route=args.route, grid=grid)))
+        print(json.dumps(time_train_step(args.layers, args.batch, args.steps, warmup=args.warmup, route=args.route, grid=grid, head=args.head)))
         return
     if args.cmd == "time-net":
         from . import PhiEstADMMNet

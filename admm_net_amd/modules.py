@@ -13,7 +13,7 @@ Inference (``.eval()`` or ``torch.no_grad()``) runs the fused forward.  In train
 enabled the call goes through ``training.unrolled_forward`` instead: differentiable tensor operations
 around the HIP eigensolver, with the reference's eigenvalue-only gradient (SURVEY.md section 8f rank 2);
 ``model.train_route = "fused"`` moves the n^2-sized layer steps of that route onto HIP kernels too, ``"full"`` the
-O(B D)-sized ones as well.
+O(B D)-sized ones as well, ``"native"`` the H layer's MLP and the head too.
 """
 from __future__ import annotations
 
@@ -204,14 +204,17 @@ class _FusedBase(nn.Module):
         ``"tensor"`` (default) as framework tensor operations, ``"fused"`` through the streaming HIP kernels of
         csrc/train_layer.hip with hand-written backwards (``training.LayerKernels``), ``"full"`` as ``"fused"`` and with the
         O(B D)-sized steps -- phi layer, H layer around its correction_net, eigenvalue map, step-size network -- on the kernels
-        of csrc/train_small.hip too (``training.SmallKernels``).  All use the HIP eigensolver and contractions; inference is
-        not affected.  Not part of the state_dict."""
+        of csrc/train_small.hip too (``training.SmallKernels``), ``"native"`` as ``"full"`` and with the whole H layer, its
+        correction_net included, on the kernels of csrc/train_hlayer.hip and ``ADMMNet``'s PeakSearchLayer head on those of
+        csrc/train_head.hip (``training.NativeKernels``); on this route the head's attention dropout draws its keep mask with
+        one ``torch.rand`` call, so under the same seed it drops other entries than the other routes do (same distribution).
+        All use the HIP eigensolver and contractions; inference is not affected.  Not part of the state_dict."""
         return self._train_route
 
     @train_route.setter
     def train_route(self, value: str):
-        if not isinstance(value, str) or value not in ("tensor", "fused", "full"):
-            raise ValueError(f"train_route must be 'tensor', 'fused' or 'full', got {value!r}")
+        if not isinstance(value, str) or value not in ("tensor", "fused", "full", "native"):
+            raise ValueError(f"train_route must be 'tensor', 'fused', 'full' or 'native', got {value!r}")
         self._train_route = value
 
     # ---- weights -----------------------------------------------------------
@@ -365,7 +368,8 @@ class _FusedBase(nn.Module):
             raise _lib.AdmmNetError(f"training runs on the GPU: parameters are on {pdev}, expected {dev} "
                                     "(move the model with .to(device) as train.py / trainPhi.py do)")
         out = training.unrolled_forward(self, y.to(dev), b.to(dev), sigma.to(dev), sub_batch=self.sub_batch,
-                                        fused=self.train_route != "tensor", small=self.train_route == "full")
+                                        fused=self.train_route != "tensor", small=self.train_route in ("full", "native"),
+                                        native=self.train_route == "native")
         if isinstance(out, tuple):
             return tuple(o.to(y.device) for o in out)
         return out.to(y.device)

@@ -343,6 +343,150 @@ def train_hproject_bwd(g_h, t, m, sigma, pw):
     return g_t, g_m, g_pw
 
 
+def _correction_net(dev, D, W1, b1, W2, b2):
+    return (_f32(W1, dev, (64, D), "W1"), None if b1 is None else _f32(b1, dev, (64,), "b1"), _f32(W2, dev, (D, 64), "W2"),
+            None if b2 is None else _f32(b2, dev, (D,), "b2"))
+
+
+def train_hlayer(g_dg, z_dg, sigma, rho, pw, W1, b1, W2, b2):
+    """The whole H layer, ``train_hinput`` -> correction_net -> ``train_hproject`` in one kernel (csrc/train_hlayer.hip;
+    admm_net.py:134-194): t = g_dg + z_dg / (softplus(rho) + eps), a1 = relu(W1 t + b1), m = tanh(W2 a1 + b2), h from
+    tc = t + 0.1 m.  W1 [64, D], b1 [64], W2 [D, 64], b2 [D] are correction_net's RAW parameters.  Returns (h, t, a1, m);
+    t, m [B, D] and a1 [B, 64] are what ``train_hlayer_bwd`` reads."""
+    lib, dev, B, D = _small_args(g_dg, "g_dg")
+    with torch.cuda.device(dev):
+        g_dg, z_dg, sigma = _f32(g_dg, dev, (B, D), "g_dg"), _f32(z_dg, dev, (B, D), "z_dg"), _f32(sigma, dev, (B,), "sigma")
+        rho, pw = _f32(rho, dev, (), "rho"), _f32(pw, dev, (), "pw")
+        W1, b1, W2, b2 = _correction_net(dev, D, W1, b1, W2, b2)
+        h, t, m = torch.empty_like(g_dg), torch.empty_like(g_dg), torch.empty_like(g_dg)
+        a1 = torch.empty(B, 64, dtype=torch.float32, device=dev)
+        _lib.check(lib.admmnet_train_hlayer_f32(D, B, _ptr(g_dg), _ptr(z_dg), _ptr(sigma), _ptr(rho), _ptr(pw), _ptr(W1), _ptr(b1),
+                                                _ptr(W2), _ptr(b2), _ptr(h), _ptr(t), _ptr(a1), _ptr(m), _stream(dev)),
+                   "admmnet_train_hlayer_f32")
+    return h, t, a1, m
+
+
+def train_hlayer_bwd(g_h, z_dg, sigma, rho, pw, W1, W2, t, a1, m):
+    """Backward of ``train_hlayer``: returns (g_gdg, g_zdg [B, D], g_rho, g_pw 0-dim, gW1 [64, D], gb1 [64], gW2 [D, 64],
+    gb2 [D], delta1 [B, 64], delta2 [B, D]) -- the deltas are the pre-activation gradients whose batch-reduced products with
+    t and a1 the weight gradients are."""
+    lib, dev, B, D = _small_args(g_h, "g_h")
+    with torch.cuda.device(dev):
+        g_h, z_dg, sigma = _f32(g_h, dev, (B, D), "g_h"), _f32(z_dg, dev, (B, D), "z_dg"), _f32(sigma, dev, (B,), "sigma")
+        rho, pw = _f32(rho, dev, (), "rho"), _f32(pw, dev, (), "pw")
+        W1, _, W2, _ = _correction_net(dev, D, W1, None, W2, None)
+        t, a1, m = _f32(t, dev, (B, D), "t"), _f32(a1, dev, (B, 64), "a1"), _f32(m, dev, (B, D), "m")
+        g_gdg, g_zdg, d2 = torch.empty_like(g_h), torch.empty_like(g_h), torch.empty_like(g_h)
+        d1 = torch.empty_like(a1)
+        gpar = torch.empty(2 + 129 * D + 64, dtype=torch.float32, device=dev)
+        need = lib.admmnet_train_hlayer_workspace(D, B)
+        if need < 0:
+            raise _lib.AdmmNetError(f"train_hlayer_bwd: bad size (D={D}, B={B})")
+        work = torch.empty(need // 4, dtype=torch.float32, device=dev)
+        _lib.check(lib.admmnet_train_hlayer_bwd_f32(D, B, _ptr(g_h), _ptr(z_dg), _ptr(sigma), _ptr(rho), _ptr(pw), _ptr(W1),
+                                                    _ptr(W2), _ptr(t), _ptr(a1), _ptr(m), _ptr(g_gdg), _ptr(g_zdg), _ptr(d1),
+                                                    _ptr(d2), _ptr(gpar), _ptr(work), _stream(dev)),
+                   "admmnet_train_hlayer_bwd_f32")
+    o = 2 + 64 * D
+    return (g_gdg, g_zdg, gpar[0], gpar[1], gpar[2:o].view(64, D), gpar[o:o + 64], gpar[o + 64:o + 64 + 64 * D].view(D, 64),
+            gpar[o + 64 + 64 * D:], d1, d2)
+
+
+_HEAD_SAVED, _HEAD_WORK, _HEAD_GRADS = 0, 1, 2                 # ADMMNET_TRAIN_HEAD_* of include/admmnet.h
+
+
+def _head_shapes(D, L):
+    """The shapes of the head's parameters in the order of ``training._head_params`` (the kernels' pointer table)."""
+    s = [(D, 2), (128, 2 * D), (128,), (128, 128), (128,), (128, 2), (128,), (384, 128), (384,), (128, 128), (128,),
+         (64, 128), (64,), (32, 64), (32,), (16, 32), (16,), (16, 16), (16,), (1, 16), (1,)]
+    return s + [(32, 16), (32,), (1, 32), (1,)] * (2 * L)
+
+
+def _head_args(phi, keep, p, L, hp):
+    _need_cuda(phi, "phi")
+    if phi.dim() != 2:
+        raise ValueError(f"phi must be [B, D], got {tuple(phi.shape)}")
+    lib, dev, (B, D) = _lib.load(), phi.device, phi.shape
+    shapes = _head_shapes(D, L)
+    if len(hp) != len(shapes):
+        raise ValueError(f"the head has {len(shapes)} parameters at L = {L}, got {len(hp)}")
+    hp = [_f32(t, dev, s, f"head parameter {i}") for i, (t, s) in enumerate(zip(hp, shapes))]
+    if keep is not None:
+        if keep.dtype not in (torch.bool, torch.uint8) or tuple(keep.shape) != (B, 4, D):
+            raise ValueError(f"keep must be a bool or uint8 [{B}, 4, {D}] tensor, got {keep.dtype} {tuple(keep.shape)}")
+        if not 0.0 <= p < 1.0:
+            raise ValueError(f"the dropout probability must be in [0, 1), got {p}")
+        _need_cuda(keep, "keep")
+        keep = keep.to(dev).contiguous()
+    table = (ctypes.c_void_p * len(hp))(*[t.data_ptr() for t in hp])
+    return lib, dev, B, D, hp, keep, table
+
+
+def _head_bytes(lib, D, L, B, part):
+    need = lib.admmnet_train_head_workspace(D, L, B, part)
+    if need < 0:
+        raise _lib.AdmmNetError(f"train_head: bad size (D={D}, L={L}, B={B})")
+    return need // 4
+
+
+def train_head(phi, keep, p, L, hp):
+    """The PeakSearchLayer head (csrc/train_head.hip; admm_net.py:570-630) on phi [B, D] complex64: returns (tau, f, conf [B, L],
+    saved).  ``hp``: the head's RAW parameters in the order of ``training._head_params``; ``keep``: the attention dropout's keep
+    mask [B, 4, D] (bool or uint8; applied as a <- a keep / (1 - p) between the softmax and the value product) or None for no
+    dropout.  ``saved`` is what ``train_head_bwd`` reads."""
+    lib, dev, B, D, hp, keep, table = _head_args(phi, keep, p, L, hp)
+    with torch.cuda.device(dev):
+        phi = _c64(phi, dev, (B, D), "phi")
+        tau, f, conf = (torch.empty(B, L, dtype=torch.float32, device=dev) for _ in range(3))
+        act = torch.empty(_head_bytes(lib, D, L, B, _HEAD_SAVED), dtype=torch.float32, device=dev)
+        _lib.check(lib.admmnet_train_head_f32(D, L, B, _ptr(phi), table, _ptr(keep), float(p), _ptr(tau), _ptr(f), _ptr(conf),
+                                              _ptr(act), _stream(dev)), "admmnet_train_head_f32")
+    return tau, f, conf, (act, tau, f, conf)
+
+
+def train_head_bwd(g_tau, g_f, g_conf, phi, keep, p, L, hp, saved):
+    """Backward of ``train_head``: returns (g_phi [B, D] complex64, [the gradient of every tensor of ``hp``]); the gradients are
+    views of one buffer."""
+    lib, dev, B, D, hp, keep, table = _head_args(phi, keep, p, L, hp)
+    act, tau, f, conf = saved
+    with torch.cuda.device(dev):
+        phi = _c64(phi, dev, (B, D), "phi")
+        g_tau, g_f, g_conf = (_f32(t, dev, (B, L), n) for t, n in ((g_tau, "g_tau"), (g_f, "g_f"), (g_conf, "g_conf")))
+        tau, f, conf = (_f32(t, dev, (B, L), n) for t, n in ((tau, "tau"), (f, "f"), (conf, "conf")))
+        act = _f32(act, dev, (_head_bytes(lib, D, L, B, _HEAD_SAVED),), "saved")
+        g_phi = torch.empty(B, D, dtype=torch.complex64, device=dev)
+        g = torch.empty(_head_bytes(lib, D, L, B, _HEAD_GRADS), dtype=torch.float32, device=dev)
+        work = torch.empty(_head_bytes(lib, D, L, B, _HEAD_WORK), dtype=torch.float32, device=dev)
+        _lib.check(lib.admmnet_train_head_bwd_f32(D, L, B, _ptr(g_tau), _ptr(g_f), _ptr(g_conf), _ptr(phi), table, _ptr(keep),
+                                                  float(p), _ptr(tau), _ptr(f), _ptr(conf), _ptr(act), _ptr(g_phi), _ptr(g),
+                                                  _ptr(work), _stream(dev)), "admmnet_train_head_bwd_f32")
+    # the buffer's layout (include/admmnet.h): confidence_net, region A, in_proj, position_projection, position_encoder
+    cur = [0]
+
+    def take(*shape):
+        n = 1
+        for s in shape:
+            n *= s
+        v = g[cur[0]:cur[0] + n].view(*shape)
+        cur[0] += n
+        return v
+
+    out = [None] * len(hp)
+    out[17], out[18], out[19], out[20] = take(16, 16), take(16), take(1, 16), take(1)
+    out[1], out[2], out[3], out[4] = take(128, 2 * D), take(128), take(128, 128), take(128)
+    out[9], out[10] = take(128, 128), take(128)
+    out[11], out[12], out[13], out[14], out[15], out[16] = take(64, 128), take(64), take(32, 64), take(32), take(16, 32), take(16)
+    for t in range(L):
+        o = 21 + 8 * t
+        out[o], out[o + 4] = take(32, 16), take(32, 16)
+        out[o + 1], out[o + 5] = take(32), take(32)
+        out[o + 2], out[o + 3], out[o + 6], out[o + 7] = take(1, 32), take(1), take(1, 32), take(1)
+    cur[0] += 256 * D                                            # gK, gV: the sums over the batch the token side starts from
+    out[7], out[8], out[5], out[6], out[0] = take(384, 128), take(384), take(128, 2), take(128), take(D, 2)
+    assert cur[0] == g.numel()
+    return g_phi, out
+
+
 def train_eigmap(w, thr, W1, b1, W2, b2) -> torch.Tensor:
     """wp = softplus(w - sigmoid(thr)) sigmoid(W2 relu(W1 |w| + b1) + b2) over [B, n] (admm_net.py:310-334); W1 [16, 1],
     b1 [16], W2 [1, 16], b2 [1] are value_net's parameters."""

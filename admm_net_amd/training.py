@@ -25,6 +25,16 @@ CPU tests).  Those kernels read the raw parameters and return raw-parameter grad
 ``1 / (softplus(rho) + eps)`` factor of the G layer stay framework operations.  On this route the two detached corner values of
 every layer are resolved with ONE device-to-host read per forward, and the detached rho feature never leaves the device.
 
+``native=True`` on top of ``small=True`` (``model.train_route = "native"``) moves ``correction_net`` into the H layer's kernels: the
+whole H layer is one autograd function over one forward kernel, one backward kernel and a batch-reduced product on the matrix
+cores for the MLP's weight gradients (csrc/train_hlayer.hip, ``NativeKernels``; ``TorchNativeKernels`` for the CPU tests), and the G
+layers' ``1 / (softplus(rho) + eps)`` is evaluated once per forward on the stacked rhos.  The PeakSearchLayer head of ``ADMMNet``
+is one autograd function too (``_PeakHead``, csrc/train_head.hip): a K/V kernel for the batch-independent position tokens, one
+per-signal forward and one per-signal backward kernel, the weight gradients and the token side's gK, gV as batch-reduced products
+on the matrix cores, and a token-backward kernel.  The attention dropout is an INPUT of that function, a keep mask [B, 4, D]
+drawn with one ``torch.rand`` call (``draw_keep_mask``) when the head is in train mode: the same distribution as
+``nn.MultiheadAttention``'s dropout, another realisation under the same seed.
+
 Gradient flow mirrors the reference as written:
   * the corner values ``1 / (softplus(lambda)^2 + eps)`` go through ``.item()`` (admm_net.py:271, 426):
     ``gLayers.k.lambda_param`` / ``zLayers.k.lambda_param`` receive no gradient;
@@ -39,6 +49,7 @@ There is no CPU fallback: without the HIP library ``ops.eigh`` raises.
 """
 from __future__ import annotations
 
+from types import SimpleNamespace
 from typing import Callable, Optional
 
 import torch
@@ -526,8 +537,224 @@ class _StepSize(torch.autograd.Function):
         return (*ctx.sk.stepsize_bwd(g_step, *ctx.saved_tensors, ctx.knorm, ctx.sub_batch), None, None, None)
 
 
+class NativeKernels:
+    """The whole H layer, ``correction_net`` included, on the HIP kernels of csrc/train_hlayer.hip: one forward and one backward
+    kernel per signal slab, and the weight gradients as one batch-reduced product on the matrix cores; and the PeakSearchLayer
+    head on those of csrc/train_head.hip.  RAW parameters in, raw-parameter gradients out, as for ``SmallKernels``."""
+
+    hlayer = staticmethod(ops.train_hlayer)            # (g_dg, z_dg, sigma, rho, pw, W1, b1, W2, b2) -> h, t, a1, m
+    hlayer_bwd = staticmethod(ops.train_hlayer_bwd)    # (g_h, z_dg, sigma, rho, pw, W1, W2, t, a1, m) -> g_gdg, g_zdg, g_rho, g_pw,
+    #                                                    gW1, gb1, gW2, gb2, delta1, delta2
+    head = staticmethod(ops.train_head)                # (phi, keep, p, L, hp) -> tau, f, conf, saved
+    head_bwd = staticmethod(ops.train_head_bwd)        # (g_tau, g_f, g_conf, phi, keep, p, L, hp, saved) -> g_phi, [g of hp]
+
+
+class TorchNativeKernels:
+    """Stand-in for tests: the same forward / backward formulas as tensor operations, any device, in the dtype it is given.
+    ``hlayer_terms`` returns the batch sums of ``hlayer_bwd`` unsummed, as the ``_terms`` forms of ``TorchSmallKernels`` do;
+    ``head_bwd(..., mag=True)`` returns the sums of the magnitudes of the head's terms (the terms themselves would be
+    B x 128 x 2 D numbers).  The head is written out without ``nn.MultiheadAttention``."""
+
+    @staticmethod
+    def hlayer(g_dg, z_dg, sigma, rho, pw, W1, b1, W2, b2):
+        t = TorchSmallKernels.hinput(g_dg, z_dg, rho)
+        a1 = torch.relu(t @ W1.t() + b1)
+        m = torch.tanh(a1 @ W2.t() + b2)
+        return TorchSmallKernels.hproject(t, m, sigma, pw), t, a1, m
+
+    @staticmethod
+    def hlayer_terms(g_h, z_dg, sigma, rho, pw, W1, W2, t, a1, m):
+        """(g_gdg, g_zdg, delta1, delta2, then one term per signal and element of g_rho [B, D], g_pw [B], gW1 [B, 64, D],
+        gb1 [B, 64], gW2 [B, D, 64], gb2 [B, D])."""
+        g_tc, _, t_pw = TorchSmallKernels.hproject_terms(g_h, t, m, sigma, pw)
+        d2 = 0.1 * g_tc * (1 - m ** 2)
+        d1 = (d2 @ W2) * (a1 > 0).to(t.dtype)                       # relu'(0) = 0
+        g_gdg, g_zdg, t_rho = TorchSmallKernels.hinput_terms(g_tc + d1 @ W1, z_dg, rho)
+        return g_gdg, g_zdg, d1, d2, t_rho, t_pw, d1.unsqueeze(2) * t.unsqueeze(1), d1, d2.unsqueeze(2) * a1.unsqueeze(1), d2
+
+    @staticmethod
+    def hlayer_bwd(g_h, z_dg, sigma, rho, pw, W1, W2, t, a1, m):
+        g_gdg, g_zdg, d1, d2, t_rho, t_pw, tW1, tb1, tW2, tb2 = TorchNativeKernels.hlayer_terms(g_h, z_dg, sigma, rho, pw, W1, W2,
+                                                                                                t, a1, m)
+        return g_gdg, g_zdg, t_rho.sum(), t_pw.sum(), tW1.sum(dim=0), tb1.sum(dim=0), tW2.sum(dim=0), tb2.sum(dim=0), d1, d2
+
+
+    # ---- the PeakSearchLayer head.  ``hp``: the head's RAW parameters in the order of ``_head_params``
+    @staticmethod
+    def _head_parts(phi, keep, p, L, hp):
+        B, D = phi.shape
+        pos, fe0w, fe0b, fe2w, fe2b, ppw, ppb, inw, inb, outw, outb, pe0w, pe0b, pe2w, pe2b, pe4w, pe4b = hp[:17]
+        s = SimpleNamespace()
+        s.feat = torch.cat([phi.real, phi.imag], dim=1)
+        s.x1 = torch.relu(s.feat @ fe0w.t() + fe0b)
+        s.x = torch.relu(s.x1 @ fe2w.t() + fe2b)
+        s.P = pos @ ppw.t() + ppb                                                                # [D, 128], batch independent
+        s.q = ((s.x @ inw[:128].t() + inb[:128]) * _ATT_SCALE).reshape(B, 4, 32)                 # scaled before the product
+        s.K = (s.P @ inw[128:256].t() + inb[128:256]).reshape(D, 4, 32)
+        s.V = (s.P @ inw[256:].t() + inb[256:]).reshape(D, 4, 32)
+        s.a = torch.softmax(torch.einsum("bhj,dhj->bhd", s.q, s.K), dim=2)
+        s.km = None if keep is None else keep.to(s.a.dtype) / (1.0 - p)
+        s.am = s.a if keep is None else s.a * s.km
+        s.ctx = torch.einsum("bhd,dhj->bhj", s.am, s.V).reshape(B, 128)
+        s.xf = s.x + s.ctx @ outw.t() + outb
+        s.u0 = torch.relu(s.xf @ pe0w.t() + pe0b)
+        s.u1 = torch.relu(s.u0 @ pe2w.t() + pe2b)
+        s.xp = torch.relu(s.u1 @ pe4w.t() + pe4b)
+        off = torch.tensor([t / L for t in range(L)], dtype=torch.float32).to(s.xp)               # t / L is a float32 constant
+        s.z = s.xp.unsqueeze(1) + off.reshape(1, L, 1)                                           # [B, L, 16]
+        return s
+
+    @staticmethod
+    def head(phi, keep, p, L, hp):
+        """(tau, f, conf [B, L], saved): ``_peak_head`` with ``keep`` [B, 4, D] (None: no dropout) as the attention's keep
+        mask, a <- a keep / (1 - p) between the softmax and the value product."""
+        s = TorchNativeKernels._head_parts(phi, keep, p, L, hp)
+        c0w, c0b, c2w, c2b = hp[17:21]
+        taus, fs, cs = [], [], []
+        for t in range(L):
+            tw0, tb0, tw2, tb2, fw0, fb0, fw2, fb2 = hp[21 + 8 * t:29 + 8 * t]
+            z = s.z[:, t]
+            taus.append(torch.sigmoid(torch.relu(z @ tw0.t() + tb0) @ tw2.t() + tb2))
+            fs.append(torch.tanh(torch.relu(z @ fw0.t() + fb0) @ fw2.t() + fb2))
+            cs.append(torch.sigmoid(torch.relu(z @ c0w.t() + c0b) @ c2w.t() + c2b))
+        return torch.cat(taus, 1), torch.cat(fs, 1), torch.cat(cs, 1), ()
+
+    @staticmethod
+    def head_bwd(g_tau, g_f, g_conf, phi, keep, p, L, hp, saved=(), mag=False):
+        """(g_phi, [gradient of every tensor of ``hp``]).  ``mag = True`` returns, instead of each batch sum, the sum of the
+        magnitudes of its terms (what an error bound in terms of sum |terms| needs); g_phi is then meaningless."""
+        B, D = phi.shape
+        s = TorchNativeKernels._head_parts(phi, keep, p, L, hp)
+        pos, fe0w, _, fe2w, _, ppw, _, inw, _, outw, _, pe0w, _, pe2w, _, pe4w, _, c0w, c0b, c2w, c2b = hp[:21]
+        ab = (lambda v: v.abs()) if mag else (lambda v: v)
+        bs = lambda d, v: ab(d).t() @ ab(v)                                  # sum_b d_b (x) v_b
+        cs = lambda d: ab(d).sum(dim=0)
+        g = [None] * len(hp)
+        g_xp = torch.zeros_like(s.xp)
+        g[17], g[18], g[19], g[20] = (torch.zeros_like(v) for v in hp[17:21])
+        for t in range(L):
+            tw0, tb0, tw2, tb2, fw0, fb0, fw2, fb2 = hp[21 + 8 * t:29 + 8 * t]
+            z, o = s.z[:, t], 21 + 8 * t
+            for w0, b0, w2, b2, gout, act, at in ((tw0, tb0, tw2, tb2, g_tau, "s", o), (fw0, fb0, fw2, fb2, g_f, "t", o + 4),
+                                                  (c0w, c0b, c2w, c2b, g_conf, "s", 17)):
+                hid = torch.relu(z @ w0.t() + b0)
+                out = hid @ w2.t() + b2
+                out = torch.sigmoid(out) if act == "s" else torch.tanh(out)
+                do = gout[:, t:t + 1] * (out * (1 - out) if act == "s" else 1 - out ** 2)     # [B, 1]
+                dh = (do @ w2) * (hid > 0).to(z.dtype)                                        # relu'(0) = 0
+                g_xp = g_xp + dh @ w0
+                new = (bs(dh, z), cs(dh), bs(do, hid), cs(do))
+                for i, v in enumerate(new):                                                   # confidence_net sums over t
+                    g[at + i] = v if at != 17 else g[at + i] + v
+        d4 = g_xp * (s.xp > 0).to(g_xp.dtype)
+        d2 = (d4 @ pe4w) * (s.u1 > 0).to(d4.dtype)
+        d0 = (d2 @ pe2w) * (s.u0 > 0).to(d4.dtype)
+        g[15], g[16], g[13], g[14], g[11], g[12] = bs(d4, s.u1), cs(d4), bs(d2, s.u0), cs(d2), bs(d0, s.xf), cs(d0)
+        g_xf = d0 @ pe0w
+        g[9], g[10] = bs(g_xf, s.ctx), cs(g_xf)
+        g_ctx = (g_xf @ outw).reshape(B, 4, 32)
+        g_am = torch.einsum("bhj,dhj->bhd", g_ctx, s.V)
+        g_a = g_am if keep is None else g_am * s.km
+        g_s = s.a * (g_a - (s.a * g_a).sum(dim=2, keepdim=True))
+        gV = torch.einsum("bhd,bhj->dhj", ab(s.am), ab(g_ctx)).reshape(D, 128)
+        gK = torch.einsum("bhd,bhj->dhj", ab(g_s), ab(s.q)).reshape(D, 128)
+        dq = torch.einsum("bhd,dhj->bhj", g_s, s.K).reshape(B, 128) * _ATT_SCALE
+        g_x = g_xf + dq @ inw[:128]
+        dp2 = g_x * (s.x > 0).to(g_x.dtype)
+        dp1 = (dp2 @ fe2w) * (s.x1 > 0).to(g_x.dtype)
+        g[3], g[4], g[1], g[2] = bs(dp2, s.x1), cs(dp2), bs(dp1, s.feat), cs(dp1)
+        g_feat = dp1 @ fe0w
+        # the token side: sums over the batch first (gK, gV), then through the K and V slices of in_proj to the tokens
+        g_P = gK @ ab(inw[128:256]) + gV @ ab(inw[256:])
+        g[7] = torch.cat([bs(dq, s.x), bs(gK, s.P), bs(gV, s.P)])
+        g[8] = torch.cat([cs(dq), cs(gK), cs(gV)])                            # in_proj_bias's K slice receives sum_d gK
+        g[5], g[6], g[0] = bs(g_P, pos), cs(g_P), g_P @ ab(ppw)
+        return torch.complex(g_feat[:, :D], g_feat[:, D:]), g
+
+
+_ATT_SCALE = 32 ** -0.5
+
+
+def _head_params(head):
+    """The head's parameters in the order of the kernels' pointer table: 21 tensors, then 8 per target."""
+    fe, pe, at, cn = head.feature_extractor, head.peak_extractor, head.attention, head.confidence_net
+    hp = [head.position_encoder, fe[0].weight, fe[0].bias, fe[2].weight, fe[2].bias, head.position_projection.weight,
+          head.position_projection.bias, at.in_proj_weight, at.in_proj_bias, at.out_proj.weight, at.out_proj.bias,
+          pe[0].weight, pe[0].bias, pe[2].weight, pe[2].bias, pe[4].weight, pe[4].bias,
+          cn[0].weight, cn[0].bias, cn[2].weight, cn[2].bias]
+    for t in range(head.L_max):
+        for net in (head.tau_regressor[t], head.f_regressor[t]):
+            hp += [net[0].weight, net[0].bias, net[2].weight, net[2].bias]
+    return hp
+
+
+def draw_keep_mask(B, D, p, device, generator=None):
+    """The attention dropout's keep mask [B, 4, D], one byte per element, with one framework call: kept with probability
+    1 - p.  The kernels scale the kept entries by exactly 1 / (1 - p)."""
+    return torch.rand(B, 4, D, device=device, generator=generator) >= p
+
+
+def _check_keep_mask(keep, B, D):
+    if keep is None:
+        return
+    if not torch.is_tensor(keep) or keep.dtype not in (torch.bool, torch.uint8):
+        raise ValueError(f"the keep mask must be a bool or uint8 tensor, got {getattr(keep, 'dtype', type(keep))}")
+    if tuple(keep.shape) != (B, 4, D):
+        raise ValueError(f"the keep mask must be [{B}, 4, {D}], got {tuple(keep.shape)}")
+
+
+class _PeakHead(torch.autograd.Function):
+    """``_peak_head`` as one function with a hand-written backward (admm_net.py:570-630).  ``keep``: the attention dropout's
+    keep mask [B, 4, D] or None; it carries no gradient and is kept for the backward."""
+
+    @staticmethod
+    def forward(ctx, phi, keep, p, L, nk, *hp):
+        _check_keep_mask(keep, *phi.shape)
+        tau, f, conf, saved = nk.head(phi, keep, p, L, hp)
+        ctx.save_for_backward(phi, *hp, *saved)
+        ctx.keep, ctx.p, ctx.L, ctx.nk, ctx.nhp = keep, p, L, nk, len(hp)
+        return tau, f, conf
+
+    @staticmethod
+    def backward(ctx, g_tau, g_f, g_conf):
+        phi, rest = ctx.saved_tensors[0], ctx.saved_tensors[1:]
+        hp, saved = rest[:ctx.nhp], rest[ctx.nhp:]
+        g_phi, g = ctx.nk.head_bwd(g_tau, g_f, g_conf, phi, ctx.keep, ctx.p, ctx.L, hp, saved)
+        return (g_phi, None, None, None, None, *g)
+
+
+def _peak_head_native(head, phi, nk, keep=None):
+    """The head on the native route.  In train mode with dropout p > 0 the keep mask is drawn here unless given."""
+    p = float(head.attention.dropout)
+    if keep is None and head.training and p > 0:
+        keep = draw_keep_mask(phi.shape[0], phi.shape[1], p, phi.device)
+    return _PeakHead.apply(phi, keep, p, head.L_max, nk, *_head_params(head))
+
+
+class _HLayerStep(torch.autograd.Function):
+    """``_h_layer`` on the gathered diagonals as one function, correction_net inside (admm_net.py:134-194); sigma carries no
+    gradient.  The tape keeps t, a1 and m."""
+
+    @staticmethod
+    def forward(ctx, g_dg, z_dg, sigma, rho, pw, W1, b1, W2, b2, nk):
+        h, t, a1, m = nk.hlayer(g_dg, z_dg, sigma, rho, pw, W1, b1, W2, b2)
+        ctx.save_for_backward(z_dg, sigma, rho, pw, W1, W2, t, a1, m)
+        ctx.nk = nk
+        return h
+
+    @staticmethod
+    def backward(ctx, g_h):
+        g_gdg, g_zdg, g_rho, g_pw, gW1, gb1, gW2, gb2, _, _ = ctx.nk.hlayer_bwd(g_h, *ctx.saved_tensors)
+        return g_gdg, g_zdg, None, g_rho, g_pw, gW1, gb1, gW2, gb2, None
+
+
+def _resolve_rinv(model, K):
+    """``1 / (softplus(rho) + eps)`` of gLayers[k], k < K - 1, evaluated once on the stacked rhos (differentiable): [K - 1]."""
+    return 1.0 / (F.softplus(torch.stack([model.gLayers[k].rho for k in range(K - 1)])) + EPS)
+
+
 def _net_params(net):
-    """(W1, b1, W2, b2) of a Linear - ReLU - Linear - Sigmoid module."""
+    """(W1, b1, W2, b2) of a Linear - ReLU - Linear - Sigmoid (or Tanh) module."""
     return net[0].weight, net[0].bias, net[2].weight, net[2].bias
 
 
@@ -570,16 +797,17 @@ def _h_layer(layer, G, Z, sigma, diags=None):
     return tc * scale
 
 
-def _g_layer(layer, phi, h, Z, solver, asm, lk=None, sk=None, corner=None):
+def _g_layer(layer, phi, h, Z, solver, asm, lk=None, sk=None, corner=None, rinv=None):
     """admm_net.py:237-354.  ``lk``: layer kernels of the fused route (None: tensor operations); ``sk``: small kernels of the
-    full route; ``corner``: the detached corner value where the caller has resolved it already."""
+    full route; ``corner``: the detached corner value where the caller has resolved it already; ``rinv``: likewise
+    ``1 / (softplus(rho) + eps)`` (the native route evaluates it for all layers at once)."""
     if corner is None:
         corner = (1.0 / (F.softplus(layer.lambda_param) ** 2 + EPS)).item()
     if lk is None:
         A = _block_matrix(phi, h, corner) - (1.0 / (F.softplus(layer.rho) + EPS)) * Z
         A = 0.5 * (A + A.transpose(1, 2).conj())
     else:
-        A = _LayerMatrix.apply(phi, h, Z, 1.0 / (F.softplus(layer.rho) + EPS), corner, lk)
+        A = _LayerMatrix.apply(phi, h, Z, 1.0 / (F.softplus(layer.rho) + EPS) if rinv is None else rinv, corner, lk)
     w, V = _EighValuesOnly.apply(A, solver, asm)
     # learned eigenvalue map, every eigenvalue through the same 1 -> 16 -> 1 network (admm_net.py:310-334)
     if sk is None:
@@ -644,7 +872,8 @@ def _peak_head(head, phi):
 
 def unrolled_forward(model, y: torch.Tensor, b: torch.Tensor, sigma: torch.Tensor,
                      solver: Optional[Callable] = None, assembler=None, sub_batch: Optional[int] = None,
-                     fused: bool = False, layer_kernels=None, small: bool = False, small_kernels=None):
+                     fused: bool = False, layer_kernels=None, small: bool = False, small_kernels=None,
+                     native: bool = False, native_kernels=None):
     """Differentiable K-layer forward on the device of ``y`` (admm_net.py:742-764 / 791-816).
 
     ``sub_batch = g`` evaluates the consecutive groups of g signals as independent batches, each with its own mean
@@ -660,6 +889,10 @@ def unrolled_forward(model, y: torch.Tensor, b: torch.Tensor, sigma: torch.Tenso
     eigenvalue map and the step-size network through ``small_kernels`` (default ``SmallKernels``, the HIP kernels of
     csrc/train_small.hip; the CPU tests pass ``TorchSmallKernels``), and reads the detached corner values of all layers from
     the device once.
+    ``native = True`` (needs ``small = True``) evaluates every H layer, its ``correction_net`` included, through
+    ``native_kernels`` (default ``NativeKernels``, the HIP kernels of csrc/train_hlayer.hip; the CPU tests pass
+    ``TorchNativeKernels``), the G layers' ``1 / (softplus(rho) + eps)`` once per forward on the stacked rhos, and the head of
+    ``ADMMNet`` through ``_PeakHead`` (csrc/train_head.hip).
     Returns phi, or (tau, f, confidences, phi) when the model has a PeakSearchLayer.
     """
     if sub_batch is not None and sub_batch < 1:
@@ -676,6 +909,11 @@ def unrolled_forward(model, y: torch.Tensor, b: torch.Tensor, sigma: torch.Tenso
     if small_kernels is not None and not small:
         raise ValueError("small_kernels is only used with small=True")
     sk = (SmallKernels if small_kernels is None else small_kernels) if small else None
+    if native and not small:
+        raise ValueError("native=True needs small=True")
+    if native_kernels is not None and not native:
+        raise ValueError("native_kernels is only used with native=True")
+    nk = (NativeKernels if native_kernels is None else native_kernels) if native else None
     K, D = model.num_layers, model.M * model.N
     if y.dim() != 2 or y.shape[1] != D or b.shape != y.shape:
         raise ValueError(f"y, b must be [B, {D}] complex; got {tuple(y.shape)}, {tuple(b.shape)}")
@@ -691,15 +929,20 @@ def unrolled_forward(model, y: torch.Tensor, b: torch.Tensor, sigma: torch.Tenso
         g_col = z_col = torch.zeros(B, D, dtype=torch.complex64, device=y.device)
         g_dg = z_dg = torch.zeros(B, D, dtype=torch.float32, device=y.device)
     corners = _resolve_corners(model, K) if sk is not None else None
+    rinv = _resolve_rinv(model, K) if nk is not None and K > 1 else None
     for k in range(K):
         if sk is not None:
             phi = _PhiStep.apply(y, b, g_col, z_col, model.phiLayers[k].rho, sk)
             if k == K - 1:
                 break
             hl = model.hLayers[k]
-            t = _HInput.apply(g_dg, z_dg, hl.rho, sk)
-            h = _HProject.apply(t, hl.correction_net(t), sigma, hl.projection_weight, sk)
-            G, g_col, g_dg = _g_layer(model.gLayers[k], phi, h, Z, solver, asm, lk, sk, corners[k][0])
+            if nk is not None:
+                h = _HLayerStep.apply(g_dg, z_dg, sigma, hl.rho, hl.projection_weight, *_net_params(hl.correction_net), nk)
+            else:
+                t = _HInput.apply(g_dg, z_dg, hl.rho, sk)
+                h = _HProject.apply(t, hl.correction_net(t), sigma, hl.projection_weight, sk)
+            G, g_col, g_dg = _g_layer(model.gLayers[k], phi, h, Z, solver, asm, lk, sk, corners[k][0],
+                                      None if rinv is None else rinv[k])
             Z = _z_layer(model.zLayers[k], k, phi, h, G, Z, sub_batch, lk, sk, corners[k][1])
             z_col, z_dg = _Gather.apply(Z, lk)
             continue
@@ -719,6 +962,9 @@ def unrolled_forward(model, y: torch.Tensor, b: torch.Tensor, sigma: torch.Tenso
             Z = _z_layer(model.zLayers[k], k, phi, h, G, Z, sub_batch, lk)
             z_col, z_dg = _Gather.apply(Z, lk)
     if getattr(model, "_HAS_HEAD", False):
-        tau, f, conf = _peak_head(model.peakSearchLayer, phi)
+        if nk is not None:
+            tau, f, conf = _peak_head_native(model.peakSearchLayer, phi, nk)
+        else:
+            tau, f, conf = _peak_head(model.peakSearchLayer, phi)
         return tau, f, conf, phi
     return phi

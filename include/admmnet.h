@@ -367,6 +367,60 @@ int admmnet_train_stepsize_bwd_f32(int64_t B, int64_t sub_batch, float knorm, co
                                    const float *rho, const float *W1, const float *b1, const float *W2, const float *b2,
                                    float *g_rn, float *g_params, float *partials, void *stream);
 
+/* Training route "native", the H layer with its correction_net inside (csrc/train_hlayer.hip): one forward kernel; one backward
+ * kernel plus a batch-reduced product on the matrix cores for the weight gradients.  1 <= D = M N <= 256, B >= 1 (at most
+ * 65535 * 128).  Conventions, alignment and the RAW parameters as for the "full" route above; W1 [64][D], b1 [64], W2 [D][64],
+ * b2 [D] are correction_net's Linear(D, 64) - ReLU - Linear(64, D) - Tanh.
+ *   admmnet_train_hlayer_f32      t = g_dg + z_dg / (softplus(*rho) + eps), a1 = relu(W1 t + b1), m = tanh(W2 a1 + b2),
+ *                                 tc = t + 0.1 m, h = the projection of admmnet_train_hproject_f32 -- HLayer, :134-194.
+ *                                 t, m [B][D] and a1 [B][64] are written for the backward.
+ *   admmnet_train_hlayer_bwd_f32  from g_h: g_gdg, g_zdg [B][D]; the pre-activation deltas delta1 [B][64] (relu'(0) = 0) and
+ *                                 delta2 [B][D]; g_params[2 + 129 D + 64] = g_rho, g_projection_weight, gW1 [64][D], gb1 [64],
+ *                                 gW2 [D][64], gb2 [D].  The weight gradients are sums over the batch: float32 on the matrix
+ *                                 cores within fixed slabs of 128 signals, the slabs added in ascending order in float64; no
+ *                                 atomics, two runs give the same bits.  `workspace` holds admmnet_train_hlayer_workspace(D, B)
+ *                                 bytes (-1 for sizes outside the range), 4-byte aligned. */
+int64_t admmnet_train_hlayer_workspace(int32_t D, int64_t B);
+int admmnet_train_hlayer_f32(int32_t D, int64_t B, const float *g_dg, const float *z_dg, const float *sigma, const float *rho,
+                             const float *projection_weight, const float *W1, const float *b1, const float *W2, const float *b2,
+                             float *h, float *t, float *a1, float *m, void *stream);
+int admmnet_train_hlayer_bwd_f32(int32_t D, int64_t B, const float *g_h, const float *z_dg, const float *sigma, const float *rho,
+                                 const float *projection_weight, const float *W1, const float *W2, const float *t, const float *a1,
+                                 const float *m, float *g_gdg, float *g_zdg, float *delta1, float *delta2, float *g_params,
+                                 void *workspace, void *stream);
+
+/* Training route "native", the PeakSearchLayer head (csrc/train_head.hip; PeakSearchLayer.forward, :570-630).  1 <= D = M N <= 256,
+ * 1 <= L <= 16, B >= 1 with B L <= 65535 * 128.  `params` is a HOST array of the 21 + 8 L device pointers to the RAW float32
+ * parameters: position_encoder, feature_extractor.{0,2}.{weight,bias}, position_projection.{weight,bias}, attention.in_proj_
+ * {weight,bias}, attention.out_proj.{weight,bias}, peak_extractor.{0,2,4}.{weight,bias}, confidence_net.{0,2}.{weight,bias}, then
+ * per target t tau_regressor.t.{0,2}.{weight,bias}, f_regressor.t.{0,2}.{weight,bias}; the array is read before the call returns.
+ * `keep` is the attention dropout's keep mask [B][4][D], one byte per element (nonzero: kept), applied as a <- a keep / (1 - p)
+ * between the softmax and the value product, 0 <= p < 1; NULL: no dropout (p is ignored).  phi, g_phi are complex64 [B][D].
+ *   admmnet_train_head_f32      tau, f, conf [B][L]; `saved` receives the activations the backward reads,
+ *                               admmnet_train_head_workspace(D, L, B, ADMMNET_TRAIN_HEAD_SAVED) bytes
+ *                               (4 B (4 D + 752 + 80 L) + 12 * 128 D).
+ *   admmnet_train_head_bwd_f32  from g_tau, g_f, g_conf [B][L] and the forward's tau, f, conf, saved: g_phi, and g_params
+ *                               (..._GRADS bytes), the raw-parameter gradients, at float offsets:
+ *                               confidence_net 0.weight 0, 0.bias 256, 2.weight 272, 2.bias 288; then from 289
+ *                               feature_extractor 0.weight, 0.bias, 2.weight, 2.bias, out_proj weight, bias, peak_extractor
+ *                               0.weight ... 4.bias, per target [tau 0.weight | f 0.weight] [tau 0.bias | f 0.bias] tau
+ *                               2.weight, 2.bias, f 2.weight, 2.bias (1154 floats), 256 D floats of scratch, in_proj_weight
+ *                               [384][128] at 289 + 512 D + 44016 + 1154 L, in_proj_bias [384] behind it, position_projection weight [128][2],
+ *                               bias [128], position_encoder [D][2].  Every batch sum runs in float32 on the matrix cores within
+ *                               fixed slabs of 128 signals, the slabs added in ascending order in float64; no atomics, two runs
+ *                               give the same bits.  `workspace` holds ..._WORK bytes.
+ * admmnet_train_head_workspace answers -1 for sizes outside the range or an unknown part. */
+#define ADMMNET_TRAIN_HEAD_SAVED 0
+#define ADMMNET_TRAIN_HEAD_WORK 1
+#define ADMMNET_TRAIN_HEAD_GRADS 2
+int64_t admmnet_train_head_workspace(int32_t D, int32_t L, int64_t B, int32_t part);
+int admmnet_train_head_f32(int32_t D, int32_t L, int64_t B, const void *phi, const void *const *params, const uint8_t *keep, float p,
+                           float *tau, float *f, float *conf, void *saved, void *stream);
+int admmnet_train_head_bwd_f32(int32_t D, int32_t L, int64_t B, const float *g_tau, const float *g_f, const float *g_conf,
+                               const void *phi, const void *const *params, const uint8_t *keep, float p, const float *tau,
+                               const float *f, const float *conf, void *saved, void *g_phi, float *g_params, void *workspace,
+                               void *stream);
+
 /* The training losses of the reference's loss.py (csrc/loss.hip): one kernel per forward (plus a float64 sum over the batch
  * that also forms the outputs) and one elementwise kernel per backward.  B >= 1, D >= 1 (any signal length), 1 <= Lmax <= 64.
  * All tensors are dense and need only their natural alignment (4 bytes float, 8 bytes complex64 and int64).  Sums over the
