@@ -6,5 +6,6 @@ Importing this package never imports the CPU oracle.
 """
 from .options import Options  # noqa: F401
 from .modules import ADMMNet, PhiEstADMMNet, PeakSearchLayer, PhiLayer, HLayer, GLayer, ZLayer  # noqa: F401
+from . import optim  # noqa: F401
 
 __all__ = ["ADMMNet", "PhiEstADMMNet", "Options"]

@@ -22,6 +22,12 @@ class Cfg(ctypes.Structure):
                 ("has_head", c_int32), ("chunk", c_int32), ("reserved", c_int32 * 2)]
 
 
+class AdamWHyper(ctypes.Structure):
+    """struct admmnet_adamw_hyper (include/admmnet.h): one set of the update's constants, computed in Python double."""
+    _fields_ = [("decay", c_double), ("one_minus_beta1", c_double), ("beta2", c_double), ("one_minus_beta2", c_double),
+                ("step_size", c_double), ("bias_correction2_sqrt", c_double), ("eps", c_double)]
+
+
 class AdmmNetError(RuntimeError):
     pass
 
@@ -97,6 +103,11 @@ SYMBOLS = {
     "admmnet_loss_anm_bwd_f32": (c_int32, [c_int32, c_int32, c_int64] + [c_void_p] * 9 + [c_float] + [c_void_p] * 5),
     "admmnet_loss_phi_c64": (c_int32, [c_int32, c_int64, c_void_p, c_void_p, c_float, c_float, c_void_p, c_void_p, c_void_p]),
     "admmnet_loss_phi_bwd_c64": (c_int32, [c_int32, c_int64, c_void_p, c_void_p, c_void_p, c_float, c_float, c_void_p, c_void_p]),
+    "admmnet_optim_partials": (c_int64, [c_int32, POINTER(c_int64)]),
+    "admmnet_optim_gradnorm_f32": (c_int32, [c_int32, POINTER(c_void_p), POINTER(c_int64), c_float] + [c_void_p] * 5),
+    "admmnet_optim_scale_f32": (c_int32, [c_int32, POINTER(c_void_p), POINTER(c_int64), c_void_p, c_void_p]),
+    "admmnet_optim_adamw_f32": (c_int32, [c_int32] + [POINTER(c_void_p)] * 4 + [POINTER(c_int64), POINTER(c_int32), c_int32,
+                                          POINTER(AdamWHyper), c_void_p, c_void_p]),
     "admmnet_spectrum_workspace_bytes": (c_int64, [c_int32, c_int32, c_int32, c_int32]),
     "admmnet_spectrum_f64": (c_int32, [c_void_p, c_int64, c_int32, c_int32, c_void_p, c_int32, c_void_p,
                                        c_int32, c_void_p, c_void_p, c_int64, c_void_p]),

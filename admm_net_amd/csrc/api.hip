@@ -1079,6 +1079,67 @@ int admmnet_loss_phi_bwd_c64(int32_t D, int64_t B, const float *g_out, const voi
                                (float2 *)g_phi, (hipStream_t)stream);
 }
 
+// ---- AdamW and gradient-norm clipping over a tensor list (optim.hip) ---------------------------------------------------------
+// a pointer may be null only where its tensor has no element
+static int optim_args_ok(const char *what, int32_t count, const int64_t *numel, bool ptrs, const void *const *const *lists, int nlists) {
+    if (count < 0 || (count > 0 && (!numel || !ptrs))) {
+        set_error("%s: bad argument (count=%d, or a null pointer)", what, count);
+        return ADMMNET_E_ARG;
+    }
+    for (int l = 0; l < nlists && count > 0; ++l)
+        if (!lists[l]) {
+            set_error("%s: pointer list %d is null", what, l);
+            return ADMMNET_E_ARG;
+        }
+    if (optim_blocks(count, numel) < 0) {
+        set_error("%s: a negative element count, or more than 2^31 - 1 blocks of 1024 elements in the list", what);
+        return ADMMNET_E_ARG;
+    }
+    for (int i = 0; i < count; ++i)
+        for (int l = 0; l < nlists; ++l)
+            if (numel[i] > 0 && !lists[l][i]) {
+                set_error("%s: tensor %d of pointer list %d is null and has %lld elements", what, i, l, (long long)numel[i]);
+                return ADMMNET_E_ARG;
+            }
+    return ADMMNET_OK;
+}
+
+int64_t admmnet_optim_partials(int32_t count, const int64_t *numel) {
+    if (count < 0 || (count > 0 && !numel)) return -1;
+    return optim_blocks(count, numel);
+}
+
+int admmnet_optim_gradnorm_f32(int32_t count, const float *const *grads, const int64_t *numel, float max_norm, double *partials,
+                               double *sumsq, float *total_norm, float *coef, void *stream) {
+    const void *const *lists[] = {(const void *const *)grads};
+    if (int rc = optim_args_ok("optim_gradnorm", count, numel, partials && sumsq && total_norm && coef, lists, 1)) return rc;
+    if (count == 0) return ADMMNET_OK;
+    return launch_optim_gradnorm(count, grads, numel, max_norm, partials, sumsq, total_norm, coef, (hipStream_t)stream);
+}
+
+int admmnet_optim_scale_f32(int32_t count, float *const *grads, const int64_t *numel, const float *coef, void *stream) {
+    const void *const *lists[] = {(const void *const *)grads};
+    if (int rc = optim_args_ok("optim_scale", count, numel, coef != nullptr, lists, 1)) return rc;
+    if (count == 0) return ADMMNET_OK;
+    return launch_optim_scale(count, grads, numel, coef, (hipStream_t)stream);
+}
+
+int admmnet_optim_adamw_f32(int32_t count, float *const *params, const float *const *grads, float *const *exp_avg,
+                            float *const *exp_avg_sq, const int64_t *numel, const int32_t *hyper_index, int32_t nhyper,
+                            const admmnet_adamw_hyper *hyper, const float *coef_or_null, void *stream) {
+    const void *const *lists[] = {(const void *const *)params, (const void *const *)grads, (const void *const *)exp_avg,
+                                  (const void *const *)exp_avg_sq};
+    if (int rc = optim_args_ok("optim_adamw", count, numel, hyper_index && hyper && nhyper >= 1, lists, 4)) return rc;
+    for (int i = 0; i < count; ++i)
+        if (hyper_index[i] < 0 || hyper_index[i] >= nhyper) {
+            set_error("optim_adamw: hyper_index[%d] = %d is outside [0, %d)", i, hyper_index[i], nhyper);
+            return ADMMNET_E_ARG;
+        }
+    if (count == 0) return ADMMNET_OK;
+    return launch_optim_adamw(count, params, grads, exp_avg, exp_avg_sq, numel, hyper_index, hyper, coef_or_null,
+                              (hipStream_t)stream);
+}
+
 int admmnet_profile_enable(int32_t on) {
     ProfState &p = prof();
     std::lock_guard<std::mutex> lk(p.mu);

@@ -291,6 +291,15 @@ int launch_loss_phi(int D, int64_t B, const float2 *phi, const float2 *phi_true,
 int launch_loss_phi_bwd(int D, int64_t B, const float *g_out, const float2 *phi, const float2 *phi_true, float amplitude_weight,
                         float phase_weight, float2 *g_phi, hipStream_t st);
 
+// optim.hip (AdamW and gradient-norm clipping over a tensor list; host arrays of device pointers)
+int64_t optim_blocks(int count, const int64_t *numel);   // blocks of the list = doubles of `partials`; -1: bad count or too many
+int launch_optim_gradnorm(int count, const float *const *grads, const int64_t *numel, float max_norm, double *partials,
+                          double *sumsq, float *total_norm, float *coef, hipStream_t st);
+int launch_optim_scale(int count, float *const *grads, const int64_t *numel, const float *coef, hipStream_t st);
+int launch_optim_adamw(int count, float *const *params, const float *const *grads, float *const *exp_avg, float *const *exp_avg_sq,
+                       const int64_t *numel, const int32_t *hyper_index, const admmnet_adamw_hyper *hyper, const float *coef,
+                       hipStream_t st);
+
 // synth.hip
 int launch_synth(int64_t B, int Nb, int Nd, int L, unsigned long long seed, double snr_lo, double snr_hi, double snr_e,
                  double rho, int label_iters, float2 *y, float2 *b, float *sigma, float *tau, float *f, float2 *C,

@@ -10,7 +10,7 @@
 
 CLI:  python -m admm_net_amd.harness time-net  --layers 5 --runs 1000 --out time_net_5.txt [--checkpoint best_model.pth]
       python -m admm_net_amd.harness time-admm --runs 1000 --out time.txt
-      python -m admm_net_amd.harness train-step --layers 10 --batch 256 --steps 20 [--route fused|full] [--grid 16x16]   (one JSON line)
+      python -m admm_net_amd.harness train-step --layers 10 --batch 256 --steps 20 [--route fused|full|native] [--grid 16x16] [--optim hip]   (one JSON line)
       python -m admm_net_amd.harness loss-step --batch 256 --targets 3 --dim 100 --steps 200                              (one JSON line)
 """
 from __future__ import annotations
@@ -140,7 +140,8 @@ def load_checkpoint(path, model, optimizer=None, scheduler=None, map_location="c
     return ckpt
 
 
-def time_train_step(layers=10, batch=256, steps=20, warmup=3, seed=0, device="cuda:0", route="tensor", grid=(NB, ND), head=False):
+def time_train_step(layers=10, batch=256, steps=20, warmup=3, seed=0, device="cuda:0", route="tensor", grid=(NB, ND), head=False,
+                    optim="torch"):
     """Wall time of one optimisation step at the reference's own training configuration (trainPhi.py:16-38: 10 x 10 grid,
     num_layers = 10, batch_size = 256, AdamW lr 1e-3 / weight decay 1e-3, gradient clipping at 1.0, :179-190): forward in
     train mode (the differentiable route of admm_net_amd.training: HIP eigensolver + HIP contractions), a phi-alignment
@@ -149,6 +150,8 @@ def time_train_step(layers=10, batch=256, steps=20, warmup=3, seed=0, device="cu
     ``route``: ``model.train_route`` ("tensor" | "fused" | "full" | "native"); ``grid`` = (M, N) of another geometry, same recipe.
     ``head = True`` times ``ADMMNet`` (the model of train.py) instead: the loss is then that phi error plus the plain squared
     error of tau and f against the generator's labels.
+    ``optim``: "torch" (``torch.nn.utils.clip_grad_norm_`` and ``torch.optim.AdamW``) or "hip": ``admm_net_amd.optim.AdamW`` with
+    ``max_grad_norm=1.0``, the clipping inside the update (csrc/optim.hip).
     Returns a dict (seconds per step, signals per second, route, geometry)."""
     from . import ADMMNet, PhiEstADMMNet, synth
     dev = torch.device(device)
@@ -157,7 +160,13 @@ def time_train_step(layers=10, batch=256, steps=20, warmup=3, seed=0, device="cu
     model = (ADMMNet if head else PhiEstADMMNet)(num_layers=layers, M=M, N=N, L=3).to(dev)
     model.train_route = route
     model.train()
-    opt = torch.optim.AdamW(model.parameters(), lr=1e-3, weight_decay=1e-3)
+    if optim not in ("torch", "hip"):
+        raise ValueError(f"optim must be 'torch' or 'hip', got {optim!r}")
+    if optim == "hip":
+        from . import optim as hip_optim
+        opt = hip_optim.AdamW(model.parameters(), lr=1e-3, weight_decay=1e-3, max_grad_norm=1.0)
+    else:
+        opt = torch.optim.AdamW(model.parameters(), lr=1e-3, weight_decay=1e-3)
     y, b, sigma, extra = synth.make_batch_device(batch, M, N, seed=20260104 + seed, device=dev, labels=True)
     label = extra["phi"].to(torch.complex64)
     scale = label.abs().pow(2).mean()
@@ -171,7 +180,8 @@ def time_train_step(layers=10, batch=256, steps=20, warmup=3, seed=0, device="cu
             phi = model(y, b, sigma)
             loss = (phi - label).abs().pow(2).mean() / scale
         loss.backward()
-        torch.nn.utils.clip_grad_norm_(model.parameters(), 1.0)
+        if optim == "torch":
+            torch.nn.utils.clip_grad_norm_(model.parameters(), 1.0)
         opt.step()
         return loss
 
@@ -186,7 +196,7 @@ def time_train_step(layers=10, batch=256, steps=20, warmup=3, seed=0, device="cu
     dt = (time.perf_counter() - t0) / steps
     losses.append(float(last.item()))
     return {"config": f"{type(model).__name__} {M}x{N} K={layers}, batch {batch}, AdamW + clip 1.0 (trainPhi.py:16-38, 179-190)",
-            "route": route, "head": bool(head), "grid": [M, N], "layers": layers, "batch": batch,
+            "route": route, "optim": optim, "head": bool(head), "grid": [M, N], "layers": layers, "batch": batch,
             "seconds_per_step": round(dt, 6), "signals_per_second": round(batch / dt, 1), "steps": steps,
             "loss_first": round(losses[0], 6), "loss_last": round(losses[-1], 6)}
 
@@ -252,6 +262,8 @@ def main(argv=None):
     c.add_argument("--grid", default=f"{NB}x{ND}", help="MxN")
     c.add_argument("--head", action="store_true", help="time ADMMNet (phi + tau + f loss) instead of PhiEstADMMNet")
     c.add_argument("--warmup", type=int, default=3)
+    c.add_argument("--optim", choices=("torch", "hip"), default="torch",
+                   help="hip: clipping and AdamW on the kernels of admm_net_amd.optim instead of torch's")
     d = sub.add_parser("loss-step")
     d.add_argument("--batch", type=int, default=256)
     d.add_argument("--targets", type=int, default=3)
@@ -269,7 +281,8 @@ def main(argv=None):
             assert len(grid) == 2 and min(grid) >= 1
         except (ValueError, AssertionError):
             ap.error(f"--grid must be MxN, got {args.grid!r}")
-        print(json.dumps(time_train_step(args.layers, args.batch, args.steps, warmup=args.warmup, route=args.route, grid=grid, head=args.head)))
+        print(json.dumps(time_train_step(args.layers, args.batch, args.steps, warmup=args.warmup, route=args.route, grid=grid, head=args.head,
+                                         optim=args.optim)))
         return
     if args.cmd == "time-net":
         from . import PhiEstADMMNet

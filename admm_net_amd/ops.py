@@ -636,6 +636,96 @@ def loss_phi_bwd(g_out, phi, phi_true, amplitude_weight: float, phase_weight: fl
     return g_phi
 
 
+# ---- AdamW and gradient-norm clipping over a tensor list (csrc/optim.hip) --------------------------------------------------------
+def _optim_lists(what, *lists):
+    """(lib, device, count, numel array, one pointer array per list) of same-length lists of dense float32 device tensors of
+    pairwise equal shapes.  ``TypeError`` for what is no float32 tensor, ``ValueError`` for a sparse, non-contiguous or host
+    tensor and for tensors on different devices: there is no other path."""
+    count = len(lists[0])
+    if any(len(l) != count for l in lists):
+        raise ValueError(f"{what}: the tensor lists have different lengths {[len(l) for l in lists]}")
+    dev = None
+    for i in range(count):
+        for l in lists:
+            t = l[i]
+            if not isinstance(t, torch.Tensor):
+                raise TypeError(f"{what}: entry {i} is a {type(t).__name__}, not a tensor")
+            if t.is_sparse or t.layout != torch.strided:
+                raise ValueError(f"{what}: tensor {i} is sparse ({t.layout}); the kernels read dense tensors")
+            if t.dtype != torch.float32:
+                raise TypeError(f"{what}: tensor {i} is {t.dtype}; the kernels read float32")
+            if not t.is_cuda:
+                raise ValueError(f"{what}: tensor {i} is on {t.device}; the kernels read HIP device tensors (no CPU path)")
+            if not t.is_contiguous():
+                raise ValueError(f"{what}: tensor {i} of shape {tuple(t.shape)} and strides {t.stride()} is not contiguous")
+            if dev is None:
+                dev = t.device
+            elif t.device != dev:
+                raise ValueError(f"{what}: tensor {i} is on {t.device}, the list began on {dev}")
+            if t.shape != lists[0][i].shape:
+                raise ValueError(f"{what}: tensor {i} has shapes {tuple(lists[0][i].shape)} and {tuple(t.shape)} in two lists")
+    numel = (ctypes.c_int64 * count)(*[t.numel() for t in lists[0]])
+    tables = [(ctypes.c_void_p * count)(*[t.data_ptr() for t in l]) for l in lists]
+    return _lib.load(), dev, count, numel, tables
+
+
+def _optim_coef(what, coef, dev):
+    """``coef`` as the kernels read it: ONE float32 element on the list's device, refused otherwise like every other tensor."""
+    if not isinstance(coef, torch.Tensor) or coef.dtype != torch.float32:
+        raise TypeError(f"{what}: coef must be a float32 tensor, got {coef.dtype if isinstance(coef, torch.Tensor) else type(coef).__name__}")
+    if coef.numel() != 1 or coef.device != dev:
+        raise ValueError(f"{what}: coef must hold one element on {dev}, got {coef.numel()} on {coef.device} (no copy is made)")
+    return coef.detach().reshape(1)
+
+
+def optim_gradnorm(grads, max_norm: float):
+    """The 2-norm of all of ``grads`` (a non-empty list) and the clipping coefficient of ``clip_grad_norm_``: returns
+    (total_norm, 0-dim float32; coef [1] float32 = clamp(max_norm / (total_norm + 1e-6), max=1); sumsq [1] float64), all on the
+    device, nothing read back."""
+    lib, dev, count, numel, (g,) = _optim_lists("optim_gradnorm", list(grads))
+    if count == 0:
+        raise ValueError("optim_gradnorm: the list is empty")
+    need = lib.admmnet_optim_partials(count, numel)
+    if need < 0:
+        raise _lib.AdmmNetError("optim_gradnorm: the list has more than 2^31 - 1 blocks of 1024 elements")
+    with torch.cuda.device(dev):
+        part = torch.empty(max(need, 1) + 1, dtype=torch.float64, device=dev)     # the last entry: sumsq
+        out = torch.empty(2, dtype=torch.float32, device=dev)
+        _lib.check(lib.admmnet_optim_gradnorm_f32(count, g, numel, float(max_norm), _ptr(part), _ptr(part[-1:]), _ptr(out[0:1]),
+                                                  _ptr(out[1:2]), _stream(dev)), "admmnet_optim_gradnorm_f32")
+    return out[0], out[1:2], part[-1:]
+
+
+def optim_scale(grads, coef) -> None:
+    """g <- g coef in place for every tensor of ``grads``; ``coef`` a device float32 tensor of one element."""
+    lib, dev, count, numel, (g,) = _optim_lists("optim_scale", list(grads))
+    if count == 0:
+        return
+    coef = _optim_coef("optim_scale", coef, dev)
+    with torch.cuda.device(dev):
+        _lib.check(lib.admmnet_optim_scale_f32(count, g, numel, _ptr(coef), _stream(dev)), "admmnet_optim_scale_f32")
+
+
+def optim_adamw(params, grads, exp_avgs, exp_avg_sqs, hyper_index, hyper, coef=None) -> None:
+    """One AdamW update of every tensor of ``params`` in place (with its state ``exp_avgs``, ``exp_avg_sqs``), tensor i with the
+    constants ``hyper[hyper_index[i]]``: 7-tuples (1 - lr wd, 1 - beta1, beta2, 1 - beta2, lr / (1 - beta1^t), sqrt(1 - beta2^t),
+    eps) of Python floats.  ``coef``: a device float32 tensor of one element that multiplies every gradient as it is read (the
+    fused clipping; the gradients stay as they are), or None."""
+    lib, dev, count, numel, (p, g, m, v) = _optim_lists("optim_adamw", list(params), list(grads), list(exp_avgs),
+                                                        list(exp_avg_sqs))
+    if count == 0:
+        return
+    if len(hyper_index) != count or not hyper or not all(0 <= int(i) < len(hyper) for i in hyper_index):
+        raise ValueError(f"optim_adamw: {count} tensors need {count} indices into the {len(hyper)} hyper-parameter sets")
+    if coef is not None:
+        coef = _optim_coef("optim_adamw", coef, dev)
+    index = (ctypes.c_int32 * count)(*[int(i) for i in hyper_index])
+    table = (_lib.AdamWHyper * len(hyper))(*[_lib.AdamWHyper(*(float(x) for x in h)) for h in hyper])
+    with torch.cuda.device(dev):
+        _lib.check(lib.admmnet_optim_adamw_f32(count, p, g, m, v, numel, index, len(hyper), table, _ptr(coef), _stream(dev)),
+                   "admmnet_optim_adamw_f32")
+
+
 def glayer(model, k: int, phi: torch.Tensor, h: torch.Tensor, Z=None):
     """GLayer.forward (admm_net.py:237-354) of layer k of ``model`` plus the Z-layer residual norm.
 

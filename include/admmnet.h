@@ -463,6 +463,47 @@ int admmnet_loss_phi_c64(int32_t D, int64_t B, const void *phi, const void *phi_
 int admmnet_loss_phi_bwd_c64(int32_t D, int64_t B, const float *g_out, const void *phi, const void *phi_true,
                              float amplitude_weight, float phase_weight, void *g_phi, void *stream);
 
+/* AdamW and gradient-norm clipping over a LIST of float32 tensors (csrc/optim.hip): what a training loop writes as
+ * torch.nn.utils.clip_grad_norm_(params, max_norm) and torch.optim.AdamW(...).step().  `count` tensors, tensor i dense with
+ * numel[i] >= 0 elements; grads, params, exp_avg, exp_avg_sq are HOST arrays of `count` DEVICE pointers (as `params` of
+ * admmnet_train_head_f32), numel and hyper_index HOST arrays.  A pointer may be NULL only where numel[i] = 0.  Tensors need only
+ * their natural 4-byte alignment; 16-byte accesses are used where every pointer of a tensor is 16-byte aligned and numel[i] is a
+ * multiple of four.  The lists travel in the kernel arguments, a longer list in consecutive launches (256 tensors each for the
+ * norm and the scaling, 64 for the update); the work is cut into blocks of 1024 elements of ONE tensor, numbered in list order,
+ * so the order of every sum depends on the list alone.  No atomics: every run gives the same bits.  count = 0 succeeds and does
+ * nothing.  The calls are stream-ordered and never synchronise with the host.
+ *   admmnet_optim_partials      the float64 entries of `partials` for this list (its number of blocks); -1 for a negative
+ *                               count or numel, or more than 2^31 - 1 blocks.
+ *   admmnet_optim_gradnorm_f32  sumsq[0] = sum of g^2 over all tensors, squares and sums in float64;
+ *                               total_norm[0] = (float) sqrt(sumsq);
+ *                               coef[0] = clamp(max_norm / (total_norm + 1e-6), max = 1) in float32 as torch evaluates it:
+ *                               (1 / (total_norm + 1e-6f)) * max_norm, a NaN kept (an infinite norm gives 0).
+ *   admmnet_optim_scale_f32     g <- g coef[0] for every tensor (it multiplies by a coefficient of 1 too, as torch does).
+ *   admmnet_optim_adamw_f32     per element, torch.optim.adam._single_tensor_adam with decoupled weight decay, in float32:
+ *                                 p <- p decay;  m <- m + (g - m) one_minus_beta1;  v <- beta2 v + (one_minus_beta2 g) g;
+ *                                 p <- p - step_size m / (sqrt(v) / bias_correction2_sqrt + eps)
+ *                               with tensor i's constants hyper[hyper_index[i]] (each rounded to float32 once; nhyper >= 1 sets,
+ *                               one per distinct (group, step count) pair; a launch holds eight).  sqrt and / are correctly
+ *                               rounded.  With coef_or_null given, g coef[0] rounded to float32 takes the place of g (the
+ *                               gradients themselves stay as they are): the same bits as admmnet_optim_scale_f32 followed by
+ *                               the update without a coefficient. */
+typedef struct admmnet_adamw_hyper {
+    double decay;                  /* 1 - lr weight_decay  */
+    double one_minus_beta1;
+    double beta2;
+    double one_minus_beta2;
+    double step_size;              /* lr / (1 - beta1^t)   */
+    double bias_correction2_sqrt;  /* sqrt(1 - beta2^t)    */
+    double eps;
+} admmnet_adamw_hyper;
+int64_t admmnet_optim_partials(int32_t count, const int64_t *numel);
+int admmnet_optim_gradnorm_f32(int32_t count, const float *const *grads, const int64_t *numel, float max_norm, double *partials,
+                               double *sumsq, float *total_norm, float *coef, void *stream);
+int admmnet_optim_scale_f32(int32_t count, float *const *grads, const int64_t *numel, const float *coef, void *stream);
+int admmnet_optim_adamw_f32(int32_t count, float *const *params, const float *const *grads, float *const *exp_avg,
+                            float *const *exp_avg_sq, const int64_t *numel, const int32_t *hyper_index, int32_t nhyper,
+                            const admmnet_adamw_hyper *hyper, const float *coef_or_null, void *stream);
+
 /* Spectrum |phi^H kron(s(f), conj d(tau))|^2 on a (tau, f) grid:
  * peak_search_func / peak_search, utils/peakSearchUtils.py:9-60, evaluated in
  * float64 like the reference.
