@@ -60,7 +60,7 @@ def vdvh(V: torch.Tensor, d: torch.Tensor) -> torch.Tensor:
     V: [B, n, n] complex64 (columns = eigenvectors), d: [B, n] float32.  Returns [B, n, n] complex64."""
     _need_cuda(V, "V")
     lib = _lib.load()
-    V = V.to(torch.complex64).contiguous()
+    V = V.to(torch.complex64).resolve_conj().contiguous()       # a lazily conjugated view keeps its conj bit through .contiguous()
     d = d.to(device=V.device, dtype=torch.float32).contiguous()
     B, n, _ = V.shape
     if d.shape != (B, n):
@@ -77,8 +77,8 @@ def vhsv(V: torch.Tensor, S: torch.Tensor) -> torch.Tensor:
     V, S: [B, n, n] complex64.  Returns [B, n] float32."""
     _need_cuda(V, "V")
     lib = _lib.load()
-    V = V.to(torch.complex64).contiguous()
-    S = S.to(device=V.device, dtype=torch.complex64).contiguous()
+    V = V.to(torch.complex64).resolve_conj().contiguous()
+    S = S.to(device=V.device, dtype=torch.complex64).resolve_conj().contiguous()
     B, n, _ = V.shape
     if S.shape != V.shape:
         raise ValueError("S must have the shape of V")

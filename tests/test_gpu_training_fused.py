@@ -242,7 +242,8 @@ def _model16(K, B, seed=3):
 def test_fused_route_at_16x16_trains_and_matches_inference():
     """16 x 16 (n = 257), K = 3, B = 8: the train-mode phi of the fused route agrees with the eval-mode inference phi to 1e-4,
     all gradients are finite, six AdamW steps lower the loss.  (No gradient comparison between eigensolvers or routes here:
-    the eigenvalue-only gradient depends on the basis returned inside the clustered bulk.)"""
+    the eigenvalue-only gradient depends on the basis returned inside the clustered bulk.  The G layer's forward and backward at
+    this size are compared with float64 on a FROZEN basis in tests/test_gpu_glayer_grad.py.)"""
     m, (ty, tb, ts) = _model16(3, 8)
     m.train_route = "fused"
     target = ty / tb
