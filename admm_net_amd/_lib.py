@@ -92,6 +92,11 @@ SYMBOLS = {
     "admmnet_train_eigmap_bwd_f32": (c_int32, [c_int32, c_int64] + [c_void_p] * 11),
     "admmnet_train_stepsize_f32": (c_int32, [c_int64, c_int64, c_float] + [c_void_p] * 8),
     "admmnet_train_stepsize_bwd_f32": (c_int32, [c_int64, c_int64, c_float] + [c_void_p] * 11),
+    "admmnet_train_stepsize_pair_partials": (c_int64, [c_int64]),
+    "admmnet_train_rnsum_f64": (c_int32, [c_int64] + [c_void_p] * 3),
+    "admmnet_train_stepsize_pair_f32": (c_int32, [c_int64, c_float] + [c_void_p] * 9),
+    "admmnet_train_stepsize_bwd_pair_front_f32": (c_int32, [c_int64, c_float] + [c_void_p] * 13),
+    "admmnet_train_stepsize_bwd_pair_back_f32": (c_int32, [c_int64] + [c_void_p] * 5),
     "admmnet_train_hlayer_workspace": (c_int64, [c_int32, c_int64]),
     "admmnet_train_hlayer_f32": (c_int32, [c_int32, c_int64] + [c_void_p] * 14),
     "admmnet_train_hlayer_bwd_f32": (c_int32, [c_int32, c_int64] + [c_void_p] * 17),
@@ -108,6 +113,8 @@ SYMBOLS = {
     "admmnet_optim_scale_f32": (c_int32, [c_int32, POINTER(c_void_p), POINTER(c_int64), c_void_p, c_void_p]),
     "admmnet_optim_adamw_f32": (c_int32, [c_int32] + [POINTER(c_void_p)] * 4 + [POINTER(c_int64), POINTER(c_int32), c_int32,
                                           POINTER(AdamWHyper), c_void_p, c_void_p]),
+    "admmnet_optim_pack_f32": (c_int32, [c_int32, POINTER(c_void_p), POINTER(c_int64), c_void_p, c_void_p]),
+    "admmnet_optim_unpack_f32": (c_int32, [c_int32, POINTER(c_void_p), POINTER(c_int64), c_void_p, c_void_p]),
     "admmnet_spectrum_workspace_bytes": (c_int64, [c_int32, c_int32, c_int32, c_int32]),
     "admmnet_spectrum_f64": (c_int32, [c_void_p, c_int64, c_int32, c_int32, c_void_p, c_int32, c_void_p,
                                        c_int32, c_void_p, c_void_p, c_int64, c_void_p]),

@@ -1028,6 +1028,47 @@ int admmnet_train_stepsize_bwd_f32(int64_t B, int64_t sub_batch, float knorm, co
                                      (hipStream_t)stream);
 }
 
+// the step size from an outside (sum, count) pair; the doubles need their natural alignment
+static int train_pair_args_ok(const char *what, int64_t B, bool ptrs, const void *d0, const void *d1, const void *d2) {
+    const bool aligned = (((uintptr_t)d0 | (uintptr_t)d1 | (uintptr_t)d2) & 7u) == 0;
+    if (B < 1 || train_pair_rows(B) > 0x7fffffffLL || !ptrs || !aligned) {
+        set_error("%s: bad argument (B=%lld, a null pointer, or float64 data that is not 8-byte aligned)", what, (long long)B);
+        return ADMMNET_E_ARG;
+    }
+    return ADMMNET_OK;
+}
+
+int64_t admmnet_train_stepsize_pair_partials(int64_t B) { return B < 1 ? -1 : train_pair_partials(B); }
+
+int admmnet_train_rnsum_f64(int64_t B, const float *rn, double *pair, void *stream) {
+    if (int rc = train_pair_args_ok("train_rnsum", B, rn && pair, pair, nullptr, nullptr)) return rc;
+    return launch_train_rnsum(B, rn, pair, (hipStream_t)stream);
+}
+
+int admmnet_train_stepsize_pair_f32(int64_t B, float knorm, const float *rn, const double *pair, const float *rho, const float *W1,
+                                    const float *b1, const float *W2, const float *b2, float *step, void *stream) {
+    if (int rc = train_pair_args_ok("train_stepsize_pair", B, rn && pair && rho && W1 && b1 && W2 && b2 && step, pair, nullptr, nullptr))
+        return rc;
+    return launch_train_stepsize_pair(B, knorm, rn, pair, rho, W1, b1, W2, b2, step, (hipStream_t)stream);
+}
+
+int admmnet_train_stepsize_bwd_pair_front_f32(int64_t B, float knorm, const float *g_step, const float *rn, const double *pair,
+                                              const float *rho, const float *W1, const float *b1, const float *W2, const float *b2,
+                                              float *g_u, float *g_params, double *total, float *partials, void *stream) {
+    if (int rc = train_pair_args_ok("train_stepsize_bwd_pair_front", B,
+                                    g_step && rn && pair && rho && W1 && b1 && W2 && b2 && g_u && g_params && total && partials, pair,
+                                    total, partials))
+        return rc;
+    return launch_train_stepsize_bwd_pair_front(B, knorm, g_step, rn, pair, rho, W1, b1, W2, b2, g_u, g_params, total, partials,
+                                                (hipStream_t)stream);
+}
+
+int admmnet_train_stepsize_bwd_pair_back_f32(int64_t B, const float *g_u, const double *pair, const double *total, float *g_rn,
+                                             void *stream) {
+    if (int rc = train_pair_args_ok("train_stepsize_bwd_pair_back", B, g_u && pair && total && g_rn, pair, total, nullptr)) return rc;
+    return launch_train_stepsize_bwd_pair_back(B, g_u, pair, total, g_rn, (hipStream_t)stream);
+}
+
 // ---- the training losses (loss.hip) ------------------------------------------------------------------------------------------
 // one lane per target slot (Lmax <= 64); the slab grid must fit 31 bits
 static int loss_args_ok(const char *what, int32_t Lmax, int32_t D, int64_t B, bool ptrs) {
@@ -1138,6 +1179,20 @@ int admmnet_optim_adamw_f32(int32_t count, float *const *params, const float *co
     if (count == 0) return ADMMNET_OK;
     return launch_optim_adamw(count, params, grads, exp_avg, exp_avg_sq, numel, hyper_index, hyper, coef_or_null,
                               (hipStream_t)stream);
+}
+
+int admmnet_optim_pack_f32(int32_t count, const float *const *tensors, const int64_t *numel, float *flat, void *stream) {
+    const void *const *lists[] = {(const void *const *)tensors};
+    if (int rc = optim_args_ok("optim_pack", count, numel, flat != nullptr, lists, 1)) return rc;
+    if (count == 0) return ADMMNET_OK;
+    return launch_optim_bucket(count, const_cast<float *const *>(tensors), numel, flat, true, (hipStream_t)stream);
+}
+
+int admmnet_optim_unpack_f32(int32_t count, float *const *tensors, const int64_t *numel, const float *flat, void *stream) {
+    const void *const *lists[] = {(const void *const *)tensors};
+    if (int rc = optim_args_ok("optim_unpack", count, numel, flat != nullptr, lists, 1)) return rc;
+    if (count == 0) return ADMMNET_OK;
+    return launch_optim_bucket(count, tensors, numel, const_cast<float *>(flat), false, (hipStream_t)stream);
 }
 
 int admmnet_profile_enable(int32_t on) {

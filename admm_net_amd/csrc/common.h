@@ -257,6 +257,17 @@ int launch_train_stepsize(int64_t B, int64_t g, float knorm, const float *rn, co
 int launch_train_stepsize_bwd(int64_t B, int64_t g, float knorm, const float *gstep, const float *rn, const float *rho_raw,
                               const float *W1, const float *b1, const float *W2, const float *b2, float *grn, float *gpar,
                               float *part, hipStream_t st);
+// the step size from an outside (sum, count) pair: slabs of 256 signals, one thread each
+int64_t train_pair_rows(int64_t B);                   // slabs of the pair kernels
+int64_t train_pair_partials(int64_t B);               // floats of `part`: one double and 162 floats per slab
+int launch_train_rnsum(int64_t B, const float *rn, double *pair, hipStream_t st);
+int launch_train_stepsize_pair(int64_t B, float knorm, const float *rn, const double *pair, const float *rho_raw, const float *W1,
+                               const float *b1, const float *W2, const float *b2, float *step, hipStream_t st);
+int launch_train_stepsize_bwd_pair_front(int64_t B, float knorm, const float *gstep, const float *rn, const double *pair,
+                                         const float *rho_raw, const float *W1, const float *b1, const float *W2, const float *b2,
+                                         float *gu, float *gpar, double *total, float *part, hipStream_t st);
+int launch_train_stepsize_bwd_pair_back(int64_t B, const float *gu, const double *pair, const double *total, float *grn,
+                                        hipStream_t st);
 
 // train_hlayer.hip (training route "native": the H layer with its correction_net inside; parameters RAW as in train_small.hip)
 int64_t train_hlayer_workspace_floats(int D, int64_t B);   // float scratch of the backward: slab rows, then the batch-slab partials
@@ -299,6 +310,8 @@ int launch_optim_scale(int count, float *const *grads, const int64_t *numel, con
 int launch_optim_adamw(int count, float *const *params, const float *const *grads, float *const *exp_avg, float *const *exp_avg_sq,
                        const int64_t *numel, const int32_t *hyper_index, const admmnet_adamw_hyper *hyper, const float *coef,
                        hipStream_t st);
+// tensors -> flat (to_flat) or flat -> tensors, in list order
+int launch_optim_bucket(int count, float *const *tensors, const int64_t *numel, float *flat, bool to_flat, hipStream_t st);
 
 // synth.hip
 int launch_synth(int64_t B, int Nb, int Nd, int L, unsigned long long seed, double snr_lo, double snr_hi, double snr_e,

@@ -5,8 +5,8 @@
 //
 // Tensor list.  A launch carries its part of the list BY VALUE in the kernel arguments (as train_head.hip carries HeadPtrs): base
 // pointers, the running count of blocks and the size of each tensor's last block.  Nothing lives in a device-side table, so no
-// host buffer has a lifetime.  The host cuts a longer list into consecutive launches of OP_LIST_T (norm, scale) or OP_ADAM_T
-// (update) list positions.
+// host buffer has a lifetime.  The host cuts a longer list into consecutive launches of OP_LIST_T (norm, scale), OP_ADAM_T
+// (update) or OP_BUCKET_T (pack, unpack: a tensor takes two of the OP_LIST_T pointers) list positions.
 //
 // Work.  A block is OP_BLOCK consecutive elements of ONE tensor, one workgroup of OP_THREADS threads, thread t owning the elements
 // 4 t .. 4 t + 3 of the block.  A tensor of n elements has ceil(n / OP_BLOCK) blocks (none for n = 0: such a tensor only takes a
@@ -172,6 +172,22 @@ __global__ __launch_bounds__(OP_THREADS) void op_scale_kernel(OpListArgs a) {
     op_store4(g, e, s, x);
 }
 
+// ---- the bucket --------------------------------------------------------------------------------------------------------------
+// pack / unpack: the list's tensors, in list order, to and from ONE contiguous buffer (the bucket of a gradient all-reduce or a
+// parameter broadcast).  A launch carries OP_BUCKET_T tensors in the same by-value list: g[i] the tensor, g[OP_BUCKET_T + i] its
+// place in the flat buffer; the vector flag asks both to be 16-byte aligned.
+constexpr int OP_BUCKET_T = OP_LIST_T / 2;
+
+template <bool TO_FLAT>
+__global__ __launch_bounds__(OP_THREADS) void op_bucket_kernel(OpListArgs a) {
+    const OpSpan s = op_locate(a.end, a.tail, a.count, blockIdx.x);
+    const int e = 4 * (int)threadIdx.x;
+    float *t = a.g[s.i] + s.off, *f = a.g[OP_BUCKET_T + s.i] + s.off;
+    float x[4];
+    op_load4(TO_FLAT ? t : f, e, s, x);
+    op_store4(TO_FLAT ? f : t, e, s, x);
+}
+
 // ---- the update --------------------------------------------------------------------------------------------------------------
 // torch.optim.adam._single_tensor_adam (decoupled weight decay, not capturable), every operation rounded to float32 on its own
 // except the three multiply-adds marked fma:
@@ -263,6 +279,31 @@ int launch_optim_gradnorm(int count, const float *const *grads, const int64_t *n
 
 int launch_optim_scale(int count, float *const *grads, const int64_t *numel, const float *coef, hipStream_t st) {
     return op_list_pass(count, grads, numel, nullptr, coef, st);
+}
+
+int launch_optim_bucket(int count, float *const *tensors, const int64_t *numel, float *flat, bool to_flat, hipStream_t st) {
+    int64_t off = 0;
+    for (int first = 0; first < count; first += OP_BUCKET_T) {
+        OpListArgs a = {};
+        a.count = count - first < OP_BUCKET_T ? count - first : OP_BUCKET_T;
+        uint32_t blocks = 0;
+        for (int i = 0; i < a.count; ++i) {
+            const int64_t n = numel[first + i];
+            a.g[i] = tensors[first + i];
+            a.g[OP_BUCKET_T + i] = flat + off;
+            blocks += (uint32_t)op_blocks(n);
+            a.end[i] = blocks;
+            a.tail[i] = op_tail(n, op_aligned(a.g[i]) && op_aligned(flat + off));
+            off += n;
+        }
+        if (!blocks) continue;
+        if (to_flat) {
+            OP_LAUNCH(op_bucket_kernel<true>, blocks, a);
+        } else {
+            OP_LAUNCH(op_bucket_kernel<false>, blocks, a);
+        }
+    }
+    return ADMMNET_OK;
 }
 
 // a launch ends after OP_ADAM_T list positions or before the tensor that would need a ninth hyper-parameter set

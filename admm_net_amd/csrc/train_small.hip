@@ -14,7 +14,8 @@
 // Launch shapes.  D <= 256 is at most four elements per lane of one wave, so phi / hinput / hproject / eigmap give every signal
 // ONE WAVE and a workgroup a slab of four consecutive signals: the per-signal reductions (max, sum, dot products) are xor-shuffle
 // butterflies and need neither LDS nor a barrier.  stepsize couples the signals of a group through their mean: one 256-thread
-// workgroup per group (one for the whole call without sub-batches).
+// workgroup per group (one for the whole call without sub-batches).  The `pair` forms take the mean from outside (the sum over
+// the ranks of a sharded batch): slabs of 256 signals, one thread each.
 // Sums over the batch (the parameter gradients) run in a fixed order without atomics: per lane serially, across the wave by
 // the butterfly, across the slab's four waves serially from LDS into one row of `partials` per workgroup; ts_colsum_kernel (one
 // workgroup) then adds the rows in float64, as tl_negsum_kernel / rn_sum_kernel do.  Two runs give the same bits.
@@ -325,8 +326,8 @@ __device__ __forceinline__ float ts_step_pre(const float *__restrict__ W1, const
     return fmaf(W1[3 * j + 2], u, fmaf(W1[3 * j + 1], f1, fmaf(W1[3 * j], f0, b1[j])));
 }
 
-// mean of the group's rn: float64, thread t adds rn[t], rn[t + 256], ..., a tree halves the 256 slots
-__device__ __forceinline__ float ts_group_mean(const float *__restrict__ rn, int64_t r, double *sh) {
+// sum of the group's rn: float64, thread t adds rn[t], rn[t + 256], ..., a tree halves the 256 slots
+__device__ __forceinline__ double ts_group_sum(const float *__restrict__ rn, int64_t r, double *sh) {
     double a = 0.0;
     for (int64_t i = threadIdx.x; i < r; i += TS_THREADS) a += (double)rn[i];
     sh[threadIdx.x] = a;
@@ -335,7 +336,28 @@ __device__ __forceinline__ float ts_group_mean(const float *__restrict__ rn, int
         if ((int)threadIdx.x < o) sh[threadIdx.x] += sh[threadIdx.x + o];
         __syncthreads();
     }
-    return (float)(sh[0] / (double)r);
+    return sh[0];
+}
+__device__ __forceinline__ float ts_group_mean(const float *__restrict__ rn, int64_t r, double *sh) {
+    return (float)(ts_group_sum(rn, r, sh) / (double)r);
+}
+
+// the output layer's pre-activation o = W2 relu(W1 [f0, f1, u] + b1) + b2
+__device__ __forceinline__ float ts_step_o(const float *__restrict__ W1, const float *__restrict__ b1, const float *__restrict__ W2,
+                                           const float *__restrict__ b2, float f0, float f1, float u) {
+    float o = b2[0];
+#pragma unroll
+    for (int j = 0; j < 32; ++j) o = fmaf(W2[j], fmaxf(ts_step_pre(W1, b1, j, f0, f1, u), 0.f), o);
+    return o;
+}
+// g_u = sum_j dy W2_j [pre_j > 0] W1[j][2]
+__device__ __forceinline__ float ts_step_gu(const float *__restrict__ W1, const float *__restrict__ b1, const float *__restrict__ W2,
+                                            float f0, float f1, float u, float dy) {
+    float gu = 0.f;
+#pragma unroll
+    for (int j = 0; j < 32; ++j)
+        if (ts_step_pre(W1, b1, j, f0, f1, u) > 0.f) gu = fmaf(dy * W2[j], W1[3 * j + 2], gu);
+    return gu;
 }
 
 __global__ __launch_bounds__(TS_THREADS) void ts_stepsize_kernel(int64_t B, int64_t g, float knorm, const float *__restrict__ rng,
@@ -347,10 +369,7 @@ __global__ __launch_bounds__(TS_THREADS) void ts_stepsize_kernel(int64_t B, int6
     const float *rn = rng + s0;
     const float den = ts_group_mean(rn, r, shd) + kEpsRef, rho = ts_softplus(rho_raw[0]);
     for (int64_t i = threadIdx.x; i < r; i += TS_THREADS) {
-        const float u = rn[i] / den;
-        float o = b2[0];
-#pragma unroll
-        for (int j = 0; j < 32; ++j) o = fmaf(W2[j], fmaxf(ts_step_pre(W1, b1, j, knorm, rho, u), 0.f), o);
+        const float o = ts_step_o(W1, b1, W2, b2, knorm, rho, rn[i] / den);
         stepg[s0 + i] = rho * (0.5f + 1.5f * ts_sigmoid(o));
     }
 }
@@ -390,14 +409,9 @@ __global__ __launch_bounds__(TS_THREADS) void ts_stepsize_bwd_kernel(int64_t B, 
     float a_rho = 0.f, a_b2 = 0.f, a_gm = 0.f;
     for (int64_t i = threadIdx.x; i < r; i += TS_THREADS) {
         const float x = rn[i], u = x / den, gs = gstep[i];
-        float o = b2[0];
-#pragma unroll
-        for (int j = 0; j < 32; ++j) o = fmaf(W2[j], fmaxf(ts_step_pre(W1, b1, j, knorm, rho, u), 0.f), o);
+        const float o = ts_step_o(W1, b1, W2, b2, knorm, rho, u);
         const float sg = ts_sigmoid(o), dy = gs * rho * 1.5f * ts_dsigmoid(o);
-        float gu = 0.f;
-#pragma unroll
-        for (int j = 0; j < 32; ++j)
-            if (ts_step_pre(W1, b1, j, knorm, rho, u) > 0.f) gu = fmaf(dy * W2[j], W1[3 * j + 2], gu);
+        const float gu = ts_step_gu(W1, b1, W2, knorm, rho, u, dy);
         a_rho = fmaf(gs, 0.5f + 1.5f * sg, a_rho);
         a_b2 += dy;
         a_gm += __fmul_rn(gu, x);
@@ -442,6 +456,132 @@ __global__ __launch_bounds__(TS_THREADS) void ts_stepsize_bwd_kernel(int64_t B, 
         const float gu = grn[i];
         grn[i] = (__fsub_rn(__fmul_rn(gu, mean), gmean) + gu * kEpsRef) / (den * den);
     }
+}
+
+// ---- step size from an OUTSIDE mean ------------------------------------------------------------------------------------------
+// The batch-sharded training (admm_net_amd/sharded.py) takes the mean over the signals of all ranks: `pair` = (sum of rn, number
+// of signals) of the whole batch in float64, all-reduced between ts_rnsum_kernel and the kernels below.  With the mean given no
+// reduction is left in the forward: a workgroup takes a slab of TS_THREADS consecutive signals, one per thread.  The backward is
+// two kernels around the second all-reduce: `front` leaves g_u_b and this call's share of sum_b g_u_b rn_b, `back` finishes g_rn
+// from the sum over all ranks.
+__device__ __forceinline__ float ts_pair_mean(const double *__restrict__ pair) { return (float)(pair[0] / pair[1]); }
+
+__global__ __launch_bounds__(TS_THREADS) void ts_rnsum_kernel(int64_t B, const float *__restrict__ rn, double *__restrict__ pair) {
+    __shared__ double shd[TS_THREADS];
+    const double s = ts_group_sum(rn, B, shd);
+    if (threadIdx.x == 0) pair[0] = s, pair[1] = (double)B;
+}
+
+__global__ __launch_bounds__(TS_THREADS) void ts_stepsize_pair_kernel(int64_t B, float knorm, const float *__restrict__ rn,
+                                                                      const double *__restrict__ pair, const float *__restrict__ rho_raw,
+                                                                      const float *__restrict__ W1, const float *__restrict__ b1,
+                                                                      const float *__restrict__ W2, const float *__restrict__ b2,
+                                                                      float *__restrict__ step) {
+    const int64_t i = (int64_t)blockIdx.x * TS_THREADS + threadIdx.x;
+    if (i >= B) return;
+    const float den = ts_pair_mean(pair) + kEpsRef, rho = ts_softplus(rho_raw[0]);
+    const float o = ts_step_o(W1, b1, W2, b2, knorm, rho, rn[i] / den);
+    step[i] = rho * (0.5f + 1.5f * ts_sigmoid(o));
+}
+
+// ts_block_sum in float64
+__device__ __forceinline__ double ts_block_sum_f64(double x, double *sh) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o, 64);
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = x;
+    __syncthreads();
+    double s = 0.0;
+    for (int w = 0; w < TS_SLAB; ++w) s += sh[w];
+    return s;
+}
+
+// ts_stepsize_bwd_kernel's passes 1 and 2 on one slab, dy_b and u_b of the slab in LDS: g_u_b to gu, one row of TS_STEP_PAR
+// partials and one double, sum_b g_u_b rn_b with products and sums in float64, per slab.
+__global__ __launch_bounds__(TS_THREADS) void ts_stepsize_bwd_pair_front_kernel(
+    int64_t B, float knorm, const float *__restrict__ gstep, const float *__restrict__ rn, const double *__restrict__ pair,
+    const float *__restrict__ rho_raw, const float *__restrict__ W1, const float *__restrict__ b1, const float *__restrict__ W2,
+    const float *__restrict__ b2, float *__restrict__ gu_out, double *__restrict__ part_gm, float *__restrict__ part) {
+    __shared__ double shd[TS_SLAB];
+    __shared__ float sh[TS_SLAB], s_dy[TS_THREADS], s_u[TS_THREADS];
+    const int64_t s0 = (int64_t)blockIdx.x * TS_THREADS;
+    const int r = B - s0 < TS_THREADS ? (int)(B - s0) : TS_THREADS, t = threadIdx.x;
+    const float den = ts_pair_mean(pair) + kEpsRef, raw = rho_raw[0], rho = ts_softplus(raw);
+    float a_rho = 0.f, dy = 0.f, u = 0.f;
+    double a_gm = 0.0;
+    if (t < r) {
+        const float x = rn[s0 + t], gs = gstep[s0 + t];
+        u = x / den;
+        const float o = ts_step_o(W1, b1, W2, b2, knorm, rho, u);
+        dy = gs * rho * 1.5f * ts_dsigmoid(o);
+        const float gu = ts_step_gu(W1, b1, W2, knorm, rho, u, dy);
+        a_rho = gs * (0.5f + 1.5f * ts_sigmoid(o));
+        a_gm = (double)gu * (double)x;
+        gu_out[s0 + t] = gu;
+    }
+    s_dy[t] = dy;
+    s_u[t] = u;
+    a_rho = ts_block_sum(a_rho, sh);            // (its barriers also order the writes of s_dy, s_u before pass 2)
+    const float a_b2 = ts_block_sum(dy, sh);
+    a_gm = ts_block_sum_f64(a_gm, shd);
+    float *row = part + (int64_t)blockIdx.x * TS_STEP_PAR;
+    {
+        const int j = t >> 3, q = t & 7;
+        const float w2 = W2[j];
+        float s1 = 0.f, s2 = 0.f, s3 = 0.f;
+        for (int i = q; i < r; i += 8) {
+            const float pre = ts_step_pre(W1, b1, j, knorm, rho, s_u[i]);
+            const float dh = pre > 0.f ? s_dy[i] * w2 : 0.f;
+            s1 += dh;
+            s2 = fmaf(s_dy[i], fmaxf(pre, 0.f), s2);
+            s3 = fmaf(dh, s_u[i], s3);
+        }
+#pragma unroll
+        for (int o = 4; o > 0; o >>= 1) {
+            s1 += __shfl_xor(s1, o, 64);
+            s2 += __shfl_xor(s2, o, 64);
+            s3 += __shfl_xor(s3, o, 64);
+        }
+        if (q == 0) {
+            row[1 + 3 * j] = knorm * s1;
+            row[2 + 3 * j] = rho * s1;
+            row[3 + 3 * j] = s3;
+            row[97 + j] = s1;
+            row[129 + j] = s2;
+        }
+    }
+    if (t == 0) {
+        row[0] = a_rho * ts_dsoftplus(raw);
+        row[161] = a_b2;
+        part_gm[blockIdx.x] = a_gm;
+    }
+}
+
+// the slabs' rows added in ascending order in float64, one thread per column; thread TS_STEP_PAR adds the slabs' doubles
+__global__ __launch_bounds__(TS_THREADS) void ts_pair_finish_kernel(int64_t rows, const double *__restrict__ part_gm,
+                                                                    const float *__restrict__ part, float *__restrict__ gpar,
+                                                                    double *__restrict__ total) {
+    const int c = threadIdx.x;
+    double a = 0.0;
+    if (c < TS_STEP_PAR) {
+        for (int64_t r = 0; r < rows; ++r) a += (double)part[r * TS_STEP_PAR + c];
+        gpar[c] = (float)a;
+    } else if (c == TS_STEP_PAR) {
+        for (int64_t r = 0; r < rows; ++r) a += part_gm[r];
+        total[0] = a;
+    }
+}
+
+// g_rn_b = ((g_u_b mean - total / count) + g_u_b eps) / den^2.  The product and the difference in float64: a float product is exact
+// there, so with a pair of ONE signal (mean = rn, total = g_u rn) the difference is an exact zero and g_u eps / den^2 remains.
+// gu and grn may be the same buffer.
+__global__ __launch_bounds__(TS_THREADS) void ts_stepsize_bwd_pair_back_kernel(int64_t B, const float *gu, const double *__restrict__ pair,
+                                                                               const double *__restrict__ total, float *grn) {
+    const int64_t i = (int64_t)blockIdx.x * TS_THREADS + threadIdx.x;
+    if (i >= B) return;
+    const float mean = ts_pair_mean(pair), den = mean + kEpsRef, g = gu[i];
+    const float diff = (float)((double)g * (double)mean - total[0] / pair[1]);
+    grn[i] = (diff + g * kEpsRef) / (den * den);
 }
 
 // ---- launchers ---------------------------------------------------------------------------------------------------------------
@@ -514,6 +654,38 @@ int launch_train_stepsize_bwd(int64_t B, int64_t g, float knorm, const float *gs
     TS_LAUNCH(ts_stepsize_bwd_kernel, groups, B, g, knorm, gstep, rn, rho_raw, W1, b1, W2, b2, grn, part + groups * TS_STEP_PAR,
               part);
     return ts_colsum(TS_STEP_PAR, groups, part, gpar, st);
+}
+
+int64_t train_pair_rows(int64_t B) { return (B + TS_THREADS - 1) / TS_THREADS; }
+int64_t train_pair_partials(int64_t B) { return train_pair_rows(B) * (2 + TS_STEP_PAR); }
+
+int launch_train_rnsum(int64_t B, const float *rn, double *pair, hipStream_t st) {
+    TS_LAUNCH(ts_rnsum_kernel, 1, B, rn, pair);
+    return ADMMNET_OK;
+}
+
+int launch_train_stepsize_pair(int64_t B, float knorm, const float *rn, const double *pair, const float *rho_raw, const float *W1,
+                               const float *b1, const float *W2, const float *b2, float *step, hipStream_t st) {
+    TS_LAUNCH(ts_stepsize_pair_kernel, train_pair_rows(B), B, knorm, rn, pair, rho_raw, W1, b1, W2, b2, step);
+    return ADMMNET_OK;
+}
+
+// part: [slabs] doubles, then [slabs][TS_STEP_PAR] floats
+int launch_train_stepsize_bwd_pair_front(int64_t B, float knorm, const float *gstep, const float *rn, const double *pair,
+                                         const float *rho_raw, const float *W1, const float *b1, const float *W2, const float *b2,
+                                         float *gu, float *gpar, double *total, float *part, hipStream_t st) {
+    const int64_t rows = train_pair_rows(B);
+    double *part_gm = reinterpret_cast<double *>(part);
+    float *rowsf = part + 2 * rows;
+    TS_LAUNCH(ts_stepsize_bwd_pair_front_kernel, rows, B, knorm, gstep, rn, pair, rho_raw, W1, b1, W2, b2, gu, part_gm, rowsf);
+    TS_LAUNCH(ts_pair_finish_kernel, 1, rows, part_gm, rowsf, gpar, total);
+    return ADMMNET_OK;
+}
+
+int launch_train_stepsize_bwd_pair_back(int64_t B, const float *gu, const double *pair, const double *total, float *grn,
+                                        hipStream_t st) {
+    TS_LAUNCH(ts_stepsize_bwd_pair_back_kernel, train_pair_rows(B), B, gu, pair, total, grn);
+    return ADMMNET_OK;
 }
 
 }  // namespace admmnet

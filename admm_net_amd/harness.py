@@ -11,6 +11,7 @@
 CLI:  python -m admm_net_amd.harness time-net  --layers 5 --runs 1000 --out time_net_5.txt [--checkpoint best_model.pth]
       python -m admm_net_amd.harness time-admm --runs 1000 --out time.txt
       python -m admm_net_amd.harness train-step --layers 10 --batch 256 --steps 20 [--route fused|full|native] [--grid 16x16] [--optim hip]   (one JSON line)
+      python -m torch.distributed.run --nproc-per-node N -m admm_net_amd.harness train-step ...   (the step through sharded.ShardedTraining; --batch per rank; rank 0's line gains n_ranks, global_batch)
       python -m admm_net_amd.harness loss-step --batch 256 --targets 3 --dim 100 --steps 200                              (one JSON line)
 """
 from __future__ import annotations
@@ -152,8 +153,22 @@ def time_train_step(layers=10, batch=256, steps=20, warmup=3, seed=0, device="cu
     error of tau and f against the generator's labels.
     ``optim``: "torch" (``torch.nn.utils.clip_grad_norm_`` and ``torch.optim.AdamW``) or "hip": ``admm_net_amd.optim.AdamW`` with
     ``max_grad_norm=1.0``, the clipping inside the update (csrc/optim.hip).
+    Under ``torch.distributed.run`` (WORLD_SIZE > 1; backend ADMMNET_DIST_BACKEND, default nccl = RCCL) every rank takes a batch
+    of ``batch`` signals of its own and the step runs through ``sharded.ShardedTraining``: the mean loss times ``st.weight``, one
+    gradient all-reduce.  The dict then holds ``n_ranks`` and ``global_batch``; ``signals_per_second`` counts the global batch.
     Returns a dict (seconds per step, signals per second, route, geometry)."""
-    from . import ADMMNet, PhiEstADMMNet, synth
+    import os
+    import torch.distributed as dist
+    from . import ADMMNet, PhiEstADMMNet, sharded, synth
+    world, rank = int(os.environ.get("WORLD_SIZE", "1")), int(os.environ.get("RANK", "0"))
+    if world > 1:
+        local = int(os.environ.get("LOCAL_RANK", "0")) % torch.cuda.device_count()     # (rehearsals put several ranks on one GPU)
+        torch.cuda.set_device(local)
+        device = f"cuda:{local}"
+        if not dist.is_initialized():
+            backend = os.environ.get("ADMMNET_DIST_BACKEND", "nccl")
+            kw = {"device_id": torch.device(device)} if backend == "nccl" else {}
+            dist.init_process_group(backend, rank=rank, world_size=world, **kw)
     dev = torch.device(device)
     torch.manual_seed(seed)
     M, N = grid
@@ -167,19 +182,26 @@ def time_train_step(layers=10, batch=256, steps=20, warmup=3, seed=0, device="cu
         opt = hip_optim.AdamW(model.parameters(), lr=1e-3, weight_decay=1e-3, max_grad_norm=1.0)
     else:
         opt = torch.optim.AdamW(model.parameters(), lr=1e-3, weight_decay=1e-3)
-    y, b, sigma, extra = synth.make_batch_device(batch, M, N, seed=20260104 + seed, device=dev, labels=True)
+    y, b, sigma, extra = synth.make_batch_device(batch, M, N, seed=20260104 + seed + 7919 * rank, device=dev, labels=True)
     label = extra["phi"].to(torch.complex64)
     scale = label.abs().pow(2).mean()
+    st = sharded.ShardedTraining(model) if world > 1 else None
+    if st is not None:                                      # one normalisation for the whole batch
+        dist.all_reduce(scale)
+        scale = scale / world
 
     def step():
         opt.zero_grad(set_to_none=True)
+        out = model(y, b, sigma) if st is None else st(y, b, sigma)
         if head:
-            tau, f, _, phi = model(y, b, sigma)
+            tau, f, _, phi = out
             loss = (phi - label).abs().pow(2).mean() / scale + (tau - extra["tau"]).pow(2).mean() + (f - extra["f"]).pow(2).mean()
         else:
-            phi = model(y, b, sigma)
-            loss = (phi - label).abs().pow(2).mean() / scale
-        loss.backward()
+            loss = (out - label).abs().pow(2).mean() / scale
+        if st is None:
+            loss.backward()
+        else:
+            st.backward(loss * st.weight)
         if optim == "torch":
             torch.nn.utils.clip_grad_norm_(model.parameters(), 1.0)
         opt.step()
@@ -195,10 +217,13 @@ def time_train_step(layers=10, batch=256, steps=20, warmup=3, seed=0, device="cu
     torch.cuda.synchronize(dev)
     dt = (time.perf_counter() - t0) / steps
     losses.append(float(last.item()))
-    return {"config": f"{type(model).__name__} {M}x{N} K={layers}, batch {batch}, AdamW + clip 1.0 (trainPhi.py:16-38, 179-190)",
-            "route": route, "optim": optim, "head": bool(head), "grid": [M, N], "layers": layers, "batch": batch,
-            "seconds_per_step": round(dt, 6), "signals_per_second": round(batch / dt, 1), "steps": steps,
-            "loss_first": round(losses[0], 6), "loss_last": round(losses[-1], 6)}
+    out = {"config": f"{type(model).__name__} {M}x{N} K={layers}, batch {batch}, AdamW + clip 1.0 (trainPhi.py:16-38, 179-190)",
+           "route": route, "optim": optim, "head": bool(head), "grid": [M, N], "layers": layers, "batch": batch,
+           "seconds_per_step": round(dt, 6), "signals_per_second": round(batch * world / dt, 1), "steps": steps,
+           "loss_first": round(losses[0], 6), "loss_last": round(losses[-1], 6)}
+    if st is not None:                                      # (the losses are this rank's mean, not the whole batch's)
+        out.update(n_ranks=world, global_batch=st.global_batch)
+    return out
 
 
 def time_loss_step(batch=256, targets=3, dim=100, steps=200, warmup=10, seed=0, device="cuda:0"):
@@ -281,8 +306,13 @@ def main(argv=None):
             assert len(grid) == 2 and min(grid) >= 1
         except (ValueError, AssertionError):
             ap.error(f"--grid must be MxN, got {args.grid!r}")
-        print(json.dumps(time_train_step(args.layers, args.batch, args.steps, warmup=args.warmup, route=args.route, grid=grid, head=args.head,
-                                         optim=args.optim)))
+        line = time_train_step(args.layers, args.batch, args.steps, warmup=args.warmup, route=args.route, grid=grid, head=args.head,
+                               optim=args.optim)
+        if line.get("n_ranks", 1) == 1 or torch.distributed.get_rank() == 0:      # one JSON line, rank 0's
+            print(json.dumps(line))
+        if torch.distributed.is_available() and torch.distributed.is_initialized():
+            torch.distributed.barrier()
+            torch.distributed.destroy_process_group()
         return
     if args.cmd == "time-net":
         from . import PhiEstADMMNet

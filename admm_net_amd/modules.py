@@ -357,9 +357,10 @@ class _FusedBase(nn.Module):
                     rows[:, :, 2].contiguous().to(out), counts.to(out), phi.to(out))
 
     # ---- training ----------------------------------------------------------
-    def forward_autograd(self, y, b, sigma):
+    def forward_autograd(self, y, b, sigma, reducer=None):
         """Differentiable forward (what ``forward`` does in train mode); usable in eval mode too, e.g. to
-        take gradients without the attention dropout.  The parameters must live on the GPU."""
+        take gradients without the attention dropout.  The parameters must live on the GPU.  ``reducer``: the all-reduce of a
+        batch-sharded step (``sharded.ShardedTraining``, ``training.unrolled_forward``); None: the call is the whole batch."""
         from . import training
         _lib.load()                                   # fail loudly without the HIP library
         dev = self._compute_device(y)
@@ -369,7 +370,7 @@ class _FusedBase(nn.Module):
                                     "(move the model with .to(device) as train.py / trainPhi.py do)")
         out = training.unrolled_forward(self, y.to(dev), b.to(dev), sigma.to(dev), sub_batch=self.sub_batch,
                                         fused=self.train_route != "tensor", small=self.train_route in ("full", "native"),
-                                        native=self.train_route == "native")
+                                        native=self.train_route == "native", reducer=reducer)
         if isinstance(out, tuple):
             return tuple(o.to(y.device) for o in out)
         return out.to(y.device)

@@ -547,6 +547,75 @@ def train_stepsize_bwd(g_step, rn, rho, W1, b1, W2, b2, knorm: float, sub_batch=
     return g_rn, out[0], out[1:97].reshape(32, 3), out[97:129], out[129:161].reshape(1, 32), out[161:162]
 
 
+# ---- the step size from a mean that comes from outside the call (the sharded training of admm_net_amd/sharded.py) ---------------
+# ``pair``: device float64 [2] = (sum of rn, number of signals) of the WHOLE batch; the kernels form the mean themselves.
+def _f64(t, dev, numel, name):
+    """A dense float64 device tensor of ``numel`` elements, as the kernels read it: no conversion is made."""
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.float64 or t.device != dev or t.numel() != numel:
+        raise ValueError(f"{name} must be a float64 tensor of {numel} element(s) on {dev}")
+    return t.detach().contiguous().reshape(numel)
+
+
+def train_rnsum(rn) -> torch.Tensor:
+    """This call's share of the pair: float64 [2] = (sum of rn in a fixed order, B)."""
+    _need_cuda(rn, "rn")
+    lib, dev, B = _lib.load(), rn.device, rn.shape[0]
+    with torch.cuda.device(dev):
+        rn = _f32(rn, dev, (B,), "rn")
+        pair = torch.empty(2, dtype=torch.float64, device=dev)
+        _lib.check(lib.admmnet_train_rnsum_f64(B, _ptr(rn), _ptr(pair), _stream(dev)), "admmnet_train_rnsum_f64")
+    return pair
+
+
+def train_stepsize_pair(rn, pair, rho, W1, b1, W2, b2, knorm: float) -> torch.Tensor:
+    """``train_stepsize`` with mean = float32(pair[0] / pair[1]) instead of the mean over the call."""
+    _need_cuda(rn, "rn")
+    lib, dev, B = _lib.load(), rn.device, rn.shape[0]
+    with torch.cuda.device(dev):
+        rn, rho, pair = _f32(rn, dev, (B,), "rn"), _f32(rho, dev, (), "rho"), _f64(pair, dev, 2, "pair")
+        W1, b1, W2, b2 = _net(dev, W1, b1, W2, b2, 32, 3)
+        step = torch.empty_like(rn)
+        _lib.check(lib.admmnet_train_stepsize_pair_f32(B, float(knorm), _ptr(rn), _ptr(pair), _ptr(rho), _ptr(W1), _ptr(b1),
+                                                       _ptr(W2), _ptr(b2), _ptr(step), _stream(dev)),
+                   "admmnet_train_stepsize_pair_f32")
+    return step
+
+
+def train_stepsize_bwd_pair_front(g_step, rn, pair, rho, W1, b1, W2, b2, knorm: float):
+    """The backward of ``train_stepsize_pair`` up to the sum over the ranks: returns (g_u [B], total float64 [1] = this call's
+    sum of g_u rn, g_rho 0-dim, gW1 [32, 3], gb1 [32], gW2 [1, 32], gb2 [1]), the parameter gradients summed over this call."""
+    _need_cuda(g_step, "g_step")
+    lib, dev, B = _lib.load(), g_step.device, g_step.shape[0]
+    with torch.cuda.device(dev):
+        g_step, rn, rho = _f32(g_step, dev, (B,), "g_step"), _f32(rn, dev, (B,), "rn"), _f32(rho, dev, (), "rho")
+        pair = _f64(pair, dev, 2, "pair")
+        W1, b1, W2, b2 = _net(dev, W1, b1, W2, b2, 32, 3)
+        g_u = torch.empty_like(rn)
+        out = torch.empty(162, dtype=torch.float32, device=dev)
+        total = torch.empty(1, dtype=torch.float64, device=dev)
+        need = lib.admmnet_train_stepsize_pair_partials(B)
+        if need < 0:
+            raise _lib.AdmmNetError(f"train_stepsize_bwd_pair_front: bad size (B={B})")
+        part = torch.empty(need, dtype=torch.float32, device=dev)
+        _lib.check(lib.admmnet_train_stepsize_bwd_pair_front_f32(B, float(knorm), _ptr(g_step), _ptr(rn), _ptr(pair), _ptr(rho),
+                                                                 _ptr(W1), _ptr(b1), _ptr(W2), _ptr(b2), _ptr(g_u), _ptr(out),
+                                                                 _ptr(total), _ptr(part), _stream(dev)),
+                   "admmnet_train_stepsize_bwd_pair_front_f32")
+    return g_u, total, out[0], out[1:97].reshape(32, 3), out[97:129], out[129:161].reshape(1, 32), out[161:162]
+
+
+def train_stepsize_bwd_pair_back(g_u, pair, total) -> torch.Tensor:
+    """g_rn = ((g_u mean - total / count) + g_u eps) / (mean + eps)^2 from the pair and ``total`` summed over the ranks."""
+    _need_cuda(g_u, "g_u")
+    lib, dev, B = _lib.load(), g_u.device, g_u.shape[0]
+    with torch.cuda.device(dev):
+        g_u, pair, total = _f32(g_u, dev, (B,), "g_u"), _f64(pair, dev, 2, "pair"), _f64(total, dev, 1, "total")
+        g_rn = torch.empty_like(g_u)
+        _lib.check(lib.admmnet_train_stepsize_bwd_pair_back_f32(B, _ptr(g_u), _ptr(pair), _ptr(total), _ptr(g_rn), _stream(dev)),
+                   "admmnet_train_stepsize_bwd_pair_back_f32")
+    return g_rn
+
+
 # ---- the training losses (csrc/loss.hip) --------------------------------------------------------------------------------------
 # out [3] float32 = (total, first part, second part); g_out [3] = the gradients of those three, a device tensor.
 _LOSS_ANM, _LOSS_PHI = range(2)
@@ -704,6 +773,40 @@ def optim_scale(grads, coef) -> None:
     coef = _optim_coef("optim_scale", coef, dev)
     with torch.cuda.device(dev):
         _lib.check(lib.admmnet_optim_scale_f32(count, g, numel, _ptr(coef), _stream(dev)), "admmnet_optim_scale_f32")
+
+
+def _optim_flat(what, flat, tensors, dev):
+    """``flat`` as the bucket kernels take it: a contiguous float32 device tensor with room for every element of the list."""
+    if not isinstance(flat, torch.Tensor) or flat.dtype != torch.float32:
+        raise TypeError(f"{what}: flat must be a float32 tensor, got {flat.dtype if isinstance(flat, torch.Tensor) else type(flat).__name__}")
+    total = sum(t.numel() for t in tensors)
+    if flat.device != dev or not flat.is_contiguous() or flat.dim() != 1 or flat.numel() < total:
+        raise ValueError(f"{what}: flat must be a contiguous 1-d tensor of at least {total} elements on {dev}, got "
+                         f"{tuple(flat.shape)} on {flat.device}")
+    return flat.detach()
+
+
+def optim_pack(tensors, flat) -> None:
+    """The tensors of the list copied, in list order, into the front of ``flat`` (what ``torch.cat([t.reshape(-1) ...])`` would
+    hold); the elements of ``flat`` behind the list's total stay as they are."""
+    tensors = list(tensors)
+    lib, dev, count, numel, (t,) = _optim_lists("optim_pack", tensors)
+    if count == 0:
+        return
+    flat = _optim_flat("optim_pack", flat, tensors, dev)
+    with torch.cuda.device(dev):
+        _lib.check(lib.admmnet_optim_pack_f32(count, t, numel, _ptr(flat), _stream(dev)), "admmnet_optim_pack_f32")
+
+
+def optim_unpack(tensors, flat) -> None:
+    """The inverse of ``optim_pack``: the front of ``flat`` copied back into the tensors of the list, in place."""
+    tensors = list(tensors)
+    lib, dev, count, numel, (t,) = _optim_lists("optim_unpack", tensors)
+    if count == 0:
+        return
+    flat = _optim_flat("optim_unpack", flat, tensors, dev)
+    with torch.cuda.device(dev):
+        _lib.check(lib.admmnet_optim_unpack_f32(count, t, numel, _ptr(flat), _stream(dev)), "admmnet_optim_unpack_f32")
 
 
 def optim_adamw(params, grads, exp_avgs, exp_avg_sqs, hyper_index, hyper, coef=None) -> None:

@@ -17,6 +17,11 @@ all-gather of the shard sizes per call checks the alignment.
 The layer engine is injected so the protocol can be exercised on CPU ranks
 (gloo) in tests; the product engine is ``HipLayerEngine`` (C ABI layer-at-a-time
 entry points of include/admmnet.h).
+
+``ShardedTraining`` is the same split for an optimisation step: the differentiable
+forward of ``training.unrolled_forward`` on every rank's shard with the layers' means
+over the whole batch (one float64 pair per layer in the forward, one float64 scalar
+per layer in the backward), and ONE all-reduce of all gradients per step.
 """
 from __future__ import annotations
 
@@ -26,7 +31,7 @@ from typing import Callable, Optional
 import torch
 import torch.distributed as dist
 
-from . import _lib
+from . import _lib, ops
 
 
 def _ptr(t):
@@ -170,6 +175,22 @@ def shard_bounds(total: int, world: int, rank: int, sub_batch: Optional[int] = N
     return min(glo * sub_batch, total), min(ghi * sub_batch, total)
 
 
+def _shard_sizes(n_local: int, world: int, dev, group):
+    """The number of signals of every rank, in rank order: one all-gather."""
+    sizes = [torch.zeros(1, dtype=torch.int64, device=dev) for _ in range(world)]
+    dist.all_gather(sizes, torch.tensor([n_local], dtype=torch.int64, device=dev), group=group)
+    return [int(s.item()) for s in sizes]
+
+
+def _check_aligned(sizes, g: int):
+    start = 0
+    for r, n in enumerate(sizes):
+        if n and start % g:
+            raise ValueError(f"sub_batch={g}: the shard of rank {r} starts at signal {start}, inside a sub-batch "
+                             f"(shard sizes {sizes}); split with shard_bounds(total, world, rank, sub_batch={g})")
+        start += n
+
+
 class ShardedForward:
     def __init__(self, model, scope: str = "global", group=None,
                  engine_factory: Optional[Callable] = None):
@@ -223,15 +244,7 @@ class ShardedForward:
     def _check_group_aligned(self, n_local: int, g: int, world: int, dev):
         """Every shard must start at a group boundary of the whole batch, i.e. every rank before the last non-empty one
         holds whole groups (shard_bounds(..., sub_batch=g) cuts that way).  Raises ValueError on every rank otherwise."""
-        sizes = [torch.zeros(1, dtype=torch.int64, device=dev) for _ in range(world)]
-        dist.all_gather(sizes, torch.tensor([n_local], dtype=torch.int64, device=dev), group=self.group)
-        sizes = [int(s.item()) for s in sizes]
-        start = 0
-        for r, n in enumerate(sizes):
-            if n and start % g:
-                raise ValueError(f"sub_batch={g}: the shard of rank {r} starts at signal {start}, inside a sub-batch "
-                                 f"(shard sizes {sizes}); split with shard_bounds(total, world, rank, sub_batch={g})")
-            start += n
+        _check_aligned(_shard_sizes(n_local, world, dev, self.group), g)
 
     def _gather(self, t, dim):
         if t.is_complex():   # collectives move real tensors
@@ -248,3 +261,131 @@ class ShardedForward:
         outs = [torch.empty_like(buf) for _ in range(world)]
         dist.all_gather(outs, buf, group=self.group)
         return torch.cat([o.narrow(dim, 0, s) for o, s in zip(outs, sizes)], dim=dim)
+
+
+class BucketKernels:
+    """A tensor list to and from ONE flat buffer on the HIP kernels of csrc/optim.hip (one launch per 128 tensors): the bucket of
+    ``ShardedTraining``'s parameter broadcast and gradient all-reduce."""
+
+    pack = staticmethod(ops.optim_pack)          # (tensors, flat): flat[: total] <- the tensors in list order
+    unpack = staticmethod(ops.optim_unpack)      # (tensors, flat): the tensors <- flat[: total]
+
+
+class TorchBucketKernels:
+    """Stand-in for tests: the same copies as tensor operations, any device."""
+
+    @staticmethod
+    def pack(tensors, flat):
+        o = 0
+        for t in tensors:
+            flat[o:o + t.numel()].copy_(t.reshape(-1))
+            o += t.numel()
+
+    @staticmethod
+    def unpack(tensors, flat):
+        o = 0
+        for t in tensors:
+            t.copy_(flat[o:o + t.numel()].view_as(t))
+            o += t.numel()
+
+
+class ShardedTraining:
+    """One optimisation step on a batch that is split across the ranks of a process group, with the gradients of the WHOLE batch:
+
+        st = ShardedTraining(model, scope="global")          # broadcasts rank 0's parameters once, as one bucket
+        out = st(y_local, b_local, sigma_local)              # differentiable forward of this rank's shard
+        loss = criterion(out, ...) * st.weight               # st.weight = B_local / B_global, set by the call
+        st.backward(loss)                                    # loss.backward(), then ONE all-reduce (sum) of every gradient
+        optimizer.step()                                     # any optimiser; the ranks stay bit-identical
+
+    The call honours ``model.train_route``, ``model.sub_batch`` and ``model.options`` and returns what
+    ``model.forward_autograd`` returns.  After ``backward`` every rank holds in ``p.grad`` the gradient of the SUM of the ranks'
+    losses, the network evaluated on the concatenated batch: what one process computes on that batch.  Parameters the reference
+    leaves at ``grad = None`` (the detached corners, the dead last layer) stay None on every rank; that set is structural, the
+    same on every rank, and the bucket holds the others in ``model.parameters()`` order.  Gradients are not accumulated across
+    calls of ``backward``: clear them (``optimizer.zero_grad()``) before every step.
+
+    Weight the LOSS before ``backward``, not the gradients after it.  Both losses of the reference are means over the batch, so
+    the local means times ``st.weight`` sum to the mean over the whole batch.  With ``scope="global"`` the backward's per-layer
+    all-reduce carries the other ranks' upstream gradients into this rank's graph, so the weights have to be in the seeds of the
+    backward; scaling ``p.grad`` afterwards cannot undo a wrong mixture.
+
+    ``scope="global"``: the mean of every Z layer (admm_net.py:459) is over the signals of all ranks -- per layer one all-reduce
+    of the float64 (sum of the residual norms, count) pair in the forward and one of a float64 scalar, the adjoint, in the
+    backward.  ``scope="shard"``: every rank uses its own mean, no per-layer collective; this is what wrapping the model in
+    ``DistributedDataParallel`` computes, and it is ANOTHER network than the one a single process evaluates on the batch.
+    ``model.sub_batch = g``: groups never span ranks (split with ``shard_bounds(total, world, rank, sub_batch=g)``; a shard that
+    starts inside a group raises ``ValueError`` on every rank), so neither scope issues a per-layer collective and the gradient
+    all-reduce is the only one of the step.
+
+    Every rank's loss must depend on its output: a rank whose loss does not reach the Z layers never issues the backward's
+    collectives and the others wait for it.  An empty shard raises ``ValueError`` on every rank.  On the ``native`` route every
+    rank draws its own keep mask for the head's attention dropout, from its own generator state.
+
+    Without a process group, or in a group of one, no collective and none of the bucket or pair kernels run: the result is
+    ``torch.equal`` to ``model.forward_autograd`` followed by ``loss.backward()``.
+
+    ``kernels``: keyword arguments of ``training.unrolled_forward`` that replace the HIP eigensolver and kernels (``solver``,
+    ``assembler``, ``layer_kernels``, ``small_kernels``, ``native_kernels``) and ``bucket`` a stand-in for ``BucketKernels``: the
+    CPU tests drive the protocol over gloo with the Torch stand-ins.  None: the product path."""
+
+    def __init__(self, model, scope: str = "global", group=None, kernels: Optional[dict] = None, bucket=None):
+        if scope not in ("global", "shard"):
+            raise ValueError("scope must be 'global' or 'shard'")
+        self.model, self.scope, self.group, self.kernels = model, scope, group, kernels
+        self.bucket = BucketKernels if bucket is None else bucket
+        self.weight = 1.0
+        self.global_batch = None
+        self._flat = None
+        if self._world() > 1:
+            params = [p.detach() for p in model.parameters()]
+            self._flat = torch.empty(sum(p.numel() for p in params), dtype=torch.float32, device=params[0].device)
+            self.bucket.pack(params, self._flat)
+            dist.broadcast(self._flat, src=0 if group is None else dist.get_global_rank(group, 0), group=group)
+            self.bucket.unpack(params, self._flat)
+
+    def _world(self):
+        return dist.get_world_size(self.group) if dist.is_available() and dist.is_initialized() else 1
+
+    def _reduce(self, t):
+        dist.all_reduce(t, op=dist.ReduceOp.SUM, group=self.group)
+        return t
+
+    def __call__(self, y_local, b_local, sigma_local):
+        world, g = self._world(), self.model.sub_batch
+        n = y_local.shape[0]
+        reducer = None
+        if world > 1:
+            sizes = _shard_sizes(n, world, y_local.device, self.group)
+            if min(sizes) == 0:
+                raise ValueError(f"every rank needs at least one signal, got shard sizes {sizes}")
+            if g:
+                _check_aligned(sizes, g)
+            elif self.scope == "global":
+                reducer = self._reduce
+            self.global_batch = sum(sizes)
+        else:
+            self.global_batch = n
+        self.weight = n / self.global_batch
+        m = self.model
+        if self.kernels is None:
+            return m.forward_autograd(y_local, b_local, sigma_local, reducer=reducer)
+        from . import training
+        route = m.train_route
+        use = {"solver": True, "assembler": True, "layer_kernels": route != "tensor", "small_kernels": route in ("full", "native"),
+               "native_kernels": route == "native"}
+        return training.unrolled_forward(m, y_local, b_local, sigma_local, sub_batch=g, fused=route != "tensor",
+                                         small=route in ("full", "native"), native=route == "native", reducer=reducer,
+                                         **{k: v for k, v in self.kernels.items() if use[k]})
+
+    def backward(self, loss):
+        """``loss.backward()``, then -- in a group of more than one rank -- one all-reduce (sum) of all gradients through the flat
+        buffer.  ``loss`` must already carry ``st.weight``."""
+        loss.backward()
+        if self._world() == 1:
+            return
+        grads = [p.grad for p in self.model.parameters() if p.grad is not None]
+        n = sum(t.numel() for t in grads)
+        self.bucket.pack(grads, self._flat)
+        self._reduce(self._flat[:n])
+        self.bucket.unpack(grads, self._flat)

@@ -35,6 +35,12 @@ on the matrix cores, and a token-backward kernel.  The attention dropout is an I
 drawn with one ``torch.rand`` call (``draw_keep_mask``) when the head is in train mode: the same distribution as
 ``nn.MultiheadAttention``'s dropout, another realisation under the same seed.
 
+``reducer`` (``unrolled_forward(..., reducer=...)``, set by ``sharded.ShardedTraining``) makes the call one SHARD of a batch that is
+split across the ranks of a process group: the mean of every Z layer is then over the signals of all ranks.  On the ``tensor`` and
+``fused`` routes the coupling is ``_ReducedSum``, whose forward and backward are both an all-reduce sum; on ``full`` and ``native``
+``_StepSize`` runs the ``pair`` kernels of csrc/train_small.hip around the two reductions.  With the default None nothing of this
+runs.
+
 Gradient flow mirrors the reference as written:
   * the corner values ``1 / (softplus(lambda)^2 + eps)`` go through ``.item()`` (admm_net.py:271, 426):
     ``gLayers.k.lambda_param`` / ``zLayers.k.lambda_param`` receive no gradient;
@@ -304,6 +310,12 @@ class SmallKernels:
     eigmap_bwd = staticmethod(ops.train_eigmap_bwd)              # (g_wp, w, thr, W1, b1, W2, b2) -> g_w, g_thr, gW1, gb1, gW2, gb2
     stepsize = staticmethod(ops.train_stepsize)                  # (rn, rho, W1, b1, W2, b2, knorm, sub_batch) -> step
     stepsize_bwd = staticmethod(ops.train_stepsize_bwd)          # (g_step, rn, ...) -> g_rn, g_rho, gW1, gb1, gW2, gb2
+    # the step size from a (sum of rn, count) pair that comes from outside the call: the mean over the ranks of a sharded batch
+    rnsum = staticmethod(ops.train_rnsum)                        # rn -> this call's pair, float64 [2]
+    stepsize_pair = staticmethod(ops.train_stepsize_pair)        # (rn, pair, rho, W1, b1, W2, b2, knorm) -> step
+    stepsize_bwd_pair_front = staticmethod(ops.train_stepsize_bwd_pair_front)   # (g_step, rn, pair, ...) -> g_u, total [1] f64, g_rho,
+    #                                                                             gW1, gb1, gW2, gb2 (this call's sums)
+    stepsize_bwd_pair_back = staticmethod(ops.train_stepsize_bwd_pair_back)     # (g_u, pair, total over the ranks) -> g_rn
 
 
 def _dsoftplus(x):
@@ -429,10 +441,13 @@ class TorchSmallKernels:
                 tW2.sum(dim=(0, 1)).reshape(W2.shape), tb2.sum().reshape(b2.shape))
 
     @staticmethod
-    def _step_parts(rn, rho, W1, b1, W2, b2, knorm, sub_batch):
+    def _step_parts(rn, rho, W1, b1, W2, b2, knorm, sub_batch, pair=None):
         r = F.softplus(rho)
-        total, count = _group_total(rn, sub_batch)
-        mean = total / count
+        if pair is None:
+            total, count = _group_total(rn, sub_batch)
+            mean = total / count
+        else:                                                       # the mean of a larger batch, rounded to the dtype as the kernels do
+            mean = (pair[0] / pair[1]).to(rn.dtype)
         den = mean + EPS
         u = rn / den
         feat = torch.stack([torch.full_like(rn, knorm), r.detach().expand_as(rn), u], dim=1)       # [B, 3]
@@ -446,22 +461,58 @@ class TorchSmallKernels:
         return r * (0.5 + 1.5 * torch.sigmoid(o))
 
     @staticmethod
-    def stepsize_terms(g_step, rn, rho, W1, b1, W2, b2, knorm, sub_batch=None):
-        r, mean, den, feat, pre, o = TorchSmallKernels._step_parts(rn, rho, W1, b1, W2, b2, knorm, sub_batch)
+    def _step_net_terms(g_step, rn, rho, W1, W2, r, feat, pre, o):
+        """(g_u [B], then one term per signal of g_rho, gW1, gb1, gW2, gb2): everything of the backward but the coupling."""
         dy = g_step * r * 1.5 * _dsigmoid(o)
         dh = dy.unsqueeze(1) * W2.reshape(-1) * (pre > 0).to(rn.dtype)                              # [B, 32]
-        g_u = dh @ W1[:, 2]
+        return (dh @ W1[:, 2], g_step * (0.5 + 1.5 * torch.sigmoid(o)) * _dsoftplus(rho), dh.unsqueeze(2) * feat.unsqueeze(1), dh,
+                dy.unsqueeze(1) * torch.relu(pre), dy)
+
+    @staticmethod
+    def stepsize_terms(g_step, rn, rho, W1, b1, W2, b2, knorm, sub_batch=None):
+        r, mean, den, feat, pre, o = TorchSmallKernels._step_parts(rn, rho, W1, b1, W2, b2, knorm, sub_batch)
+        g_u, *terms = TorchSmallKernels._step_net_terms(g_step, rn, rho, W1, W2, r, feat, pre, o)
         # g_u / den - mean(g_u rn) / den^2 with both parts over den^2: in a group of ONE signal they cancel to g_u eps / den^2,
         # which this form keeps (g_u mean - mean(g_u rn) is then an exact zero) and the plain difference loses to round-off
         total, count = _group_total(g_u * rn, sub_batch)
         g_rn = ((g_u * mean - total / count) + g_u * EPS) / den ** 2
-        return (g_rn, g_step * (0.5 + 1.5 * torch.sigmoid(o)) * _dsoftplus(rho), dh.unsqueeze(2) * feat.unsqueeze(1), dh,
-                dy.unsqueeze(1) * torch.relu(pre), dy)
+        return (g_rn, *terms)
 
     @staticmethod
     def stepsize_bwd(g_step, rn, rho, W1, b1, W2, b2, knorm, sub_batch=None):
         g_rn, t_rho, tW1, tb1, tW2, tb2 = TorchSmallKernels.stepsize_terms(g_step, rn, rho, W1, b1, W2, b2, knorm, sub_batch)
         return g_rn, t_rho.sum(), tW1.sum(dim=0), tb1.sum(dim=0), tW2.sum(dim=0).reshape(W2.shape), tb2.sum().reshape(b2.shape)
+
+    # ---- the step size from a pair (sum of rn, count) float64 [2] of a LARGER batch than the call (the ranks of a sharded batch)
+    @staticmethod
+    def rnsum(rn):
+        return torch.stack([rn.to(torch.float64).sum(), torch.tensor(float(rn.shape[0]), dtype=torch.float64, device=rn.device)])
+
+    @staticmethod
+    def stepsize_pair(rn, pair, rho, W1, b1, W2, b2, knorm):
+        r, _, _, _, _, o = TorchSmallKernels._step_parts(rn, rho, W1, b1, W2, b2, knorm, None, pair)
+        return r * (0.5 + 1.5 * torch.sigmoid(o))
+
+    @staticmethod
+    def stepsize_pair_terms(g_step, rn, pair, rho, W1, b1, W2, b2, knorm):
+        """(g_u [B], then one term per signal of total (float64), g_rho, gW1, gb1, gW2, gb2)."""
+        r, _, _, feat, pre, o = TorchSmallKernels._step_parts(rn, rho, W1, b1, W2, b2, knorm, None, pair)
+        g_u, *terms = TorchSmallKernels._step_net_terms(g_step, rn, rho, W1, W2, r, feat, pre, o)
+        return (g_u, g_u.to(torch.float64) * rn.to(torch.float64), *terms)
+
+    @staticmethod
+    def stepsize_bwd_pair_front(g_step, rn, pair, rho, W1, b1, W2, b2, knorm):
+        g_u, t_tot, t_rho, tW1, tb1, tW2, tb2 = TorchSmallKernels.stepsize_pair_terms(g_step, rn, pair, rho, W1, b1, W2, b2, knorm)
+        return (g_u, t_tot.sum().reshape(1), t_rho.sum(), tW1.sum(dim=0), tb1.sum(dim=0), tW2.sum(dim=0).reshape(W2.shape),
+                tb2.sum().reshape(b2.shape))
+
+    @staticmethod
+    def stepsize_bwd_pair_back(g_u, pair, total):
+        """``stepsize_terms``' cancellation-safe g_rn with the mean and the coupling sum of the larger batch; the difference is
+        taken in float64, where the product of two float32 numbers is exact (a pair of ONE signal leaves g_u eps / den^2)."""
+        mean = (pair[0] / pair[1]).to(g_u.dtype)
+        diff = (g_u.to(torch.float64) * mean.to(torch.float64) - total.reshape(()) / pair[1]).to(g_u.dtype)
+        return (diff + g_u * EPS) / (mean + EPS) ** 2
 
 
 class _PhiStep(torch.autograd.Function):
@@ -527,14 +578,43 @@ class _StepSize(torch.autograd.Function):
     """The adaptive step with the group mean and residual_scale_net inside (admm_net.py:440-474)."""
 
     @staticmethod
-    def forward(ctx, rn, rho, W1, b1, W2, b2, knorm, sub_batch, sk):
-        ctx.save_for_backward(rn, rho, W1, b1, W2, b2)
-        ctx.knorm, ctx.sub_batch, ctx.sk = knorm, sub_batch, sk
-        return sk.stepsize(rn, rho, W1, b1, W2, b2, knorm, sub_batch)
+    def forward(ctx, rn, rho, W1, b1, W2, b2, knorm, sub_batch, sk, reducer=None):
+        ctx.knorm, ctx.sub_batch, ctx.sk, ctx.reducer = knorm, sub_batch, sk, reducer
+        if reducer is None:
+            ctx.save_for_backward(rn, rho, W1, b1, W2, b2)
+            return sk.stepsize(rn, rho, W1, b1, W2, b2, knorm, sub_batch)
+        pair = reducer(sk.rnsum(rn))                  # (sum of rn, count) over all ranks
+        ctx.save_for_backward(rn, rho, W1, b1, W2, b2, pair)
+        return sk.stepsize_pair(rn, pair, rho, W1, b1, W2, b2, knorm)
 
     @staticmethod
     def backward(ctx, g_step):
-        return (*ctx.sk.stepsize_bwd(g_step, *ctx.saved_tensors, ctx.knorm, ctx.sub_batch), None, None, None)
+        if ctx.reducer is None:
+            return (*ctx.sk.stepsize_bwd(g_step, *ctx.saved_tensors, ctx.knorm, ctx.sub_batch), None, None, None, None)
+        rn, rho, W1, b1, W2, b2, pair = ctx.saved_tensors
+        g_u, total, *g_par = ctx.sk.stepsize_bwd_pair_front(g_step, rn, pair, rho, W1, b1, W2, b2, ctx.knorm)
+        g_rn = ctx.sk.stepsize_bwd_pair_back(g_u, pair, ctx.reducer(total))     # the adjoint of the forward's sum: a sum again
+        return (g_rn, *g_par, None, None, None, None)
+
+
+class _ReducedSum(torch.autograd.Function):
+    """(sum of rn over the signals of ALL ranks, their number), both float64 0-dim: ``reducer`` all-reduces (sum) a float64
+    tensor across the ranks.  The forward moves the pair, the backward the one float64 gradient of the sum; the count carries
+    none."""
+
+    @staticmethod
+    def forward(ctx, rn, reducer):
+        ctx.reducer, ctx.dtype, ctx.B = reducer, rn.dtype, rn.shape[0]
+        pair = reducer(torch.stack([rn.to(torch.float64).sum(),
+                                    torch.tensor(float(rn.shape[0]), dtype=torch.float64, device=rn.device)]))
+        total, count = pair[0].clone(), pair[1].clone()
+        ctx.mark_non_differentiable(count)
+        return total, count
+
+    @staticmethod
+    def backward(ctx, g_total, _g_count):
+        g = ctx.reducer(g_total.to(torch.float64).reshape(1).clone())
+        return g.to(ctx.dtype).expand(ctx.B), None
 
 
 class NativeKernels:
@@ -819,10 +899,14 @@ def _g_layer(layer, phi, h, Z, solver, asm, lk=None, sk=None, corner=None, rinv=
     return _Rebuild.apply(V, wp, asm)
 
 
-def _group_mean(rn: torch.Tensor, sub_batch: Optional[int]) -> torch.Tensor:
+def _group_mean(rn: torch.Tensor, sub_batch: Optional[int], reducer: Optional[Callable] = None) -> torch.Tensor:
     """The batch mean of admm_net.py:459 for every signal: over the whole call, or over its group of ``sub_batch``
-    consecutive signals (the last group may be shorter)."""
+    consecutive signals (the last group may be shorter).  ``reducer`` (see ``unrolled_forward``): the mean over the signals of
+    all ranks, the float64 quotient rounded to the dtype of ``rn``."""
     B = rn.shape[0]
+    if reducer is not None:
+        total, count = _ReducedSum.apply(rn, reducer)
+        return (total / count).to(rn.dtype)
     if sub_batch is None or sub_batch >= B:
         return rn.mean()
     gid = torch.arange(B, device=rn.device) // sub_batch
@@ -830,13 +914,13 @@ def _group_mean(rn: torch.Tensor, sub_batch: Optional[int]) -> torch.Tensor:
     return (sums / torch.bincount(gid).to(rn.dtype))[gid]
 
 
-def _z_layer(layer, k, phi, h, G, Z, sub_batch=None, lk=None, sk=None, corner=None):
-    """admm_net.py:388-474.  ``lk``, ``sk``, ``corner``: as for ``_g_layer``."""
+def _z_layer(layer, k, phi, h, G, Z, sub_batch=None, lk=None, sk=None, corner=None, reducer=None):
+    """admm_net.py:388-474.  ``lk``, ``sk``, ``corner``: as for ``_g_layer``; ``reducer``: as for ``unrolled_forward``."""
     if corner is None:
         corner = (1.0 / (F.softplus(layer.lambda_param) ** 2 + EPS)).item()
     if sk is not None:
         rn = _ResidualNorm.apply(G, phi, h, corner, lk)
-        step = _StepSize.apply(rn, layer.rho, *_net_params(layer.residual_scale_net), k / 10.0, sub_batch, sk)
+        step = _StepSize.apply(rn, layer.rho, *_net_params(layer.residual_scale_net), k / 10.0, sub_batch, sk, reducer)
         return _StateUpdate.apply(Z, G, phi, h, step, corner, lk)
     rho = F.softplus(layer.rho)
     if lk is None:
@@ -847,7 +931,7 @@ def _z_layer(layer, k, phi, h, G, Z, sub_batch=None, lk=None, sk=None, corner=No
     B = rn.shape[0]
     feat = torch.stack([torch.full((B,), k / 10.0, device=rn.device),
                         torch.full((B,), rho.item(), device=rn.device),
-                        rn / (_group_mean(rn, sub_batch) + EPS)], dim=1)
+                        rn / (_group_mean(rn, sub_batch, reducer) + EPS)], dim=1)
     step = rho * (0.5 + 1.5 * layer.residual_scale_net(feat)).squeeze(1)
     if lk is None:
         return Z + step.reshape(-1, 1, 1) * R
@@ -873,7 +957,7 @@ def _peak_head(head, phi):
 def unrolled_forward(model, y: torch.Tensor, b: torch.Tensor, sigma: torch.Tensor,
                      solver: Optional[Callable] = None, assembler=None, sub_batch: Optional[int] = None,
                      fused: bool = False, layer_kernels=None, small: bool = False, small_kernels=None,
-                     native: bool = False, native_kernels=None):
+                     native: bool = False, native_kernels=None, reducer: Optional[Callable] = None):
     """Differentiable K-layer forward on the device of ``y`` (admm_net.py:742-764 / 791-816).
 
     ``sub_batch = g`` evaluates the consecutive groups of g signals as independent batches, each with its own mean
@@ -893,10 +977,16 @@ def unrolled_forward(model, y: torch.Tensor, b: torch.Tensor, sigma: torch.Tenso
     ``native_kernels`` (default ``NativeKernels``, the HIP kernels of csrc/train_hlayer.hip; the CPU tests pass
     ``TorchNativeKernels``), the G layers' ``1 / (softplus(rho) + eps)`` once per forward on the stacked rhos, and the head of
     ``ADMMNet`` through ``_PeakHead`` (csrc/train_head.hip).
+    ``reducer(t) -> t`` all-reduces (sum) a small float64 tensor across the ranks of a batch-sharded step
+    (``sharded.ShardedTraining``): the mean of every Z layer is then over the signals of ALL ranks, one reduction of a
+    (sum, count) pair per layer in the forward and one of a scalar per layer in the backward.  None (default): the call is the
+    whole batch, today's code path.  Not combined with ``sub_batch``: groups never span ranks.
     Returns phi, or (tau, f, confidences, phi) when the model has a PeakSearchLayer.
     """
     if sub_batch is not None and sub_batch < 1:
         raise ValueError(f"sub_batch must be None or >= 1, got {sub_batch}")
+    if reducer is not None and sub_batch is not None:
+        raise ValueError("reducer and sub_batch exclude each other: a sub-batch never spans ranks")
     if solver is None:   # the HIP eigensolver under the model's own option set (``model.options``; None = the process defaults)
         opts = getattr(model, "options", None)
         solver = ops.eigh if opts is None else (lambda A: ops.eigh(A, options=opts))
@@ -943,7 +1033,7 @@ def unrolled_forward(model, y: torch.Tensor, b: torch.Tensor, sigma: torch.Tenso
                 h = _HProject.apply(t, hl.correction_net(t), sigma, hl.projection_weight, sk)
             G, g_col, g_dg = _g_layer(model.gLayers[k], phi, h, Z, solver, asm, lk, sk, corners[k][0],
                                       None if rinv is None else rinv[k])
-            Z = _z_layer(model.zLayers[k], k, phi, h, G, Z, sub_batch, lk, sk, corners[k][1])
+            Z = _z_layer(model.zLayers[k], k, phi, h, G, Z, sub_batch, lk, sk, corners[k][1], reducer)
             z_col, z_dg = _Gather.apply(Z, lk)
             continue
         if lk is None:
@@ -955,11 +1045,11 @@ def unrolled_forward(model, y: torch.Tensor, b: torch.Tensor, sigma: torch.Tenso
         if lk is None:
             h = _h_layer(model.hLayers[k], G, Z, sigma)
             G = _g_layer(model.gLayers[k], phi, h, Z, solver, asm)
-            Z = _z_layer(model.zLayers[k], k, phi, h, G, Z, sub_batch)
+            Z = _z_layer(model.zLayers[k], k, phi, h, G, Z, sub_batch, reducer=reducer)
         else:
             h = _h_layer(model.hLayers[k], None, None, sigma, (g_dg, z_dg))
             G, g_col, g_dg = _g_layer(model.gLayers[k], phi, h, Z, solver, asm, lk)
-            Z = _z_layer(model.zLayers[k], k, phi, h, G, Z, sub_batch, lk)
+            Z = _z_layer(model.zLayers[k], k, phi, h, G, Z, sub_batch, lk, reducer=reducer)
             z_col, z_dg = _Gather.apply(Z, lk)
     if getattr(model, "_HAS_HEAD", False):
         if nk is not None:

@@ -367,6 +367,35 @@ int admmnet_train_stepsize_bwd_f32(int64_t B, int64_t sub_batch, float knorm, co
                                    const float *rho, const float *W1, const float *b1, const float *W2, const float *b2,
                                    float *g_rn, float *g_params, float *partials, void *stream);
 
+/* The step size from a mean that comes from OUTSIDE the call (csrc/train_small.hip): the batch-sharded training of
+ * admm_net_amd/sharded.py, where the mean of admm_net.py:459 is over the signals of all ranks.  `pair` is a DEVICE double[2] =
+ * (sum of rn, number of signals) of the whole batch, 8-byte aligned; every kernel forms mean = (float)(pair[0] / pair[1]) itself
+ * and den = mean + eps.  No reduction over the batch is left in the forward, so the grids are over slabs of 256 signals, one
+ * thread each.  B >= 1; parameters RAW and conventions as above.  Sums run in a fixed order without atomics, float64 across
+ * workgroups: two runs give the same bits.
+ *   admmnet_train_rnsum_f64                  pair[0] = sum of rn[0 .. B) in float64 (thread t of one workgroup adds rn[t],
+ *                                            rn[t + 256], ..., a tree halves the 256 slots), pair[1] = (double) B: this call's
+ *                                            share, to be summed over the ranks.
+ *   admmnet_train_stepsize_pair_f32          step_b as admmnet_train_stepsize_f32 computes it, from the mean of `pair`.
+ *   admmnet_train_stepsize_bwd_pair_front_f32  from g_step: g_u [B] (the gradient of u_b = rn_b / den), g_params[162] as
+ *                                            admmnet_train_stepsize_bwd_f32 lays them out (sums over THIS call's signals) and
+ *                                            total[0] = sum_b g_u_b rn_b, products and sums in float64: this call's share of the
+ *                                            coupling through the mean.  (dy_b of the kernel comment stays in LDS.)  `partials` holds
+ *                                            admmnet_train_stepsize_pair_partials(B) floats (-1 for B < 1), 8-byte aligned.
+ *   admmnet_train_stepsize_bwd_pair_back_f32 from g_u, the pair and total[0] summed over the ranks:
+ *                                            g_rn_b = ((g_u_b mean - total / count) + g_u_b eps) / den^2, the cancellation-safe form
+ *                                            of admmnet_train_stepsize_bwd_f32: with a pair of ONE signal the difference is an exact
+ *                                            zero and g_u eps / den^2 remains.  g_rn may be g_u (in place). */
+int64_t admmnet_train_stepsize_pair_partials(int64_t B);
+int admmnet_train_rnsum_f64(int64_t B, const float *rn, double *pair, void *stream);
+int admmnet_train_stepsize_pair_f32(int64_t B, float knorm, const float *rn, const double *pair, const float *rho, const float *W1,
+                                    const float *b1, const float *W2, const float *b2, float *step, void *stream);
+int admmnet_train_stepsize_bwd_pair_front_f32(int64_t B, float knorm, const float *g_step, const float *rn, const double *pair,
+                                              const float *rho, const float *W1, const float *b1, const float *W2, const float *b2,
+                                              float *g_u, float *g_params, double *total, float *partials, void *stream);
+int admmnet_train_stepsize_bwd_pair_back_f32(int64_t B, const float *g_u, const double *pair, const double *total, float *g_rn,
+                                             void *stream);
+
 /* Training route "native", the H layer with its correction_net inside (csrc/train_hlayer.hip): one forward kernel; one backward
  * kernel plus a batch-reduced product on the matrix cores for the weight gradients.  1 <= D = M N <= 256, B >= 1 (at most
  * 65535 * 128).  Conventions, alignment and the RAW parameters as for the "full" route above; W1 [64][D], b1 [64], W2 [D][64],
@@ -486,7 +515,12 @@ int admmnet_loss_phi_bwd_c64(int32_t D, int64_t B, const float *g_out, const voi
  *                               one per distinct (group, step count) pair; a launch holds eight).  sqrt and / are correctly
  *                               rounded.  With coef_or_null given, g coef[0] rounded to float32 takes the place of g (the
  *                               gradients themselves stay as they are): the same bits as admmnet_optim_scale_f32 followed by
- *                               the update without a coefficient. */
+ *                               the update without a coefficient.
+ *   admmnet_optim_pack_f32      the list's tensors copied, in list order, into the contiguous buffer `flat` (the sum of numel
+ *                               floats; anything behind stays untouched): the bucket of a gradient all-reduce or a parameter
+ *                               broadcast, one launch per 256 tensors instead of one copy per tensor.
+ *   admmnet_optim_unpack_f32    `flat` copied back into the list's tensors.  Both use the 16-byte path for a tensor whose
+ *                               pointer AND place in `flat` are 16-byte aligned and whose numel is a multiple of four. */
 typedef struct admmnet_adamw_hyper {
     double decay;                  /* 1 - lr weight_decay  */
     double one_minus_beta1;
@@ -503,6 +537,8 @@ int admmnet_optim_scale_f32(int32_t count, float *const *grads, const int64_t *n
 int admmnet_optim_adamw_f32(int32_t count, float *const *params, const float *const *grads, float *const *exp_avg,
                             float *const *exp_avg_sq, const int64_t *numel, const int32_t *hyper_index, int32_t nhyper,
                             const admmnet_adamw_hyper *hyper, const float *coef_or_null, void *stream);
+int admmnet_optim_pack_f32(int32_t count, const float *const *tensors, const int64_t *numel, float *flat, void *stream);
+int admmnet_optim_unpack_f32(int32_t count, float *const *tensors, const int64_t *numel, const float *flat, void *stream);
 
 /* Spectrum |phi^H kron(s(f), conj d(tau))|^2 on a (tau, f) grid:
  * peak_search_func / peak_search, utils/peakSearchUtils.py:9-60, evaluated in
