@@ -26,6 +26,7 @@ import torch
 
 from . import classical
 from .synth import pskdemod, pskmod, steering
+from .training import TRAIN_ROUTES
 
 NB = ND = 10
 F = np.array([-0.25, 0, 0.14])                       # test_time_net.py:16-18
@@ -148,7 +149,7 @@ def time_train_step(layers=10, batch=256, steps=20, warmup=3, seed=0, device="cu
     train mode (the differentiable route of admm_net_amd.training: HIP eigensolver + HIP contractions), a phi-alignment
     loss against the classical solver's phi labels (generated on the device, csrc/synth.hip), backward, clip, step.
     The loss is a plain normalised squared error: the reference's loss.py is user code outside this path.
-    ``route``: ``model.train_route`` ("tensor" | "fused" | "full" | "native"); ``grid`` = (M, N) of another geometry, same recipe.
+    ``route``: ``model.train_route`` (one of ``training.TRAIN_ROUTES``); ``grid`` = (M, N) of another geometry, same recipe.
     ``head = True`` times ``ADMMNet`` (the model of train.py) instead: the loss is then that phi error plus the plain squared
     error of tau and f against the generator's labels.
     ``optim``: "torch" (``torch.nn.utils.clip_grad_norm_`` and ``torch.optim.AdamW``) or "hip": ``admm_net_amd.optim.AdamW`` with
@@ -283,7 +284,7 @@ def main(argv=None):
     c.add_argument("--layers", type=int, default=10)
     c.add_argument("--batch", type=int, default=256)
     c.add_argument("--steps", type=int, default=20)
-    c.add_argument("--route", choices=("tensor", "fused", "full", "native"), default="tensor")
+    c.add_argument("--route", choices=TRAIN_ROUTES, default="tensor")
     c.add_argument("--grid", default=f"{NB}x{ND}", help="MxN")
     c.add_argument("--head", action="store_true", help="time ADMMNet (phi + tau + f loss) instead of PhiEstADMMNet")
     c.add_argument("--warmup", type=int, default=3)

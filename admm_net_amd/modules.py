@@ -213,8 +213,9 @@ class _FusedBase(nn.Module):
 
     @train_route.setter
     def train_route(self, value: str):
-        if not isinstance(value, str) or value not in ("tensor", "fused", "full", "native"):
-            raise ValueError(f"train_route must be 'tensor', 'fused', 'full' or 'native', got {value!r}")
+        from .training import TRAIN_ROUTES
+        if not isinstance(value, str) or value not in TRAIN_ROUTES:
+            raise ValueError(f"train_route must be one of {TRAIN_ROUTES}, got {value!r}")
         self._train_route = value
 
     # ---- weights -----------------------------------------------------------
@@ -368,9 +369,8 @@ class _FusedBase(nn.Module):
         if pdev != dev:
             raise _lib.AdmmNetError(f"training runs on the GPU: parameters are on {pdev}, expected {dev} "
                                     "(move the model with .to(device) as train.py / trainPhi.py do)")
-        out = training.unrolled_forward(self, y.to(dev), b.to(dev), sigma.to(dev), sub_batch=self.sub_batch,
-                                        fused=self.train_route != "tensor", small=self.train_route in ("full", "native"),
-                                        native=self.train_route == "native", reducer=reducer)
+        out = training.unrolled_forward(self, y.to(dev), b.to(dev), sigma.to(dev), sub_batch=self.sub_batch, reducer=reducer,
+                                        **training.route_kwargs(self.train_route))
         if isinstance(out, tuple):
             return tuple(o.to(y.device) for o in out)
         return out.to(y.device)

@@ -191,6 +191,15 @@ def _check_aligned(sizes, g: int):
         start += n
 
 
+def _layer_back(eng, k: int, sc: torch.Tensor, grouped: bool):
+    """The Z step of layer k from its (sum, count) pairs ``sc`` (``grouped``: one pair per sub-batch): the means are formed on
+    the device (csrc/zstep.hip) where the engine has the pair call and ``sc`` is what it takes, else here."""
+    if hasattr(eng, "back_pair") and sc.is_cuda and sc.dtype == torch.float64:
+        eng.back_pair(k, sc)
+    else:
+        eng.back(k, sc[0::2] / sc[1::2] if grouped else sc[0] / sc[1])
+
+
 class ShardedForward:
     def __init__(self, model, scope: str = "global", group=None,
                  engine_factory: Optional[Callable] = None):
@@ -219,18 +228,10 @@ class ShardedForward:
             sc = eng.front(k)
             if k == K - 1:
                 break
-            if g:   # sub-batches never span ranks: each rank's own per-group pairs, no collective
-                if hasattr(eng, "back_pair") and sc.is_cuda and sc.dtype == torch.float64:
-                    eng.back_pair(k, sc)
-                else:
-                    eng.back(k, sc[0::2] / sc[1::2])
-                continue
-            if self.scope == "global" and world > 1:
+            # sub-batches never span ranks: each rank's own per-group pairs, no collective
+            if not g and self.scope == "global" and world > 1:
                 dist.all_reduce(sc, op=dist.ReduceOp.SUM, group=self.group)
-            if hasattr(eng, "back_pair") and sc.is_cuda and sc.dtype == torch.float64:
-                eng.back_pair(k, sc)            # (the mean from the pair on the device: csrc/zstep.hip)
-            else:
-                eng.back(k, sc[0] / sc[1])
+            _layer_back(eng, k, sc, bool(g))
         phi, head = eng.finish()
         # status words of the C ABI after the forward: [0] eigensolver failures, [1] matrix-layers the matrix-function route
         # handed to the eigensolver, [2] matrix-layers it evaluated itself, [3] of [1] those rejected by the model of f
@@ -367,16 +368,11 @@ class ShardedTraining:
         else:
             self.global_batch = n
         self.weight = n / self.global_batch
-        m = self.model
-        if self.kernels is None:
-            return m.forward_autograd(y_local, b_local, sigma_local, reducer=reducer)
+        if self.kernels is None:           # the product path: the model places the tensors and checks its parameters' device
+            return self.model.forward_autograd(y_local, b_local, sigma_local, reducer=reducer)
         from . import training
-        route = m.train_route
-        use = {"solver": True, "assembler": True, "layer_kernels": route != "tensor", "small_kernels": route in ("full", "native"),
-               "native_kernels": route == "native"}
-        return training.unrolled_forward(m, y_local, b_local, sigma_local, sub_batch=g, fused=route != "tensor",
-                                         small=route in ("full", "native"), native=route == "native", reducer=reducer,
-                                         **{k: v for k, v in self.kernels.items() if use[k]})
+        return training.unrolled_forward(self.model, y_local, b_local, sigma_local, sub_batch=g, reducer=reducer,
+                                         **training.route_kwargs(self.model.train_route, self.kernels))
 
     def backward(self, loss):
         """``loss.backward()``, then -- in a group of more than one rank -- one all-reduce (sum) of all gradients through the flat

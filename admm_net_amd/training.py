@@ -35,6 +35,13 @@ on the matrix cores, and a token-backward kernel.  The attention dropout is an I
 drawn with one ``torch.rand`` call (``draw_keep_mask``) when the head is in train mode: the same distribution as
 ``nn.MultiheadAttention``'s dropout, another realisation under the same seed.
 
+The four routes nest, ``TRAIN_ROUTES = ("tensor", "fused", "full", "native")``, and ``route_kwargs`` is the one place that turns a
+name into the flags and kernel sets of ``unrolled_forward``.  ``unrolled_forward`` resolves its arguments once into the kernel sets
+``lk``, ``sk``, ``nk`` (None where the route does not use them) and runs ONE layer loop -- phi step, H step, G step, Z step, the last
+two leaving the gathered border column and diagonal of their result for the next layer -- in which every step function
+(``_phi_step``, ``_h_step``, ``_g_step`` / ``_g_layer``, ``_z_step`` / ``_z_layer``) holds its own choice between the tensor form and
+the kernels.  A new route is a new name in ``TRAIN_ROUTES``, its flag in ``route_kwargs`` and a branch in the steps it changes.
+
 ``reducer`` (``unrolled_forward(..., reducer=...)``, set by ``sharded.ShardedTraining``) makes the call one SHARD of a batch that is
 split across the ranks of a process group: the mean of every Z layer is then over the signals of all ranks.  On the ``tensor`` and
 ``fused`` routes the coupling is ``_ReducedSum``, whose forward and backward are both an all-reduce sum; on ``full`` and ``native``
@@ -64,6 +71,20 @@ import torch.nn.functional as F
 from . import ops
 
 EPS = 1e-8   # every layer's epsilon (admm_net.py:74, 114, 211, 360)
+TRAIN_ROUTES = ("tensor", "fused", "full", "native")   # ``model.train_route``: each name adds a kernel set to the one before it
+_STAND_INS = ("solver", "assembler", "layer_kernels", "small_kernels", "native_kernels")
+
+
+def route_kwargs(route: str, kernels: Optional[dict] = None) -> dict:
+    """The keyword arguments of ``unrolled_forward`` for a ``train_route`` name: the flags ``fused``, ``small``, ``native`` and,
+    out of ``kernels`` (stand-ins by keyword, as the CPU tests pass them), the eigensolver, the assembler and the kernel sets
+    that the route uses.  This is the one place that knows what a route name means."""
+    if not isinstance(route, str) or route not in TRAIN_ROUTES:
+        raise ValueError(f"train_route must be one of {TRAIN_ROUTES}, got {route!r}")
+    level = TRAIN_ROUTES.index(route)
+    kw = {"fused": level >= 1, "small": level >= 2, "native": level >= 3}
+    kw.update({name: kernels[name] for name in _STAND_INS[:2 + level] if kernels and name in kernels})
+    return kw
 
 
 class Assembler:
@@ -605,8 +626,7 @@ class _ReducedSum(torch.autograd.Function):
     @staticmethod
     def forward(ctx, rn, reducer):
         ctx.reducer, ctx.dtype, ctx.B = reducer, rn.dtype, rn.shape[0]
-        pair = reducer(torch.stack([rn.to(torch.float64).sum(),
-                                    torch.tensor(float(rn.shape[0]), dtype=torch.float64, device=rn.device)]))
+        pair = reducer(TorchSmallKernels.rnsum(rn))
         total, count = pair[0].clone(), pair[1].clone()
         ctx.mark_non_differentiable(count)
         return total, count
@@ -849,14 +869,12 @@ def _resolve_corners(model, K):
 
 
 def _phi_layer(layer, y, b, G, Z):
-    """admm_net.py:79-105."""
-    rho = F.softplus(layer.rho)
-    b_sq = torch.abs(b) ** 2 + EPS
-    return b_sq / (1 + rho * b_sq) * (y / (b + EPS) + rho * G[:, :-1, -1] + Z[:, :-1, -1])
+    """admm_net.py:79-105: the phi layer reads the border columns of G and Z only."""
+    return _phi_layer_gathered(layer, y, b, G[:, :-1, -1], Z[:, :-1, -1])
 
 
 def _phi_layer_gathered(layer, y, b, g_col, z_col):
-    """``_phi_layer`` on the border columns of G and Z."""
+    """``_phi_layer`` on the border columns of G and Z (slices on the tensor route, gathered vectors on the fused one)."""
     rho = F.softplus(layer.rho)
     b_sq = torch.abs(b) ** 2 + EPS
     return b_sq / (1 + rho * b_sq) * (y / (b + EPS) + rho * g_col + z_col)
@@ -915,27 +933,24 @@ def _group_mean(rn: torch.Tensor, sub_batch: Optional[int], reducer: Optional[Ca
 
 
 def _z_layer(layer, k, phi, h, G, Z, sub_batch=None, lk=None, sk=None, corner=None, reducer=None):
-    """admm_net.py:388-474.  ``lk``, ``sk``, ``corner``: as for ``_g_layer``; ``reducer``: as for ``unrolled_forward``."""
+    """admm_net.py:388-474.  ``lk``, ``sk``, ``corner``: as for ``_g_layer``; ``reducer``: as for ``unrolled_forward``.  Residual
+    norm and update follow ``lk``, the step size between them follows ``sk``."""
     if corner is None:
         corner = (1.0 / (F.softplus(layer.lambda_param) ** 2 + EPS)).item()
-    if sk is not None:
-        rn = _ResidualNorm.apply(G, phi, h, corner, lk)
-        step = _StepSize.apply(rn, layer.rho, *_net_params(layer.residual_scale_net), k / 10.0, sub_batch, sk, reducer)
-        return _StateUpdate.apply(Z, G, phi, h, step, corner, lk)
-    rho = F.softplus(layer.rho)
     if lk is None:
         R = G - _block_matrix(phi, h, corner)
         rn = torch.linalg.matrix_norm(R)                               # Frobenius, [B]
     else:
         rn = _ResidualNorm.apply(G, phi, h, corner, lk)
-    B = rn.shape[0]
-    feat = torch.stack([torch.full((B,), k / 10.0, device=rn.device),
-                        torch.full((B,), rho.item(), device=rn.device),
-                        rn / (_group_mean(rn, sub_batch, reducer) + EPS)], dim=1)
-    step = rho * (0.5 + 1.5 * layer.residual_scale_net(feat)).squeeze(1)
-    if lk is None:
-        return Z + step.reshape(-1, 1, 1) * R
-    return _StateUpdate.apply(Z, G, phi, h, step, corner, lk)
+    if sk is None:
+        rho, B = F.softplus(layer.rho), rn.shape[0]
+        feat = torch.stack([torch.full((B,), k / 10.0, device=rn.device),
+                            torch.full((B,), rho.item(), device=rn.device),
+                            rn / (_group_mean(rn, sub_batch, reducer) + EPS)], dim=1)
+        step = rho * (0.5 + 1.5 * layer.residual_scale_net(feat)).squeeze(1)
+    else:
+        step = _StepSize.apply(rn, layer.rho, *_net_params(layer.residual_scale_net), k / 10.0, sub_batch, sk, reducer)
+    return Z + step.reshape(-1, 1, 1) * R if lk is None else _StateUpdate.apply(Z, G, phi, h, step, corner, lk)
 
 
 def _peak_head(head, phi):
@@ -954,11 +969,48 @@ def _peak_head(head, phi):
     return torch.cat(taus, 1), torch.cat(fs, 1), torch.cat(cs, 1)
 
 
+# ---- the four steps of a layer.  ``r``: what ``unrolled_forward`` resolved its arguments to (kernel sets that are None where the
+# route does not use them); ``s``: the running state G, Z and, with layer kernels, their gathered border columns and diagonals
+def _phi_step(r, s, layer, y, b):
+    if r.sk is not None:
+        return _PhiStep.apply(y, b, s.g_col, s.z_col, layer.rho, r.sk)
+    if r.lk is not None:
+        return _phi_layer_gathered(layer, y, b, s.g_col, s.z_col)
+    return _phi_layer(layer, y, b, s.G, s.Z)
+
+
+def _h_step(r, s, layer, sigma):
+    if r.nk is not None:
+        return _HLayerStep.apply(s.g_dg, s.z_dg, sigma, layer.rho, layer.projection_weight, *_net_params(layer.correction_net), r.nk)
+    if r.sk is not None:
+        t = _HInput.apply(s.g_dg, s.z_dg, layer.rho, r.sk)
+        return _HProject.apply(t, layer.correction_net(t), sigma, layer.projection_weight, r.sk)
+    return _h_layer(layer, s.G, s.Z, sigma, None if r.lk is None else (s.g_dg, s.z_dg))
+
+
+def _g_step(r, s, layer, k, phi, h):
+    out = _g_layer(layer, phi, h, s.Z, r.solver, r.asm, r.lk, r.sk, r.corners[k][0], r.rinv[k])
+    if r.lk is None:
+        s.G = out
+    else:
+        s.G, s.g_col, s.g_dg = out
+
+
+def _z_step(r, s, layer, k, phi, h):
+    s.Z = _z_layer(layer, k, phi, h, s.G, s.Z, r.sub_batch, r.lk, r.sk, r.corners[k][1], r.reducer)
+    if r.lk is not None:
+        s.z_col, s.z_dg = _Gather.apply(s.Z, r.lk)
+
+
 def unrolled_forward(model, y: torch.Tensor, b: torch.Tensor, sigma: torch.Tensor,
                      solver: Optional[Callable] = None, assembler=None, sub_batch: Optional[int] = None,
                      fused: bool = False, layer_kernels=None, small: bool = False, small_kernels=None,
                      native: bool = False, native_kernels=None, reducer: Optional[Callable] = None):
     """Differentiable K-layer forward on the device of ``y`` (admm_net.py:742-764 / 791-816).
+
+    The flags ``fused`` ⊂ ``small`` ⊂ ``native`` and the ``*_kernels`` stand-ins are what ``route_kwargs(model.train_route,
+    kernels)`` returns; a stand-in without its flag, or a flag without the one below it, raises ``ValueError``.  The arguments
+    are resolved once; the layer loop below is the same for every route, and the step functions choose the form.
 
     ``sub_batch = g`` evaluates the consecutive groups of g signals as independent batches, each with its own mean
     (``_FusedBase.sub_batch``); None: the call is one batch.
@@ -979,8 +1031,8 @@ def unrolled_forward(model, y: torch.Tensor, b: torch.Tensor, sigma: torch.Tenso
     ``ADMMNet`` through ``_PeakHead`` (csrc/train_head.hip).
     ``reducer(t) -> t`` all-reduces (sum) a small float64 tensor across the ranks of a batch-sharded step
     (``sharded.ShardedTraining``): the mean of every Z layer is then over the signals of ALL ranks, one reduction of a
-    (sum, count) pair per layer in the forward and one of a scalar per layer in the backward.  None (default): the call is the
-    whole batch, today's code path.  Not combined with ``sub_batch``: groups never span ranks.
+    (sum, count) pair per live layer (K - 1) in the forward and one of a scalar per live layer in the backward.  None (default):
+    the call is the whole batch and no reduction runs.  Not combined with ``sub_batch``: groups never span ranks.
     Returns phi, or (tau, f, confidences, phi) when the model has a PeakSearchLayer.
     """
     if sub_batch is not None and sub_batch < 1:
@@ -1011,46 +1063,23 @@ def unrolled_forward(model, y: torch.Tensor, b: torch.Tensor, sigma: torch.Tenso
     b = b.to(torch.complex64)
     sigma = sigma.to(torch.float32).reshape(-1)
     B, n = y.shape[0], D + 1
-    G = torch.zeros(B, n, n, dtype=torch.complex64, device=y.device)
-    Z = torch.zeros_like(G)
+    # the phi and H layers read only the border column and the diagonal of G and Z: with layer kernels, gathered once per layer
+    col = None if lk is None else torch.zeros(B, D, dtype=torch.complex64, device=y.device)
+    dg = None if lk is None else torch.zeros(B, D, dtype=torch.float32, device=y.device)
+    s = SimpleNamespace(G=torch.zeros(B, n, n, dtype=torch.complex64, device=y.device), g_col=col, z_col=col, g_dg=dg, z_dg=dg)
+    s.Z = torch.zeros_like(s.G)
+    # what the call resolved to.  Per layer (corner_g, corner_z) and rinv; None: the layer evaluates it itself
+    r = SimpleNamespace(solver=solver, asm=asm, lk=lk, sk=sk, nk=nk, sub_batch=sub_batch, reducer=reducer,
+                        corners=_resolve_corners(model, K) if sk is not None else [(None, None)] * K,
+                        rinv=_resolve_rinv(model, K) if nk is not None and K > 1 else [None] * K)
     phi = None
-    if lk is not None:
-        # the phi and H layers read only the border column and the diagonal of G and Z: gathered once per layer
-        g_col = z_col = torch.zeros(B, D, dtype=torch.complex64, device=y.device)
-        g_dg = z_dg = torch.zeros(B, D, dtype=torch.float32, device=y.device)
-    corners = _resolve_corners(model, K) if sk is not None else None
-    rinv = _resolve_rinv(model, K) if nk is not None and K > 1 else None
     for k in range(K):
-        if sk is not None:
-            phi = _PhiStep.apply(y, b, g_col, z_col, model.phiLayers[k].rho, sk)
-            if k == K - 1:
-                break
-            hl = model.hLayers[k]
-            if nk is not None:
-                h = _HLayerStep.apply(g_dg, z_dg, sigma, hl.rho, hl.projection_weight, *_net_params(hl.correction_net), nk)
-            else:
-                t = _HInput.apply(g_dg, z_dg, hl.rho, sk)
-                h = _HProject.apply(t, hl.correction_net(t), sigma, hl.projection_weight, sk)
-            G, g_col, g_dg = _g_layer(model.gLayers[k], phi, h, Z, solver, asm, lk, sk, corners[k][0],
-                                      None if rinv is None else rinv[k])
-            Z = _z_layer(model.zLayers[k], k, phi, h, G, Z, sub_batch, lk, sk, corners[k][1], reducer)
-            z_col, z_dg = _Gather.apply(Z, lk)
-            continue
-        if lk is None:
-            phi = _phi_layer(model.phiLayers[k], y, b, G, Z)
-        else:
-            phi = _phi_layer_gathered(model.phiLayers[k], y, b, g_col, z_col)
+        phi = _phi_step(r, s, model.phiLayers[k], y, b)
         if k == K - 1:
             break
-        if lk is None:
-            h = _h_layer(model.hLayers[k], G, Z, sigma)
-            G = _g_layer(model.gLayers[k], phi, h, Z, solver, asm)
-            Z = _z_layer(model.zLayers[k], k, phi, h, G, Z, sub_batch, reducer=reducer)
-        else:
-            h = _h_layer(model.hLayers[k], None, None, sigma, (g_dg, z_dg))
-            G, g_col, g_dg = _g_layer(model.gLayers[k], phi, h, Z, solver, asm, lk)
-            Z = _z_layer(model.zLayers[k], k, phi, h, G, Z, sub_batch, lk, reducer=reducer)
-            z_col, z_dg = _Gather.apply(Z, lk)
+        h = _h_step(r, s, model.hLayers[k], sigma)
+        _g_step(r, s, model.gLayers[k], k, phi, h)
+        _z_step(r, s, model.zLayers[k], k, phi, h)
     if getattr(model, "_HAS_HEAD", False):
         if nk is not None:
             tau, f, conf = _peak_head_native(model.peakSearchLayer, phi, nk)

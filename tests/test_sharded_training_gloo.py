@@ -201,12 +201,7 @@ def test_without_a_process_group_it_is_the_plain_path(path, route):
             assert st.weight == 1.0 and st.global_batch == int(z["meta"][3])
             st.backward(TT.loss_of(out, t, head) * st.weight)
         else:
-            out = training.unrolled_forward(m, t("y"), t("b"), t("sigma"), fused=route != "tensor", small=route in ("full", "native"),
-                                            native=route == "native",
-                                            **{k: v for k, v in KERNELS.items()
-                                               if k in ("solver", "assembler") or (k == "layer_kernels" and route != "tensor")
-                                               or (k == "small_kernels" and route in ("full", "native"))
-                                               or (k == "native_kernels" and route == "native")})
+            out = training.unrolled_forward(m, t("y"), t("b"), t("sigma"), **training.route_kwargs(route, KERNELS))
             TT.loss_of(out, t, head).backward()
         grads.append(([o.detach() for o in out] if head else [out.detach()], [p.grad for p in m.parameters()]))
     (out_a, g_a), (out_b, g_b) = grads
