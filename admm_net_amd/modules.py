@@ -23,7 +23,7 @@ from typing import Optional
 import torch
 import torch.nn as nn
 
-from . import _lib
+from . import _lib, ops
 from ._lib import Cfg
 from .options import Options
 
@@ -300,9 +300,8 @@ class _FusedBase(nn.Module):
         if y.dim() != 2 or y.shape[1] != D or b.shape != y.shape:
             raise ValueError(f"y, b must be [B, {D}] complex; got {tuple(y.shape)}, {tuple(b.shape)}")
         B = y.shape[0]
-        yd = y.detach().to(dev, torch.complex64).contiguous()
-        bd = b.detach().to(dev, torch.complex64).contiguous()
-        sd = sigma.detach().to(dev, torch.float32).reshape(-1).contiguous()
+        yd, bd = ops._c64(y, dev, (B, D), "y"), ops._c64(b, dev, (B, D), "b")   # the one place a caller's tensor becomes a pointer
+        sd = ops._f32(sigma.reshape(-1), dev, None, "sigma")
         if sd.numel() != B:
             raise ValueError("sigma must have one entry per signal")
         with torch.cuda.device(dev):

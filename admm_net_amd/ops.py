@@ -2,6 +2,11 @@
 
 Every function takes CUDA (HIP) tensors, enqueues on the current stream and
 returns device tensors.  No CPU path exists.
+
+Tensor inputs: an input in any form -- strided, lazily conjugated or negated, of a wider dtype, part
+of a graph, unaligned -- gives the bits of the call on the plain tensor of the same value (``_plain``); an in-place or
+caller-owned argument is never copied and refuses what the kernel could not write faithfully (``_no_lazy_bits`` and the
+checks around it).
 """
 from __future__ import annotations
 
@@ -34,7 +39,7 @@ def eigh(A: torch.Tensor, options=None):
     """
     _need_cuda(A, "A")
     lib = _lib.load()
-    A = A.to(torch.complex64).contiguous()
+    A = _c64(A, A.device, None, "A")
     B, n, _ = A.shape
     dev = A.device
     with torch.cuda.device(dev):
@@ -60,11 +65,9 @@ def vdvh(V: torch.Tensor, d: torch.Tensor) -> torch.Tensor:
     V: [B, n, n] complex64 (columns = eigenvectors), d: [B, n] float32.  Returns [B, n, n] complex64."""
     _need_cuda(V, "V")
     lib = _lib.load()
-    V = V.to(torch.complex64).resolve_conj().contiguous()       # a lazily conjugated view keeps its conj bit through .contiguous()
-    d = d.to(device=V.device, dtype=torch.float32).contiguous()
+    V = _c64(V, V.device, None, "V")
     B, n, _ = V.shape
-    if d.shape != (B, n):
-        raise ValueError(f"d must be [{B}, {n}], got {tuple(d.shape)}")
+    d = _f32(d, V.device, (B, n), "d")
     with torch.cuda.device(V.device):
         out = torch.empty_like(V)
         _lib.check(lib.admmnet_vdvh_c64(n, B, _ptr(V), _ptr(d), _ptr(out), _stream(V.device)), "admmnet_vdvh_c64")
@@ -77,11 +80,9 @@ def vhsv(V: torch.Tensor, S: torch.Tensor) -> torch.Tensor:
     V, S: [B, n, n] complex64.  Returns [B, n] float32."""
     _need_cuda(V, "V")
     lib = _lib.load()
-    V = V.to(torch.complex64).resolve_conj().contiguous()
-    S = S.to(device=V.device, dtype=torch.complex64).resolve_conj().contiguous()
+    V = _c64(V, V.device, None, "V")
     B, n, _ = V.shape
-    if S.shape != V.shape:
-        raise ValueError("S must have the shape of V")
+    S = _c64(S, V.device, V.shape, "S")
     with torch.cuda.device(V.device):
         q = torch.empty(B, n, dtype=torch.float32, device=V.device)
         _lib.check(lib.admmnet_vhsv_f32(n, B, _ptr(V), _ptr(S), _ptr(q), _stream(V.device)), "admmnet_vhsv_f32")
@@ -91,18 +92,43 @@ def vhsv(V: torch.Tensor, S: torch.Tensor) -> torch.Tensor:
 # ---- training route: the n^2-sized steps of one layer (csrc/train_layer.hip) --------------------------------------------------
 # C(phi, h, c) = [[diag h, phi], [phi^H, c]], herm(X) = (X + X^H) / 2.  Matrices [B, n, n] complex64, phi [B, D] complex64,
 # h [B, D] float32 (D = n - 1); r (0-dim) and s [B] are float32 DEVICE tensors, corner a Python float.
-def _c64(t, dev, shape, name):
-    t = t.detach().to(device=dev, dtype=torch.complex64).resolve_conj().contiguous()
-    if tuple(t.shape) != tuple(shape):
+def _plain(t, dev, dtype, shape, name):
+    """THE place a caller's input tensor becomes what a kernel may read through ``data_ptr()``: detached, on ``dev``, of
+    ``dtype``, with the conj and the neg bit resolved (both survive ``.to`` of the same dtype, ``.detach()`` and
+    ``.contiguous()``, and the memory behind them holds the conjugate / the negative) and contiguous.  A tensor that is all of
+    that already comes back as it is, without a copy.  The memory is 16-byte aligned, as a fresh allocation is: the streaming
+    kernels of csrc/train_layer.hip choose their vector path, and with it the order of their sums, by the pointers' alignment,
+    so a contiguous view one element into a buffer would otherwise give other bits than its own copy.  ``shape``: checked
+    unless None."""
+    t = t.detach()
+    if not (t.dtype == dtype and t.device == dev and t.is_contiguous() and t.data_ptr() % 16 == 0) or t.is_conj() or t.is_neg():
+        t = t.to(device=dev, dtype=dtype).resolve_conj().resolve_neg().contiguous()
+        if t.data_ptr() % 16:
+            t = t.clone()
+    if shape is not None and tuple(t.shape) != tuple(shape):
         raise ValueError(f"{name} must be {tuple(shape)}, got {tuple(t.shape)}")
     return t
 
 
-def _f32(t, dev, shape, name):
-    t = t.detach().to(device=dev, dtype=torch.float32).contiguous()
-    if tuple(t.shape) != tuple(shape):
-        raise ValueError(f"{name} must be {tuple(shape)}, got {tuple(t.shape)}")
-    return t
+def _c64(t, dev, shape=None, name="tensor"):
+    return _plain(t, dev, torch.complex64, shape, name)
+
+
+def _f32(t, dev, shape=None, name="tensor"):
+    return _plain(t, dev, torch.float32, shape, name)
+
+
+def _num(t, dev, dtype, shape=None, name="tensor"):
+    """``_plain`` for the inputs the kernels read as float64 or as integers (grids, images, counts, masks)."""
+    return _plain(t, dev, dtype, shape, name)
+
+
+def _no_lazy_bits(t, what):
+    """Refuses a tensor a kernel is to WRITE (or reads without a copy) whose conj or neg bit is set: its memory holds the
+    conjugate / the negative of its value, and resolving the bit would hand the kernel a copy."""
+    if t.is_conj() or t.is_neg():
+        raise ValueError(f"{what} is a lazily {'conjugated' if t.is_conj() else 'negated'} view (its memory holds the "
+                         f"{'conjugate' if t.is_conj() else 'negative'} of its value); pass a resolved tensor")
 
 
 def _train_args(M, name):
@@ -417,7 +443,7 @@ def _head_args(phi, keep, p, L, hp):
         if not 0.0 <= p < 1.0:
             raise ValueError(f"the dropout probability must be in [0, 1), got {p}")
         _need_cuda(keep, "keep")
-        keep = keep.to(dev).contiguous()
+        keep = _num(keep, dev, keep.dtype, None, "keep")
     table = (ctypes.c_void_p * len(hp))(*[t.data_ptr() for t in hp])
     return lib, dev, B, D, hp, keep, table
 
@@ -550,9 +576,11 @@ def train_stepsize_bwd(g_step, rn, rho, W1, b1, W2, b2, knorm: float, sub_batch=
 # ---- the step size from a mean that comes from outside the call (the sharded training of admm_net_amd/sharded.py) ---------------
 # ``pair``: device float64 [2] = (sum of rn, number of signals) of the WHOLE batch; the kernels form the mean themselves.
 def _f64(t, dev, numel, name):
-    """A dense float64 device tensor of ``numel`` elements, as the kernels read it: no conversion is made."""
+    """A dense float64 device tensor of ``numel`` elements, as the kernels read it: no conversion is made, so another dtype or
+    device and a lazily negated view are refused (``ValueError``)."""
     if not isinstance(t, torch.Tensor) or t.dtype != torch.float64 or t.device != dev or t.numel() != numel:
         raise ValueError(f"{name} must be a float64 tensor of {numel} element(s) on {dev}")
+    _no_lazy_bits(t, name)
     return t.detach().contiguous().reshape(numel)
 
 
@@ -643,9 +671,7 @@ def _anm_args(tau, f, conf, tau_true, f_true, L_true, phi):
     with torch.cuda.device(dev):
         real = [_f32(t, dev, (B, Lmax), name) for t, name in ((tau, "tau"), (f, "f"), (conf, "conf"), (tau_true, "tau_true"),
                                                               (f_true, "f_true"))]
-        L_true = L_true.detach().to(device=dev, dtype=torch.int64).contiguous()
-        if tuple(L_true.shape) != (B,):
-            raise ValueError(f"L_true must be ({B},), got {tuple(L_true.shape)}")
+        L_true = _num(L_true, dev, torch.int64, (B,), "L_true")
         phi = _c64(phi, dev, (B, D), "phi")
     return _lib.load(), dev, B, Lmax, D, (*real, L_true, phi)
 
@@ -708,8 +734,8 @@ def loss_phi_bwd(g_out, phi, phi_true, amplitude_weight: float, phase_weight: fl
 # ---- AdamW and gradient-norm clipping over a tensor list (csrc/optim.hip) --------------------------------------------------------
 def _optim_lists(what, *lists):
     """(lib, device, count, numel array, one pointer array per list) of same-length lists of dense float32 device tensors of
-    pairwise equal shapes.  ``TypeError`` for what is no float32 tensor, ``ValueError`` for a sparse, non-contiguous or host
-    tensor and for tensors on different devices: there is no other path."""
+    pairwise equal shapes.  ``TypeError`` for what is no float32 tensor, ``ValueError`` for a sparse, non-contiguous, lazily
+    negated or host tensor and for tensors on different devices: there is no other path."""
     count = len(lists[0])
     if any(len(l) != count for l in lists):
         raise ValueError(f"{what}: the tensor lists have different lengths {[len(l) for l in lists]}")
@@ -727,6 +753,7 @@ def _optim_lists(what, *lists):
                 raise ValueError(f"{what}: tensor {i} is on {t.device}; the kernels read HIP device tensors (no CPU path)")
             if not t.is_contiguous():
                 raise ValueError(f"{what}: tensor {i} of shape {tuple(t.shape)} and strides {t.stride()} is not contiguous")
+            _no_lazy_bits(t, f"{what}: tensor {i}")
             if dev is None:
                 dev = t.device
             elif t.device != dev:
@@ -744,6 +771,7 @@ def _optim_coef(what, coef, dev):
         raise TypeError(f"{what}: coef must be a float32 tensor, got {coef.dtype if isinstance(coef, torch.Tensor) else type(coef).__name__}")
     if coef.numel() != 1 or coef.device != dev:
         raise ValueError(f"{what}: coef must hold one element on {dev}, got {coef.numel()} on {coef.device} (no copy is made)")
+    _no_lazy_bits(coef, f"{what}: coef")
     return coef.detach().reshape(1)
 
 
@@ -783,6 +811,7 @@ def _optim_flat(what, flat, tensors, dev):
     if flat.device != dev or not flat.is_contiguous() or flat.dim() != 1 or flat.numel() < total:
         raise ValueError(f"{what}: flat must be a contiguous 1-d tensor of at least {total} elements on {dev}, got "
                          f"{tuple(flat.shape)} on {flat.device}")
+    _no_lazy_bits(flat, f"{what}: flat")
     return flat.detach()
 
 
@@ -850,9 +879,8 @@ def glayer(model, k: int, phi: torch.Tensor, h: torch.Tensor, Z=None):
         w = torch.empty(B, n, dtype=torch.float32, device=dev)
         rn = torch.empty(B, dtype=torch.float32, device=dev)
         status = torch.zeros(4, dtype=torch.int32, device=dev)
-        phi = phi.to(torch.complex64).contiguous()
-        h = h.to(torch.float32).contiguous()
-        Zc = None if Z is None else Z.to(torch.complex64).contiguous()
+        phi, h = _c64(phi, dev, (B, D), "phi"), _f32(h, dev, (B, D), "h")
+        Zc = None if Z is None else _c64(Z, dev, (B, n, n), "Z")
         _lib.check(lib.admmnet_glayer_f32(ctypes.byref(cfg), _ptr(lw), _ptr(phi), _ptr(h), _ptr(Zc), B, _ptr(G),
                                           _ptr(w), _ptr(rn), _ptr(ws), need, _ptr(status), _stream(dev)),
                    "admmnet_glayer_f32")
@@ -865,8 +893,9 @@ def glayer(model, k: int, phi: torch.Tensor, h: torch.Tensor, Z=None):
 def glayer_spectral(model, k: int, phi: torch.Tensor, h: torch.Tensor, Z: torch.Tensor, G: torch.Tensor, rn: torch.Tensor,
                     mode: int = 0, alpha=None, phi_prev=None, h_prev=None, waves: int = 0):
     """The matrix-function G-layer of layer k of ``model`` (csrc/spectral_fused.hip, admmnet_glayer_spectral_f32) on
-    caller-supplied state, IN PLACE: Z, G [B, n, n] complex64 and rn [B] float32 must be contiguous device tensors; only
-    their lower triangles are read or written, G and rn only for accepted matrices.
+    caller-supplied state, IN PLACE: Z, G [B, n, n] complex64 and rn [B] float32 must be contiguous device tensors without conj
+    or neg bit (``ValueError`` otherwise, before any launch); only their lower triangles are read or written, G and rn only for
+    accepted matrices.
 
     mode 0: Z is the state layer k reads.  mode 1: the Z-layer update of layer k-1, Z <- Z + alpha (G - C_prev), is applied
     first (G holds G of layer k-1 on entry; alpha [B], phi_prev [B, D], h_prev [B, D] of layer k-1).  mode 2: as 1 with
@@ -882,6 +911,7 @@ def glayer_spectral(model, k: int, phi: torch.Tensor, h: torch.Tensor, Z: torch.
                                (rn, "rn", torch.float32, (B,))):
         if t.device != dev or t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous():
             raise ValueError(f"{name} must be a contiguous {dt} tensor {shape} on {dev}")
+        _no_lazy_bits(t, name)
     if mode not in (0, 1, 2):
         raise ValueError(f"mode must be 0, 1 or 2, got {mode}")
     cfg = model.cfg()
@@ -889,12 +919,10 @@ def glayer_spectral(model, k: int, phi: torch.Tensor, h: torch.Tensor, Z: torch.
         W = model.packed_weights(dev)
         lw = W[lib.admmnet_layer_weight_offset(ctypes.byref(cfg), k):]
         lwp = W[lib.admmnet_layer_weight_offset(ctypes.byref(cfg), k - 1):] if mode else None
-        phi = phi.to(torch.complex64).contiguous()
-        h = h.to(torch.float32).contiguous()
+        phi, h = _c64(phi, dev, (B, D), "phi"), _f32(h, dev, (B, D), "h")
         if mode:
-            alpha = alpha.to(dev, torch.float32).contiguous()
-            phi_prev = phi_prev.to(dev, torch.complex64).contiguous()
-            h_prev = h_prev.to(dev, torch.float32).contiguous()
+            alpha = _f32(alpha, dev, (B,), "alpha")
+            phi_prev, h_prev = _c64(phi_prev, dev, (B, D), "phi_prev"), _f32(h_prev, dev, (B, D), "h_prev")
         else:
             alpha = phi_prev = h_prev = None
         flag = torch.full((B,), -1, dtype=torch.int32, device=dev)
@@ -914,10 +942,9 @@ def spectrum(phi: torch.Tensor, xbase: int, ybase: int, taus: torch.Tensor, fs: 
     _need_cuda(phi, "phi")
     lib = _lib.load()
     dev = phi.device
-    phi = phi.to(torch.complex64).contiguous()
+    phi = _c64(phi, dev, None, "phi")
     B = phi.shape[0]
-    taus = taus.to(dev, torch.float64).contiguous()
-    fs = fs.to(dev, torch.float64).contiguous()
+    taus, fs = _num(taus, dev, torch.float64, None, "taus"), _num(fs, dev, torch.float64, None, "fs")
     nx, ny = taus.numel(), fs.numel()
     with torch.cuda.device(dev):
         need = lib.admmnet_spectrum_workspace_bytes(xbase, ybase, nx, ny)
@@ -958,7 +985,7 @@ def peak_search(phi: torch.Tensor, xbase: int, ybase: int, opts=None, max_peaks:
         ws = torch.empty(need, dtype=torch.uint8, device=dev)
         o7 = (_ct.c_double * 7)(so["xmin"], so["xmax"], so["xstep"], so["ymin"], so["ymax"], so["ystep"],
                                so["reducefactor"])
-        phi = phi.to(torch.complex64).contiguous()
+        phi = _c64(phi, dev, (B, D), "phi")
         _lib.check(lib.admmnet_peak_search_f64(_ptr(phi), B, xbase, ybase, _ptr(tx), nx, _ptr(ty), ny, o7,
                                                int(so["iter"]), max_peaks, _ptr(peaks), _ptr(counts), _ptr(ws), need,
                                                _stream(dev)), "admmnet_peak_search_f64")
@@ -993,9 +1020,7 @@ def peak_top(phi: torch.Tensor, xbase: int, ybase: int, opts=None, top: int = 3,
         rows = torch.full((B, top, 3), float("nan"), dtype=torch.float64, device=dev)
         counts = torch.zeros(B, dtype=torch.int32, device=dev)
         if top_n is not None:
-            top_n = torch.as_tensor(top_n).to(device=dev, dtype=torch.int32).contiguous()
-            if tuple(top_n.shape) != (B,):
-                raise ValueError(f"top_n must be [{B}], got {tuple(top_n.shape)}")
+            top_n = _num(torch.as_tensor(top_n), dev, torch.int32, (B,), "top_n")
         if nx == 0 or ny == 0:
             return rows, counts
         tx = torch.from_numpy(ax).to(dev)
@@ -1006,7 +1031,7 @@ def peak_top(phi: torch.Tensor, xbase: int, ybase: int, opts=None, top: int = 3,
         ws = torch.empty(need, dtype=torch.uint8, device=dev)
         o7 = (ctypes.c_double * 7)(so["xmin"], so["xmax"], so["xstep"], so["ymin"], so["ymax"], so["ystep"],
                                    so["reducefactor"])
-        phi = phi.detach().to(torch.complex64).contiguous()
+        phi = _c64(phi, dev, (B, D), "phi")
         _lib.check(lib.admmnet_peak_top_f64(_ptr(phi), B, xbase, ybase, _ptr(tx), nx, _ptr(ty), ny, o7, int(so["iter"]),
                                             top, _ptr(top_n), _ptr(rows), _ptr(counts), _ptr(ws), need, _stream(dev)),
                    "admmnet_peak_top_f64")
@@ -1019,7 +1044,7 @@ def regional_maxima(Z: torch.Tensor):
     _need_cuda(Z, "Z")
     lib = _lib.load()
     dev = Z.device
-    Z = Z.to(torch.float64).contiguous()
+    Z = _num(Z, dev, torch.float64, None, "Z")
     B, ny, nx = Z.shape
     cap = nx * ny
     with torch.cuda.device(dev):

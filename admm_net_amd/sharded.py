@@ -97,9 +97,8 @@ class HipLayerEngine:
         self.B = y.shape[0]
         g = model.sub_batch
         self.ngroups = -(-self.B // g) if g else 1   # (sum, count) pairs per layer: one per sub-batch
-        self.y = y.detach().to(dev, torch.complex64).contiguous()
-        self.b = b.detach().to(dev, torch.complex64).contiguous()
-        self.sigma = sigma.detach().to(dev, torch.float32).reshape(-1).contiguous()
+        self.y, self.b = ops._c64(y, dev, (self.B, D), "y"), ops._c64(b, dev, (self.B, D), "b")
+        self.sigma = ops._f32(sigma.reshape(-1), dev, None, "sigma")
         with torch.cuda.device(dev):
             self.W = model.packed_weights(dev)
             self.ws = model.workspace(self.B, dev)
