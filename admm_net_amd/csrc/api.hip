@@ -10,6 +10,7 @@
 
 #include "common.h"
 #include "options.h"
+#include "score_core.h"
 
 namespace admmnet {
 
@@ -1118,6 +1119,45 @@ int admmnet_loss_phi_bwd_c64(int32_t D, int64_t B, const float *g_out, const voi
     if (int rc = loss_args_ok("loss_phi_bwd", 1, D, B, g_out && phi && phi_true && g_phi)) return rc;
     return launch_loss_phi_bwd(D, B, g_out, (const float2 *)phi, (const float2 *)phi_true, amplitude_weight, phase_weight,
                                (float2 *)g_phi, (hipStream_t)stream);
+}
+
+// ---- estimates against ground truth (score.hip) ------------------------------------------------------------------------------
+// one lane per estimate and per target (<= 64 each); the slab grid must fit 31 bits
+static int score_args_ok(const char *what, int32_t Le, int32_t Lt, int64_t B, bool ptrs) {
+    if (Le < 1 || Le > SC_MAX || Lt < 1 || Lt > SC_MAX || B < 1 || train_small_rows(B) > 0x7fffffffLL || !ptrs) {
+        set_error("%s: bad argument (Le=%d, Lt=%d, B=%lld, or a null pointer)", what, Le, Lt, (long long)B);
+        return ADMMNET_E_ARG;
+    }
+    return ADMMNET_OK;
+}
+
+int64_t admmnet_score_partials(int64_t B) {
+    if (B < 1) return -1;
+    return score_partials(B);
+}
+
+int admmnet_score_match_f64(int32_t Le, int32_t Lt, int64_t B, const double *est, const int32_t *n_est, const float *tau_true,
+                            const float *f_true, const int64_t *L_true, const double *opts, int32_t *match, double *stats,
+                            double *totals, int32_t *status, double *partials, void *stream) {
+    if (int rc = score_args_ok("score_match", Le, Lt, B, est && tau_true && f_true && opts && match && stats && totals && status && partials))
+        return rc;
+    if (!sc_opts_ok(opts) || !sc_finite(opts[2] * opts[2])) {
+        set_error("score_match: bad options (sx=%g, sy=%g must be > 0, cutoff=%g > 0 with a finite square, periods %g, %g >= 0)",
+                  opts[0], opts[1], opts[2], opts[3], opts[4]);
+        return ADMMNET_E_ARG;
+    }
+    return launch_score_match(Le, Lt, B, est, n_est, tau_true, f_true, L_true, opts, match, stats, totals, status, partials,
+                              (hipStream_t)stream);
+}
+
+int admmnet_score_ordered_f32(int32_t Lmax, int64_t B, const float *tau_est, const float *f_est, const float *tau_true,
+                              const float *f_true, const int64_t *L_true, double *per_sample, double *out, int32_t *status,
+                              double *partials, void *stream) {
+    if (int rc = score_args_ok("score_ordered", Lmax, Lmax, B,
+                               tau_est && f_est && tau_true && f_true && L_true && per_sample && out && status && partials))
+        return rc;
+    return launch_score_ordered(Lmax, B, tau_est, f_est, tau_true, f_true, L_true, per_sample, out, status, partials,
+                                (hipStream_t)stream);
 }
 
 // ---- AdamW and gradient-norm clipping over a tensor list (optim.hip) ---------------------------------------------------------

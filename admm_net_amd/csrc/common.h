@@ -302,6 +302,14 @@ int launch_loss_phi(int D, int64_t B, const float2 *phi, const float2 *phi_true,
 int launch_loss_phi_bwd(int D, int64_t B, const float *g_out, const float2 *phi, const float2 *phi_true, float amplitude_weight,
                         float phase_weight, float2 *g_phi, hipStream_t st);
 
+// score.hip (estimates against ground truth: the truncated-cost assignment and the ordered RMSE; float64 sums over the batch)
+int64_t score_partials(int64_t B);                    // doubles of partial-sum scratch of either call
+int launch_score_match(int Le, int Lt, int64_t B, const double *est, const int32_t *n_est, const float *tau_true,
+                       const float *f_true, const int64_t *L_true, const double *opts, int32_t *match, double *stats, double *totals,
+                       int32_t *status, double *part, hipStream_t st);
+int launch_score_ordered(int Lmax, int64_t B, const float *tau_est, const float *f_est, const float *tau_true, const float *f_true,
+                         const int64_t *L_true, double *per_sample, double *out, int32_t *status, double *part, hipStream_t st);
+
 // optim.hip (AdamW and gradient-norm clipping over a tensor list; host arrays of device pointers)
 int64_t optim_blocks(int count, const int64_t *numel);   // blocks of the list = doubles of `partials`; -1: bad count or too many
 int launch_optim_gradnorm(int count, const float *const *grads, const int64_t *numel, float max_norm, double *partials,

@@ -13,6 +13,9 @@ CLI:  python -m admm_net_amd.harness time-net  --layers 5 --runs 1000 --out time
       python -m admm_net_amd.harness train-step --layers 10 --batch 256 --steps 20 [--route fused|full|native] [--grid 16x16] [--optim hip]   (one JSON line)
       python -m torch.distributed.run --nproc-per-node N -m admm_net_amd.harness train-step ...   (the step through sharded.ShardedTraining; --batch per rank; rank 0's line gains n_ranks, global_batch)
       python -m admm_net_amd.harness loss-step --batch 256 --targets 3 --dim 100 --steps 200                              (one JSON line)
+      python -m admm_net_amd.harness score-step [--steps 50] [--repeats 5] [--host-signals 2048]                          (one JSON line)
+      python -m admm_net_amd.harness evaluate --grid 10x10 --layers 10 [--checkpoint P] --snr 5 15 25 --signals 4096 --targets 3 --cutoff 1.0 [--baseline classical]
+                                                                                                    (one JSON line per SNR and method)
 """
 from __future__ import annotations
 
@@ -267,6 +270,100 @@ def time_loss_step(batch=256, targets=3, dim=100, steps=200, warmup=10, seed=0, 
     return out
 
 
+def _score_case(batch, n_est, n_true, seed, dev):
+    """Scenes drawn like ``synth.make_batch`` with estimates = shuffled truth + N(0, 0.03) and strays, as device tensors."""
+    rng = np.random.default_rng(seed)
+    from .synth import F_RANGE, TAU_RANGE
+    tt = rng.uniform(*TAU_RANGE, size=(batch, n_true)).astype(np.float32)
+    ft = rng.uniform(*F_RANGE, size=(batch, n_true)).astype(np.float32)
+    est = np.stack([rng.uniform(*TAU_RANGE, size=(batch, n_est)), rng.uniform(*F_RANGE, size=(batch, n_est)),
+                    rng.uniform(size=(batch, n_est))], axis=2)
+    k = min(n_est, n_true)
+    est[:, :k, 0] = tt[:, :k] + rng.normal(0, 0.03, size=(batch, k))
+    est[:, :k, 1] = ft[:, :k] + rng.normal(0, 0.03, size=(batch, k))
+    order = rng.random((batch, n_est)).argsort(axis=1)               # one row order per signal
+    est = np.take_along_axis(est, order[:, :, None], axis=1)
+    return torch.from_numpy(est).to(dev), torch.from_numpy(tt).to(dev), torch.from_numpy(ft).to(dev)
+
+
+def time_score_step(steps=50, warmup=5, repeats=5, host_signals=2048, seed=0, device="cuda:0",
+                    cases=((65536, 3, 3), (4096, 64, 64)), cutoff=0.1):
+    """Median wall time of ``metrics.match_targets`` (each call bracketed by a device synchronisation) at B = 65 536 with three
+    estimates and three targets and at B = 4096 with 64 of each, and of the host alternative in the same run: the batch copied to
+    the host, then the ``metrics.match_host`` loop -- timed over the first ``host_signals`` signals and reported per signal, the
+    copy of the whole batch apart.  ``repeats`` medians of ``steps`` calls each give the figure (their median) and its spread
+    (largest less smallest).  Returns a dict."""
+    from . import metrics
+    dev = torch.device(device)
+    out = {"steps": steps, "repeats": repeats, "cutoff": cutoff, "cases": []}
+    for batch, n_est, n_true in cases:
+        est, tt, ft = _score_case(batch, n_est, n_true, seed, dev)
+        medians = []
+        for rep in range(repeats):
+            times = []
+            for i in range(warmup + steps):
+                torch.cuda.synchronize(dev)
+                t0 = time.perf_counter()
+                metrics.match_targets(est, tt, ft, cutoff=cutoff)
+                torch.cuda.synchronize(dev)
+                if i >= warmup:
+                    times.append(time.perf_counter() - t0)
+            medians.append(float(np.median(times)) * 1e3)
+        t0 = time.perf_counter()
+        h_est, h_tt, h_ft = est.cpu().numpy(), tt.cpu().numpy(), ft.cpu().numpy()
+        copy_ms = (time.perf_counter() - t0) * 1e3
+        n = min(batch, host_signals)
+        t0 = time.perf_counter()
+        for i in range(n):
+            metrics.match_host(h_est[i, :, 0], h_est[i, :, 1], h_tt[i], h_ft[i], cutoff=cutoff)
+        host_us = (time.perf_counter() - t0) / n * 1e6
+        dev_ms = float(np.median(medians))
+        out["cases"].append({"batch": batch, "n_est": n_est, "n_true": n_true, "device_ms": round(dev_ms, 4),
+                             "device_ms_spread": round(max(medians) - min(medians), 4),
+                             "device_us_per_signal": round(dev_ms * 1e3 / batch, 5), "host_copy_ms": round(copy_ms, 3),
+                             "host_signals": n, "host_us_per_signal": round(host_us, 2),
+                             "host_ms_whole_batch": round(copy_ms + host_us * batch / 1e3, 1)})
+    return out
+
+
+def evaluate_snr(grid=(NB, ND), layers=10, checkpoint=None, snrs=(5.0, 15.0, 25.0), signals=4096, targets=3, cutoff=1.0,
+                 baseline=None, seed=0, device="cuda:0"):
+    """Detection and accuracy against the noise level: per SNR one batch of ``signals`` scenes at exactly that SNR
+    (``synth.make_batch_device(snr_range=(S, S))``), ``model.evaluate`` and ``metrics.summary`` -- scene, forward, peak search and
+    score without a host loop.  ``baseline="classical"`` scores the peaks of the classical solver's phi (the generator's labels)
+    the same way.  The model is ``PhiEstADMMNet`` at seed 0, or the checkpoint's.  Yields one dict per SNR and method."""
+    from . import PhiEstADMMNet, metrics, ops, synth
+    if baseline not in (None, "classical"):
+        raise ValueError(f"baseline must be None or 'classical', got {baseline!r}")
+    dev = torch.device(device)
+    M, N = grid
+    torch.manual_seed(seed)
+    model = PhiEstADMMNet(num_layers=layers, M=M, N=N, L=targets)
+    if checkpoint:
+        load_checkpoint(checkpoint, model)
+    model.eval()
+    head = {"grid": [M, N], "layers": layers, "signals": signals, "targets": targets, "cutoff": cutoff}
+    for i, snr in enumerate(snrs):
+        y, b, sigma, truth = synth.make_batch_device(signals, M, N, L=targets, seed=20260104 + seed + 7919 * i, snr_range=(snr, snr),
+                                                     device=dev, labels=baseline is not None)
+        res = model.evaluate(y, b, sigma, truth["tau"], truth["f"], cutoff=cutoff, top=targets)
+        yield {"snr": snr, "method": "net", **head, **metrics.summary(res)}
+        if baseline is not None:
+            opts = {"xstep": 1 / (10 * N), "ystep": 1 / (10 * M), "iter": 3}            # estimate's defaults
+            rows, _ = ops.peak_top(truth["phi"], M, N, opts, top=targets)
+            res = metrics.match_targets(rows, truth["tau"], truth["f"], cutoff=cutoff, scale=(float(N), float(M)), period=(1.0, 1.0))
+            yield {"snr": snr, "method": "classical", **head, **metrics.summary(res)}
+
+
+def _grid(ap, text):
+    try:
+        grid = tuple(int(v) for v in text.lower().split("x"))
+        assert len(grid) == 2 and min(grid) >= 1
+    except (ValueError, AssertionError):
+        ap.error(f"--grid must be MxN, got {text!r}")
+    return grid
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     sub = ap.add_subparsers(dest="cmd", required=True)
@@ -295,7 +392,30 @@ def main(argv=None):
     d.add_argument("--targets", type=int, default=3)
     d.add_argument("--dim", type=int, default=100)
     d.add_argument("--steps", type=int, default=200)
+    e = sub.add_parser("score-step")
+    e.add_argument("--steps", type=int, default=50)
+    e.add_argument("--repeats", type=int, default=5)
+    e.add_argument("--host-signals", type=int, default=2048)
+    f = sub.add_parser("evaluate")
+    f.add_argument("--grid", default=f"{NB}x{ND}", help="MxN")
+    f.add_argument("--layers", type=int, default=10)
+    f.add_argument("--checkpoint", default=None)
+    f.add_argument("--snr", type=float, nargs="+", default=[5.0, 15.0, 25.0])
+    f.add_argument("--signals", type=int, default=4096)
+    f.add_argument("--targets", type=int, default=3)
+    f.add_argument("--cutoff", type=float, default=1.0, help="in resolution cells")
+    f.add_argument("--baseline", choices=("classical",), default=None)
     args = ap.parse_args(argv)
+    if args.cmd == "score-step":
+        import json
+        print(json.dumps(time_score_step(args.steps, repeats=args.repeats, host_signals=args.host_signals)))
+        return
+    if args.cmd == "evaluate":
+        import json
+        for line in evaluate_snr(_grid(ap, args.grid), args.layers, args.checkpoint, args.snr, args.signals, args.targets,
+                                 args.cutoff, args.baseline):
+            print(json.dumps(line), flush=True)
+        return
     if args.cmd == "loss-step":
         import json
         print(json.dumps(time_loss_step(args.batch, args.targets, args.dim, args.steps)))

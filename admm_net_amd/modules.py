@@ -343,7 +343,13 @@ class _FusedBase(nn.Module):
 
         Returns (tau [B, top], f [B, top], height [B, top] float64, rank order, NaN where a signal has fewer peaks;
         counts [B] int32, the number of regional maxima; phi [B, M*N] complex64)."""
-        from . import ops
+        rows, counts, phi = self._estimate_rows(y, b, sigma, top, top_n, opts, xbase, ybase)
+        out = y.device
+        return (rows[:, :, 0].contiguous().to(out), rows[:, :, 1].contiguous().to(out),
+                rows[:, :, 2].contiguous().to(out), counts.to(out), phi.to(out))
+
+    def _estimate_rows(self, y, b, sigma, top=None, top_n=None, opts=None, xbase=None, ybase=None):
+        """``estimate`` up to its device results: (rows [B, top, 3] float64, counts [B] int32, phi) on the compute device."""
         top = self.L if top is None else top
         xbase = self.M if xbase is None else xbase
         ybase = self.N if ybase is None else ybase
@@ -352,9 +358,31 @@ class _FusedBase(nn.Module):
         with torch.no_grad():
             phi, _ = self._run(y, b, sigma, to_caller=False)
             rows, counts = ops.peak_top(phi, xbase, ybase, opts, top=top, top_n=top_n)
-            out = y.device
-            return (rows[:, :, 0].contiguous().to(out), rows[:, :, 1].contiguous().to(out),
-                    rows[:, :, 2].contiguous().to(out), counts.to(out), phi.to(out))
+        return rows, counts, phi
+
+    def evaluate(self, y, b, sigma, tau_true, f_true, L_true=None, *, cutoff, scale=None, period=(1.0, 1.0), top=None, opts=None):
+        """``estimate`` scored against the truth in one call: the forward, the peak search, the top rows and the optimal
+        assignment of ``metrics.match_targets`` run on the device with no host loop and, with ``check_status = False``, no host
+        read; the rows never leave it.  ``top`` and ``opts`` as in ``estimate``; tau_true, f_true [B, Lt] and L_true as in
+        ``match_targets`` (moved to the compute device if they are elsewhere); ``cutoff`` in units of ``scale``.
+
+        ``scale = None`` means one resolution cell per axis, the length of that axis's steering vector: in the signal model
+        (synth.py:47-48, ``make_batch(B, M, N)``) tau's steering vector has N entries and f's has M, and the flattening
+        index = i_f N + i_tau is the ``phi.reshape(ybase, xbase)`` of peak_search.py with x = tau, so scale = (N, M) -- a
+        distance of 1 is one cell of the tau axis (1 / N) or of the f axis (1 / M).  (``estimate``'s default bases read
+        main_for_net.py literally, xbase = M; on the square grids the reference uses the two are the same.)
+        ``period = (1.0, 1.0)``: both axes are periodic with period 1, as the steering vectors are.
+
+        Returns a ``metrics.MatchResult`` of device tensors; ``metrics.summary`` reads it."""
+        from . import metrics
+        rows, _, _ = self._estimate_rows(y, b, sigma, top, None, opts)
+        dev = rows.device
+        if scale is None:
+            scale = (float(self.N), float(self.M))
+        tau_true, f_true = tau_true.to(dev), f_true.to(dev)
+        if L_true is not None:
+            L_true = L_true.to(dev)
+        return metrics.match_targets(rows, tau_true, f_true, L_true, cutoff=cutoff, scale=scale, period=period)
 
     # ---- training ----------------------------------------------------------
     def forward_autograd(self, y, b, sigma, reducer=None):

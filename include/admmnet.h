@@ -492,6 +492,42 @@ int admmnet_loss_phi_c64(int32_t D, int64_t B, const void *phi, const void *phi_
 int admmnet_loss_phi_bwd_c64(int32_t D, int64_t B, const float *g_out, const void *phi, const void *phi_true,
                              float amplitude_weight, float phase_weight, void *g_phi, void *stream);
 
+/* Target estimates scored against ground truth (csrc/score.hip, scalar core csrc/score_core.h): one wave per signal, sums over
+ * the batch in a fixed order without atomics (float64 across workgroups), so two runs give the same bits.  B >= 1; `partials` is
+ * double scratch of admmnet_score_partials(B) entries.  All tensors are dense with their natural alignment.
+ *   admmnet_score_match_f64   one optimal assignment per signal.  1 <= Le, Lt <= 64.
+ *       est       double [B][Le][3], the rows of admmnet_peak_top_f64: (tau, f, height).  The height is ignored; a row whose tau
+ *                 or f is not finite is absent.
+ *       n_est     int32 [B] or NULL (= Le): only the first n_est rows count, held to 0 .. Le.
+ *       tau_true, f_true   float [B][Lt];  L_true int64 [B] or NULL (= Lt): the first L_true slots are the targets.
+ *       opts      HOST double[5] = {sx, sy, cutoff, period_tau, period_f}: scales > 0, cutoff c > 0, a period 0 means the plain
+ *                 difference, P > 0 wraps it into [-P/2, P/2).
+ *     Definition, all in float64: with the present estimates i (n_est of them) and the targets j (n_true),
+ *       d2_ij = (sx dtau_ij)^2 + (sy df_ij)^2, the assignment matches k = min(n_est, n_true) pairs and minimises
+ *       sum min(d2, c^2); a matched pair with d2 < c^2 is a HIT, no other pair is reported.  This is the GOSPA assignment
+ *       (alpha = 2, p = 2): the truncation is inside the cost that is minimised -- solving without it and gating afterwards
+ *       gives another, wrong answer.  The solver is a shortest-augmenting-path search with potentials (rows = the smaller side,
+ *       costs recomputed from the coordinates, lowest lane first on ties).
+ *       match     int32 [B][Lt]: the index in `est` of the estimate that hit target j, else -1.
+ *       stats     double [B][8] = n_hit, n_miss = n_true - n_hit, n_false = n_est - n_hit, sum_hits dtau^2, sum_hits df^2,
+ *                 sum_hits d2, gospa^2 = sum_hits d2 + c^2 / 2 (n_miss + n_false), the optimal truncated cost.
+ *       totals    double [8]: the column sums of stats over the signals that were scored.
+ *       status    int32 [2]: [0] signals whose L_true lies outside [0, Lt], [1] signals with a non-finite tau_true or f_true
+ *                 among their first L_true.  Either kind gets NaN stats and a match row of -1 and is left out of totals;
+ *                 nothing is read out of bounds.
+ *   admmnet_score_ordered_f32   the validation RMSE of train.py:262-274, slot j against slot j.  tau_est, f_est, tau_true,
+ *       f_true float [B][Lmax], 1 <= Lmax <= 64, L_true int64 [B].  For L = L_true[b] > 0:
+ *       per_sample [B][2] = sqrt(mean_{j<L} (tau_est - tau_true)^2), the same for f, in float64 from the float inputs; NaN
+ *       where L = 0.  out [3] = the mean of each column over the signals with L > 0 (0 when there are none), and their count.
+ *       status [1] = signals whose L_true lies outside [0, Lmax]; they are evaluated with L held to that range. */
+int64_t admmnet_score_partials(int64_t B);
+int admmnet_score_match_f64(int32_t Le, int32_t Lt, int64_t B, const double *est, const int32_t *n_est, const float *tau_true,
+                            const float *f_true, const int64_t *L_true, const double *opts, int32_t *match, double *stats,
+                            double *totals, int32_t *status, double *partials, void *stream);
+int admmnet_score_ordered_f32(int32_t Lmax, int64_t B, const float *tau_est, const float *f_est, const float *tau_true,
+                              const float *f_true, const int64_t *L_true, double *per_sample, double *out, int32_t *status,
+                              double *partials, void *stream);
+
 /* AdamW and gradient-norm clipping over a LIST of float32 tensors (csrc/optim.hip): what a training loop writes as
  * torch.nn.utils.clip_grad_norm_(params, max_norm) and torch.optim.AdamW(...).step().  `count` tensors, tensor i dense with
  * numel[i] >= 0 elements; grads, params, exp_avg, exp_avg_sq are HOST arrays of `count` DEVICE pointers (as `params` of
