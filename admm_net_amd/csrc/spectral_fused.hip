@@ -1,6 +1,7 @@
 // spectral_fused.hip -- the matrix-function evaluation of the G-layer (spectral.hip has the mathematics and the checks) as ONE
-// kernel per chunk: a 768-thread workgroup per matrix reads the lower triangle of the state Z (six times, five of them from the
-// L2 / the memory-side cache), and writes the lower triangle of G once.  Nothing else goes through HBM -- no n x n scratch matrix.
+// kernel per chunk: a 768-thread workgroup per matrix reads the lower triangle of the state Z about six times (at n > 129 the
+// re-reads miss the L2 and come from HBM / the memory-side cache as well: DESIGN.md section 4, "Where its time goes"; below that
+// they hit it), and writes the lower triangle of G once.  Nothing else goes through HBM -- no n x n scratch matrix.
 //
 //   P1  the two outlier eigenpairs by subspace iteration, A x formed from the lower triangle of Z on the fly
 //       (A = [[diag h, phi], [phi^H, corner]] - Z / rho is never stored): wave w owns the rows i = w mod 12, lane l the columns
@@ -165,6 +166,24 @@ __device__ __forceinline__ float2 sf_a_elem(int i, int j, int D, float2 z, float
     return a;
 }
 
+// The clamped read of the lower triangle, one form for the row sweep and the assembly: a lane whose element (i, j) lies outside
+// the triangle or the matrix reads the nearest element inside instead -- row min(i, n - 1), column min(j, row), always within the
+// matrix's own lower triangle -- and drops what it read with a select (never a multiplication: the element read may be anything).
+// The load is then issued by every lane of every wave, which is what lets the compiler count the loads behind an
+// `s_waitcnt vmcnt(N)`.  (Columns unsigned: the compiler then knows the offset's range and adds it to a scalar row base.)
+__device__ __forceinline__ int sf_tri_row(int i, int n) { return i < n ? i : n - 1; }
+__device__ __forceinline__ unsigned sf_tri_col(unsigned j, unsigned i) { return j < i ? j : i; }
+__device__ __forceinline__ float2 sf_keep(bool v, float2 z) { return v ? z : make_float2(0.f, 0.f); }
+__device__ __forceinline__ float2 sf_tri_load(const float2 *Z, int n, int i, int j) {   // (the caller applies sf_keep)
+    const unsigned ic = sf_tri_row(i, n), jc = sf_tri_col(j, ic);
+    // (a 32-bit byte offset -- n <= 257: below 2^20 -- that the load adds to the matrix's scalar base: one register per address)
+    return *reinterpret_cast<const float2 *>(reinterpret_cast<const char *>(Z) + (ic * (unsigned)n + jc) * 8u);
+}
+
+__device__ __forceinline__ float2 *sf_elem(float2 *M, int n, int i, int j) {   // &M[i][j], addressed the same way
+    return reinterpret_cast<float2 *>(reinterpret_cast<char *>(M) + ((unsigned)i * (unsigned)n + (unsigned)j) * 8u);
+}
+
 // W waves (64 W threads) per matrix: 12 for n > 129 (one workgroup per CU), 4 for n <= 129 -- three matrices per CU then overlap
 // each other's latencies (at those sizes the triangle stays in the L2 and the kernel is bound by its dependent phases)
 template <int TPW, int W>
@@ -228,7 +247,13 @@ __global__ __launch_bounds__(64 * W, W == 12 ? 1 : 3) void sp_fused_kernel(int D
     // at least two passes, then until both Ritz pairs have residuals below 2e-6 of their gap to the bulk (the acceptance test of
     // P4 asks for 1e-5), at most `iters`: the arrowhead start is so good that two or three passes are the rule
     bool last = false;
+    const int tid_k = tid;
     for (int it = 0; it < iters; ++it) {
+        // (opaque copy of the thread index, as in the staging below: what a pass derives from it -- the addresses of its first rows,
+        //  of its partial sums -- is the same in every pass, and would be hoisted out of this loop and spilled around the sweep)
+        int tid_o = tid_k;
+        asm volatile("" : "+v"(tid_o));
+        const int tid = tid_o, lane = tid & 63;
         v2f x0[SF_MAXM], x1[SF_MAXM], c0[SF_MAXM], c1[SF_MAXM];
 #pragma unroll
         for (int m = 0; m < SF_MAXM; ++m) {
@@ -240,51 +265,61 @@ __global__ __launch_bounds__(64 * W, W == 12 ? 1 : 3) void sp_fused_kernel(int D
             c1[m] = v2f{0.f, 0.f};
         }
         float trl = 0.f;
-        // (the sweep in two instances: the first pass with the folded Z update carries the rows of the old G as well; the others
-        //  must not pay for its registers)
-        auto run_pass = [&](auto updc) {
-        constexpr bool UPD = decltype(updc)::value;
-        float2 za[SF_MAXM], zb[SF_MAXM], zc[SF_MAXM], zd[SF_MAXM];
-        float2 ga[SF_MAXM], gb[SF_MAXM], gc[SF_MAXM], gd[SF_MAXM];   // (first pass with the Z update: the rows of the old G)
-        auto load_row = [&](int i, float2(&z)[SF_MAXM], float2(&g)[SF_MAXM]) {
+        // (the sweep in three instances: the first pass with the folded Z update carries the rows of the old G as well, and the
+        //  others must not pay for its registers; in mode 2 it requests no row of the stored Z.
+        //  The memory operations of the sweep are UNCONDITIONAL and the same number for every row: an `s_waitcnt vmcnt(N)` can
+        //  leave the younger N operations in flight only if the compiler can count them, and one load or store behind a branch
+        //  (a per-lane guard becomes one) makes that count 0 -- the wait in front of a row's arithmetic then drains the rows just
+        //  requested and every trip pays a whole memory round trip.  So a lane outside the row's part of the triangle reads, and
+        //  in the update pass writes, the row's DIAGONAL element instead (sf_tri_col); what it read is discarded by a select.)
+        constexpr int NM = W == 4 ? 3 : SF_MAXM;   // column chunks a row is read in (4 waves: n <= 129, columns 0 .. 128)
+        auto run_pass = [&](auto updc, auto zldc) {
+        constexpr bool UPD = decltype(updc)::value;     // the Z update rides this pass
+        constexpr bool ZLD = decltype(zldc)::value;     // the stored Z is read (not in mode 2: it was never written)
+        float2 za[NM], zb[NM], zc[NM], zd[NM];
+        float2 ga[NM], gb[NM], gc[NM], gd[NM];   // (first pass with the Z update: the rows of the old G)
 #pragma unroll
-            for (int m = 0; m < SF_MAXM; ++m) {
-                const int j = lane + 64 * m;
-                const bool v = i < n && j <= i;
-                z[m] = (v && !(UPD && up.mode == 2)) ? Z[(int64_t)i * n + j] : make_float2(0.f, 0.f);
-                if (UPD) g[m] = v ? Gold[(int64_t)i * n + j] : make_float2(0.f, 0.f);
+        for (int m = 0; m < NM; ++m) zc[m] = zd[m] = gc[m] = gd[m] = make_float2(0.f, 0.f);
+        auto load_row = [&](int i, float2(&z)[NM], float2(&g)[NM]) {   // NM (2 NM with the update) loads, whatever i and the lane
+            const int ic = sf_tri_row(i, n);
+            const float2 *zr = Z + (int64_t)ic * n, *gr = Gold + (int64_t)ic * n;   // (wave-uniform)
+#pragma unroll
+            for (int m = 0; m < NM; ++m) {
+                const unsigned jc = sf_tri_col(lane + 64 * m, ic);
+                z[m] = ZLD ? zr[jc] : make_float2(0.f, 0.f);
+                if (UPD) g[m] = gr[jc];
             }
         };
-        auto proc_row = [&](int i, float2(&zc)[SF_MAXM], const float2(&gq)[SF_MAXM]) {
+        auto proc_row = [&](int i, float2(&zc)[NM], const float2(&gq)[NM], auto cornc) {   // (i < n)
             if (UPD) {   // Z <- Z + alpha (G - C_prev) for this row, written back; the rest of the kernel reads the new Z
                 const float hpi = cv.hp[i];
+                float2 *zw = Z + (int64_t)i * n;
 #pragma unroll
-                for (int m = 0; m < SF_MAXM; ++m) {
-                    if (64 * m <= i) {
-                        const int j = lane + 64 * m;
-                        if (j <= i) {
-                            float2 c;
-                            if (i < D) c = make_float2(i == j ? hpi : 0.f, 0.f);
-                            else if (j == D) c = make_float2(corner_zp, 0.f);
-                            else {
-                                const float2 pp = cv.Ob[j];
-                                c = make_float2(pp.x, -pp.y);   // C[D][j] = conj(phi_prev_j)
-                            }
-                            const float2 zn = make_float2(zc[m].x + al * (gq[m].x - c.x), zc[m].y + al * (gq[m].y - c.y));
-                            zc[m] = zn;
-                            Z[(int64_t)i * n + j] = zn;
-                        }
+                for (int m = 0; m < NM; ++m) {
+                    // (every lane stores: the lanes beyond the diagonal hold the diagonal element's operands -- the clamped loads
+                    //  gave them to it -- so they write its new value, bit for bit, to its address once more)
+                    const int jc = (int)sf_tri_col(lane + 64 * m, i);
+                    float2 c;
+                    if (i < D) c = make_float2(i == jc ? hpi : 0.f, 0.f);
+                    else if (jc == D) c = make_float2(corner_zp, 0.f);
+                    else {
+                        const float2 pp = cv.Ob[jc];
+                        c = make_float2(pp.x, -pp.y);   // C[D][j] = conj(phi_prev_j)
                     }
+                    const float2 zn = make_float2(zc[m].x + al * (gq[m].x - c.x), zc[m].y + al * (gq[m].y - c.y));
+                    zc[m] = zn;
+                    zw[(unsigned)jc] = zn;
                 }
             }
             const v2f xi0 = pk2(cv.X0[i]), xi1 = pk2(cv.X1[i]);
             const float hi = cv.hh[i];
             v2f r0 = {0.f, 0.f}, r1 = {0.f, 0.f};
 #pragma unroll
-            for (int m = 0; m < SF_MAXM; ++m) {
+            for (int m = 0; m < NM; ++m) {
                 if (64 * m <= i) {   // (wave-uniform)
                     const int j = lane + 64 * m;
-                    float2 a = sf_a_elem(i, j, D, zc[m], ir, corner, hi, (i == D && j < D) ? cv.ph[j] : make_float2(0.f, 0.f));
+                    const float2 zv = sf_keep(j <= i, zc[m]);
+                    float2 a = sf_a_elem(i, j, D, zv, ir, corner, hi, (i == D && j < D) ? cv.ph[j] : make_float2(0.f, 0.f));
                     if (j > i) a = make_float2(0.f, 0.f);
                     if (j == i) trl += a.x;
                     const v2f av = pk2(a);
@@ -295,9 +330,11 @@ __global__ __launch_bounds__(64 * W, W == 12 ? 1 : 3) void sp_fused_kernel(int D
                     c1[m] = pk_cfma_conj(c1[m], ac, xi1);
                 }
             }
-            if (i == 64 * SF_MAXM && lane == 0) {   // (n = 257, row 256) the corner element Z[256][256]: no chunk holds it
+            if (W == SF_WAVES && decltype(cornc)::value && i == 64 * SF_MAXM && lane == 0) {
+                // (n = 257, row 256) the corner element Z[256][256]: no chunk holds it.  Conditional loads and a conditional
+                // store: only the rows after the last whole trip come here
                 const int64_t idx = (int64_t)i * n + i;
-                float2 z = (UPD && up.mode == 2) ? make_float2(0.f, 0.f) : Z[idx];
+                float2 z = ZLD ? Z[idx] : make_float2(0.f, 0.f);
                 if (UPD) {
                     const float2 g = Gold[idx];
                     z = make_float2(z.x + al * (g.x - corner_zp), z.y + al * g.y);
@@ -315,25 +352,42 @@ __global__ __launch_bounds__(64 * W, W == 12 ? 1 : 3) void sp_fused_kernel(int D
                 dst[2 * i + ((lane >> 4) & 1)] = t;
             }
         };
-        // two rows per trip, the next two in flight behind them (the loads are what bounds this phase)
-        load_row(wave, za, ga);
-        load_row(wave + W, zb, gb);
-        for (int i = wave; i < n; i += 2 * W) {
+        // Four rows per trip in two halves, each half working on two rows with the other half's two in flight: the buffers
+        // alternate (no register copy waits for a load that was only just requested), and the trips hold no condition at all, so
+        // the wait in front of a half is vmcnt(2 NM) or more (4 NM with the update; the stores of the half before count as well)
+        // and a pass exposes its first round trip only.  That is what bounds the phase where the triangle stays in the L2
+        // (n <= 129: matvec 132 k -> 108 k cycles at D = 100); at D = 256 the phase moves what HBM delivers either way
+        // (profiles/r13/README.md).  The rows a wave has left after its last whole trip (with row 256 among them: nmain) go
+        // one by one.
+        const int nmain = n < 64 * SF_MAXM ? n : 64 * SF_MAXM;
+        int i = wave;
+        load_row(i, za, ga);
+        load_row(i + W, zb, gb);
+        for (; i + 3 * W < nmain; i += 4 * W) {
             load_row(i + 2 * W, zc, gc);
             load_row(i + 3 * W, zd, gd);
-            proc_row(i, za, ga);
-            if (i + W < n) proc_row(i + W, zb, gb);
+            proc_row(i, za, ga, std::false_type{});
+            proc_row(i + W, zb, gb, std::false_type{});
+            load_row(i + 4 * W, za, ga);
+            load_row(i + 5 * W, zb, gb);
+            proc_row(i + 2 * W, zc, gc, std::false_type{});
+            proc_row(i + 3 * W, zd, gd, std::false_type{});
+        }
+        if (i + 2 * W < n) load_row(i + 2 * W, zc, gc);   // (uniform)
+        for (; i < n; i += W) {
+            proc_row(i, za, ga, std::true_type{});
+            if (i + 3 * W < n) load_row(i + 3 * W, zd, gd);
 #pragma unroll
-            for (int m = 0; m < SF_MAXM; ++m) {
-                za[m] = zc[m];
-                zb[m] = zd[m];
-                ga[m] = gc[m];
-                gb[m] = gd[m];
+            for (int m = 0; m < NM; ++m) {
+                za[m] = zb[m]; zb[m] = zc[m]; zc[m] = zd[m];
+                ga[m] = gb[m]; gb[m] = gc[m]; gc[m] = gd[m];
             }
         }
         };
-        if (up.mode != 0 && it == 0) run_pass(std::true_type{});   // (uniform)
-        else run_pass(std::false_type{});
+        // (uniform: three instances of the sweep)
+        if (up.mode == 0 || it != 0) run_pass(std::false_type{}, std::true_type{});
+        else if (up.mode == 2) run_pass(std::true_type{}, std::false_type{});
+        else run_pass(std::true_type{}, std::true_type{});
         // the mirrored part: per-wave partial sums, then one add per column
 #pragma unroll
         for (int m = 0; m < SF_MAXM; ++m) {
@@ -722,10 +776,16 @@ __global__ __launch_bounds__(64 * W, W == 12 ? 1 : 3) void sp_fused_kernel(int D
                 for (int qb = 0; qb < 16; qb += AB) {
                     float2 zq[AB];
 #pragma unroll
-                    for (int u = 0; u < AB; ++u) {   // (the loads of the tile first)
+                    for (int u = 0; u < AB; ++u) {   // (the loads of the tile first, by every lane: the waits between the stores
+                                                     //  below can then be counted, and no store is drained before the next)
                         const int q = qb + u, gi = 32 * tI[s] + (q & 3) + 8 * (q >> 2) + 4 * kh;
-                        zq[u] = (gi < D && gj <= gi) ? Z[(int64_t)gi * n + gj] : make_float2(0.f, 0.f);
+                        zq[u] = sf_tri_load(Z, n, gi, gj);
                     }
+                    // (every element of the tile is waited for HERE, in the one block all lanes pass: a store sits behind its
+                    //  lane's guard, and a wait left to the guarded blocks is counted as if no store had been issued -- vmcnt(15 - u)
+                    //  in front of store u, which drains the stores before it)
+#pragma unroll
+                    for (int u = 0; u < AB; ++u) asm volatile("" : "+v"(zq[u].x), "+v"(zq[u].y));
 #pragma unroll
                     for (int u = 0; u < AB; ++u) {
                         const int q = qb + u, gi = 32 * tI[s] + (q & 3) + 8 * (q >> 2) + 4 * kh;
@@ -741,7 +801,7 @@ __global__ __launch_bounds__(64 * W, W == 12 ? 1 : 3) void sp_fused_kernel(int D
                                 g.y = 0.f;
                                 cz = hi;
                             }
-                            Gb[(int64_t)gi * n + gj] = g;
+                            *sf_elem(Gb, n, gi, gj) = g;
                             const float dr = g.x - cz;
                             acc += (gi == gj ? 1.f : 2.f) * (dr * dr + g.y * g.y);
                         }
