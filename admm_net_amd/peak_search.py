@@ -35,9 +35,24 @@ def peak_search_func(phi, x, x_base, y, y_base):
 
 
 def spectrum_grid(phi, xs, x_base, ys, y_base):
-    """|phi^H kron(s(y), conj d(x))|^2 for all (y, x) in ys x xs -> [len(ys), len(xs)] float64."""
+    """|phi^H kron(s(y), conj d(x))|^2 for all (y, x) in ys x xs -> [len(ys), len(xs)] float64.
+
+    An axis whose base is 1 has the steering vector [1]: the reference's kron + dot and the device's sp_image give an
+    image that is exactly constant along it, whole rows or columns of equal values that the regional maxima treat as
+    plateaus.  A BLAS matrix product does not keep that: it may round the columns of one product differently (blocked
+    and remainder columns take different code), and a plateau broken in the last bit loses or gains maxima.  So that
+    factor is left out of the product and the one remaining vector is repeated along the axis."""
     phi = np.asarray(phi).reshape(-1).astype(np.complex128)
     Phi = phi.reshape(y_base, x_base)
+    xs, ys = np.asarray(xs, dtype=np.float64), np.asarray(ys, dtype=np.float64)
+    if x_base == 1 or y_base == 1:
+        if x_base == 1:
+            z = _vander(ys, y_base) @ np.conj(Phi[:, 0])     # [ny]: one value per row
+            line = (np.abs(z) ** 2)[:, None]
+        else:
+            z = np.conj(_vander(xs, x_base)) @ np.conj(Phi[0])   # [nx]: one value per column
+            line = (np.abs(z) ** 2)[None, :]
+        return np.broadcast_to(line, (len(ys), len(xs))).copy()
     S = _vander(ys, y_base)            # [ny, y_base]
     Dm = _vander(xs, x_base)           # [nx, x_base]
     U = np.conj(Phi) @ np.conj(Dm).T   # [y_base, nx]
