@@ -11,6 +11,7 @@
 #include "common.h"
 #include "options.h"
 #include "score_core.h"
+#include "crb_core.h"
 
 namespace admmnet {
 
@@ -1158,6 +1159,27 @@ int admmnet_score_ordered_f32(int32_t Lmax, int64_t B, const float *tau_est, con
         return rc;
     return launch_score_ordered(Lmax, B, tau_est, f_est, tau_true, f_true, L_true, per_sample, out, status, partials,
                                 (hipStream_t)stream);
+}
+
+// ---- the Cramer-Rao bound of a scene's targets (crb.hip) ----------------------------------------------------------------------
+// one lane per parameter (4 Lt <= 64); the scenes are those the generator makes (synth.hip's ceiling on Nb * Nd)
+int64_t admmnet_crb_partials(int64_t B) {
+    if (B < 1 || B > 2147483647) return -1;
+    return crb_partials(B);
+}
+
+int admmnet_crb_f64(int32_t Nb, int32_t Nd, int32_t Lt, int64_t B, const float *tau_true, const float *f_true, const void *C,
+                    const int64_t *L_true, const int32_t *match, const double *noise, int32_t noise_is_snr, double *bound,
+                    double *totals, int32_t *status, double *partials, void *stream) {
+    if (Lt < 1 || Lt > CRB_MAXL || B < 1 || B > 2147483647 || Nb < 1 || Nd < 1 || (int64_t)Nb * Nd > synth_max_cells() ||
+        (noise_is_snr != 0 && noise_is_snr != 1) || !tau_true || !f_true || !C || !noise || !bound || !totals || !status ||
+        !partials) {
+        set_error("crb: bad argument (Nb=%d, Nd=%d with Nb * Nd <= %lld, Lt=%d in 1 .. %d, B=%lld, noise_is_snr=%d, or a null pointer)",
+                  Nb, Nd, (long long)synth_max_cells(), Lt, CRB_MAXL, (long long)B, noise_is_snr);
+        return ADMMNET_E_ARG;
+    }
+    return launch_crb(Nb, Nd, Lt, B, tau_true, f_true, (const float2 *)C, L_true, match, noise, noise_is_snr, bound, totals, status,
+                      partials, (hipStream_t)stream);
 }
 
 // ---- AdamW and gradient-norm clipping over a tensor list (optim.hip) ---------------------------------------------------------

@@ -310,6 +310,12 @@ int launch_score_match(int Le, int Lt, int64_t B, const double *est, const int32
 int launch_score_ordered(int Lmax, int64_t B, const float *tau_est, const float *f_est, const float *tau_true, const float *f_true,
                          const int64_t *L_true, double *per_sample, double *out, int32_t *status, double *part, hipStream_t st);
 
+// crb.hip (the Cramer-Rao bound of a scene's targets; 1 <= Lt <= 16)
+int64_t crb_partials(int64_t B);                      // doubles of partial-sum scratch
+int launch_crb(int Nb, int Nd, int Lt, int64_t B, const float *tau_true, const float *f_true, const float2 *C,
+               const int64_t *L_true, const int32_t *match, const double *noise, int noise_is_snr, double *bound, double *totals,
+               int32_t *status, double *part, hipStream_t st);
+
 // optim.hip (AdamW and gradient-norm clipping over a tensor list; host arrays of device pointers)
 int64_t optim_blocks(int count, const int64_t *numel);   // blocks of the list = doubles of `partials`; -1: bad count or too many
 int launch_optim_gradnorm(int count, const float *const *grads, const int64_t *numel, float max_norm, double *partials,
@@ -322,6 +328,7 @@ int launch_optim_adamw(int count, float *const *params, const float *const *grad
 int launch_optim_bucket(int count, float *const *tensors, const int64_t *numel, float *flat, bool to_flat, hipStream_t st);
 
 // synth.hip
+int64_t synth_max_cells();                            // the largest Nb * Nd a scene may have
 int launch_synth(int64_t B, int Nb, int Nd, int L, unsigned long long seed, double snr_lo, double snr_hi, double snr_e,
                  double rho, int label_iters, float2 *y, float2 *b, float *sigma, float *tau, float *f, float2 *C,
                  float2 *phi_label, hipStream_t st);

@@ -14,58 +14,14 @@
 // per workgroup, added in a fixed order by ONE workgroup.
 #include "common.h"
 #include "score_core.h"
-#include "slab_partials.h"
+#include "batch_sums.h"
 
 namespace admmnet {
 
 constexpr int SC_MATCH_COLS = SC_STATS + 2;   // the stats, then signals whose L_true was outside, signals with a non-finite truth
 constexpr int SC_ORD_COLS = 4;                // sum rmse_tau, sum rmse_f, signals with L > 0, signals whose L_true was outside
-constexpr int SC_FIN_THREADS = 1024;
-constexpr int SC_FIN_SLICES = 64;             // row slices of the finishing sum per column
 static_assert(SC_FIN_SLICES * SC_MATCH_COLS <= SC_FIN_THREADS, "one thread per column and slice");
 constexpr int SC_STEPS = SC_MAX + 1;          // no search and no path is longer than the columns there are
-
-__device__ __forceinline__ double sc_wave_sum(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
-// ts_slab_partials in float64
-template <int COUNT>
-__device__ __forceinline__ void sc_slab_partials(const double (&v)[COUNT], double *sh, double *__restrict__ part) {
-    const int wave = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-        for (int c = 0; c < COUNT; ++c) sh[wave * COUNT + c] = v[c];
-    }
-    __syncthreads();
-    if ((int)threadIdx.x < COUNT) {
-        double s = 0.0;
-        for (int w = 0; w < TS_SLAB; ++w) s += sh[w * COUNT + threadIdx.x];
-        part[(int64_t)blockIdx.x * COUNT + threadIdx.x] = s;
-    }
-}
-
-// column sums of part [rows][COLS], fixed order (la_colsum's scheme): thread (c, s) adds the rows s, s + NS, ..., a tree halves
-// the NS slices; the sums are left in sh[0 .. COLS).  One workgroup, every thread calls it.
-template <int COLS>
-__device__ __forceinline__ void sc_colsum(int64_t rows, const double *__restrict__ part, double *sh) {
-    constexpr int NS = SC_FIN_SLICES;
-    const int c = threadIdx.x % COLS, s = threadIdx.x / COLS;
-    const bool live = s < NS;
-    double a = 0.0;
-    if (live)
-        for (int64_t r = s; r < rows; r += NS) a += part[r * COLS + c];
-    if (live) sh[s * COLS + c] = a;
-    __syncthreads();
-    for (int o = NS >> 1; o > 0; o >>= 1) {
-        if (live && s < o) sh[s * COLS + c] += sh[(s + o) * COLS + c];
-        __syncthreads();
-    }
-}
-
-__device__ __forceinline__ int32_t sc_count(double v) { return (int32_t)fmin(v, 2147483647.0); }   // exact in float64; saturates
 
 // ---- the assignment ----------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(TS_THREADS) void sc_match_kernel(int Le, int Lt, int64_t B, const double *__restrict__ est,

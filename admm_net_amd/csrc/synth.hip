@@ -171,6 +171,8 @@ __global__ __launch_bounds__(SY_THREADS) void synth_kernel(int Nb, int Nd, int L
     for (int i = tid; i < D; i += SY_THREADS) phi_out[s * D + i] = make_float2((float)ph[i].x, (float)ph[i].y);
 }
 
+int64_t synth_max_cells() { return SY_MAX_D; }
+
 int launch_synth(int64_t B, int Nb, int Nd, int L, unsigned long long seed, double snr_lo, double snr_hi, double snr_e,
                  double rho, int label_iters, float2 *y, float2 *b, float *sigma, float *tau, float *f, float2 *C,
                  float2 *phi_label, hipStream_t st) {

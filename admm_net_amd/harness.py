@@ -327,11 +327,13 @@ def time_score_step(steps=50, warmup=5, repeats=5, host_signals=2048, seed=0, de
 
 
 def evaluate_snr(grid=(NB, ND), layers=10, checkpoint=None, snrs=(5.0, 15.0, 25.0), signals=4096, targets=3, cutoff=1.0,
-                 baseline=None, seed=0, device="cuda:0"):
+                 baseline=None, seed=0, device="cuda:0", crb=False):
     """Detection and accuracy against the noise level: per SNR one batch of ``signals`` scenes at exactly that SNR
     (``synth.make_batch_device(snr_range=(S, S))``), ``model.evaluate`` and ``metrics.summary`` -- scene, forward, peak search and
     score without a host loop.  ``baseline="classical"`` scores the peaks of the classical solver's phi (the generator's labels)
-    the same way.  The model is ``PhiEstADMMNet`` at seed 0, or the checkpoint's.  Yields one dict per SNR and method."""
+    the same way.  The model is ``PhiEstADMMNet`` at seed 0, or the checkpoint's.  Yields one dict per SNR and method.
+    ``crb=True`` adds the root-mean Cramer-Rao bound of the same scenes, pooled over that method's own hits (``metrics.crb``), as
+    ``crb_tau`` / ``crb_f``, and the pooled RMSE over it as ``rmse_over_crb_tau`` / ``rmse_over_crb_f``."""
     from . import PhiEstADMMNet, metrics, ops, synth
     if baseline not in (None, "classical"):
         raise ValueError(f"baseline must be None or 'classical', got {baseline!r}")
@@ -343,16 +345,26 @@ def evaluate_snr(grid=(NB, ND), layers=10, checkpoint=None, snrs=(5.0, 15.0, 25.
         load_checkpoint(checkpoint, model)
     model.eval()
     head = {"grid": [M, N], "layers": layers, "signals": signals, "targets": targets, "cutoff": cutoff}
+
+    def scored(res, truth, snr):
+        line = metrics.summary(res)
+        if crb:
+            c = metrics.crb_summary(metrics.crb(truth["tau"], truth["f"], truth["C"], (M, N), snr_db=snr, match=res.match))
+            for axis in ("tau", "f"):
+                line[f"crb_{axis}"] = c[f"crb_{axis}_hits"]
+                line[f"rmse_over_crb_{axis}"] = line[f"rmse_{axis}"] / c[f"crb_{axis}_hits"]
+        return line
+
     for i, snr in enumerate(snrs):
         y, b, sigma, truth = synth.make_batch_device(signals, M, N, L=targets, seed=20260104 + seed + 7919 * i, snr_range=(snr, snr),
                                                      device=dev, labels=baseline is not None)
         res = model.evaluate(y, b, sigma, truth["tau"], truth["f"], cutoff=cutoff, top=targets)
-        yield {"snr": snr, "method": "net", **head, **metrics.summary(res)}
+        yield {"snr": snr, "method": "net", **head, **scored(res, truth, snr)}
         if baseline is not None:
             opts = {"xstep": 1 / (10 * N), "ystep": 1 / (10 * M), "iter": 3}            # estimate's defaults
             rows, _ = ops.peak_top(truth["phi"], M, N, opts, top=targets)
             res = metrics.match_targets(rows, truth["tau"], truth["f"], cutoff=cutoff, scale=(float(N), float(M)), period=(1.0, 1.0))
-            yield {"snr": snr, "method": "classical", **head, **metrics.summary(res)}
+            yield {"snr": snr, "method": "classical", **head, **scored(res, truth, snr)}
 
 
 def _grid(ap, text):
@@ -405,6 +417,7 @@ def main(argv=None):
     f.add_argument("--targets", type=int, default=3)
     f.add_argument("--cutoff", type=float, default=1.0, help="in resolution cells")
     f.add_argument("--baseline", choices=("classical",), default=None)
+    f.add_argument("--crb", action="store_true", help="add the Cramer-Rao bound pooled over each method's hits, and RMSE over it")
     args = ap.parse_args(argv)
     if args.cmd == "score-step":
         import json
@@ -413,7 +426,7 @@ def main(argv=None):
     if args.cmd == "evaluate":
         import json
         for line in evaluate_snr(_grid(ap, args.grid), args.layers, args.checkpoint, args.snr, args.signals, args.targets,
-                                 args.cutoff, args.baseline):
+                                 args.cutoff, args.baseline, crb=args.crb):
             print(json.dumps(line), flush=True)
         return
     if args.cmd == "loss-step":

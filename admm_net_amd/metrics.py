@@ -18,6 +18,8 @@ order, so comparing them needs an assignment, and that part was never written.
 ``summary``        the one host read: detection probability, false alarms, pooled RMSE and GOSPA of a batch.
 ``match_host``     the float64 numpy statement of ``match_targets`` for one signal.  The tests hold the kernel to it; it is NOT a
                    fallback -- the device calls raise without the HIP library.
+``crb``            the Cramer-Rao bound of every target of every scene (csrc/crb.hip), the yardstick of the pooled RMSE;
+``crb_summary``    its one host read; ``crb_host`` the float64 numpy statement for one scene (a test yardstick, no fallback).
 
 Tensor inputs follow INTEGRATION.md section 3: every pointer is taken through ``ops._f32`` / ``ops._num`` (``ops._plain``).
 """
@@ -294,3 +296,168 @@ def ordered_rmse_host(tau_est, f_est, tau_true, f_true, L_true):
     n = int((L > 0).sum())
     out = np.array([per[L > 0, 0].mean() if n else 0.0, per[L > 0, 1].mean() if n else 0.0, float(n)])
     return per, out
+
+
+# ---- the Cramer-Rao bound of a scene ---------------------------------------------------------------------------------------------
+MAX_TARGETS = 16                 # crb: 4 parameters per target, one lane each
+PIVOT_MIN = 2.0 ** -40           # a pivot of the unit-diagonal Cholesky below this: not positive definite
+
+
+class CrbResult(NamedTuple):
+    bound: torch.Tensor    # [B, Lt, 2] float64: the variance bound of tau_j and of f_j; +inf on an axis of length 1, NaN past L_true
+    totals: torch.Tensor   # [8] float64: sum tau, sum f, count tau, count f over j < L_true; the same four over match >= 0
+    status: torch.Tensor   # [3] int32 scenes: L_true outside [0, Lt]; non-finite input or noise; not positive definite
+
+
+def _noise(snr_db, noise_var, B, dev):
+    if (snr_db is None) == (noise_var is None):
+        raise ValueError("crb needs exactly one of snr_db= and noise_var=")
+    value, name = (snr_db, "snr_db") if noise_var is None else (noise_var, "noise_var")
+    if isinstance(value, torch.Tensor):
+        if value.is_complex() or value.dtype == torch.bool:
+            raise ValueError(f"{name} must hold real numbers, got {value.dtype}")
+        ops._need_cuda(value, name)
+        return ops._num(value, dev, torch.float64, (B,), name), noise_var is None
+    try:
+        value = float(value)
+    except (TypeError, ValueError):
+        raise TypeError(f"{name} must be a number or a [B] tensor, got {type(value).__name__}") from None
+    return torch.full((B,), value, dtype=torch.float64, device=dev), noise_var is None
+
+
+def crb(tau_true, f_true, C, grid, *, snr_db=None, noise_var=None, L_true=None, match=None) -> CrbResult:
+    """The Cramer-Rao bound of the targets of every scene, in one kernel and without a host read.
+
+    Scene model (``synth.make_batch``), grid = (Nb, Nd) = the (M, N) of a model, D = Nb Nd:
+
+        mu[i_b Nd + i_d] = s[i] sum_l C_l exp(j 2 pi (i_b f_l - i_d tau_l)),  |s[i]| = 1 (PSK),     y = mu + w,  w ~ CN(0, v).
+
+    theta = (tau_1..L, f_1..L, Re C_1..L, Im C_1..L); the information matrix is F = (2 / v) Re(J^H J), J = d mu / d theta, and the
+    bound of target l is [F^-1] at the diagonal entries of tau_l and f_l.  This is the bound of a receiver that KNOWS the
+    transmitted symbols s: with |s| = 1 they drop out of J^H J.  The network only knows the demodulated ``b``, so for it the
+    figure is a lower bound, not one it could reach.
+
+    tau_true, f_true [B, Lt], C [B, Lt] complex (1 <= Lt <= 16); L_true: None (every slot is a target) or [B] integers.
+    Exactly one of ``snr_db`` (the generator's definition, v = sum |mu|^2 / (10^(snr / 10) D)) and ``noise_var`` (v itself), as a
+    number or a [B] tensor.  match: None or a ``MatchResult.match`` ([B, Lt] int32), for the totals over the hits.
+
+    An axis of length 1 carries no information about its parameter: the bound is +inf and is left out of sums and counts.  A scene
+    whose unit-diagonal F is not positive definite (coincident targets, C_l = 0) has NaN bounds and is counted in ``status[2]``."""
+    for t, name in ((tau_true, "tau_true"), (f_true, "f_true"), (C, "C")):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"{name} must be a tensor, got {type(t).__name__}")
+        ops._need_cuda(t, name)
+    try:
+        Nb, Nd = (int(v) for v in grid)
+    except (TypeError, ValueError):
+        raise ValueError(f"grid must be a pair (Nb, Nd), got {grid!r}") from None
+    if tau_true.dim() != 2:
+        raise ValueError(f"tau_true must be [B, Lt], got {tuple(tau_true.shape)}")
+    if not C.is_complex():
+        raise ValueError(f"C must be complex, got {C.dtype}")
+    lib = _lib.load()
+    dev = tau_true.device
+    B, Lt = tau_true.shape
+    if not (1 <= Lt <= MAX_TARGETS and B >= 1 and Nb >= 1 and Nd >= 1):
+        raise ValueError(f"crb needs 1 <= Lt <= {MAX_TARGETS}, B >= 1 and a grid of at least 1 x 1, got Lt={Lt}, B={B}, grid={grid!r}")
+    with torch.cuda.device(dev):
+        noise, is_snr = _noise(snr_db, noise_var, B, dev)
+        tau_true, f_true = ops._f32(tau_true, dev, (B, Lt), "tau_true"), ops._f32(f_true, dev, (B, Lt), "f_true")
+        C = ops._c64(C, dev, (B, Lt), "C")
+        if L_true is not None:
+            _integers(L_true, "L_true")
+            L_true = ops._num(L_true, dev, torch.int64, (B,), "L_true")
+        if match is not None:
+            _integers(match, "match")
+            ops._need_cuda(match, "match")
+            match = ops._num(match, dev, torch.int32, (B, Lt), "match")
+        need = lib.admmnet_crb_partials(B)
+        if need < 0:
+            raise _lib.AdmmNetError(f"crb: bad size (B={B})")
+        part = torch.empty(need, dtype=torch.float64, device=dev)
+        bound = torch.empty(B, Lt, 2, dtype=torch.float64, device=dev)
+        totals = torch.empty(8, dtype=torch.float64, device=dev)
+        status = torch.empty(3, dtype=torch.int32, device=dev)
+        _lib.check(lib.admmnet_crb_f64(Nb, Nd, Lt, B, ops._ptr(tau_true), ops._ptr(f_true), ops._ptr(C), ops._ptr(L_true),
+                                       ops._ptr(match), ops._ptr(noise), int(is_snr), ops._ptr(bound), ops._ptr(totals),
+                                       ops._ptr(status), ops._ptr(part), ops._stream(dev)), "admmnet_crb_f64")
+    return CrbResult(bound, totals, status)
+
+
+def crb_summary(result) -> dict:
+    """The figures of a batch from ``crb``'s totals, with ONE device-to-host read: root-mean bounds, to be held against the pooled
+    RMSE of ``summary``.  ``crb_tau`` / ``crb_f`` = sqrt(mean bound) over the targets j < L_true, ``crb_tau_hits`` / ``crb_f_hits``
+    over the targets with ``match >= 0`` -- the pool of ``summary``'s ``rmse_tau`` / ``rmse_f`` -- (NaN for an empty pool), the four
+    counts, and the three scene counts of ``status``."""
+    if not isinstance(result, CrbResult):
+        raise TypeError(f"crb_summary takes a CrbResult, got {type(result).__name__}")
+    t = torch.cat((result.totals.reshape(-1), result.status.to(torch.float64).reshape(-1))).tolist()   # the read
+    root = lambda s, n: math.sqrt(s / n) if n > 0 else float("nan")  # noqa: E731
+    return {"crb_tau": root(t[0], t[2]), "crb_f": root(t[1], t[3]), "crb_tau_hits": root(t[4], t[6]), "crb_f_hits": root(t[5], t[7]),
+            "targets_tau": int(t[2]), "targets_f": int(t[3]), "hits_tau": int(t[6]), "hits_f": int(t[7]),
+            "outside": int(t[8]), "nonfinite": int(t[9]), "not_positive_definite": int(t[10])}
+
+
+class CrbHost(NamedTuple):
+    bound: np.ndarray      # [L, 2] float64
+    state: int             # -1: bounded; 1: non-finite input or noise; 2: not positive definite (the columns of ``status``)
+    noise_var: float
+    kappa: float           # the 2-norm condition number of the unit-diagonal information matrix
+    jacobian: np.ndarray   # [D, P] complex: d mu / d theta, the columns of an axis of length 1 left out
+    fisher: np.ndarray     # [P, P]
+
+
+def crb_signal(tau, f, C, grid):
+    """mu [Nb Nd] of the scene model with s = 1, from ``synth.steering``."""
+    from .synth import steering
+    Nb, Nd = grid
+    tau, f, C = (np.asarray(v).reshape(-1) for v in (tau, f, C))
+    return np.einsum("l,li,lj->ij", C.astype(np.complex128), steering(f.astype(np.float64), Nb),
+                     np.conj(steering(tau.astype(np.float64), Nd))).reshape(Nb * Nd)
+
+
+def crb_host(tau, f, C, grid, *, snr_db=None, noise_var=None) -> CrbHost:
+    """``crb`` for ONE scene in float64 numpy (all L targets count), written the other way round: the explicit D x P Jacobian with
+    ``np.exp``, F = (2 / v) Re(J^H J), ``np.linalg.inv`` of the unit-diagonal matrix.  The tests hold the kernel to it; it is NOT
+    a fallback."""
+    if (snr_db is None) == (noise_var is None):
+        raise ValueError("crb_host needs exactly one of snr_db= and noise_var=")
+    Nb, Nd = (int(v) for v in grid)
+    tau, f = (np.asarray(v, dtype=np.float64).reshape(-1) for v in (tau, f))
+    C = np.asarray(C, dtype=np.complex128).reshape(-1)
+    L, D = len(tau), Nb * Nd
+    nan = np.full((L, 2), np.nan)
+    empty = CrbHost(nan, -1, float("nan"), float("nan"), np.zeros((D, 0), dtype=np.complex128), np.zeros((0, 0)))
+    given = float(snr_db if noise_var is None else noise_var)
+    if not (np.isfinite(tau).all() and np.isfinite(f).all() and np.isfinite(C).all() and math.isfinite(given)) or \
+            (noise_var is not None and not given > 0):
+        return empty._replace(state=1)
+    if L == 0:
+        return empty
+    ib, idd = np.divmod(np.arange(D), Nd)
+    E = np.exp(2j * np.pi * (np.multiply.outer(ib, f) - np.multiply.outer(idd, tau)))          # [D, L]
+    v = float((np.abs(E @ C) ** 2).sum() / (10.0 ** (given / 10.0) * D)) if noise_var is None else given
+    if not (v > 0 and math.isfinite(v)):
+        return empty._replace(state=1, noise_var=v)
+    cols = ([-2j * np.pi * idd[:, None] * C * E] if Nd > 1 else []) + ([2j * np.pi * ib[:, None] * C * E] if Nb > 1 else []) + [E, 1j * E]
+    J = np.concatenate(cols, axis=1)
+    F = (2.0 / v) * (J.conj().T @ J).real
+    out = empty._replace(noise_var=v, jacobian=J, fisher=F)
+    g = np.diag(F)
+    if not (np.isfinite(F).all() and (g > 0).all()):
+        return out._replace(state=2)
+    d = 1.0 / np.sqrt(g)
+    A = F * np.multiply.outer(d, d)
+    np.fill_diagonal(A, 1.0)
+    R = A.copy()                                            # the pivots of its Cholesky, by elimination
+    for j in range(len(R)):
+        if not R[j, j] >= PIVOT_MIN:
+            return out._replace(state=2)
+        R[j + 1:, j + 1:] -= np.multiply.outer(R[j + 1:, j], R[j + 1:, j]) / R[j, j]
+    var = np.diag(np.linalg.inv(A)) * d * d
+    bound = np.full((L, 2), np.inf)
+    if Nd > 1:
+        bound[:, 0] = var[:L]
+    if Nb > 1:
+        bound[:, 1] = var[L:2 * L] if Nd > 1 else var[:L]
+    return out._replace(bound=bound, kappa=float(np.linalg.cond(A, 2)))

@@ -528,6 +528,34 @@ int admmnet_score_ordered_f32(int32_t Lmax, int64_t B, const float *tau_est, con
                               const float *f_true, const int64_t *L_true, double *per_sample, double *out, int32_t *status,
                               double *partials, void *stream);
 
+/* The Cramer-Rao bound of a scene's targets (csrc/crb.hip, scalar core csrc/crb_core.h): one wave per scene, sums over the batch
+ * as admmnet_score_match_f64 forms them (fixed order, no atomics: two runs give the same bits).  All in float64.
+ *   Scene model (admmnet_synth_batch), Nb entries along f and Nd along tau, D = Nb Nd:
+ *       mu[i_b Nd + i_d] = s[i] sum_l C_l exp(j 2 pi (i_b f_l - i_d tau_l)),  |s[i]| = 1,    y = mu + w,  w ~ CN(0, v) per entry.
+ *   theta = (tau_1..L, f_1..L, Re C_1..L, Im C_1..L), F = (2 / v) Re(J^H J) with J = d mu / d theta; the bound of target l is
+ *   [F^-1] at the diagonal entries of tau_l and f_l.  It is the bound of a receiver that KNOWS the symbols s (|s| = 1 drops out of
+ *   J^H J), hence a lower bound for one that only has the demodulated b.  Every entry of J^H J for a pair (l, m) is a constant
+ *   times S_p(f_m - f_l; Nb) S_q(-(tau_m - tau_l); Nd), S_p(x; N) = sum_{k<N} k^p exp(j 2 pi k x): O(L^2 (Nb + Nd)) per scene.
+ *   F is scaled to unit diagonal, factored by Cholesky and unscaled.
+ *       1 <= Lt <= 16, B >= 1, Nb, Nd >= 1 with Nb Nd within admmnet_synth_batch's ceiling.
+ *       tau_true, f_true   float [B][Lt];  C: complex64 [B][Lt];  L_true int64 [B] or NULL (= Lt): the first L_true slots count.
+ *       match     int32 [B][Lt] or NULL: admmnet_score_match_f64's match; target j is a hit where match >= 0.
+ *       noise     double [B]: v itself (noise_is_snr = 0), or the SNR in dB of the generator's definition (noise_is_snr = 1),
+ *                 v = sum |mu|^2 / (10^(snr / 10) D), the energy evaluated from the same power sums.
+ *       bound     double [B][Lt][2]: the variance bound of tau_j and of f_j.  An axis of length 1 carries no information about its
+ *                 parameter: it leaves theta and its bound is +inf.  Slots j >= L_true are NaN.
+ *       totals    double [8]: sum of the tau bounds, sum of the f bounds and their two counts over the targets j < L_true, then
+ *                 the same four over the hits (zeros without `match`); +inf bounds are left out of sums and counts.
+ *       status    int32 [3] counts scenes: [0] L_true outside [0, Lt]; [1] a non-finite tau, f, C or noise entry, or a noise
+ *                 variance that is not positive and finite; [2] an information matrix that is not positive definite: a diagonal
+ *                 entry that is not positive, or a pivot of the unit-diagonal Cholesky below 2^-40 (coincident targets, C_l = 0).
+ *                 Such a scene has NaN bounds and enters no total.
+ *   `partials` is double scratch of admmnet_crb_partials(B) entries (-1: bad B). */
+int64_t admmnet_crb_partials(int64_t B);
+int admmnet_crb_f64(int32_t Nb, int32_t Nd, int32_t Lt, int64_t B, const float *tau_true, const float *f_true, const void *C,
+                    const int64_t *L_true, const int32_t *match, const double *noise, int32_t noise_is_snr, double *bound,
+                    double *totals, int32_t *status, double *partials, void *stream);
+
 /* AdamW and gradient-norm clipping over a LIST of float32 tensors (csrc/optim.hip): what a training loop writes as
  * torch.nn.utils.clip_grad_norm_(params, max_norm) and torch.optim.AdamW(...).step().  `count` tensors, tensor i dense with
  * numel[i] >= 0 elements; grads, params, exp_avg, exp_avg_sq are HOST arrays of `count` DEVICE pointers (as `params` of
