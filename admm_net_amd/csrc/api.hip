@@ -12,6 +12,7 @@
 #include "options.h"
 #include "score_core.h"
 #include "crb_core.h"
+#include "refine_core.h"
 
 namespace admmnet {
 
@@ -1180,6 +1181,37 @@ int admmnet_crb_f64(int32_t Nb, int32_t Nd, int32_t Lt, int64_t B, const float *
     }
     return launch_crb(Nb, Nd, Lt, B, tau_true, f_true, (const float2 *)C, L_true, match, noise, noise_is_snr, bound, totals, status,
                       partials, (hipStream_t)stream);
+}
+
+// ---- target estimates refined against the received signal (refine.hip) -------------------------------------------------------
+// one lane per parameter (4 Le <= 64); x, the matrix and the twiddle tables of a scene stay in the LDS of its workgroup
+static bool refine_sizes_ok(int32_t Nb, int32_t Nd, int32_t Le) {
+    return Le >= 1 && Le <= CRB_MAXL && Nb >= 1 && Nd >= 1 && (int64_t)Nb * Nd <= synth_max_cells();
+}
+
+int64_t admmnet_refine_lds_bytes(int32_t Nb, int32_t Nd, int32_t Le) {
+    return refine_sizes_ok(Nb, Nd, Le) ? refine_lds_bytes(Nb, Nd, Le) : -1;
+}
+
+int admmnet_refine_f64(int32_t Nb, int32_t Nd, int32_t Le, int64_t B, const void *y, const void *b, const double *rows_in,
+                       const int32_t *n_est, int32_t mode, int32_t psk_m, double psk_phase, int32_t iters, double tol,
+                       double *rows_out, void *C_out, double *info, int32_t *symbols_out, int32_t *status, void *stream) {
+    if (!refine_sizes_ok(Nb, Nd, Le) || B < 1 || B > 2147483647 || (mode != 0 && mode != 1) || psk_m < 2 || psk_m > REFINE_MAX_M ||
+        !sc_finite(psk_phase) || iters < 1 || iters > REFINE_MAX_ITERS || !(tol > 0.0) || !sc_finite(tol) || !y || !b || !rows_in ||
+        !rows_out || !C_out || !info || !status) {
+        set_error("refine: bad argument (Nb=%d, Nd=%d with Nb * Nd <= %lld, Le=%d in 1 .. %d, B=%lld, mode=%d, psk_m=%d in 2 .. %d, "
+                  "psk_phase=%g, iters=%d in 1 .. %d, tol=%g > 0, or a null pointer)",
+                  Nb, Nd, (long long)synth_max_cells(), Le, CRB_MAXL, (long long)B, mode, psk_m, REFINE_MAX_M, psk_phase, iters,
+                  REFINE_MAX_ITERS, tol);
+        return ADMMNET_E_ARG;
+    }
+    if (refine_lds_bytes(Nb, Nd, Le) > refine_lds_limit()) {
+        set_error("refine: a %d x %d grid with Le=%d needs %lld bytes of LDS, a workgroup has %lld", Nb, Nd, Le,
+                  (long long)refine_lds_bytes(Nb, Nd, Le), (long long)refine_lds_limit());
+        return ADMMNET_E_ARG;
+    }
+    return launch_refine(Nb, Nd, Le, B, (const float2 *)y, (const float2 *)b, rows_in, n_est, mode, psk_m, psk_phase, iters, tol,
+                         rows_out, (double2 *)C_out, info, symbols_out, status, (hipStream_t)stream);
 }
 
 // ---- AdamW and gradient-norm clipping over a tensor list (optim.hip) ---------------------------------------------------------

@@ -316,6 +316,13 @@ int launch_crb(int Nb, int Nd, int Lt, int64_t B, const float *tau_true, const f
                const int64_t *L_true, const int32_t *match, const double *noise, int noise_is_snr, double *bound, double *totals,
                int32_t *status, double *part, hipStream_t st);
 
+// refine.hip (target estimates refined against the received signal; 1 <= Le <= 16)
+int64_t refine_lds_bytes(int Nb, int Nd, int Le);     // dynamic + static LDS of one workgroup
+int64_t refine_lds_limit();
+int launch_refine(int Nb, int Nd, int Le, int64_t B, const float2 *y, const float2 *b, const double *rows_in, const int32_t *n_est,
+                  int mode, int psk_m, double psk_phase, int iters, double tol, double *rows_out, double2 *C_out, double *info,
+                  int32_t *symbols_out, int32_t *status, hipStream_t st);
+
 // optim.hip (AdamW and gradient-norm clipping over a tensor list; host arrays of device pointers)
 int64_t optim_blocks(int count, const int64_t *numel);   // blocks of the list = doubles of `partials`; -1: bad count or too many
 int launch_optim_gradnorm(int count, const float *const *grads, const int64_t *numel, float max_norm, double *partials,

@@ -14,7 +14,7 @@ CLI:  python -m admm_net_amd.harness time-net  --layers 5 --runs 1000 --out time
       python -m torch.distributed.run --nproc-per-node N -m admm_net_amd.harness train-step ...   (the step through sharded.ShardedTraining; --batch per rank; rank 0's line gains n_ranks, global_batch)
       python -m admm_net_amd.harness loss-step --batch 256 --targets 3 --dim 100 --steps 200                              (one JSON line)
       python -m admm_net_amd.harness score-step [--steps 50] [--repeats 5] [--host-signals 2048]                          (one JSON line)
-      python -m admm_net_amd.harness evaluate --grid 10x10 --layers 10 [--checkpoint P] --snr 5 15 25 --signals 4096 --targets 3 --cutoff 1.0 [--baseline classical]
+      python -m admm_net_amd.harness evaluate --grid 10x10 --layers 10 [--checkpoint P] --snr 5 15 25 --signals 4096 --targets 3 --cutoff 1.0 [--baseline classical] [--refine given|psk] [--crb]
                                                                                                     (one JSON line per SNR and method)
 """
 from __future__ import annotations
@@ -327,16 +327,22 @@ def time_score_step(steps=50, warmup=5, repeats=5, host_signals=2048, seed=0, de
 
 
 def evaluate_snr(grid=(NB, ND), layers=10, checkpoint=None, snrs=(5.0, 15.0, 25.0), signals=4096, targets=3, cutoff=1.0,
-                 baseline=None, seed=0, device="cuda:0", crb=False):
+                 baseline=None, seed=0, device="cuda:0", refine=None, crb=False):
     """Detection and accuracy against the noise level: per SNR one batch of ``signals`` scenes at exactly that SNR
     (``synth.make_batch_device(snr_range=(S, S))``), ``model.evaluate`` and ``metrics.summary`` -- scene, forward, peak search and
     score without a host loop.  ``baseline="classical"`` scores the peaks of the classical solver's phi (the generator's labels)
     the same way.  The model is ``PhiEstADMMNet`` at seed 0, or the checkpoint's.  Yields one dict per SNR and method.
     ``crb=True`` adds the root-mean Cramer-Rao bound of the same scenes, pooled over that method's own hits (``metrics.crb``), as
-    ``crb_tau`` / ``crb_f``, and the pooled RMSE over it as ``rmse_over_crb_tau`` / ``rmse_over_crb_f``."""
+    ``crb_tau`` / ``crb_f``, and the pooled RMSE over it as ``rmse_over_crb_tau`` / ``rmse_over_crb_f``.
+    ``refine="given"`` or ``"psk"`` yields, after each method's line, a line ``method + "+refine"``: the same rows fitted to the
+    received signal (``refine.refine_targets`` with that symbol mode) and scored the same way, the bound pooled over that line's
+    own hits.  The lines without ``+refine`` are those of a run without it."""
     from . import PhiEstADMMNet, metrics, ops, synth
+    from . import refine as refinement
     if baseline not in (None, "classical"):
         raise ValueError(f"baseline must be None or 'classical', got {baseline!r}")
+    if refine is not None and refine not in refinement.MODES:
+        raise ValueError(f"refine must be None or one of {sorted(refinement.MODES)}, got {refine!r}")
     dev = torch.device(device)
     M, N = grid
     torch.manual_seed(seed)
@@ -355,16 +361,30 @@ def evaluate_snr(grid=(NB, ND), layers=10, checkpoint=None, snrs=(5.0, 15.0, 25.
                 line[f"rmse_over_crb_{axis}"] = line[f"rmse_{axis}"] / c[f"crb_{axis}_hits"]
         return line
 
+    match = lambda rows, truth: metrics.match_targets(rows, truth["tau"], truth["f"], cutoff=cutoff, scale=(float(N), float(M)),  # noqa: E731
+                                                      period=(1.0, 1.0))
+
+    def refined(method, rows, y, b, truth, snr):
+        fit = refinement.refine_targets(y, b, rows, (M, N), symbols=refine)
+        return {"snr": snr, "method": method + "+refine", **head, **scored(match(fit.rows, truth), truth, snr)}
+
     for i, snr in enumerate(snrs):
         y, b, sigma, truth = synth.make_batch_device(signals, M, N, L=targets, seed=20260104 + seed + 7919 * i, snr_range=(snr, snr),
                                                      device=dev, labels=baseline is not None)
-        res = model.evaluate(y, b, sigma, truth["tau"], truth["f"], cutoff=cutoff, top=targets)
+        if refine is None:
+            res = model.evaluate(y, b, sigma, truth["tau"], truth["f"], cutoff=cutoff, top=targets)
+        else:                                                                          # evaluate, with the rows kept
+            rows, _, _ = model._estimate_rows(y, b, sigma, targets)
+            res = match(rows, truth)
         yield {"snr": snr, "method": "net", **head, **scored(res, truth, snr)}
+        if refine is not None:
+            yield refined("net", rows, y, b, truth, snr)
         if baseline is not None:
             opts = {"xstep": 1 / (10 * N), "ystep": 1 / (10 * M), "iter": 3}            # estimate's defaults
             rows, _ = ops.peak_top(truth["phi"], M, N, opts, top=targets)
-            res = metrics.match_targets(rows, truth["tau"], truth["f"], cutoff=cutoff, scale=(float(N), float(M)), period=(1.0, 1.0))
-            yield {"snr": snr, "method": "classical", **head, **scored(res, truth, snr)}
+            yield {"snr": snr, "method": "classical", **head, **scored(match(rows, truth), truth, snr)}
+            if refine is not None:
+                yield refined("classical", rows, y, b, truth, snr)
 
 
 def _grid(ap, text):
@@ -417,6 +437,8 @@ def main(argv=None):
     f.add_argument("--targets", type=int, default=3)
     f.add_argument("--cutoff", type=float, default=1.0, help="in resolution cells")
     f.add_argument("--baseline", choices=("classical",), default=None)
+    f.add_argument("--refine", choices=("given", "psk"), default=None,
+                   help="after each method's line, the same rows fitted to the received signal with these symbols")
     f.add_argument("--crb", action="store_true", help="add the Cramer-Rao bound pooled over each method's hits, and RMSE over it")
     args = ap.parse_args(argv)
     if args.cmd == "score-step":
@@ -426,7 +448,7 @@ def main(argv=None):
     if args.cmd == "evaluate":
         import json
         for line in evaluate_snr(_grid(ap, args.grid), args.layers, args.checkpoint, args.snr, args.signals, args.targets,
-                                 args.cutoff, args.baseline, crb=args.crb):
+                                 args.cutoff, args.baseline, refine=args.refine, crb=args.crb):
             print(json.dumps(line), flush=True)
         return
     if args.cmd == "loss-step":

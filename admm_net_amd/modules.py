@@ -360,6 +360,23 @@ class _FusedBase(nn.Module):
             rows, counts = ops.peak_top(phi, xbase, ybase, opts, top=top, top_n=top_n)
         return rows, counts, phi
 
+    def estimate_refined(self, y, b, sigma, top=None, top_n=None, opts=None, *, symbols="given", **refine_kw):
+        """``estimate`` followed by the stage every delay-Doppler estimator puts after the peak search: a local maximum-
+        likelihood fit of the targets to the RECEIVED signal ``y``, started at the peaks (``refine.refine_targets``: one more
+        kernel on the compute device, no host read).  ``top``, ``top_n`` and ``opts`` as in ``estimate`` (``top`` <= 16);
+        ``symbols``: "given" (s = b / |b|) or "psk" (the symbols re-decided inside the fit); ``refine_kw``: ``psk``, ``iters``,
+        ``tol`` of ``refine_targets``.
+
+        Returns (tau [B, top], f [B, top], amplitude [B, top] = |C| float64, in the peak search's rank order, NaN where a
+        signal has fewer peaks; C [B, top] complex128; counts [B] int32; phi [B, M*N] complex64; state [B] int32, the index
+        into ``refine.STATES``) on ``y.device``."""
+        from . import refine
+        rows, counts, phi = self._estimate_rows(y, b, sigma, top, top_n, opts)
+        dev, out = rows.device, y.device
+        r = refine.refine_targets(y.to(dev), b.to(dev), rows, (self.M, self.N), symbols=symbols, **refine_kw)
+        return (r.rows[:, :, 0].contiguous().to(out), r.rows[:, :, 1].contiguous().to(out), r.rows[:, :, 2].contiguous().to(out),
+                r.C.to(out), counts.to(out), phi.to(out), r.state.to(out))
+
     def evaluate(self, y, b, sigma, tau_true, f_true, L_true=None, *, cutoff, scale=None, period=(1.0, 1.0), top=None, opts=None):
         """``estimate`` scored against the truth in one call: the forward, the peak search, the top rows and the optimal
         assignment of ``metrics.match_targets`` run on the device with no host loop and, with ``check_status = False``, no host

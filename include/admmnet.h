@@ -556,6 +556,54 @@ int admmnet_crb_f64(int32_t Nb, int32_t Nd, int32_t Lt, int64_t B, const float *
                     const int64_t *L_true, const int32_t *match, const double *noise, int32_t noise_is_snr, double *bound,
                     double *totals, int32_t *status, double *partials, void *stream);
 
+/* Target estimates refined against the received signal (csrc/refine.hip, scalar core csrc/refine_core.h): a local maximum-
+ * likelihood fit of a scene's targets to y, started at the rows of a peak search.  One workgroup runs every iteration of a scene;
+ * y and b are read once.  All arithmetic is float64; every sum has a fixed order and there are no atomics, so the bits of a scene
+ * depend on neither B, nor its place in the batch, nor its neighbours.
+ *   Model.   Grid (Nb, Nd), D = Nb Nd, i = i_b Nd + i_d.  As in admmnet_crb_f64,
+ *                mu_i(theta) = sum_l C_l exp(j 2 pi (i_b f_l - i_d tau_l)),   theta = (Re C, Im C, tau, f) of the present estimates.
+ *   Data.    x_i = y_i conj(s_i) with |s_i| = 1.          Cost.   Q(theta, s) = sum_i |x_i - mu_i(theta)|^2.
+ *   Symbols. mode 0 ("given"): s_i = b_i / |b_i| throughout; an entry b_i = 0 or a non-finite b_i makes the scene non-finite.
+ *            mode 1 ("psk"): before every linearisation s_i is the point of {p_k = exp(j (2 pi k / psk_m + psk_phase)), k < psk_m}
+ *            nearest in angle to y_i conj(mu_i(theta)) -- the k of greatest Re(y_i conj(mu_i) conj(p_k)), ties to the smaller k.
+ *            b only gives the starting symbols, the point nearest to b_i (b_i = 0 gives k = 0; a non-finite b_i makes the scene
+ *            non-finite).  flips = the number of entries whose final s_i differs from the point nearest to b_i.  Both steps
+ *            minimise Q over their own variables, so Q never increases.
+ *   Start.   rows_in as admmnet_score_match_f64 reads them: (tau, f, .), a row with a non-finite tau or f is absent, only the
+ *            first n_est rows count.  The starting C is the least-squares solution at the starting (tau, f): the Cholesky of the
+ *            unit-diagonal C-block with admmnet_crb_f64's pivot floor 2^-40.
+ *   One iteration.  G = Re(J^H J) and g = Re(J^H r), r = x - mu, at the current theta; A = D G D with D = diag(G)^-1/2; solve
+ *            (A + lambda I) d' = D g, d = D d'; d is scaled so that no target moves more than half a cell (0.5 / Nd in tau,
+ *            0.5 / Nb in f).  Accepted if Q(theta + d) <= Q(theta) with s held fixed, then lambda <- lambda / 10; otherwise
+ *            lambda <- 10 lambda and the solve is repeated.  lambda starts at 1e-4.
+ *   Stop.    state 0, converged: an accepted step moves every target by at most `tol` cells, or a rejected trial step is that
+ *                     small (a scene without a present row is converged after 0 iterations, Q = sum |y|^2);
+ *            state 1, limit: `iters` linearisations (1 .. 64) are used up;
+ *            state 2, gave up: lambda > 1e8, a diagonal entry of G that is not positive and finite, or a starting C-block that
+ *                     is not positive definite.  The last accepted theta is returned; on a failed start rows_out holds the input
+ *                     (tau, f) with |C| = NaN and C_out is NaN;
+ *            state 3, non-finite: an entry of y (or of b, above) is not finite.  rows_out, C_out, Q and Q / D of the scene are NaN,
+ *                     its two counts 0;
+ *            state 4, outside: n_est is not in 0 .. Le.  As state 3.
+ *   An axis of length 1 carries no information about its parameter, which leaves theta and passes through unchanged.  Outputs
+ *   are not wrapped into a period.
+ *       1 <= Le <= 16, B >= 1, Nb, Nd >= 1 with Nb Nd within admmnet_synth_batch's ceiling (3406) and the scene's tables within
+ *       the LDS of one workgroup (admmnet_refine_lds_bytes(Nb, Nd, Le) <= 160 KiB: 26 x 131 with Le = 16 fits, 2 x 1703 fits with Le <= 3);
+ *       mode 0 or 1, 2 <= psk_m <= 64, a finite psk_phase, 1 <= iters <= 64, tol > 0 and finite.  Anything else: ADMMNET_E_ARG.
+ *       y, b          complex64 [B][D];  rows_in double [B][Le][3];  n_est int32 [B] or NULL (= Le).
+ *       rows_out      double [B][Le][3] = (tau, f, |C|); absent rows are NaN, the order is kept.
+ *       C_out         complex128 [B][Le], NaN on absent rows.
+ *       info          double [B][5] = Q, Q / D, linearisations used, flips, state (the codes above: exact in float64).
+ *       symbols_out   int32 [B][D] or NULL: the k of the final s_i in mode 1, of the point nearest to b_i in mode 0
+ *                     (-1 throughout a scene of state 3 or 4).
+ *       status        int32 [4] counts scenes: [0] outside, [1] non-finite, [2] gave up, [3] limit reached -- added from `info`
+ *                     by one workgroup in a fixed order.
+ *   No host read, no allocation, stream-ordered. */
+int64_t admmnet_refine_lds_bytes(int32_t Nb, int32_t Nd, int32_t Le);   /* -1: bad sizes */
+int admmnet_refine_f64(int32_t Nb, int32_t Nd, int32_t Le, int64_t B, const void *y, const void *b, const double *rows_in,
+                       const int32_t *n_est, int32_t mode, int32_t psk_m, double psk_phase, int32_t iters, double tol,
+                       double *rows_out, void *C_out, double *info, int32_t *symbols_out, int32_t *status, void *stream);
+
 /* AdamW and gradient-norm clipping over a LIST of float32 tensors (csrc/optim.hip): what a training loop writes as
  * torch.nn.utils.clip_grad_norm_(params, max_norm) and torch.optim.AdamW(...).step().  `count` tensors, tensor i dense with
  * numel[i] >= 0 elements; grads, params, exp_avg, exp_avg_sq are HOST arrays of `count` DEVICE pointers (as `params` of
