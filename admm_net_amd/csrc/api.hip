@@ -191,6 +191,73 @@ static int chunk_streams(hipStream_t out[2]) {
     return ADMMNET_OK;
 }
 
+// The eigensolver fallback beside the next chunk (default; ADMMNET_STREAMS=1 turns it off): behind the matrix-function kernel of a
+// chunk the eigen-pipeline only runs the few matrices that kernel flagged -- one workgroup per flagged matrix in eight dependent
+// kernels, each with a tail of its own, during which most of the chip idles.  It depends on its own chunk alone (reads the
+// chunk's flags, Z, phi and h, writes the flagged matrices' G and rn), so admmnet_layer_front enqueues it on a side stream while
+// the caller's stream goes on with prep_kernel and sp_fused_kernel of the next chunk.  One side stream per device (non-blocking,
+// the higher of the device's priorities: the handful of fallback workgroups are placed as CUs come free), created on first
+// use; the events that order it against the caller's stream come from a per-device pool.  A call leases three events
+// (one fork, two alternating "fallback done") for its duration; concurrent calls share the stream, never an event.
+struct SideStream {
+    std::mutex mu;
+    hipStream_t s = nullptr;
+    int dev = -1;
+    std::vector<hipEvent_t> idle;   // created events no call holds
+};
+struct SideLease {
+    hipStream_t s = nullptr;
+    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};   // [0], [1]: fallback of an even / odd chunk done; [2]: fork and join
+    SideStream *from = nullptr;
+};
+static void side_release(SideLease *l) {
+    if (!l->from) return;
+    std::lock_guard<std::mutex> lk(l->from->mu);
+    for (hipEvent_t &e : l->ev)
+        if (e) l->from->idle.push_back(e), e = nullptr;
+    l->from = nullptr;
+}
+static int side_acquire(SideLease *l) {
+    static SideStream ss[16];
+    int dev = 0;
+    ADMM_HIP(hipGetDevice(&dev));
+    SideStream &c = ss[dev & 15];
+    std::lock_guard<std::mutex> lk(c.mu);
+    if (c.s == nullptr || c.dev != dev) {
+        int least = 0, greatest = 0;
+        ADMM_HIP(hipDeviceGetStreamPriorityRange(&least, &greatest));
+        hipStream_t s;
+        ADMM_HIP(hipStreamCreateWithPriority(&s, hipStreamNonBlocking, greatest));
+        c.s = s;
+        c.dev = dev;
+        c.idle.clear();   // (events of another device: never reused here)
+    }
+    hipEvent_t got[3] = {nullptr, nullptr, nullptr};
+    for (int i = 0; i < 3; ++i) {
+        if (!c.idle.empty()) {
+            got[i] = c.idle.back();
+            c.idle.pop_back();
+            continue;
+        }
+        const hipError_t e = hipEventCreateWithFlags(&got[i], hipEventDisableTiming);
+        if (e != hipSuccess) {
+            for (int j = 0; j < i; ++j) c.idle.push_back(got[j]);
+            set_error("hipEventCreateWithFlags failed: %s (%s:%d)", hipGetErrorString(e), __FILE__, __LINE__);
+            return ADMMNET_E_HIP;
+        }
+    }
+    l->s = c.s;
+    for (int i = 0; i < 3; ++i) l->ev[i] = got[i];
+    l->from = &c;
+    return ADMMNET_OK;
+}
+// the caller's stream continues behind everything the side stream holds
+static int side_join(const SideLease &l, hipStream_t st) {
+    ADMM_HIP(hipEventRecord(l.ev[2], l.s));
+    ADMM_HIP(hipStreamWaitEvent(st, l.ev[2], 0));
+    return ADMMNET_OK;
+}
+
 static int carve_workspace(const admmnet_cfg *cfg, int64_t B, void *base, int64_t bytes, Ws *ws, bool state) {
     const int D = cfg->M * cfg->N;
     const int64_t n = D + 1;
@@ -504,50 +571,86 @@ int admmnet_layer_front(const admmnet_cfg *cfg, const float *W, int32_t k, const
         ADMM_HIP(hipStreamWaitEvent(ss[1], e0, 0));
         ADMM_HIP(hipEventDestroy(e0));
     }
+    // The eigensolver fallback of chunk c on the side stream, beside prep and the matrix-function kernel of chunk c + 1 (SideStream
+    // above).  Only where the fallback touches nothing the caller's stream touches meanwhile: the fused matrix function (prep then
+    // writes no image, the chunk buffers belong to the eigen-pipeline alone), a dense layer, several chunks.  With the event
+    // profiler on the call stays on one stream -- its per-class times are serial times (bench.py --full) -- and so it does with a
+    // developer phase timer on, with ADMMNET_STREAMS=2 and with ADMMNET_STREAMS=1.
+    // Flags: sp_fused_kernel of chunk c + 1 must not overwrite the flags the fallback of chunk c still reads, so consecutive chunks
+    // alternate between ws.spec_flag and a second buffer, and the kernel of chunk c + 2 waits for the fallback of chunk c.  The
+    // second buffer is ws.headkv read as int[256 D]: the head's K / V projections, which launch_head (admmnet_finish) writes
+    // and then reads in one call, behind every layer -- nothing lives there while a layer runs, and this call joins the side
+    // stream before it returns.  A chunk whose flags do not fit there stays on one stream.
+    const bool timers = sw.sf_timing || sw.pn_timing || sw.dc_timing || sw.br_timing;
+    const bool fork = r.matfun == MF_FUSED && !arrow && B > ws.chunk && !sw.two_streams && !sw.one_stream && !prof().on && !timers &&
+                      ws.spec_flag && ws.chunk <= (int64_t)256 * D;
+    SideLease side;
+    if (fork && (rc = side_acquire(&side))) return rc;
+    int *const flags[2] = {ws.spec_flag, reinterpret_cast<int *>(ws.headkv)};   // (fork only)
     // The matrix-function kernel's shape follows the size of the matrix's group, as a separate call of that group would
     // choose it (spectral_waves).  Full groups of g and a short last group may take different shapes: no chunk then
     // straddles the start of the last group.  Without sub-batches both are spectral_waves(D, B) and nothing splits.
     const int64_t gsz = group_size(cfg, B), last0 = (group_count(cfg, B) - 1) * gsz;
     const int waves_full = spectral_waves(D, gsz, sw), waves_last = spectral_waves(D, B - last0, sw);
-    int ci = 0;
-    int64_t nb = 0;
-    for (int64_t b0 = 0; b0 < B; b0 += nb, ++ci) {
-        nb = (B - b0 < ws.chunk) ? (B - b0) : ws.chunk;
-        if (waves_full != waves_last && b0 < last0 && b0 + nb > last0) nb = last0 - b0;
-        const int waves = b0 >= last0 ? waves_last : waves_full;
-        const Ws &wc = sets[ci & 1];
-        hipStream_t sc = ss[ci & 1];
-        float2 *Zk = ws.Z + b0 * n * n;
-        GLayerIO io{lw, ws.phi[cur] + b0 * D, ws.h[cur] + b0 * D, r.storage == ST_LEAN ? Zk : nullptr, ws.G + b0 * n * n,
-                    ws.rn + b0, nullptr, r.lean()};
-        if (arrow) {
-            if ((rc = launch_prep(cfg, W, k, yy, bb, sigma, b0, nb, wc, PM_NO_MATRIX, r.eig_dim, sc))) return rc;
-            if ((rc = launch_arrow_rebuild(r, sw, nb, io.lw, io.phi, io.h, io.G, io.rn, io.w_out, status, wc, sc, io.lower_only)))
-                return rc;
-            continue;
+    const auto run_chunks = [&]() -> int {
+        int rc, ci = 0;
+        int64_t nb = 0;
+        for (int64_t b0 = 0; b0 < B; b0 += nb, ++ci) {
+            nb = (B - b0 < ws.chunk) ? (B - b0) : ws.chunk;
+            if (waves_full != waves_last && b0 < last0 && b0 + nb > last0) nb = last0 - b0;
+            const int waves = b0 >= last0 ? waves_last : waves_full;
+            Ws wc = sets[ci & 1];
+            if (fork) wc.spec_flag = flags[ci & 1];
+            hipStream_t sc = ss[ci & 1];
+            float2 *Zk = ws.Z + b0 * n * n;
+            GLayerIO io{lw, ws.phi[cur] + b0 * D, ws.h[cur] + b0 * D, r.storage == ST_LEAN ? Zk : nullptr, ws.G + b0 * n * n,
+                        ws.rn + b0, nullptr, r.lean()};
+            if (arrow) {
+                if ((rc = launch_prep(cfg, W, k, yy, bb, sigma, b0, nb, wc, PM_NO_MATRIX, r.eig_dim, sc))) return rc;
+                if ((rc = launch_arrow_rebuild(r, sw, nb, io.lw, io.phi, io.h, io.G, io.rn, io.w_out, status, wc, sc, io.lower_only)))
+                    return rc;
+                continue;
+            }
+            // the lazy Z update of the previous layer rides the first sweep of the fused kernel: prep then only computes phi and h
+            const bool fold = r.fold && k >= 1;
+            const int mode = (r.storage == ST_HALF ? PM_HALF : r.storage == ST_LEAN ? PM_LEAN : 0) | (r.late_image ? PM_NOIMG : 0) |
+                             (fold ? PM_SMALL : 0);
+            if ((rc = launch_prep(cfg, W, k, yy, bb, sigma, b0, nb, wc, mode, r.eig_dim, sc))) return rc;
+            Ws wf = wc;
+            // G as a matrix function where the spectrum allows it (checked per matrix, spectral.hip); the eigen-pipeline below then
+            // only runs the matrices it flagged
+            if (r.matfun != MF_OFF) {
+                const int prv = cur ^ 1;
+                const float *lwp = k >= 1 ? W + (int64_t)(k - 1) * L.size() : lw;
+                // (these flags were chunk ci - 2's: its fallback has read them.  The side stream runs the fallbacks in order, so
+                //  this also puts the fallback of chunk ci - 1 at most one chunk behind)
+                if (fork && ci >= 2) ADMM_HIP(hipStreamWaitEvent(st, side.ev[ci & 1], 0));
+                if ((rc = launch_spectral(sw, D, nb, lw, io.phi, io.h, Zk, io.G, io.rn, wc, status, sc, r.matfun, waves,
+                                          fold ? ws.alpha + b0 : nullptr, fold ? ws.phi[prv] + b0 * D : nullptr,
+                                          fold ? ws.h[prv] + b0 * D : nullptr, fold ? lwp : nullptr, fold ? (k == 1 ? 2 : 1) : 0)))
+                    return rc;
+                wf.skip = wc.spec_flag;
+                if (fork) {   // the rest of this chunk on the side stream, behind its matrix-function kernel
+                    ADMM_HIP(hipEventRecord(side.ev[2], st));
+                    ADMM_HIP(hipStreamWaitEvent(side.s, side.ev[2], 0));
+                    sc = side.s;
+                }
+                // (the image only for the flagged matrices, afterwards)
+                if (r.late_image && (rc = launch_half_image(D, nb, lw, io.phi, io.h, Zk, wf, r.eig_dim, sc))) return rc;
+            }
+            // (ST_LEAN: the tridiagonalisation's own loader forms A from the lower triangle of Z; ST_HALF reads the half image)
+            if ((rc = eig_chunk(r, sw, nb, wf, status, sc, &io))) return rc;
+            if (fork) ADMM_HIP(hipEventRecord(side.ev[ci & 1], side.s));
         }
-        // the lazy Z update of the previous layer rides the first sweep of the fused kernel: prep then only computes phi and h
-        const bool fold = r.fold && k >= 1;
-        const int mode = (r.storage == ST_HALF ? PM_HALF : r.storage == ST_LEAN ? PM_LEAN : 0) | (r.late_image ? PM_NOIMG : 0) |
-                         (fold ? PM_SMALL : 0);
-        if ((rc = launch_prep(cfg, W, k, yy, bb, sigma, b0, nb, wc, mode, r.eig_dim, sc))) return rc;
-        Ws wf = wc;
-        // G as a matrix function where the spectrum allows it (checked per matrix, spectral.hip); the eigen-pipeline below then
-        // only runs the matrices it flagged
-        if (r.matfun != MF_OFF) {
-            const int prv = cur ^ 1;
-            const float *lwp = k >= 1 ? W + (int64_t)(k - 1) * L.size() : lw;
-            if ((rc = launch_spectral(sw, D, nb, lw, io.phi, io.h, Zk, io.G, io.rn, wc, status, sc, r.matfun, waves,
-                                      fold ? ws.alpha + b0 : nullptr, fold ? ws.phi[prv] + b0 * D : nullptr,
-                                      fold ? ws.h[prv] + b0 * D : nullptr, fold ? lwp : nullptr, fold ? (k == 1 ? 2 : 1) : 0)))
-                return rc;
-            wf.skip = wc.spec_flag;
-            // (the image only for the flagged matrices, afterwards)
-            if (r.late_image && (rc = launch_half_image(D, nb, lw, io.phi, io.h, Zk, wf, r.eig_dim, sc))) return rc;
-        }
-        // (ST_LEAN: the tridiagonalisation's own loader forms A from the lower triangle of Z; ST_HALF reads the half image)
-        if ((rc = eig_chunk(r, sw, nb, wf, status, sc, &io))) return rc;
+        return ADMMNET_OK;
+    };
+    rc = run_chunks();
+    if (fork) {   // the batch sums below read every chunk's rn; a launch that failed above leaves nothing running beside the caller either
+        const int jrc = side_join(side, st);
+        side_release(&side);
+        if (!rc) rc = jrc;
     }
+    if (rc) return rc;
     if (dual) {   // the caller's stream continues behind both chunk streams
         for (int q = 0; q < 2; ++q) {
             hipEvent_t e1;

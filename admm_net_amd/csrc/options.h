@@ -25,7 +25,7 @@ inline bool same_switches(const Switches &a, const Switches &b) {   // field by 
            a.eig_ql == b.eig_ql && a.arrow == b.arrow && a.arrow_fused == b.arrow_fused && a.ar_timing == b.ar_timing &&
            a.lean == b.lean && a.fuse_back == b.fuse_back && a.br_timing == b.br_timing && a.tridiag_lds == b.tridiag_lds &&
            a.tridiag_sweep == b.tridiag_sweep && a.back_q == b.back_q && a.rebuild_tiles == b.rebuild_tiles &&
-           a.pad_min_set == b.pad_min_set && a.pad_min == b.pad_min && a.two_streams == b.two_streams && a.tr_occ3 == b.tr_occ3 &&
+           a.pad_min_set == b.pad_min_set && a.pad_min == b.pad_min && a.two_streams == b.two_streams && a.one_stream == b.one_stream && a.tr_occ3 == b.tr_occ3 &&
            a.tr_pad_lds == b.tr_pad_lds && a.pn_split == b.pn_split && a.pn_timing == b.pn_timing && a.dc_occ == b.dc_occ &&
            a.dc_blocks == b.dc_blocks && a.dc_poison == b.dc_poison && a.dc_timing == b.dc_timing;
 }

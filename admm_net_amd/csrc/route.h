@@ -48,6 +48,9 @@ struct Switches {   // (INTEGRATION.md section 6 is the user-facing table of the
     // MI355X, K = 16, 4096 signals, padded vs sweep per forward: D = 160 306 vs 280 ms, D = 176 312 vs 368 ms, D = 192 319 vs 396 ms)
     bool pad_min_set; int pad_min;
     bool two_streams;      // ADMMNET_STREAMS=2: two chunks in flight on two internal streams (api.hip)
+    // ADMMNET_STREAMS=1: everything on the caller's stream (default: the eigensolver fallback of a chunk runs on a side stream
+    // beside the next chunk's matrix-function kernel, api.hip)
+    bool one_stream;
     bool tr_occ3;          // ADMMNET_TR_OCC=2 clears it: the two-workgroup build of tridiag_reg_kernel<7> for A/B runs
     int tr_pad_lds;        // ADMMNET_TR_PAD_LDS=<bytes> of unused dynamic LDS per tridiag_reg workgroup (developer knob)
     int pn_split;          // ADMMNET_PN_SPLIT: stages of the panel tridiagonalisation -- "0" one (0), "8" two (8), else three (84)
@@ -65,7 +68,7 @@ inline Switches builtin_switches() {
     s.spectral_tol = 1e-6f;
     s.spectral_iters = 5;
     s.sf_timing = s.ar_timing = s.br_timing = s.pn_timing = s.dc_timing = s.dc_poison = false;
-    s.eig_ql = s.tridiag_lds = s.tridiag_sweep = s.back_q = s.rebuild_tiles = s.two_streams = false;
+    s.eig_ql = s.tridiag_lds = s.tridiag_sweep = s.back_q = s.rebuild_tiles = s.two_streams = s.one_stream = false;
     s.pad_min_set = false;
     s.pad_min = 0;
     s.tr_occ3 = true;
@@ -107,6 +110,7 @@ inline Switches switches_from_env(const Switches &base, const Lookup &env) {
     s.pad_min_set = set("ADMMNET_PAD_MIN", base.pad_min_set);
     s.pad_min = num("ADMMNET_PAD_MIN", base.pad_min);
     s.two_streams = env("ADMMNET_STREAMS") ? atoi(env("ADMMNET_STREAMS")) == 2 : base.two_streams;
+    s.one_stream = env("ADMMNET_STREAMS") ? atoi(env("ADMMNET_STREAMS")) == 1 : base.one_stream;
     s.tr_occ3 = env("ADMMNET_TR_OCC") ? atoi(env("ADMMNET_TR_OCC")) != 2 : base.tr_occ3;
     s.tr_pad_lds = num("ADMMNET_TR_PAD_LDS", base.tr_pad_lds);
     s.pn_split = !env("ADMMNET_PN_SPLIT") ? base.pn_split : is("ADMMNET_PN_SPLIT", "0", false) ? 0 : is("ADMMNET_PN_SPLIT", "8", false) ? 8 : 84;

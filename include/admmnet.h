@@ -14,7 +14,11 @@
  *     (thread-local).
  *   - the CALLER owns every buffer (device and host); nothing here allocates
  *     device memory.  All device work is enqueued on the caller's stream and is
- *     asynchronous; no call synchronises the device.
+ *     asynchronous; no call synchronises the device.  (admmnet_layer_front may
+ *     run part of a layer on an internal stream beside the caller's, ordered
+ *     by events and joined before it returns: what the caller enqueues next on
+ *     its stream runs behind all of it.  INTEGRATION.md section 6,
+ *     ADMMNET_STREAMS.)
  *   - device = the caller's current HIP device.
  *   - complex64 = interleaved (re, im) float pairs, as torch.complex64.
  *   - D = M*N (signal length), n = D + 1 (state dimension), B = batch,
