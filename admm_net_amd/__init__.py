@@ -7,5 +7,7 @@ Importing this package never imports the CPU oracle.
 from .options import Options  # noqa: F401
 from .modules import ADMMNet, PhiEstADMMNet, PeakSearchLayer, PhiLayer, HLayer, GLayer, ZLayer  # noqa: F401
 from . import optim  # noqa: F401
+from . import order  # noqa: F401
+from .order import select_targets, select_refined  # noqa: F401
 
-__all__ = ["ADMMNet", "PhiEstADMMNet", "Options"]
+__all__ = ["ADMMNet", "PhiEstADMMNet", "Options", "select_targets", "select_refined"]

@@ -1317,6 +1317,36 @@ int admmnet_refine_f64(int32_t Nb, int32_t Nd, int32_t Le, int64_t B, const void
                          rows_out, (double2 *)C_out, info, symbols_out, status, (hipStream_t)stream);
 }
 
+// ---- the number of targets of a scene selected among candidate rows (order.hip) ----------------------------------------------
+// the sizes of the refinement; a thread per pair of rows, the rows taken in a 32-bit mask
+int64_t admmnet_order_lds_bytes(int32_t Nb, int32_t Nd, int32_t Le) {
+    if (!refine_sizes_ok(Nb, Nd, Le)) return -1;
+    return order_lds_bytes(Nb, Nd, Le) <= order_lds_limit() ? order_lds_bytes(Nb, Nd, Le) : -1;
+}
+
+int admmnet_order_f64(int32_t Nb, int32_t Nd, int32_t Le, int64_t B, const void *y, const void *b, const double *rows_in,
+                      const int32_t *n_cand, const int32_t *n_held, const int32_t *symbols, int32_t psk_m, double psk_phase,
+                      double penalty, int32_t max_order, int32_t *perm, int32_t *n_sel, double *rss, double *rows_out, void *C_out,
+                      void *residual, double *info, int32_t *status, void *stream) {
+    if (!refine_sizes_ok(Nb, Nd, Le) || B < 1 || B > 2147483647 || psk_m < 2 || psk_m > REFINE_MAX_M || !sc_finite(psk_phase) ||
+        !(penalty >= 0.0) || !sc_finite(penalty) || max_order < 1 || max_order > Le || !y || !b || !rows_in || !perm || !n_sel ||
+        !rss || !rows_out || !C_out || !residual || !info || !status || rows_out == rows_in) {
+        set_error("order: bad argument (Nb=%d, Nd=%d with Nb * Nd <= %lld, Le=%d in 1 .. %d, B=%lld, psk_m=%d in 2 .. %d, "
+                  "psk_phase=%g, penalty=%g >= 0, max_order=%d in 1 .. Le, a null pointer, or rows_out = rows_in)",
+                  Nb, Nd, (long long)synth_max_cells(), Le, CRB_MAXL, (long long)B, psk_m, REFINE_MAX_M, psk_phase, penalty,
+                  max_order);
+        return ADMMNET_E_ARG;
+    }
+    if (order_lds_bytes(Nb, Nd, Le) > order_lds_limit()) {
+        set_error("order: a %d x %d grid with Le=%d needs %lld bytes of LDS, a workgroup has %lld", Nb, Nd, Le,
+                  (long long)order_lds_bytes(Nb, Nd, Le), (long long)order_lds_limit());
+        return ADMMNET_E_ARG;
+    }
+    return launch_order(Nb, Nd, Le, B, (const float2 *)y, (const float2 *)b, rows_in, n_cand, n_held, symbols, psk_m, psk_phase,
+                        penalty, max_order, perm, n_sel, rss, rows_out, (double2 *)C_out, (float2 *)residual, info, status,
+                        (hipStream_t)stream);
+}
+
 // ---- AdamW and gradient-norm clipping over a tensor list (optim.hip) ---------------------------------------------------------
 // a pointer may be null only where its tensor has no element
 static int optim_args_ok(const char *what, int32_t count, const int64_t *numel, bool ptrs, const void *const *const *lists, int nlists) {

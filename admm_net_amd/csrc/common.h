@@ -323,6 +323,14 @@ int launch_refine(int Nb, int Nd, int Le, int64_t B, const float2 *y, const floa
                   int mode, int psk_m, double psk_phase, int iters, double tol, double *rows_out, double2 *C_out, double *info,
                   int32_t *symbols_out, int32_t *status, hipStream_t st);
 
+// order.hip (the number of targets of a scene selected among candidate rows; 1 <= Le <= 16)
+int64_t order_lds_bytes(int Nb, int Nd, int Le);      // dynamic LDS of one workgroup
+int64_t order_lds_limit();
+int launch_order(int Nb, int Nd, int Le, int64_t B, const float2 *y, const float2 *b, const double *rows_in, const int32_t *n_cand,
+                 const int32_t *n_held, const int32_t *symbols, int psk_m, double psk_phase, double penalty, int max_order,
+                 int32_t *perm, int32_t *n_sel, double *rss, double *rows_out, double2 *C_out, float2 *residual, double *info,
+                 int32_t *status, hipStream_t st);
+
 // optim.hip (AdamW and gradient-norm clipping over a tensor list; host arrays of device pointers)
 int64_t optim_blocks(int count, const int64_t *numel);   // blocks of the list = doubles of `partials`; -1: bad count or too many
 int launch_optim_gradnorm(int count, const float *const *grads, const int64_t *numel, float max_norm, double *partials,

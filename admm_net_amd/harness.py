@@ -14,7 +14,7 @@ CLI:  python -m admm_net_amd.harness time-net  --layers 5 --runs 1000 --out time
       python -m torch.distributed.run --nproc-per-node N -m admm_net_amd.harness train-step ...   (the step through sharded.ShardedTraining; --batch per rank; rank 0's line gains n_ranks, global_batch)
       python -m admm_net_amd.harness loss-step --batch 256 --targets 3 --dim 100 --steps 200                              (one JSON line)
       python -m admm_net_amd.harness score-step [--steps 50] [--repeats 5] [--host-signals 2048]                          (one JSON line)
-      python -m admm_net_amd.harness evaluate --grid 10x10 --layers 10 [--checkpoint P] --snr 5 15 25 --signals 4096 --targets 3 --cutoff 1.0 [--baseline classical] [--refine given|psk] [--crb]
+      python -m admm_net_amd.harness evaluate --grid 10x10 --layers 10 [--checkpoint P] --snr 5 15 25 --signals 4096 --targets 3 --cutoff 1.0 [--baseline classical] [--refine given|psk] [--crb] [--order TOP]
                                                                                                     (one JSON line per SNR and method)
 """
 from __future__ import annotations
@@ -327,7 +327,7 @@ def time_score_step(steps=50, warmup=5, repeats=5, host_signals=2048, seed=0, de
 
 
 def evaluate_snr(grid=(NB, ND), layers=10, checkpoint=None, snrs=(5.0, 15.0, 25.0), signals=4096, targets=3, cutoff=1.0,
-                 baseline=None, seed=0, device="cuda:0", refine=None, crb=False):
+                 baseline=None, seed=0, device="cuda:0", order=None, refine=None, crb=False):
     """Detection and accuracy against the noise level: per SNR one batch of ``signals`` scenes at exactly that SNR
     (``synth.make_batch_device(snr_range=(S, S))``), ``model.evaluate`` and ``metrics.summary`` -- scene, forward, peak search and
     score without a host loop.  ``baseline="classical"`` scores the peaks of the classical solver's phi (the generator's labels)
@@ -336,13 +336,19 @@ def evaluate_snr(grid=(NB, ND), layers=10, checkpoint=None, snrs=(5.0, 15.0, 25.
     ``crb_tau`` / ``crb_f``, and the pooled RMSE over it as ``rmse_over_crb_tau`` / ``rmse_over_crb_f``.
     ``refine="given"`` or ``"psk"`` yields, after each method's line, a line ``method + "+refine"``: the same rows fitted to the
     received signal (``refine.refine_targets`` with that symbol mode) and scored the same way, the bound pooled over that line's
-    own hits.  The lines without ``+refine`` are those of a run without it."""
+    own hits.  The lines without ``+refine`` are those of a run without it.
+    ``order=TOP`` (targets .. 16) yields, after those, a line ``method + "+order"``: TOP candidate peaks of the same phi through
+    ``order.select_refined`` with the symbol mode of ``refine`` ("given" if that is None), the selected rows scored with
+    ``n_est = n_sel``.  The other lines are those of a run without it."""
     from . import PhiEstADMMNet, metrics, ops, synth
+    from . import order as ordering
     from . import refine as refinement
     if baseline not in (None, "classical"):
         raise ValueError(f"baseline must be None or 'classical', got {baseline!r}")
     if refine is not None and refine not in refinement.MODES:
         raise ValueError(f"refine must be None or one of {sorted(refinement.MODES)}, got {refine!r}")
+    if order is not None and (isinstance(order, bool) or int(order) != order or not max(1, targets) <= order <= metrics.MAX_TARGETS):
+        raise ValueError(f"order must be None or an int in targets .. {metrics.MAX_TARGETS}, got {order!r}")
     dev = torch.device(device)
     M, N = grid
     torch.manual_seed(seed)
@@ -368,6 +374,15 @@ def evaluate_snr(grid=(NB, ND), layers=10, checkpoint=None, snrs=(5.0, 15.0, 25.
         fit = refinement.refine_targets(y, b, rows, (M, N), symbols=refine)
         return {"snr": snr, "method": method + "+refine", **head, **scored(match(fit.rows, truth), truth, snr)}
 
+    est_opts = {"xstep": 1 / (10 * N), "ystep": 1 / (10 * M), "iter": 3}              # estimate's defaults
+
+    def ordered(method, phi, y, b, truth, snr):
+        cand, _ = ops.peak_top(phi, M, N, est_opts, top=int(order))
+        sel, _ = ordering.select_refined(y, b, cand, (M, N), symbols=refine or "given")
+        res = metrics.match_targets(sel.rows_out, truth["tau"], truth["f"], n_est=sel.n_sel, cutoff=cutoff, scale=(float(N), float(M)),
+                                    period=(1.0, 1.0))
+        return {"snr": snr, "method": method + "+order", **head, **scored(res, truth, snr)}
+
     for i, snr in enumerate(snrs):
         y, b, sigma, truth = synth.make_batch_device(signals, M, N, L=targets, seed=20260104 + seed + 7919 * i, snr_range=(snr, snr),
                                                      device=dev, labels=baseline is not None)
@@ -379,12 +394,18 @@ def evaluate_snr(grid=(NB, ND), layers=10, checkpoint=None, snrs=(5.0, 15.0, 25.
         yield {"snr": snr, "method": "net", **head, **scored(res, truth, snr)}
         if refine is not None:
             yield refined("net", rows, y, b, truth, snr)
+        if order is not None:
+            with torch.no_grad():
+                phi, _ = model._run(y, b, sigma, to_caller=False)
+            yield ordered("net", phi, y, b, truth, snr)
         if baseline is not None:
             opts = {"xstep": 1 / (10 * N), "ystep": 1 / (10 * M), "iter": 3}            # estimate's defaults
             rows, _ = ops.peak_top(truth["phi"], M, N, opts, top=targets)
             yield {"snr": snr, "method": "classical", **head, **scored(match(rows, truth), truth, snr)}
             if refine is not None:
                 yield refined("classical", rows, y, b, truth, snr)
+            if order is not None:
+                yield ordered("classical", truth["phi"], y, b, truth, snr)
 
 
 def _grid(ap, text):
@@ -440,6 +461,8 @@ def main(argv=None):
     f.add_argument("--refine", choices=("given", "psk"), default=None,
                    help="after each method's line, the same rows fitted to the received signal with these symbols")
     f.add_argument("--crb", action="store_true", help="add the Cramer-Rao bound pooled over each method's hits, and RMSE over it")
+    f.add_argument("--order", type=int, default=None, metavar="TOP",
+                   help="after each method's lines, TOP candidate peaks with the number of targets selected against the received signal")
     args = ap.parse_args(argv)
     if args.cmd == "score-step":
         import json
@@ -448,7 +471,7 @@ def main(argv=None):
     if args.cmd == "evaluate":
         import json
         for line in evaluate_snr(_grid(ap, args.grid), args.layers, args.checkpoint, args.snr, args.signals, args.targets,
-                                 args.cutoff, args.baseline, refine=args.refine, crb=args.crb):
+                                 args.cutoff, args.baseline, refine=args.refine, crb=args.crb, order=args.order):
             print(json.dumps(line), flush=True)
         return
     if args.cmd == "loss-step":

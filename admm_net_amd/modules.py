@@ -377,6 +377,27 @@ class _FusedBase(nn.Module):
         return (r.rows[:, :, 0].contiguous().to(out), r.rows[:, :, 1].contiguous().to(out), r.rows[:, :, 2].contiguous().to(out),
                 r.C.to(out), counts.to(out), phi.to(out), r.state.to(out))
 
+    def estimate_selected(self, y, b, sigma, top=None, opts=None, *, rounds=2, grow=0, symbols="given", penalty=None, **refine_kw):
+        """``estimate`` for an UNKNOWN number of targets: ``top`` candidate peaks (None: min(2 L, 16)) go through the selection-
+        and-refinement loop of ``order.select_refined`` -- the candidates ranked against the received signal ``y``, their number
+        chosen by a penalised log residual, the chosen ones fitted, ``rounds`` times, ``grow`` more times with the highest peak
+        of the residual added -- on the compute device, without a host read.  ``opts`` as in ``estimate``; ``symbols``,
+        ``penalty`` and ``refine_kw`` as in ``select_refined``.
+
+        Returns (tau [B, top], f [B, top], amplitude [B, top] = |C| float64, NaN past n_sel; C [B, top] complex128; n_sel [B]
+        int32, the number of targets selected; counts [B] int32; phi [B, M*N] complex64; state [B] int32: 0, or the code of
+        ``refine.STATES`` for a scene that was not ranked) on ``y.device``."""
+        from . import order
+        top = min(2 * self.L, 16) if top is None else top
+        rows, counts, phi = self._estimate_rows(y, b, sigma, top, None, opts)
+        dev, out = rows.device, y.device
+        sel, _ = order.select_refined(y.to(dev), b.to(dev), rows, (self.M, self.N), rounds=rounds, grow=grow, symbols=symbols,
+                                      penalty=penalty, **refine_kw)
+        chosen = (torch.arange(rows.shape[1], device=dev)[None, :] < sel.n_sel[:, None])
+        est = torch.where(chosen[:, :, None], sel.rows_out, torch.full_like(sel.rows_out, float("nan")))
+        return (est[:, :, 0].contiguous().to(out), est[:, :, 1].contiguous().to(out), est[:, :, 2].contiguous().to(out),
+                sel.C.to(out), sel.n_sel.to(out), counts.to(out), phi.to(out), sel.state.to(out))
+
     def evaluate(self, y, b, sigma, tau_true, f_true, L_true=None, *, cutoff, scale=None, period=(1.0, 1.0), top=None, opts=None):
         """``estimate`` scored against the truth in one call: the forward, the peak search, the top rows and the optimal
         assignment of ``metrics.match_targets`` run on the device with no host loop and, with ``check_status = False``, no host

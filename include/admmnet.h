@@ -608,6 +608,48 @@ int admmnet_refine_f64(int32_t Nb, int32_t Nd, int32_t Le, int64_t B, const void
                        const int32_t *n_est, int32_t mode, int32_t psk_m, double psk_phase, int32_t iters, double tol,
                        double *rows_out, void *C_out, double *info, int32_t *symbols_out, int32_t *status, void *stream);
 
+/* The number of targets of a scene selected among candidate rows (csrc/order.hip, scalar core csrc/order_core.h): the rows ranked
+ * by greedy orthogonal least squares against the received signal, the order chosen by a penalised log residual.  One workgroup per
+ * scene, one launch; y and b are read once.  All arithmetic is float64; every sum has a fixed order and there are no atomics, so
+ * the bits of a scene depend on neither B, nor its place in the batch, nor its neighbours.
+ *   Data.    Grid (Nb, Nd), D = Nb Nd, i = i_b Nd + i_d, x_i = y_i conj(s_i) as in admmnet_refine_f64: s_i = b_i / |b_i| where
+ *            `symbols` is NULL, else s_i = p_k with k = symbols_i and p_k = exp(j (2 pi k / psk_m + psk_phase)) -- what
+ *            admmnet_refine_f64 writes to symbols_out.
+ *   Atoms.   a_l(i) = exp(j 2 pi (i_b f_l - i_d tau_l)) for every present row: l < n_cand with a finite tau_l and f_l.
+ *   Ranking. The present rows l < n_held are taken first, in their given order.  After them every step takes the remaining row
+ *            of greatest gain |a~_j^H r|^2 / |a~_j|^2, a~_j = a_j made orthogonal to the rows already taken, r the present
+ *            residual; ties go to the smaller index.  A row with |a~_j|^2 < 2^-40 D is never taken, held or not (it coincides with
+ *            rows already taken).  The ranking ends when max_order rows are taken or none can be.  RSS_0 = sum |x_i|^2,
+ *            RSS_k = RSS_(k-1) - gain_k.
+ *   Order.   n_sel = the smallest k in h .. K that minimises D ln(max(RSS_k, 2^-80 RSS_0) / D) + penalty k, K the number of rows
+ *            ranked, h <= n_held the number of held rows among them.
+ *   States.  0, ranked;
+ *            3, non-finite: an entry of y or b is not finite, or b_i = 0 where `symbols` is NULL;
+ *            4, outside: n_cand not in 0 .. Le, n_held not in 0 .. n_cand, or a symbol not in 0 .. psk_m - 1 (admmnet_refine_f64
+ *               marks a scene it did not fit with -1).  State 4 is looked for first.  The codes are admmnet_refine_f64's.
+ *            A scene of state 3 or 4 is not ranked: perm is 0 .. Le - 1, n_sel = 0, everything else NaN.
+ *       1 <= Le <= 16, B >= 1, Nb Nd <= 3406 and admmnet_order_lds_bytes(Nb, Nd, Le) != -1 (the scene's tables within the 160 KiB of
+ *       LDS of one workgroup), 2 <= psk_m <= 64, a finite psk_phase, a finite penalty >= 0, 1 <= max_order <= Le, rows_out not
+ *       rows_in.  Anything else: ADMMNET_E_ARG before a launch.
+ *       y, b          complex64 [B][D];  rows_in double [B][Le][3] = (tau, f, .);  n_cand, n_held int32 [B] or NULL (= Le, = 0);
+ *                     symbols int32 [B][D] or NULL.
+ *       perm          int32 [B][Le]: the ranked rows in the order they were taken, then the other rows in index order.
+ *       n_sel         int32 [B].
+ *       rss           double [B][Le + 1]: RSS_0 .. RSS_K, NaN past K.
+ *       rows_out      double [B][Le][3]: row perm[j] of rows_in, the third column |C_j| for j < n_sel and NaN beyond -- with
+ *                     n_est = n_sel what admmnet_refine_f64 starts from.
+ *       C_out         complex128 [B][Le]: the least-squares amplitudes of the selected rows, NaN beyond n_sel.
+ *       residual      complex64 [B][D] = x - sum_(j < n_sel) C_j a_perm[j], evaluated entry by entry (not from RSS, whose closed
+ *                     form cancels).
+ *       info          double [B][4] = cost (the sum of |residual|^2, added in float64 before the rounding), cost / D, K, state.
+ *       status        int32 [2] counts scenes: [0] non-finite, [1] outside -- added from `info` by one workgroup in a fixed order.
+ *   No host read, no allocation, stream-ordered. */
+int64_t admmnet_order_lds_bytes(int32_t Nb, int32_t Nd, int32_t Le);   /* -1: bad sizes, or more than a workgroup has */
+int admmnet_order_f64(int32_t Nb, int32_t Nd, int32_t Le, int64_t B, const void *y, const void *b, const double *rows_in,
+                      const int32_t *n_cand, const int32_t *n_held, const int32_t *symbols, int32_t psk_m, double psk_phase,
+                      double penalty, int32_t max_order, int32_t *perm, int32_t *n_sel, double *rss, double *rows_out, void *C_out,
+                      void *residual, double *info, int32_t *status, void *stream);
+
 /* AdamW and gradient-norm clipping over a LIST of float32 tensors (csrc/optim.hip): what a training loop writes as
  * torch.nn.utils.clip_grad_norm_(params, max_norm) and torch.optim.AdamW(...).step().  `count` tensors, tensor i dense with
  * numel[i] >= 0 elements; grads, params, exp_avg, exp_avg_sq are HOST arrays of `count` DEVICE pointers (as `params` of
