@@ -1568,4 +1568,22 @@ int admmnet_synth_batch(int64_t B, int32_t Nb, int32_t Nd, int32_t L, uint64_t s
                         f, (float2 *)C, (float2 *)phi_label, (hipStream_t)stream);
 }
 
+int admmnet_synth_scenes(int64_t B, int32_t Nb, int32_t Nd, int32_t L_min, int32_t L_max, double min_sep, uint64_t seed,
+                         double snr_lo, double snr_hi, double snr_e, double rho, int32_t label_iters, void *y, void *b,
+                         float *sigma, float *tau, float *f, void *C, void *phi_label, int64_t *L_true, double *snr_db,
+                         double *noise_var, float *ser, int32_t *state, void *stream) {
+    // (launch_synth_scenes refuses an Nb * Nd whose three float64 arrays do not fit the LDS)
+    if (B < 1 || B > 2147483647 || Nb < 1 || Nd < 1 || L_min < 1 || L_max > 8 || L_min > L_max || !(min_sep >= 0.0) ||
+        !__builtin_isfinite(min_sep) || label_iters < 0 || !y || !b || !sigma || !tau || !f || !C || !L_true || !snr_db ||
+        !noise_var || !ser || !state) {
+        set_error("synth_scenes: needs 1 <= B < 2^31, Nb, Nd >= 1, 1 <= L_min <= L_max <= 8, a finite min_sep >= 0, label_iters "
+                  ">= 0 and every output but phi_label (got B %lld, grid %d x %d, targets %d .. %d, min_sep %g, label_iters %d)",
+                  (long long)B, Nb, Nd, L_min, L_max, min_sep, label_iters);
+        return ADMMNET_E_ARG;
+    }
+    return launch_synth_scenes(B, Nb, Nd, L_min, L_max, min_sep, seed, snr_lo, snr_hi, snr_e, rho, label_iters, (float2 *)y,
+                               (float2 *)b, sigma, tau, f, (float2 *)C, (float2 *)phi_label, L_true, snr_db, noise_var, ser,
+                               state, (hipStream_t)stream);
+}
+
 }  // extern "C"

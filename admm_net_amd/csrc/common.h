@@ -347,6 +347,10 @@ int64_t synth_max_cells();                            // the largest Nb * Nd a s
 int launch_synth(int64_t B, int Nb, int Nd, int L, unsigned long long seed, double snr_lo, double snr_hi, double snr_e,
                  double rho, int label_iters, float2 *y, float2 *b, float *sigma, float *tau, float *f, float2 *C,
                  float2 *phi_label, hipStream_t st);
+int launch_synth_scenes(int64_t B, int Nb, int Nd, int L_min, int L_max, double min_sep, unsigned long long seed, double snr_lo,
+                        double snr_hi, double snr_e, double rho, int label_iters, float2 *y, float2 *b, float *sigma,
+                        float *tau, float *f, float2 *C, float2 *phi_label, int64_t *L_true, double *snr_db,
+                        double *noise_var, float *ser, int32_t *state, hipStream_t st);
 
 // ---- optional per-kernel-class HIP-event profiler (bench.py roofline leg) ------
 enum KernelClass { KC_PREP = 0, KC_TRIDIAG, KC_TQL, KC_ROTAPPLY, KC_REBUILD, KC_ZSTEP, KC_HEAD, KC_SPECTRUM, KC_GFUNC, KC_COUNT };

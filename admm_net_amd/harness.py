@@ -22,6 +22,7 @@ from __future__ import annotations
 import argparse
 import contextlib
 import io
+import math
 import time
 
 import numpy as np
@@ -327,7 +328,7 @@ def time_score_step(steps=50, warmup=5, repeats=5, host_signals=2048, seed=0, de
 
 
 def evaluate_snr(grid=(NB, ND), layers=10, checkpoint=None, snrs=(5.0, 15.0, 25.0), signals=4096, targets=3, cutoff=1.0,
-                 baseline=None, seed=0, device="cuda:0", order=None, refine=None, crb=False):
+                 baseline=None, seed=0, device="cuda:0", targets_min=None, min_sep=0.0, order=None, refine=None, crb=False):
     """Detection and accuracy against the noise level: per SNR one batch of ``signals`` scenes at exactly that SNR
     (``synth.make_batch_device(snr_range=(S, S))``), ``model.evaluate`` and ``metrics.summary`` -- scene, forward, peak search and
     score without a host loop.  ``baseline="classical"`` scores the peaks of the classical solver's phi (the generator's labels)
@@ -339,7 +340,14 @@ def evaluate_snr(grid=(NB, ND), layers=10, checkpoint=None, snrs=(5.0, 15.0, 25.
     own hits.  The lines without ``+refine`` are those of a run without it.
     ``order=TOP`` (targets .. 16) yields, after those, a line ``method + "+order"``: TOP candidate peaks of the same phi through
     ``order.select_refined`` with the symbol mode of ``refine`` ("given" if that is None), the selected rows scored with
-    ``n_est = n_sel``.  The other lines are those of a run without it."""
+    ``n_est = n_sel``.  The other lines are those of a run without it.
+    ``targets_min=LO`` (1 .. targets) and / or ``min_sep=CELLS`` > 0 draw the scenes with ``synth.make_scenes_device``: LO ..
+    ``targets`` targets per scene, at least CELLS resolution cells apart.  The ``net`` and ``classical`` lines and their
+    ``+refine`` lines are then GIVEN each scene's count (``top_n = n_est = L_true``), the ``+order`` lines are not: they select
+    it, and gain ``order_under`` / ``order_exact`` / ``order_over``, the shares of the scenes where ``n_sel`` <, ==, > ``L_true``.
+    Every line gains ``targets_min``, ``min_sep``, ``unseparated`` (scenes where a target stayed closer than ``min_sep``) and
+    ``ser`` (the mean percentage of symbols decided wrongly); everything is scored against ``L_true``, the bound included.  With
+    both at their defaults the scenes, the lines and their keys are those of ``make_batch_device``."""
     from . import PhiEstADMMNet, metrics, ops, synth
     from . import order as ordering
     from . import refine as refinement
@@ -349,6 +357,11 @@ def evaluate_snr(grid=(NB, ND), layers=10, checkpoint=None, snrs=(5.0, 15.0, 25.
         raise ValueError(f"refine must be None or one of {sorted(refinement.MODES)}, got {refine!r}")
     if order is not None and (isinstance(order, bool) or int(order) != order or not max(1, targets) <= order <= metrics.MAX_TARGETS):
         raise ValueError(f"order must be None or an int in targets .. {metrics.MAX_TARGETS}, got {order!r}")
+    varied = targets_min is not None or min_sep != 0.0
+    if targets_min is not None and (isinstance(targets_min, bool) or int(targets_min) != targets_min or not 1 <= targets_min <= targets):
+        raise ValueError(f"targets_min must be None or an int in 1 .. targets, got {targets_min!r}")
+    if not (min_sep >= 0.0 and math.isfinite(min_sep)):
+        raise ValueError(f"min_sep must be finite and >= 0, got {min_sep!r}")
     dev = torch.device(device)
     M, N = grid
     torch.manual_seed(seed)
@@ -357,21 +370,35 @@ def evaluate_snr(grid=(NB, ND), layers=10, checkpoint=None, snrs=(5.0, 15.0, 25.
         load_checkpoint(checkpoint, model)
     model.eval()
     head = {"grid": [M, N], "layers": layers, "signals": signals, "targets": targets, "cutoff": cutoff}
+    if varied:
+        head.update(targets_min=targets if targets_min is None else int(targets_min), min_sep=float(min_sep))
 
-    def scored(res, truth, snr):
-        line = metrics.summary(res)
+    def scored(res, truth, snr, n_sel=None):
+        if varied:                                                                     # in summary's one read
+            extra = {"unseparated": truth["state"].sum(), "ser": truth["ser"].mean()}
+            if n_sel is not None:
+                extra["order"] = metrics.order_counts(n_sel, truth["L_true"])
+            line = metrics.summary(res, extra=extra)
+            line["unseparated"] = int(line["unseparated"])
+            if n_sel is not None:
+                for name, count in zip(("order_under", "order_exact", "order_over"), line.pop("order")):
+                    line[name] = count / signals
+        else:
+            line = metrics.summary(res)
         if crb:
-            c = metrics.crb_summary(metrics.crb(truth["tau"], truth["f"], truth["C"], (M, N), snr_db=snr, match=res.match))
+            c = metrics.crb_summary(metrics.crb(truth["tau"], truth["f"], truth["C"], (M, N), snr_db=snr, L_true=truth.get("L_true"),
+                                                match=res.match))
             for axis in ("tau", "f"):
                 line[f"crb_{axis}"] = c[f"crb_{axis}_hits"]
                 line[f"rmse_over_crb_{axis}"] = line[f"rmse_{axis}"] / c[f"crb_{axis}_hits"]
         return line
 
-    match = lambda rows, truth: metrics.match_targets(rows, truth["tau"], truth["f"], cutoff=cutoff, scale=(float(N), float(M)),  # noqa: E731
-                                                      period=(1.0, 1.0))
+    # truth["L_true"]: the count of every scene, which these rows were cut to (None: every scene has ``targets``)
+    match = lambda rows, truth: metrics.match_targets(rows, truth["tau"], truth["f"], truth.get("L_true"), truth.get("L_true"),  # noqa: E731
+                                                      cutoff=cutoff, scale=(float(N), float(M)), period=(1.0, 1.0))
 
     def refined(method, rows, y, b, truth, snr):
-        fit = refinement.refine_targets(y, b, rows, (M, N), symbols=refine)
+        fit = refinement.refine_targets(y, b, rows, (M, N), n_est=truth.get("L_true"), symbols=refine)
         return {"snr": snr, "method": method + "+refine", **head, **scored(match(fit.rows, truth), truth, snr)}
 
     est_opts = {"xstep": 1 / (10 * N), "ystep": 1 / (10 * M), "iter": 3}              # estimate's defaults
@@ -379,17 +406,22 @@ def evaluate_snr(grid=(NB, ND), layers=10, checkpoint=None, snrs=(5.0, 15.0, 25.
     def ordered(method, phi, y, b, truth, snr):
         cand, _ = ops.peak_top(phi, M, N, est_opts, top=int(order))
         sel, _ = ordering.select_refined(y, b, cand, (M, N), symbols=refine or "given")
-        res = metrics.match_targets(sel.rows_out, truth["tau"], truth["f"], n_est=sel.n_sel, cutoff=cutoff, scale=(float(N), float(M)),
-                                    period=(1.0, 1.0))
-        return {"snr": snr, "method": method + "+order", **head, **scored(res, truth, snr)}
+        res = metrics.match_targets(sel.rows_out, truth["tau"], truth["f"], truth.get("L_true"), n_est=sel.n_sel, cutoff=cutoff,
+                                    scale=(float(N), float(M)), period=(1.0, 1.0))
+        return {"snr": snr, "method": method + "+order", **head, **scored(res, truth, snr, sel.n_sel)}
 
     for i, snr in enumerate(snrs):
-        y, b, sigma, truth = synth.make_batch_device(signals, M, N, L=targets, seed=20260104 + seed + 7919 * i, snr_range=(snr, snr),
-                                                     device=dev, labels=baseline is not None)
-        if refine is None:
+        if varied:
+            y, b, sigma, truth = synth.make_scenes_device(signals, M, N, targets=(head["targets_min"], targets), min_sep=min_sep,
+                                                          seed=20260104 + seed + 7919 * i, snr_range=(snr, snr), device=dev,
+                                                          labels=baseline is not None)
+        else:
+            y, b, sigma, truth = synth.make_batch_device(signals, M, N, L=targets, seed=20260104 + seed + 7919 * i, snr_range=(snr, snr),
+                                                         device=dev, labels=baseline is not None)
+        if refine is None and not varied:
             res = model.evaluate(y, b, sigma, truth["tau"], truth["f"], cutoff=cutoff, top=targets)
         else:                                                                          # evaluate, with the rows kept
-            rows, _, _ = model._estimate_rows(y, b, sigma, targets)
+            rows, _, _ = model._estimate_rows(y, b, sigma, targets, truth.get("L_true"))
             res = match(rows, truth)
         yield {"snr": snr, "method": "net", **head, **scored(res, truth, snr)}
         if refine is not None:
@@ -400,7 +432,7 @@ def evaluate_snr(grid=(NB, ND), layers=10, checkpoint=None, snrs=(5.0, 15.0, 25.
             yield ordered("net", phi, y, b, truth, snr)
         if baseline is not None:
             opts = {"xstep": 1 / (10 * N), "ystep": 1 / (10 * M), "iter": 3}            # estimate's defaults
-            rows, _ = ops.peak_top(truth["phi"], M, N, opts, top=targets)
+            rows, _ = ops.peak_top(truth["phi"], M, N, opts, top=targets, top_n=truth.get("L_true"))
             yield {"snr": snr, "method": "classical", **head, **scored(match(rows, truth), truth, snr)}
             if refine is not None:
                 yield refined("classical", rows, y, b, truth, snr)
@@ -461,6 +493,10 @@ def main(argv=None):
     f.add_argument("--refine", choices=("given", "psk"), default=None,
                    help="after each method's line, the same rows fitted to the received signal with these symbols")
     f.add_argument("--crb", action="store_true", help="add the Cramer-Rao bound pooled over each method's hits, and RMSE over it")
+    f.add_argument("--targets-min", type=int, default=None, metavar="LO",
+                   help="draw LO .. --targets targets per scene; the lines without +order are given each scene's count")
+    f.add_argument("--min-sep", type=float, default=0.0, metavar="CELLS",
+                   help="keep the targets of a scene at least this many resolution cells apart")
     f.add_argument("--order", type=int, default=None, metavar="TOP",
                    help="after each method's lines, TOP candidate peaks with the number of targets selected against the received signal")
     args = ap.parse_args(argv)
@@ -471,7 +507,8 @@ def main(argv=None):
     if args.cmd == "evaluate":
         import json
         for line in evaluate_snr(_grid(ap, args.grid), args.layers, args.checkpoint, args.snr, args.signals, args.targets,
-                                 args.cutoff, args.baseline, refine=args.refine, crb=args.crb, order=args.order):
+                                 args.cutoff, args.baseline, targets_min=args.targets_min, min_sep=args.min_sep,
+                                 refine=args.refine, crb=args.crb, order=args.order):
             print(json.dumps(line), flush=True)
         return
     if args.cmd == "loss-step":

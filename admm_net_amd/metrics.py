@@ -16,6 +16,7 @@ order, so comparing them needs an assignment, and that part was never written.
     gating it leaves nothing).
 ``ordered_rmse``   the reference's RMSE, slot j against slot j (``ADMMNet``'s head is trained in truth order).
 ``summary``        the one host read: detection probability, false alarms, pooled RMSE and GOSPA of a batch.
+``order_counts``   scenes whose selected number of targets lies below, at and above the true one, without a host read.
 ``match_host``     the float64 numpy statement of ``match_targets`` for one signal.  The tests hold the kernel to it; it is NOT a
                    fallback -- the device calls raise without the HIP library.
 ``crb``            the Cramer-Rao bound of every target of every scene (csrc/crb.hip), the yardstick of the pooled RMSE;
@@ -173,19 +174,23 @@ def ordered_rmse(tau_est, f_est, tau_true, f_true, L_true):
     return per_sample, out, status
 
 
-def summary(totals, signals=None) -> dict:
+def summary(totals, signals=None, extra=None) -> dict:
     """The figures of a batch from ``match_targets``' totals, with ONE device-to-host read.
 
     totals: a ``MatchResult`` -- the signals that were scored are then its batch less the two counts of ``status`` -- or the [8]
     tensor itself (or a sum of several) with ``signals`` given.  Returns a dict: ``pd`` = hits / (hits + misses),
     ``false_per_signal``, ``rmse_tau`` / ``rmse_f`` pooled over the hits (NaN without a hit; the wrapped, unscaled differences),
-    ``gospa`` = sqrt(mean gospa^2), ``signals``, and the three counts."""
+    ``gospa`` = sqrt(mean gospa^2), ``signals``, and the three counts.  ``extra`` (with a ``MatchResult``): a dict of device
+    tensors that travel in the same read and come back under their names, as a float or a list of floats."""
     if isinstance(totals, MatchResult):
         if signals is not None:
             raise ValueError("signals is taken from the MatchResult")
-        t = torch.cat((totals.totals.reshape(-1), totals.status.to(torch.float64).reshape(-1))).tolist()   # the read
+        more = {k: v.to(device=totals.totals.device, dtype=torch.float64).reshape(-1) for k, v in (extra or {}).items()}
+        t = torch.cat((totals.totals.reshape(-1), totals.status.to(torch.float64).reshape(-1), *more.values())).tolist()   # the read
         signals = totals.stats.shape[0] - int(t[8]) - int(t[9])
     else:
+        if extra is not None:
+            raise ValueError("extra= goes with a MatchResult")
         if signals is None:
             raise ValueError("summary of a bare totals tensor needs signals=")
         t = torch.as_tensor(totals).reshape(-1).to(torch.float64).tolist()                                   # the read
@@ -194,12 +199,29 @@ def summary(totals, signals=None) -> dict:
         signals = int(signals)
     hit, miss, false = t[0], t[1], t[2]
     nan = float("nan")
-    return {"pd": hit / (hit + miss) if hit + miss > 0 else nan,
+    line = {"pd": hit / (hit + miss) if hit + miss > 0 else nan,
             "false_per_signal": false / signals if signals > 0 else nan,
             "rmse_tau": math.sqrt(t[3] / hit) if hit > 0 else nan,
             "rmse_f": math.sqrt(t[4] / hit) if hit > 0 else nan,
             "gospa": math.sqrt(t[6] / signals) if signals > 0 else nan,
             "signals": signals, "hits": int(hit), "misses": int(miss), "false_alarms": int(false)}
+    at = 10
+    for k, v in (more.items() if isinstance(totals, MatchResult) else ()):
+        line[k] = t[at] if v.numel() == 1 else t[at:at + v.numel()]
+        at += v.numel()
+    return line
+
+
+def order_counts(n_sel, L_true) -> torch.Tensor:
+    """How a selected number of targets compares with the true one: [3] int64 on the device = the scenes with ``n_sel`` <, ==, >
+    ``L_true`` ([B] integer tensors, e.g. ``order.select_targets(...).n_sel`` and ``make_scenes_device``'s ``L_true``).
+    Comparisons and sums only: no host read."""
+    _integers(n_sel, "n_sel")
+    _integers(L_true, "L_true")
+    if n_sel.dim() != 1 or n_sel.shape != L_true.shape:
+        raise ValueError(f"order_counts needs two [B] tensors, got {tuple(n_sel.shape)} and {tuple(L_true.shape)}")
+    L_true = L_true.to(n_sel.device)
+    return torch.stack(((n_sel < L_true).sum(), (n_sel == L_true).sum(), (n_sel > L_true).sum()))
 
 
 # ---- the float64 host statement ----------------------------------------------------------------------------------------------

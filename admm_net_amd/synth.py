@@ -101,3 +101,59 @@ def make_batch_device(batch, Nb, Nd, L=3, seed=20260104, snr_range=(5.0, 25.0), 
     if labels:
         truth["phi"] = phi
     return y, b, sigma, truth
+
+
+def _target_range(targets):
+    """(lo, hi) of ``targets`` = an int or a pair of ints, 1 <= lo <= hi <= 8."""
+    try:
+        lo, hi = (targets, targets) if isinstance(targets, int) else targets
+        ok = not isinstance(lo, bool) and not isinstance(hi, bool) and int(lo) == lo and int(hi) == hi and 1 <= lo <= hi <= 8
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        raise ValueError(f"targets must be an int or a pair (lo, hi) with 1 <= lo <= hi <= 8, got {targets!r}")
+    return int(lo), int(hi)
+
+
+def make_scenes_device(batch, Nb, Nd, targets=(1, 3), min_sep=0.0, seed=20260104, snr_range=(5.0, 25.0), snr_e=7.0,
+                       device=None, labels=False, rho=1.0, label_iters=5):
+    """``make_batch_device`` with a number of targets drawn per scene, uniform on ``targets`` = (lo, hi) (an int: exactly that
+    many), and kept at least ``min_sep`` resolution cells apart -- the distance of ``metrics.match_targets(scale=(Nd, Nb),
+    period=(1, 1))``; 0: as drawn.  A target closer than that to an earlier one is drawn again, up to 32 times; a scene in
+    which one stayed too close is kept as it is and has ``state`` 1.  One launch (csrc/synth.hip, scenes_kernel), ordered on
+    the current stream, no host read.
+
+    Returns (y [B,D] c64, b [B,D] c64, sigma [B] f32, truth): ``tau``, ``f`` [B,hi] f32 and ``C`` [B,hi] c64 with exact zeros
+    in the slots past the scene's count (the reference's padding, generate_data.py:91-103); ``L_true`` [B] int64, as
+    ``match_targets`` and ``crb`` take it; ``snr_db`` and ``noise_var`` [B] f64, the drawn SNR and the variance of a complex
+    noise entry, either of which ``crb`` takes; ``ser`` [B] f32, the percentage of symbols decided wrongly (:219); ``state``
+    [B] int32; ``phi`` with ``labels=True``.  With ``targets=L, min_sep=0`` the scenes are ``make_batch_device``'s, bit for bit.
+    """
+    import ctypes
+    import torch
+    from . import _lib
+    lo, hi = _target_range(targets)
+    lib = _lib.load()
+    if device is None:
+        if not torch.cuda.is_available():
+            raise _lib.AdmmNetError("make_scenes_device needs the GPU")
+        device = torch.device("cuda", torch.cuda.current_device())
+    device = torch.device(device)
+    D = Nb * Nd
+    with torch.cuda.device(device):
+        new = lambda dtype, *shape: torch.empty(*shape, dtype=dtype, device=device)  # noqa: E731
+        y, b, sigma = new(torch.complex64, batch, D), new(torch.complex64, batch, D), new(torch.float32, batch)
+        truth = dict(tau=new(torch.float32, batch, hi), f=new(torch.float32, batch, hi), C=new(torch.complex64, batch, hi),
+                     L_true=new(torch.int64, batch), snr_db=new(torch.float64, batch), noise_var=new(torch.float64, batch),
+                     ser=new(torch.float32, batch), state=new(torch.int32, batch))
+        phi = new(torch.complex64, batch, D) if labels else None
+        p = lambda t: ctypes.c_void_p(0 if t is None else t.data_ptr())  # noqa: E731
+        stream = ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+        _lib.check(lib.admmnet_synth_scenes(batch, Nb, Nd, lo, hi, float(min_sep), int(seed) & (2 ** 64 - 1), float(snr_range[0]),
+                                            float(snr_range[1]), float(snr_e), float(rho), int(label_iters), p(y), p(b), p(sigma),
+                                            p(truth["tau"]), p(truth["f"]), p(truth["C"]), p(phi), p(truth["L_true"]),
+                                            p(truth["snr_db"]), p(truth["noise_var"]), p(truth["ser"]), p(truth["state"]), stream),
+                   "admmnet_synth_scenes")
+    if labels:
+        truth["phi"] = phi
+    return y, b, sigma, truth

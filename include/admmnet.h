@@ -769,6 +769,29 @@ int admmnet_synth_batch(int64_t B, int32_t Nb, int32_t Nd, int32_t L, uint64_t s
                         double snr_e, double rho, int32_t label_iters, void *y, void *b, float *sigma, float *tau,
                         float *f, void *C, void *phi_label, void *stream);
 
+/* admmnet_synth_batch with a varying number of targets per scene, an optional minimum separation between them, and what a
+ * scene's consumer needs to know about it.  Same recipe, arithmetic, generator, geometry and LDS (Nb * Nd <= 3406).
+ *   count      n = L_min + min(L_max - L_min, floor(u (L_max - L_min + 1))), u in (0, 1] the draw of stream 8, index 0.
+ *   positions  target l < n, attempt t = 0 .. 31: tau = 0.1 + 0.8 u(stream tau, l + 8 t), f = -0.4 + 0.8 u(stream f, l + 8 t);
+ *              attempt 0 is admmnet_synth_batch's draw.  Targets are placed in order l = 0, 1, ..; an attempt is accepted when
+ *              every target j < l already placed has (Nd wrap(dtau))^2 + (Nb wrap(df))^2 >= min_sep^2, wrap(d) = d - round(d):
+ *              a distance in resolution cells with period 1 on both axes, the measure of admmnet_score_match_f64 with
+ *              scale (Nd, Nb) and period (1, 1).  min_sep = 0 accepts attempt 0 without evaluating anything.  If none of the
+ *              32 attempts is accepted the last one stays and the scene's state is 1: no scene is dropped or redrawn whole.
+ *   C          of target l as admmnet_synth_batch draws it, whatever the attempt.
+ *   padding    slots l >= n of tau, f, C [B][L_max] are exact zeros (generate_data.py:91-103) and add nothing to Psi.
+ *   outputs besides admmnet_synth_batch's (device, all required): L_true int64 [B] = n, as admmnet_score_match_f64 and
+ *              admmnet_crb_f64 read it; snr_db double [B], the drawn SNR; noise_var double [B], the variance of a complex
+ *              entry of w; ser float [B] = 100 #{decided symbol != sent symbol} / (Nb Nd) (generate_data.py:219);
+ *              state int32 [B], 0 or 1.
+ *   With L_min = L_max = L and min_sep = 0 the seven outputs shared with admmnet_synth_batch have its bits.
+ *   1 <= L_min <= L_max <= 8, min_sep finite and >= 0, label_iters >= 0, 1 <= B < 2^31, Nb, Nd >= 1, Nb * Nd <= 3406, no
+ *   null pointer but phi_label: anything else returns ADMMNET_E_ARG with a message, before anything is launched. */
+int admmnet_synth_scenes(int64_t B, int32_t Nb, int32_t Nd, int32_t L_min, int32_t L_max, double min_sep, uint64_t seed,
+                         double snr_lo, double snr_hi, double snr_e, double rho, int32_t label_iters, void *y, void *b,
+                         float *sigma, float *tau, float *f, void *C, void *phi_label, int64_t *L_true, double *snr_db,
+                         double *noise_var, float *ser, int32_t *state, void *stream);
+
 /* ---- measurement hooks (bench.py roofline leg) ---------------------------------
  * When enabled, every kernel launcher brackets its launch with HIP events on the
  * caller's stream.  admmnet_profile_read synchronises those events, returns the
