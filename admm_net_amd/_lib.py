@@ -108,6 +108,11 @@ SYMBOLS = {
     "admmnet_loss_anm_bwd_f32": (c_int32, [c_int32, c_int32, c_int64] + [c_void_p] * 9 + [c_float] + [c_void_p] * 5),
     "admmnet_loss_phi_c64": (c_int32, [c_int32, c_int64, c_void_p, c_void_p, c_float, c_float, c_void_p, c_void_p, c_void_p]),
     "admmnet_loss_phi_bwd_c64": (c_int32, [c_int32, c_int64, c_void_p, c_void_p, c_void_p, c_float, c_float, c_void_p, c_void_p]),
+    "admmnet_loss_spectrum_workspace_bytes": (c_int64, [c_int32, c_int32, c_int32, c_int64]),
+    "admmnet_loss_spectrum_f64": (c_int32, [c_int32, c_int32, c_int32, c_int32, c_int64] + [c_void_p] * 5 + [c_float] * 3 +
+                                           [c_void_p] * 3 + [c_int64, c_void_p]),
+    "admmnet_loss_spectrum_bwd_f64": (c_int32, [c_int32, c_int32, c_int32, c_int32, c_int64] + [c_void_p] * 5 + [c_float] * 3 +
+                                               [c_int32, c_void_p, c_int64, c_void_p, c_void_p]),
     "admmnet_score_partials": (c_int64, [c_int64]),
     "admmnet_score_match_f64": (c_int32, [c_int32, c_int32, c_int64] + [c_void_p] * 5 + [POINTER(c_double)] + [c_void_p] * 6),
     "admmnet_score_ordered_f32": (c_int32, [c_int32, c_int64] + [c_void_p] * 10),

@@ -1226,6 +1226,62 @@ int admmnet_loss_phi_bwd_c64(int32_t D, int64_t B, const float *g_out, const voi
                                (float2 *)g_phi, (hipStream_t)stream);
 }
 
+// ---- the spectral terms of the phi loss (loss_spectrum.hip) ------------------------------------------------------------------
+// bases of at most 1024 keep every index product inside 31 bits; the LDS limit (workspace_bytes < 0) is far below that
+static int64_t loss_spectrum_need(int32_t xbase, int32_t ybase, int32_t oversample, int64_t B) {
+    if (xbase < 1 || ybase < 1 || xbase > 1024 || ybase > 1024 || oversample < 1 || oversample > LS_MAX_OVERSAMPLE || B < 1 ||
+        B > 0x7fffffffLL)
+        return -1;
+    return loss_spectrum_workspace_bytes(xbase, ybase, oversample, B);
+}
+
+int64_t admmnet_loss_spectrum_workspace_bytes(int32_t xbase, int32_t ybase, int32_t oversample, int64_t B) {
+    return loss_spectrum_need(xbase, ybase, oversample, B);
+}
+
+static int loss_spectrum_args_ok(const char *what, int32_t xbase, int32_t ybase, int32_t oversample, int32_t Lmax, int64_t B,
+                                 bool ptrs, bool target, const void *workspace, int64_t workspace_bytes) {
+    const int64_t need = loss_spectrum_need(xbase, ybase, oversample, B);
+    if (need < 0 || Lmax < 0 || Lmax > LS_MAX_TARGETS || (target && Lmax < 1) || !ptrs || !workspace) {
+        set_error("%s: bad argument (xbase=%d, ybase=%d, oversample=%d, Lmax=%d, B=%lld, a null pointer, or a grid beyond the LDS)",
+                  what, xbase, ybase, oversample, Lmax, (long long)B);
+        return ADMMNET_E_ARG;
+    }
+    if (workspace_bytes < need) {
+        set_error("%s: workspace too small (%lld < %lld bytes)", what, (long long)workspace_bytes, (long long)need);
+        return ADMMNET_E_WORKSPACE;
+    }
+    return ADMMNET_OK;
+}
+
+int admmnet_loss_spectrum_f64(int32_t xbase, int32_t ybase, int32_t oversample, int32_t Lmax, int64_t B, const void *phi,
+                              const void *phi_true, const float *tau_true, const float *f_true, const int64_t *L_true,
+                              float spectral_weight, float distribution_weight, float target_weight, float *out,
+                              int32_t *status, void *workspace, int64_t workspace_bytes, void *stream) {
+    const bool target = L_true != nullptr;
+    if (int rc = loss_spectrum_args_ok("loss_spectrum", xbase, ybase, oversample, Lmax, B,
+                                       phi && out && status && (phi_true || target) && (!target || (tau_true && f_true)), target,
+                                       workspace, workspace_bytes))
+        return rc;
+    return launch_loss_spectrum(xbase, ybase, oversample, Lmax, B, (const float2 *)phi, (const float2 *)phi_true, tau_true, f_true,
+                                L_true, spectral_weight, distribution_weight, target_weight, out, status, workspace,
+                                (hipStream_t)stream);
+}
+
+int admmnet_loss_spectrum_bwd_f64(int32_t xbase, int32_t ybase, int32_t oversample, int32_t Lmax, int64_t B, const float *g_out,
+                                  const void *phi, const float *tau_true, const float *f_true, const int64_t *L_true,
+                                  float spectral_weight, float distribution_weight, float target_weight, int32_t skip,
+                                  const void *workspace, int64_t workspace_bytes, void *g_phi, void *stream) {
+    const bool target = !(skip & ADMMNET_LOSS_SPECTRUM_SKIP_TARGET);
+    if (int rc = loss_spectrum_args_ok("loss_spectrum_bwd", xbase, ybase, oversample, Lmax, B,
+                                       g_out && phi && g_phi && skip >= 0 && skip < 8 && (!target || (tau_true && f_true && L_true)),
+                                       target, workspace, workspace_bytes))
+        return rc;
+    return launch_loss_spectrum_bwd(xbase, ybase, oversample, Lmax, B, g_out, (const float2 *)phi, tau_true, f_true, L_true,
+                                    spectral_weight, distribution_weight, target_weight, skip, workspace, (float2 *)g_phi,
+                                    (hipStream_t)stream);
+}
+
 // ---- estimates against ground truth (score.hip) ------------------------------------------------------------------------------
 // one lane per estimate and per target (<= 64 each); the slab grid must fit 31 bits
 static int score_args_ok(const char *what, int32_t Le, int32_t Lt, int64_t B, bool ptrs) {

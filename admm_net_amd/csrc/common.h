@@ -302,6 +302,19 @@ int launch_loss_phi(int D, int64_t B, const float2 *phi, const float2 *phi_true,
 int launch_loss_phi_bwd(int D, int64_t B, const float *g_out, const float2 *phi, const float2 *phi_true, float amplitude_weight,
                         float phase_weight, float2 *g_phi, hipStream_t st);
 
+// loss_spectrum.hip (the spectral, distribution and target terms of the phi loss on the delay-Doppler spectrum; one workgroup
+// per signal, float64).  phi_true == nullptr: no grid terms; L_true == nullptr: no target term.
+constexpr int LS_MAX_TARGETS = 16, LS_MAX_OVERSAMPLE = 4;
+int64_t loss_spectrum_workspace_bytes(int xbase, int ybase, int oversample, int64_t B);   // -1: does not fit
+int launch_loss_spectrum(int xbase, int ybase, int oversample, int Lmax, int64_t B, const float2 *phi, const float2 *phi_true,
+                         const float *tau_true, const float *f_true, const int64_t *L_true, float spectral_weight,
+                         float distribution_weight, float target_weight, float *out, int32_t *status, void *workspace,
+                         hipStream_t st);
+int launch_loss_spectrum_bwd(int xbase, int ybase, int oversample, int Lmax, int64_t B, const float *g_out, const float2 *phi,
+                             const float *tau_true, const float *f_true, const int64_t *L_true, float spectral_weight,
+                             float distribution_weight, float target_weight, int skip, const void *workspace, float2 *g_phi,
+                             hipStream_t st);
+
 // score.hip (estimates against ground truth: the truncated-cost assignment and the ordered RMSE; float64 sums over the batch)
 int64_t score_partials(int64_t B);                    // doubles of partial-sum scratch of either call
 int launch_score_match(int Le, int Lt, int64_t B, const double *est, const int32_t *n_est, const float *tau_true,

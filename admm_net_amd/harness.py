@@ -271,6 +271,43 @@ def time_loss_step(batch=256, targets=3, dim=100, steps=200, warmup=10, seed=0, 
     return out
 
 
+def time_spectral_loss_step(batch=256, targets=3, dim=100, steps=200, warmup=10, repeats=5, seed=0, device="cuda:0"):
+    """Device-event time of one forward + backward of ``losses.PhiSpectralLoss`` (default weights plus ``target_weight = 0.5``,
+    ``check_status = False``) on ``route = "hip"`` and ``route = "tensor"``: [batch, dim] complex phi on the square grid of
+    ``dim`` entries, ``targets`` slots with L_true cycling through 0 .. targets.  ``steps`` forward + backward pairs are enqueued
+    between two events; ``repeats`` such windows give the figure (their median) and its range.  Returns a dict of milliseconds."""
+    from . import losses
+    dev = torch.device(device)
+    side = int(round(dim ** 0.5))
+    if side * side != dim:
+        raise ValueError(f"--dim must be a square for --spectral, got {dim}")
+    g = torch.Generator().manual_seed(seed)
+    phi = torch.randn(batch, dim, dtype=torch.complex64, generator=g).to(dev).requires_grad_(True)
+    phi_true = torch.randn(batch, dim, dtype=torch.complex64, generator=g).to(dev)
+    truth = {"tau_true": torch.rand(batch, targets, generator=g).to(dev), "f_true": (torch.rand(batch, targets, generator=g) - 0.5).to(dev),
+             "L_true": (torch.arange(batch) % (targets + 1)).to(dev)}
+    out = {"batch": batch, "targets": targets, "dim": dim, "steps": steps, "repeats": repeats}
+    for route in losses.ROUTES:
+        crit = losses.PhiSpectralLoss(side, side, target_weight=0.5)
+        crit.route, crit.check_status = route, False
+
+        def window(n):
+            start, stop = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            start.record()
+            for _ in range(n):
+                phi.grad = None
+                crit(phi, phi_true, truth)[0].backward()
+            stop.record()
+            stop.synchronize()
+            return start.elapsed_time(stop) / n
+
+        window(warmup)
+        times = sorted(window(steps) for _ in range(repeats))
+        out[f"spectral_{route}_ms"] = round(times[len(times) // 2], 4)
+        out[f"spectral_{route}_range_ms"] = [round(times[0], 4), round(times[-1], 4)]
+    return out
+
+
 def _score_case(batch, n_est, n_true, seed, dev):
     """Scenes drawn like ``synth.make_batch`` with estimates = shuffled truth + N(0, 0.03) and strays, as device tensors."""
     rng = np.random.default_rng(seed)
@@ -477,6 +514,8 @@ def main(argv=None):
     d.add_argument("--targets", type=int, default=3)
     d.add_argument("--dim", type=int, default=100)
     d.add_argument("--steps", type=int, default=200)
+    d.add_argument("--spectral", action="store_true",
+                   help="time PhiSpectralLoss (device events, median and range of five windows) instead of the two reference losses")
     e = sub.add_parser("score-step")
     e.add_argument("--steps", type=int, default=50)
     e.add_argument("--repeats", type=int, default=5)
@@ -513,7 +552,8 @@ def main(argv=None):
         return
     if args.cmd == "loss-step":
         import json
-        print(json.dumps(time_loss_step(args.batch, args.targets, args.dim, args.steps)))
+        step = time_spectral_loss_step if args.spectral else time_loss_step
+        print(json.dumps(step(args.batch, args.targets, args.dim, args.steps)))
         return
     if args.cmd == "train-step":
         import json

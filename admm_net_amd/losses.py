@@ -10,6 +10,9 @@ Definitions, with B signals, Lmax target slots, L = L_true[b]:
     PhiAlignmentLoss  amplitude = mean (|phi| - |phi_true|)^2,  phase = mean wrap(arg phi - arg phi_true)^2,
                       wrap(d) = ((d + pi) mod 2 pi) - pi (Python's %, so +pi maps to -pi),
                       total = amplitude_weight amplitude + phase_weight phase
+    PhiSpectralLoss   PhiAlignmentLoss plus three terms on the delay-Doppler spectrum |phi^H a(tau, f)|^2 (csrc/loss_spectrum.hip):
+                      the spectral and distribution terms whose weights the reference declares and never uses, and a term on
+                      the scene's true targets; the definitions are in the class's docstring
 
 Two sets of kernels evaluate them (in the manner of ``training.SmallKernels`` / ``TorchSmallKernels``): ``HipLossKernels`` (the
 device entry points of ``ops``) and ``TensorLossKernels``, the same formulas as masked [B, Lmax] tensor operations without a
@@ -41,6 +44,9 @@ class HipLossKernels:
     anm_bwd = staticmethod(ops.loss_anm_bwd)   # (g_out, tau, ..., phi, norms, lambda_reg) -> g_tau, g_f, g_conf, g_phi
     phi = staticmethod(ops.loss_phi)           # (phi, phi_true, amplitude_weight, phase_weight) -> out [3]
     phi_bwd = staticmethod(ops.loss_phi_bwd)   # (g_out, phi, phi_true, amplitude_weight, phase_weight) -> g_phi
+    # csrc/loss_spectrum.hip: (phi, phi_true, truth, xbase, ybase, weights, oversample) -> out [4], workspace, status [3]
+    spectrum = staticmethod(ops.loss_spectrum)
+    spectrum_bwd = staticmethod(ops.loss_spectrum_bwd)   # (g_out, phi, truth, ..., oversample, workspace, skip) -> g_phi
 
 
 class TensorLossKernels:
@@ -109,6 +115,110 @@ class TensorLossKernels:
         cp = (g_out[0] * phase_weight + g_out[2]) * (2.0 / phi.numel())
         g = (ca * (r - phi_true.abs())) * unit + (cp * w / rs) * (1j * unit)      # i (x + i y) = -y + i x
         return torch.where(live, g, torch.zeros_like(phi))
+
+    # ---- the terms on the delay-Doppler spectrum (PhiSpectralLoss; csrc/loss_spectrum.hip) --------------------------------------
+    @staticmethod
+    def spectrum_tables(xbase, ybase, oversample, device, cdtype):
+        """(Sm [ny, ybase] = s_q[ks], Dm [nx, xbase] = conj(d_p[kd])) of the uniform full-period grid taus_p = p / nx,
+        fs_q = -0.5 + q / ny, so that the atom of grid point (q, p) is Sm[q, ks] Dm[p, kd]; evaluated in float64 from the
+        argument reduced to a fraction of a turn, then cast."""
+        def table(points, base, sign):
+            t = points.reshape(-1, 1) * torch.arange(base, dtype=torch.float64, device=device)
+            return torch.polar(torch.ones_like(t), sign * 2 * math.pi * (t - torch.round(t))).to(cdtype)
+        nx, ny = (oversample * xbase if xbase > 1 else 1), (oversample * ybase if ybase > 1 else 1)
+        taus = torch.arange(nx, dtype=torch.float64, device=device) / nx
+        fs = -0.5 + torch.arange(ny, dtype=torch.float64, device=device) / ny
+        return table(fs, ybase, 1.0), table(taus, xbase, -1.0)
+
+    @staticmethod
+    def _spectrum_parts(phi, phi_true, truth, xbase, ybase, oversample, grid=True):
+        """Everything the forward and the backward share, as a dict; rows that contribute nothing (``live`` false) are
+        evaluated with their divisors set to 1 and masked afterwards.  ``grid = False`` (a backward that leaves both grid terms
+        out) skips the contraction over the grid and nothing else: ``live`` is the forward's, zero phi_true rows included."""
+        B, D = phi.shape
+        if D != xbase * ybase:
+            raise ValueError(f"phi must be [B, {xbase * ybase}] for a {xbase} x {ybase} grid, got {tuple(phi.shape)}")
+        rdt, dev = phi.real.dtype, phi.device
+        P = phi.reshape(B, ybase, xbase)
+        n2 = (phi.real ** 2 + phi.imag ** 2).sum(dim=1)
+        zero = n2 == 0
+        zero_true = torch.zeros_like(zero)
+        p = {"P": P, "n2s": torch.where(zero, torch.ones_like(n2), n2), "zero": zero}
+        zeros = torch.zeros_like(n2)
+        p["spec"] = p["dist"] = p["targ"] = zeros
+        if phi_true is not None:
+            T = phi_true.to(phi.dtype).reshape(B, ybase, xbase)
+            zero_true = (T.real ** 2 + T.imag ** 2).sum(dim=(1, 2)) == 0
+        live = ~zero & ~zero_true
+        p["live"], p["zero_true"] = live, zero_true
+        if phi_true is not None and grid:
+            Sm, Dm = TensorLossKernels.spectrum_tables(xbase, ybase, oversample, dev, phi.dtype)
+            z = torch.einsum("bsd,qs,pd->bqp", P.conj(), Sm, Dm)
+            zt = torch.einsum("bsd,qs,pd->bqp", T.conj(), Sm, Dm)
+            S, St = z.real ** 2 + z.imag ** 2, zt.real ** 2 + zt.imag ** 2
+            G = S.shape[1] * S.shape[2]
+            one = torch.ones_like(n2)
+            A, At = torch.where(live, S.sum(dim=(1, 2)), one), torch.where(live, St.sum(dim=(1, 2)), one)
+            m, mt = (A / G).reshape(B, 1, 1), (At / G).reshape(B, 1, 1)
+            u, v = S / m, St / mt
+            H = (z.abs() * zt.abs()).sum(dim=(1, 2))
+            p.update(Sm=Sm, Dm=Dm, z=z, S=S, St=St, G=G, A=A, At=At, m=m, u=u, v=v, H=H)
+            p["spec"] = torch.where(live, ((u - v) ** 2).mean(dim=(1, 2)), zeros)
+            p["dist"] = torch.where(live, 1 - H / torch.sqrt(A * At), zeros)
+        outside = torch.zeros((), dtype=torch.int64, device=dev)
+        if truth is not None:
+            tau, f, L_true = truth
+            Lmax = tau.shape[1]
+            L = L_true.clamp(0, Lmax).reshape(B, 1)
+            mask = (torch.arange(Lmax, device=dev) < L).to(rdt)
+            turn = lambda t: torch.polar(torch.ones_like(t), 2 * math.pi * (t - torch.round(t))).to(phi.dtype)
+            ef = turn(f.to(rdt).unsqueeze(-1) * torch.arange(ybase, dtype=rdt, device=dev))        # [B, Lmax, ybase]
+            et = turn(-(tau.to(rdt).unsqueeze(-1) * torch.arange(xbase, dtype=rdt, device=dev)))   # [B, Lmax, xbase]
+            zl = torch.einsum("bsd,bls,bld->bl", P.conj(), ef, et)
+            rho = (zl.real ** 2 + zl.imag ** 2) / (D * p["n2s"]).reshape(B, 1)
+            use = (live & (L.reshape(-1) > 0)).reshape(B, 1)
+            p.update(ef=ef, et=et, zl=zl, rho=rho, Lc=L.clamp(min=1).to(rdt), mask=mask * use.to(rdt))
+            p["targ"] = ((1 - rho) * p["mask"]).sum(dim=1) / p["Lc"].reshape(-1)
+            outside = ((L_true < 0) | (L_true > Lmax)).sum()
+        p["status"] = torch.stack([outside, zero.sum(), zero_true.sum()]).to(torch.int32)
+        return p
+
+    @staticmethod
+    def spectrum(phi, phi_true, truth, xbase, ybase, weights, oversample):
+        """(out [4] = (total, spectral, distribution, target), what ``spectrum_bwd`` needs beside its arguments (here phi_true),
+        status [3] = (L_true outside [0, Lmax], zero phi rows, zero phi_true rows)).  ``truth``: None or (tau_true, f_true
+        [B, Lmax], L_true [B]); ``phi_true``: None for the target term alone; ``weights``: (spectral, distribution, target)."""
+        p = TensorLossKernels._spectrum_parts(phi, phi_true, truth, xbase, ybase, oversample)
+        spec, dist, targ = p["spec"].mean(), p["dist"].mean(), p["targ"].mean()
+        return torch.stack([weights[0] * spec + weights[1] * dist + weights[2] * targ, spec, dist, targ]), phi_true, p["status"]
+
+    @staticmethod
+    def spectrum_bwd(g_out, phi, truth, xbase, ybase, weights, oversample, saved, skip=0):
+        """g_phi from g_out [4]; ``skip``: bit 0 the spectral, bit 1 the distribution, bit 2 the target term is left out."""
+        phi_true = saved
+        B, D = phi.shape
+        grid = phi_true is not None and (skip & 3) != 3
+        if skip & 4:
+            truth = None
+        p = TensorLossKernels._spectrum_parts(phi, phi_true, truth, xbase, ybase, oversample, grid)
+        g_out = g_out.to(phi.real.dtype)
+        cs, cd, ct = ((0.0 if skip & (1 << i) else (g_out[0] * weights[i] + g_out[i + 1]) / B) for i in range(3))
+        g = torch.zeros_like(p["P"])
+        if grid:
+            S, St, u, v, m, A, At, G = (p[k] for k in ("S", "St", "u", "v", "m", "A", "At", "G"))
+            E = ((u - v) * u).mean(dim=(1, 2), keepdim=True)
+            c = cs * 2 / (G * m) * ((u - v) - E)
+            some = S > 0                                               # d|z| / dz is taken as 0 at z = 0
+            ratio = torch.sqrt(St / torch.where(some, S, torch.ones_like(S)))
+            c = c - torch.where(some, cd / (2 * torch.sqrt(A * At)).reshape(B, 1, 1) * (ratio - (p["H"] / A).reshape(B, 1, 1)),
+                                torch.zeros_like(S))
+            g = g + 2 * torch.einsum("bqp,qs,pd->bsd", c * p["z"].conj(), p["Sm"], p["Dm"])
+        if truth is not None:
+            coef = -2 * ct / p["Lc"] * p["mask"]                       # [B, Lmax]
+            dn = (D * p["n2s"]).reshape(B, 1)
+            g = g + torch.einsum("bl,bls,bld->bsd", (coef * p["zl"].conj() / dn).to(phi.dtype), p["ef"], p["et"])
+            g = g - ((coef * p["rho"]).sum(dim=1) / p["n2s"]).reshape(B, 1, 1) * p["P"]
+        return torch.where(p["live"].reshape(B, 1), g.reshape(B, D), torch.zeros_like(phi))
 
 
 def _kernels(route):
@@ -218,3 +328,112 @@ class PhiAlignmentLoss(nn.Module):
         total, amp, phase = _PhiLossFn.apply(phi_final, phi_true, float(self.amplitude_weight), float(self.phase_weight),
                                              _kernels(self.route))
         return total, {'total_loss': total, 'amplitude_loss': amp, 'phase_loss': phase}
+
+
+SKIP_SPECTRAL, SKIP_DISTRIBUTION, SKIP_TARGET = 1, 2, 4     # ADMMNET_LOSS_SPECTRUM_SKIP_* of include/admmnet.h
+
+
+class _PhiSpectralFn(torch.autograd.Function):
+    """(total, spectral, distribution, target, status) of the spectrum terms of PhiSpectralLoss; gradients arriving through any
+    of the first four are honoured.  A term is left out of the backward (a launch argument, no host read) when its weight is
+    0 and autograd sent no gradient through its own output, or when the forward did not evaluate it."""
+
+    @staticmethod
+    def forward(ctx, phi, phi_true, tau_true, f_true, L_true, xbase, ybase, weights, oversample, lk):
+        truth = None if L_true is None else (tau_true, f_true, L_true)
+        out, saved, status = lk.spectrum(phi, phi_true, truth, xbase, ybase, weights, oversample)
+        ctx.save_for_backward(phi, saved, tau_true, f_true, L_true)
+        ctx.args, ctx.lk = (xbase, ybase, weights, oversample), lk
+        ctx.absent = (SKIP_SPECTRAL | SKIP_DISTRIBUTION if phi_true is None else 0) | (SKIP_TARGET if L_true is None else 0)
+        ctx.set_materialize_grads(False)
+        ctx.mark_non_differentiable(status)
+        return (*out.unbind(0), status)
+
+    @staticmethod
+    def backward(ctx, g_total, *g_parts):
+        phi, saved, tau_true, f_true, L_true = ctx.saved_tensors
+        xbase, ybase, weights, oversample = ctx.args
+        skip = ctx.absent
+        for i, g in enumerate(g_parts[:3]):
+            if g is None and (g_total is None or weights[i] == 0):
+                skip |= 1 << i
+        zero = torch.zeros((), dtype=phi.real.dtype, device=phi.device)
+        g_out = _g_out([zero if g is None else g for g in (g_total, *g_parts[:3])], zero)
+        truth = None if L_true is None else (tau_true, f_true, L_true)
+        g_phi = ctx.lk.spectrum_bwd(g_out, phi, truth, xbase, ybase, weights, oversample, saved, skip)
+        return (g_phi.to(phi.dtype),) + (None,) * 9
+
+
+class PhiSpectralLoss(nn.Module):
+    """``PhiAlignmentLoss`` plus the terms that are defined on the delay-Doppler spectrum S = |phi^H a(tau, f)|^2 -- the
+    quantity ``peak_top``, ``estimate`` and ``select_refined`` read -- on the uniform full-period grid of
+    ``oversample`` x (xbase, ybase) points (x = delay: ``xbase = Nd``, ``ybase = Nb`` for the generator's scenes):
+
+        spectral      mean_b mean_grid (S / mean_grid S - S* / mean_grid S*)^2
+        distribution  mean_b 1 - sum_grid |z| |z*| / sqrt(sum_grid S sum_grid S*)      (squared Hellinger distance, in [0, 1])
+        target        mean_b mean_{l<L} (1 - |z(tau_true_l, f_true_l)|^2 / (D ||phi||^2)), 0 for L = 0
+
+    with S*, z* those of ``phi_true``.  All three are unchanged by phi -> c e^{j theta} phi.  ``forward(phi_final, phi_true,
+    truth)`` returns (total, dict); ``truth`` holds ``tau_true``, ``f_true`` [B, Lmax <= 16] and ``L_true`` [B].  With
+    ``phi_true=None`` only the target term runs (the four label weights must be 0); with ``truth=None`` ``target_weight`` must
+    be 0.  A signal whose phi row (or phi_true row) is all zero contributes 0 to the three terms and gets no gradient from them.
+    The grid terms count as asked for whenever ``phi_true`` is given, whatever their weights: both are evaluated and reported,
+    and a gradient may arrive through their dict entries; so a zero phi_true row is then dead for the target term too, in the
+    forward and in the backward alike (pass ``phi_true=None`` for the target term on its own).
+    The dict carries ``PhiAlignmentLoss``'s entries, ``spectral_loss``, ``distribution_loss``, ``target_loss`` and ``status``
+    (device int32 [3]: L_true outside [0, Lmax], zero phi rows, zero phi_true rows); ``check_status = True`` reads it once per
+    call and raises ``ValueError`` for the first count."""
+
+    def __init__(self, xbase, ybase, amplitude_weight=1.0, phase_weight=0.5, spectral_weight=0.2, distribution_weight=0.3,
+                 target_weight=0.0, oversample=2):
+        super().__init__()
+        if int(xbase) < 1 or int(ybase) < 1 or int(oversample) != oversample or not 1 <= oversample <= 4:
+            raise ValueError(f"PhiSpectralLoss needs xbase, ybase >= 1 and an integer oversample in 1 .. 4, got {xbase}, {ybase}, {oversample}")
+        self.xbase, self.ybase, self.oversample = int(xbase), int(ybase), int(oversample)
+        self.amplitude_weight = amplitude_weight
+        self.phase_weight = phase_weight
+        self.spectral_weight = spectral_weight
+        self.distribution_weight = distribution_weight
+        self.target_weight = target_weight
+        self.route = "hip"
+        self.check_status = True
+
+    def forward(self, phi_final, phi_true=None, truth=None):
+        D = self.xbase * self.ybase
+        if phi_final.dim() < 1 or phi_final.numel() == 0 or phi_final.numel() % D:
+            raise ValueError(f"phi_final must hold rows of {D} entries, got {tuple(phi_final.shape)}")
+        label_weights = (self.amplitude_weight, self.phase_weight, self.spectral_weight, self.distribution_weight)
+        if phi_true is None and (truth is None or any(w != 0 for w in label_weights)):
+            raise ValueError("without phi_true the loss is the target term alone: pass truth, and set amplitude_weight, phase_weight, "
+                             "spectral_weight and distribution_weight to 0")
+        if truth is None and self.target_weight != 0:
+            raise ValueError("target_weight is not 0 but truth (tau_true, f_true, L_true) was not given")
+        lk = _kernels(self.route)
+        phi = phi_final.reshape(-1, D)
+        if phi_true is not None:
+            _constant(phi_true=phi_true)
+            if phi_true.shape != phi_final.shape:
+                raise ValueError(f"phi_final and phi_true must have one shape, got {tuple(phi_final.shape)} and {tuple(phi_true.shape)}")
+            phi_true = phi_true.reshape(-1, D)
+            label, amp, phase = _PhiLossFn.apply(phi, phi_true, float(self.amplitude_weight), float(self.phase_weight), lk)
+        tau_true = f_true = L_true = None
+        if truth is not None:
+            tau_true, f_true, L_true = truth["tau_true"], truth["f_true"], truth["L_true"]
+            _constant(tau_true=tau_true, f_true=f_true)
+            if tau_true.dim() != 2 or tau_true.shape != f_true.shape or tau_true.shape[0] != phi.shape[0] or \
+                    not 1 <= tau_true.shape[1] <= 16 or L_true.shape != (phi.shape[0],):
+                raise ValueError(f"tau_true and f_true must be [{phi.shape[0]}, Lmax <= 16] and L_true [{phi.shape[0]}], got "
+                                 f"{tuple(tau_true.shape)}, {tuple(f_true.shape)}, {tuple(L_true.shape)}")
+        weights = (float(self.spectral_weight), float(self.distribution_weight), float(self.target_weight))
+        total, spec, dist, targ, status = _PhiSpectralFn.apply(phi, phi_true, tau_true, f_true, L_true, self.xbase, self.ybase,
+                                                               weights, self.oversample, lk)
+        if phi_true is None:
+            amp = phase = total.new_zeros(())
+        else:
+            total = label + total
+        if self.check_status:
+            bad = int(status[0].item())                    # the call's one device-to-host read
+            if bad:
+                raise ValueError(f"L_true of {bad} sample(s) lies outside [0, {tau_true.shape[1]}]")
+        return total, {'total_loss': total, 'amplitude_loss': amp, 'phase_loss': phase, 'spectral_loss': spec,
+                       'distribution_loss': dist, 'target_loss': targ, 'status': status}

@@ -1059,3 +1059,7 @@ def regional_maxima(Z: torch.Tensor):
         if k:
             mask[i, peaks[i, :k, 1].long(), peaks[i, :k, 0].long()] = True
     return mask
+
+
+# ---- the spectral terms of the phi loss (csrc/loss_spectrum.hip); defined in spectral_ops.py on the helpers above ------------------
+from .spectral_ops import loss_spectrum, loss_spectrum_bwd  # noqa: E402,F401

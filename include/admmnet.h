@@ -496,6 +496,43 @@ int admmnet_loss_phi_c64(int32_t D, int64_t B, const void *phi, const void *phi_
 int admmnet_loss_phi_bwd_c64(int32_t D, int64_t B, const float *g_out, const void *phi, const void *phi_true,
                              float amplitude_weight, float phase_weight, void *g_phi, void *stream);
 
+/* The terms of the phi loss that are defined on the delay-Doppler spectrum (csrc/loss_spectrum.hip): one workgroup per signal,
+ * float64 arithmetic, fixed-order sums without atomics (a signal's figures depend on neither B nor its place), no host read.
+ * phi complex64 [B][ybase * xbase] laid out [ybase][xbase] (x = delay).  With the atom a(tau, f)[ks xbase + kd] =
+ * exp(j 2 pi (ks f - kd tau)), z_b(tau, f) = sum_i conj(phi_b[i]) a(tau, f)[i], S = |z|^2 (admmnet_spectrum_f64's image), on the
+ * uniform full-period grid taus_p = p / nx, fs_q = -0.5 + q / ny, nx = oversample xbase, ny = oversample ybase (an axis of
+ * base 1 has one point), 1 <= oversample <= 4, G = nx ny points, m = mean_grid S, and S*, z*, m* the same of phi_true:
+ *   spectral_b     = mean_grid (S / m - S* / m*)^2
+ *   distribution_b = 1 - sum_grid |z| |z*| / sqrt(sum_grid S sum_grid S*)            (squared Hellinger distance)
+ *   target_b       = mean_{l < L} (1 - rho_l), rho_l = |z_b(tau_true_l, f_true_l)|^2 / (D ||phi_b||^2), L = L_true[b] held to
+ *                    [0, Lmax]; 0 for L = 0.  0 <= Lmax <= 16; tau_true, f_true float [B][Lmax], L_true int64 [B].
+ * Each term is its mean over the batch; out[4] = {spectral_weight spectral + distribution_weight distribution + target_weight
+ * target, spectral, distribution, target}.  phi_true == NULL: no grid terms (both are 0); L_true == NULL: no target term.
+ * A signal whose phi row is all zero, or whose phi_true row is all zero when the grid terms run, gives 0 to every term and gets
+ * a zero gradient row.  status[3] = {signals with L_true outside [0, Lmax], zero phi rows, zero phi_true rows}.
+ * `workspace` (admmnet_loss_spectrum_workspace_bytes, -1 for sizes the kernels do not take: the working set must fit 150 KiB
+ * of LDS) receives the steering tables, z, S* and the per-signal scalars; the backward reads it and leaves it unchanged.
+ *   admmnet_loss_spectrum_bwd_f64  g_out: DEVICE float[4], the gradients of out[0 .. 3].  g_phi complex64 [B][D], torch's
+ *                    convention: 2 sum_grid c conj(z) a[i] with c = d total / d S, plus the target rows 2 c_l conj(z_l) a_l[i]
+ *                    and the derivative of ||phi||^2; d|z| / dz is taken as 0 at z = 0.  `skip`: bit 0 the spectral, bit 1 the
+ *                    distribution, bit 2 the target term is left out of the gradient (its weight and its upstream gradient are
+ *                    known to be zero on the host).  A term the forward did not evaluate (phi_true or L_true NULL there) is a
+ *                    constant and adds nothing, whatever `skip` says: the forward records what it ran in the workspace. */
+enum {
+    ADMMNET_LOSS_SPECTRUM_SKIP_SPECTRAL = 1,
+    ADMMNET_LOSS_SPECTRUM_SKIP_DISTRIBUTION = 2,
+    ADMMNET_LOSS_SPECTRUM_SKIP_TARGET = 4
+};
+int64_t admmnet_loss_spectrum_workspace_bytes(int32_t xbase, int32_t ybase, int32_t oversample, int64_t B);
+int admmnet_loss_spectrum_f64(int32_t xbase, int32_t ybase, int32_t oversample, int32_t Lmax, int64_t B, const void *phi,
+                              const void *phi_true, const float *tau_true, const float *f_true, const int64_t *L_true,
+                              float spectral_weight, float distribution_weight, float target_weight, float *out,
+                              int32_t *status, void *workspace, int64_t workspace_bytes, void *stream);
+int admmnet_loss_spectrum_bwd_f64(int32_t xbase, int32_t ybase, int32_t oversample, int32_t Lmax, int64_t B, const float *g_out,
+                                  const void *phi, const float *tau_true, const float *f_true, const int64_t *L_true,
+                                  float spectral_weight, float distribution_weight, float target_weight, int32_t skip,
+                                  const void *workspace, int64_t workspace_bytes, void *g_phi, void *stream);
+
 /* Target estimates scored against ground truth (csrc/score.hip, scalar core csrc/score_core.h): one wave per signal, sums over
  * the batch in a fixed order without atomics (float64 across workgroups), so two runs give the same bits.  B >= 1; `partials` is
  * double scratch of admmnet_score_partials(B) entries.  All tensors are dense with their natural alignment.
