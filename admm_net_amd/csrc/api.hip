@@ -263,6 +263,8 @@ static int carve_workspace(const admmnet_cfg *cfg, int64_t B, void *base, int64_
     const int64_t n = D + 1;
     Carver c{reinterpret_cast<char *>(base)};
     memset(ws, 0, sizeof(*ws));
+    const Switches &sw = cfg_switches(cfg);
+    const Route r = route_for(D, sw);
     if (state) {
         ws->G = c.take<float2>(B * n * n);
         ws->Z = c.take<float2>(B * n * n);
@@ -274,9 +276,14 @@ static int carve_workspace(const admmnet_cfg *cfg, int64_t B, void *base, int64_
         ws->sum = c.take<double>(2 * ng);
         ws->mean = c.take<float>(ng > 4 ? ng : 4);
         ws->headkv = c.take<float>((int64_t)2 * D * 128);
+        // The compact diagonals (common.h), behind everything admmnet_state_layout reports.  Written by the fused matrix-function
+        // kernel of a layer k >= 1 whose update is folded, read by prep_kernel of layer k + 1 <= K - 2 (the last layer forms
+        // phi alone): a model of fewer than four layers has no reader and no buffers.
+        if (r.fold && cfg->K >= 4) {
+            ws->diag = c.take<float>(B * 2 * D);
+            ws->diag_ok = c.take<int>(B);
+        }
     }
-    const Switches &sw = cfg_switches(cfg);
-    const Route r = route_for(D, sw);
     carve_chunk(c, r, pick_chunk(cfg, B), ws);
     ws->set2_offset = 0;
     if (state && sw.two_streams && B > ws->chunk) {   // room for a second chunk in flight: a second set, same layout
@@ -519,6 +526,8 @@ int admmnet_begin(const admmnet_cfg *cfg, int64_t B, void *workspace, int64_t wo
     Ws ws;
     if ((rc = carve_workspace(cfg, B, workspace, workspace_bytes, &ws, true))) return rc;
     if (status) ADMM_HIP(hipMemsetAsync(status, 0, 4 * sizeof(int32_t), (hipStream_t)stream));
+    // (no row of the compact diagonals describes the state this forward starts from, whatever the workspace held before)
+    if (ws.diag_ok) ADMM_HIP(hipMemsetAsync(ws.diag_ok, 0, sizeof(int) * (size_t)B, (hipStream_t)stream));
     return ADMMNET_OK;
 }
 
@@ -581,6 +590,9 @@ int admmnet_layer_front(const admmnet_cfg *cfg, const float *W, int32_t k, const
     // second buffer is ws.headkv read as int[256 D]: the head's K / V projections, which launch_head (admmnet_finish) writes
     // and then reads in one call, behind every layer -- nothing lives there while a layer runs, and this call joins the side
     // stream before it returns.  A chunk whose flags do not fit there stays on one stream.
+    // The compact diagonals (common.h, Ws::diag) need no event of their own: sp_fused_kernel writes its chunk's slice on the stream
+    // that launched it (the caller's, or a chunk stream of ADMMNET_STREAMS=2, joined before the layer ends), the fallback on the
+    // side stream touches neither buffer, and their reader is prep_kernel of the NEXT layer, behind the join.
     const bool timers = sw.sf_timing || sw.pn_timing || sw.dc_timing || sw.br_timing;
     const bool fork = r.matfun == MF_FUSED && !arrow && B > ws.chunk && !sw.two_streams && !sw.one_stream && !prof().on && !timers &&
                       ws.spec_flag && ws.chunk <= (int64_t)256 * D;
@@ -614,7 +626,7 @@ int admmnet_layer_front(const admmnet_cfg *cfg, const float *W, int32_t k, const
             // the lazy Z update of the previous layer rides the first sweep of the fused kernel: prep then only computes phi and h
             const bool fold = r.fold && k >= 1;
             const int mode = (r.storage == ST_HALF ? PM_HALF : r.storage == ST_LEAN ? PM_LEAN : 0) | (r.late_image ? PM_NOIMG : 0) |
-                             (fold ? PM_SMALL : 0);
+                             (fold ? PM_SMALL : 0) | (fold && !sw.prep_gather ? PM_DIAG : 0);
             if ((rc = launch_prep(cfg, W, k, yy, bb, sigma, b0, nb, wc, mode, r.eig_dim, sc))) return rc;
             Ws wf = wc;
             // G as a matrix function where the spectrum allows it (checked per matrix, spectral.hip); the eigen-pipeline below then
@@ -627,7 +639,8 @@ int admmnet_layer_front(const admmnet_cfg *cfg, const float *W, int32_t k, const
                 if (fork && ci >= 2) ADMM_HIP(hipStreamWaitEvent(st, side.ev[ci & 1], 0));
                 if ((rc = launch_spectral(sw, D, nb, lw, io.phi, io.h, Zk, io.G, io.rn, wc, status, sc, r.matfun, waves,
                                           fold ? ws.alpha + b0 : nullptr, fold ? ws.phi[prv] + b0 * D : nullptr,
-                                          fold ? ws.h[prv] + b0 * D : nullptr, fold ? lwp : nullptr, fold ? (k == 1 ? 2 : 1) : 0)))
+                                          fold ? ws.h[prv] + b0 * D : nullptr, fold ? lwp : nullptr, fold ? (k == 1 ? 2 : 1) : 0, ws.diag ? ws.diag + b0 * 2 * D : nullptr,
+                                          ws.diag ? ws.diag_ok + b0 : nullptr)))
                     return rc;
                 wf.skip = wc.spec_flag;
                 if (fork) {   // the rest of this chunk on the side stream, behind its matrix-function kernel
@@ -810,7 +823,7 @@ int admmnet_glayer_spectral_f32(const admmnet_cfg *cfg, const float *layer_weigh
     return launch_spectral_fused(sw, D, B, layer_weights, (const float2 *)phi, h, (float2 *)Z, (float2 *)G, rn_out, flag, status,
                                  mode ? alpha : nullptr, mode ? (const float2 *)phi_prev : nullptr,
                                  mode ? h_prev : nullptr, mode ? prev_layer_weights : nullptr, mode,
-                                 waves ? waves : spectral_waves(D, B, sw), st);
+                                 waves ? waves : spectral_waves(D, B, sw), /* no compact diagonals */ nullptr, nullptr, st);
 }
 
 int64_t admmnet_eigh_workspace_bytes(int32_t n, int64_t B) { return admmnet_eigh_workspace_bytes_o(n, B, 0); }

@@ -90,6 +90,12 @@ struct Ws {
     double *sum;              // [2] scratch for the batch sum ([ngroups][2] with sub-batches)
     float *mean;              // [1] batch mean (single-rank path; [ngroups] with sub-batches)
     float *headkv;            // [2][D][128] batch independent K / V projections of the head
+    // The compact diagonals (null where no layer reads them: carve_workspace).  prep_kernel needs Re G_ii and Re Z_ii, i < D: 2 D floats
+    // out of 2 D cache lines when it gathers them from the matrices.  sp_fused_kernel holds both while it writes G, so it leaves
+    // them as two rows for the next layer's prep_kernel.  A matrix that kernel rejects gets its G from the eigen-pipeline, which
+    // writes no row: diag_ok is 0 there and prep_kernel gathers as it always did.
+    float *diag;              // [B][2][D]: row 0 = Re G_ii, row 1 = Re Z_ii -- the floats stored at G[i][i].x and Z[i][i].x
+    int *diag_ok;             // [B] 1 = sp_fused_kernel wrote this matrix's G and its rows in its last launch, 0 = it rejected the matrix
     // chunk-sized eigensolver buffers
     float2 *Mbuf;             // [chunk][D*D + D + 1]: M row-major, arrow a[D], corner (re only)
     float *QV;                // [chunk][n][2D] planar transposed: QT (D columns) then VT (n columns)
@@ -132,6 +138,7 @@ constexpr int PM_NOIMG = 64;     // with PM_HALF: only the lazy Z update streams
 constexpr int PM_SMALL = 128;    // phi and h only: the lazy Z update is folded into the first sweep of the matrix-function kernel
 constexpr int PM_LEAN = 16;      // G / Z kept as lower triangles, A built by the tridiagonalisation's own loader
                                  // (tridiag_reg.hip): only the lazy Z update streams here, 24 n^2 / 2 bytes per signal
+constexpr int PM_DIAG = 256;     // with PM_SMALL, k >= 2: Re diag G and Re diag Z from the compact rows Ws::diag wherever Ws::diag_ok says so
 // (eig_dim, here and below: Route::eig_dim -- the matrix lands in an eig_dim x eig_dim image, zero outside its own D x D block)
 int launch_prep(const admmnet_cfg *cfg, const float *lw, int k, const float2 *y, const float2 *b,
                 const float *sigma, int64_t b0, int64_t nb, const Ws &ws, int mode, int eig_dim, hipStream_t st);
@@ -206,12 +213,13 @@ int launch_spectrum_main(const float2 *phi, int64_t B, int xbase, int ybase, con
 // spectral.hip (form: MF_KERNELS, the five kernels there) / spectral_fused.hip (MF_FUSED: the whole evaluation in one kernel)
 int launch_spectral_fused(const Switches &sw, int D, int64_t nb, const float *lw, const float2 *phi, const float *h, float2 *Z,
                           float2 *G, float *rn, int *flag, int32_t *status, const float *alpha, const float2 *phi_prev,
-                          const float *h_prev, const float *lw_prev, int update_mode, int waves, hipStream_t st);
+                          const float *h_prev, const float *lw_prev, int update_mode, int waves, float *diag, int *diag_ok, hipStream_t st);
 // update_mode 0: Z is current; 1 / 2: the fused kernel applies Z <- Z + alpha (G - C_prev) in its first sweep (2: stored Z still zero)
+// diag, diag_ok: Ws::diag / Ws::diag_ok of the chunk's first matrix, or both null: nothing is written
 // waves: spectral_waves(D, B, sw) of the call the chunk belongs to; sw: the call's tolerance, pass cap and phase timer
 int launch_spectral(const Switches &sw, int D, int64_t nb, const float *lw, const float2 *phi, const float *h, float2 *Z, float2 *G,
                     float *rn, const Ws &ws, int32_t *status, hipStream_t st, MatFun form, int waves, const float *alpha,
-                    const float2 *phi_prev, const float *h_prev, const float *lw_prev, int update_mode);
+                    const float2 *phi_prev, const float *h_prev, const float *lw_prev, int update_mode, float *diag, int *diag_ok);
 // vdvh.hip (training route)
 int launch_vdvh(int n, int64_t nb, const float2 *V, const float *d, float2 *out, hipStream_t st);
 int launch_vhsv(int n, int64_t nb, const float2 *V, const float2 *S, float *q, hipStream_t st);

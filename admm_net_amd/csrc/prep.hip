@@ -114,7 +114,8 @@ __global__ __launch_bounds__(PR_THREADS) void prep_kernel(
     const float2 *__restrict__ y, const float2 *__restrict__ bsym, const float *__restrict__ sigma,
     float2 *__restrict__ G, float2 *__restrict__ Z, const float2 *__restrict__ phi_prev,
     const float *__restrict__ h_prev, const float *__restrict__ alpha, float2 *__restrict__ phi_out,
-    float *__restrict__ h_out, float2 *__restrict__ Mbuf, int Dimg) {
+    float *__restrict__ h_out, float2 *__restrict__ Mbuf, int Dimg, const float *__restrict__ diag,
+    const int *__restrict__ diag_ok) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int n = D + 1;
     const int tid = threadIdx.x;
@@ -132,6 +133,9 @@ __global__ __launch_bounds__(PR_THREADS) void prep_kernel(
     const float rho_phi = lw[S_RHO_PHI], rho_h_eps = lw[S_RHO_H_EPS];
     float2 *Gs = G + s * (int64_t)n * n;
     float2 *Zs = Z + s * (int64_t)n * n;
+    // (uniform) the diagonals of G and Z from the rows sp_fused_kernel left, where it wrote this matrix's G (common.h, Ws::diag)
+    const bool compact = (mode & PM_DIAG) && diag_ok[s] != 0;
+    const float *dg = diag + s * (int64_t)(2 * D);
 
     for (int i = tid; i < D; i += PR_THREADS) {
         float2 g = make_float2(0.f, 0.f), zeta = make_float2(0.f, 0.f);
@@ -148,10 +152,18 @@ __global__ __launch_bounds__(PR_THREADS) void prep_kernel(
             const float zni = Zl.y + al * (Gl.y + pp.y);
             g = make_float2(Gl.x, -Gl.y);
             zeta = make_float2(znr, -zni);
-            const float Gd = Gs[(int64_t)i * n + i].x;
-            const float Zd = zzero ? 0.f : Zs[(int64_t)i * n + i].x;
-            const float Znd = Zd + al * (Gd - hpv);
-            t = Gd + Znd / rho_h_eps;
+            if (!phi_only) {   // (t feeds the H layer alone)
+                float Gd, Zd;
+                if (compact) {
+                    Gd = dg[i];
+                    Zd = dg[D + i];
+                } else {   // one cache line per float
+                    Gd = Gs[(int64_t)i * n + i].x;
+                    Zd = zzero ? 0.f : Zs[(int64_t)i * n + i].x;
+                }
+                const float Znd = Zd + al * (Gd - hpv);
+                t = Gd + Znd / rho_h_eps;
+            }
         }
         const float2 bv = bsym[s * D + i];
         const float ab = hypotf(bv.x, bv.y);
@@ -369,13 +381,15 @@ int launch_prep(const admmnet_cfg *cfg, const float *lw_all, int k, const float2
     const float *lwp = k > 0 ? lw_all + (int64_t)(k - 1) * L.size() : lw;
     if (k == 0) mode |= PM_FIRST;
     if (k == 1) mode |= PM_ZZERO;
+    if (k < 2 || !(mode & PM_SMALL) || !ws.diag) mode &= ~PM_DIAG;   // (layer 1 reads the G of the arrowhead layer, which leaves no rows)
     const int cur = k & 1, prv = cur ^ 1;
     const size_t lds = sizeof(float2) * 2 * D + sizeof(float) * (3 * D + kHid + 8);
     auto kern = (mode & PM_HALF) ? prep_kernel<true> : prep_kernel<false>;
     hipLaunchKernelGGL(kern, dim3((unsigned)nb), dim3(PR_THREADS), lds, st, D, mode, lw, lwp,
                        y + b0 * D, b + b0 * D, sigma + b0, ws.G + b0 * (int64_t)n * n,
                        ws.Z + b0 * (int64_t)n * n, ws.phi[prv] + b0 * D, ws.h[prv] + b0 * D, ws.alpha + b0,
-                       ws.phi[cur] + b0 * D, ws.h[cur] + b0 * D, ws.Mbuf, eig_dim);
+                       ws.phi[cur] + b0 * D, ws.h[cur] + b0 * D, ws.Mbuf, eig_dim,
+                       ws.diag ? ws.diag + b0 * 2 * D : nullptr, ws.diag ? ws.diag_ok + b0 : nullptr);
     ADMM_HIP(hipGetLastError());
     return ADMMNET_OK;
 }

@@ -23,6 +23,9 @@ struct Switches {   // (INTEGRATION.md section 6 is the user-facing table of the
     // ADMMNET_SF_FOLD=0: the lazy Z update of the previous layer streamed by prep_kernel (default: it rides the first sweep of the
     // fused kernel, prep then only computes phi and h)
     bool sf_fold;
+    // ADMMNET_SF_FOLD=2: the fold as by default, but prep_kernel gathers the diagonals of G and Z from the matrices in every layer
+    // (default: from layer 2 on it reads the compact pairs the fused kernel left in G, common.h diag_pairs) -- for A/B runs and tests
+    bool prep_gather;
     bool sf_smallwg;       // ADMMNET_SF_SMALLWG=0: never the 4-wave shape of the fused kernel (spectral_waves)
     bool sf_timing;        // ADMMNET_SF_TIMING: developer phase timer of sp_fused_kernel (this and the other *_TIMING: never on by default)
     bool eig_ql;           // ADMMNET_EIG=ql: tridiagonal eigensolver = QL + rotation replay (default: divide & conquer)
@@ -68,7 +71,7 @@ inline Switches builtin_switches() {
     s.spectral_tol = 1e-6f;
     s.spectral_iters = 5;
     s.sf_timing = s.ar_timing = s.br_timing = s.pn_timing = s.dc_timing = s.dc_poison = false;
-    s.eig_ql = s.tridiag_lds = s.tridiag_sweep = s.back_q = s.rebuild_tiles = s.two_streams = s.one_stream = false;
+    s.eig_ql = s.tridiag_lds = s.tridiag_sweep = s.back_q = s.rebuild_tiles = s.two_streams = s.one_stream = s.prep_gather = false;
     s.pad_min_set = false;
     s.pad_min = 0;
     s.tr_occ3 = true;
@@ -94,6 +97,7 @@ inline Switches switches_from_env(const Switches &base, const Lookup &env) {
     s.spectral_tol = env("ADMMNET_SPECTRAL_TOL") ? (float)atof(env("ADMMNET_SPECTRAL_TOL")) : base.spectral_tol;
     s.spectral_iters = num("ADMMNET_SPECTRAL_ITERS", base.spectral_iters);
     s.sf_fold = on("ADMMNET_SF_FOLD", base.sf_fold);
+    s.prep_gather = env("ADMMNET_SF_FOLD") ? atoi(env("ADMMNET_SF_FOLD")) == 2 : base.prep_gather;
     s.sf_smallwg = on("ADMMNET_SF_SMALLWG", base.sf_smallwg);
     s.sf_timing = set("ADMMNET_SF_TIMING", base.sf_timing);
     s.eig_ql = is("ADMMNET_EIG", "ql", base.eig_ql);

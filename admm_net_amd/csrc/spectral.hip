@@ -417,7 +417,7 @@ __global__ __launch_bounds__(SP_THREADS) void sp_assemble_kernel(int D, const fl
 // eigen-pipeline with Ws::skip = flag.
 int launch_spectral(const Switches &sw, int D, int64_t nb, const float *lw, const float2 *phi, const float *h, float2 *Z, float2 *G,
                     float *rn, const Ws &ws, int32_t *status, hipStream_t st, MatFun form, int waves, const float *alpha,
-                    const float2 *phi_prev, const float *h_prev, const float *lw_prev, int update_mode) {
+                    const float2 *phi_prev, const float *h_prev, const float *lw_prev, int update_mode, float *diag, int *diag_ok) {
     ProfScope _prof(KC_GFUNC, st);
     if (nb <= 0) return ADMMNET_OK;
     const int n = D + 1;
@@ -428,7 +428,7 @@ int launch_spectral(const Switches &sw, int D, int64_t nb, const float *lw, cons
             return ADMMNET_E_WORKSPACE;
         }
         return launch_spectral_fused(sw, D, nb, lw, phi, h, Z, G, rn, ws.spec_flag, status, alpha, phi_prev, h_prev, lw_prev,
-                                     update_mode, waves, st);
+                                     update_mode, waves, diag, diag_ok, st);
     }
     if (!ws.spec_flag || !ws.spec_vec || !ws.spec_val || !ws.spec_mat) {
         set_error("spectral: workspace without the fast-path buffers");

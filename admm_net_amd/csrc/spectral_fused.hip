@@ -153,6 +153,8 @@ struct SfUpdate {
     const float *h_prev;       // [B][D]
     const float *lw_prev;      // packed weights of the previous layer (S_CORNER_Z)
     int mode;
+    float *diag;               // [B][2][D] Ws::diag: Re diag G, Re diag Z for the next layer's prep_kernel (null: not written)
+    int *diag_ok;              // [B] Ws::diag_ok
 };
 
 // A_ij (i >= j) of the layer matrix from the state element z = Z_ij
@@ -225,6 +227,14 @@ __global__ __launch_bounds__(64 * W, W == 12 ? 1 : 3) void sp_fused_kernel(int D
             cv.Ob[tid] = tid < D ? up.phi_prev[b * D + tid] : make_float2(0.f, 0.f);
             cv.hp[tid] = tid < D ? up.h_prev[b * D + tid] : 0.f;
         }
+    }
+    // (the addresses of this matrix's compact diagonals wait in LDS for the end of the kernel: two more pointers held in scalar
+    //  registers across every phase cost the assembly of the first tile its registers -- the scalar file already spills into them)
+    float **const drow_p = reinterpret_cast<float **>(cv.coef + 8);
+    int **const dok_p = reinterpret_cast<int **>(cv.coef + 10);
+    if (tid == 0) {
+        *drow_p = up.diag ? up.diag + b * (int64_t)(2 * D) : nullptr;
+        *dok_p = up.diag_ok ? up.diag_ok + b : nullptr;
     }
     const float al = up.mode ? up.alpha[b] : 0.f;
     const float corner_zp = up.mode ? up.lw_prev[S_CORNER_Z] : 0.f;
@@ -749,6 +759,7 @@ __global__ __launch_bounds__(64 * W, W == 12 ? 1 : 3) void sp_fused_kernel(int D
             cv.coef[4] = (float)(f1k - a0 - a1 * (dl1 - c));
             cv.flags[0] = why;
             flag[b] = why;
+            if (int *const dok = *dok_p) *dok = (why == 0);
             if (status) {
                 atomicAdd(status + (why ? 1 : 2), 1);
                 if (why == 4) atomicAdd(status + 3, 1);
@@ -764,10 +775,12 @@ __global__ __launch_bounds__(64 * W, W == 12 ? 1 : 3) void sp_fused_kernel(int D
     const float corner_z = lw[S_CORNER_Z];
     float2 *Gb = G + b * (int64_t)n * n;
     float acc = 0.f;
+    float dgv[TPW], dzv[TPW];
     {
         const int r32 = lane & 31, kh = lane >> 5;
 #pragma unroll
         for (int s = 0; s < TPW; ++s) {
+            dgv[s] = dzv[s] = 0.f;
             if (wave * TPW + s < ntri) {
                 const int gj = 32 * tJ[s] + r32;
                 const float2 vj0 = cv.X0[gj < n ? gj : 0], vj1 = cv.X1[gj < n ? gj : 0];
@@ -800,6 +813,10 @@ __global__ __launch_bounds__(64 * W, W == 12 ? 1 : 3) void sp_fused_kernel(int D
                                 g.x += k0c;
                                 g.y = 0.f;
                                 cz = hi;
+                                if (W == SF_WAVES) {   // (compile time; below)
+                                    dgv[s] = g.x;
+                                    dzv[s] = zq[u].x;
+                                }
                             }
                             *sf_elem(Gb, n, gi, gj) = g;
                             const float dr = g.x - cz;
@@ -807,6 +824,31 @@ __global__ __launch_bounds__(64 * W, W == 12 ? 1 : 3) void sp_fused_kernel(int D
                         }
                     }
                 }
+            }
+        }
+    }
+    // The compact diagonals for the next layer's prep_kernel (common.h, Ws::diag): the floats stored to G[i][i].x and loaded from
+    // Z[i][i].x, stored here, behind the tiles -- two more guarded stores inside the first tile, which holds every accumulator, cost it
+    // registers.  Diagonal element 32 tI + r of a diagonal tile belongs to lane r of half kh = (r >> 2) & 1 (row = (q & 3) +
+    // 8 (q >> 2) + 4 kh).  Twelve waves (one workgroup per CU, nothing to hide a round trip behind): that lane kept both floats
+    // (dgv, dzv).  Four waves: keeping them costs the first tile two registers more than it has; the lane reads its own store
+    // back instead, and Z[i][i] once more (a thread's own store: program order, no fence), and the CU's other two workgroups
+    // cover the round trip.
+    // (the four-wave loads are in flight across the border row and the last sum; their stores are the kernel's last)
+    float *const drow = *drow_p;
+    bool dmine[TPW];
+#pragma unroll
+    for (int s = 0; s < TPW; ++s) {
+        const int r32 = lane & 31, gi = 32 * tI[s] + r32;
+        dmine[s] = drow && wave * TPW + s < ntri && tI[s] == tJ[s] && gi < D && (lane >> 5) == ((r32 >> 2) & 1);
+        if (W != SF_WAVES) dgv[s] = dzv[s] = 0.f;
+        if (dmine[s]) {
+            if (W == SF_WAVES) {
+                drow[gi] = dgv[s];
+                drow[D + gi] = dzv[s];
+            } else {
+                dgv[s] = sf_elem(Gb, n, gi, gi)->x;
+                dzv[s] = sf_elem(Z, n, gi, gi)->x;
             }
         }
     }
@@ -831,6 +873,15 @@ __global__ __launch_bounds__(64 * W, W == 12 ? 1 : 3) void sp_fused_kernel(int D
         sf_block_sum4<W>(acc, z1, z2, z3, cv.red);
     }
     if (tid == 0) rn[b] = sqrtf(acc);
+    if (W != SF_WAVES) {
+#pragma unroll
+        for (int s = 0; s < TPW; ++s)
+            if (dmine[s]) {
+                float *d = drow + 32 * tI[s] + (lane & 31);
+                d[0] = dgv[s];
+                d[D] = dzv[s];
+            }
+    }
     mark(7);
 }
 
@@ -860,8 +911,8 @@ static_assert(SF_WAVES == 12, "spectral_waves (route.h) names the shapes 4 and 1
 
 int launch_spectral_fused(const Switches &sw, int D, int64_t nb, const float *lw, const float2 *phi, const float *h, float2 *Z,
                           float2 *G, float *rn, int *flag, int32_t *status, const float *alpha, const float2 *phi_prev,
-                          const float *h_prev, const float *lw_prev, int update_mode, int waves, hipStream_t st) {
-    const SfUpdate up{alpha, phi_prev, h_prev, lw_prev, update_mode};
+                          const float *h_prev, const float *lw_prev, int update_mode, int waves, float *diag, int *diag_ok, hipStream_t st) {
+    const SfUpdate up{alpha, phi_prev, h_prev, lw_prev, update_mode, diag, diag_ok};
     if (D < 2 || D > 256) {
         set_error("spectral: D=%d outside 2..256", D);
         return ADMMNET_E_ARG;

@@ -115,7 +115,9 @@ class HipLayerEngine:
 
     def state(self) -> LayerState:
         """The per-forward state the layer calls keep in ``self.ws``, as writable views: read it, or overwrite it, between
-        any two of begin / front / back / finish (on the stream the calls run on)."""
+        any two of begin / front / back / finish (on the stream the calls run on).  One exception: from layer 2 on, ``front``
+        takes the diagonals of G and Z from rows the layer before left behind the state (``diag``); to
+        overwrite those diagonals by hand between two layers, run the model under ``Options(sf_fold=2)``."""
         return LayerState(self.ws, self.cfg, self.B)
 
     def begin(self):
