@@ -15,8 +15,13 @@
 // eigenvector is V[i][c] = p_i X[c][i] with X REAL, so G_ij = p_i conj(p_j) S_ij with S = X^T diag(f) X real symmetric.
 // After P6 the kernel generates X in slabs of AF_KS eigenvectors straight into LDS (one fast division per entry, from
 // O(n) data already there), accumulates all 36 lower 32 x 32 tiles of S as resident f32 matrix-core accumulators and
-// applies the phases in the epilogue (arrow_fused_tail below).  ADMMNET_ARROW_FUSED=0 keeps the former pair: this kernel
-// writing the image to the global VT buffer (AR_GLOBAL), then rebuild.hip's kernel.
+// applies the phases in the epilogue (arrow_fused_tail below).  By default that is two launches: the solver phases P0 - P6 as
+// arrow_rebuild_kernel<AR_SOLVE> (63 VGPRs, seven workgroups per CU -- inside one kernel they ran at the occupancy of the tail's
+// nine accumulator tiles), a record per matrix in the chunk's VT buffer (ArRecord), and arrow_tail_kernel, which loads the record
+// into LDS and runs the same arrow_fused_tail.  ADMMNET_ARROW_FUSED=2 keeps both in one kernel (arrow_rebuild_kernel<AR_FUSED>),
+// for A/B runs: the same bits.  ADMMNET_ARROW_FUSED=0 keeps the former pair: this kernel writing the image to the global VT
+// buffer (AR_GLOBAL), then rebuild.hip's kernel.
+// In every form the roots of P4 read their poles from plain LDS arrays, direct or reflected (arrow_core.h ArrowPoles).
 #include <cstdio>
 #include <cstdlib>
 
@@ -45,6 +50,36 @@ __host__ __device__ inline size_t ar_lds_bytes(const BrGeom &g) {
     const size_t NP = ar_np(g.D);
     return sizeof(float) * (g.vt_floats() + g.small_floats() + 12 * NP) + sizeof(int) * 5 * NP + sizeof(DcRot) * NP;
 }
+// the solver kernel of the split form: no image, no rowb, and hraw / zraw / src / org share other arrays' memory (the kernel's carve)
+__host__ __device__ inline size_t ar_solve_lds_bytes(const BrGeom &g) {
+    return ar_lds_bytes(g) - sizeof(float) * (g.vt_floats() + 2 * g.Dp + 4 * ar_np(g.D));
+}
+
+// The split form of AR_FUSED (the default at 128 < D <= 256): arrow_rebuild_kernel<AR_SOLVE> runs the solver phases at its own
+// occupancy and leaves, per matrix, the record below (4-byte words) in the chunk's eigenvector-image buffer ws.VT, which nothing
+// else uses while the first layer runs; arrow_tail_kernel reads it back and runs arrow_fused_tail.  Word 0: 1, or 0 = non-finite
+// input, nothing else written and nothing to do; word 1: the number of rotations (only those are copied).
+constexpr int AR_SOLVE = 4;   // (a mode of the kernel template only: the route stays AR_FUSED)
+struct ArRecord {
+    int F, fs, phr, lamc, tauc, zh, dl, kidx, perm, rnk, rot, words;
+    __host__ __device__ explicit ArRecord(int D) {
+        const int NP = (int)ar_np(D);
+        F = (D + 1 + 4) & ~3;        // fs / w0f / z0s: n + 1 entries each
+        fs = 4;
+        phr = fs + 3 * F;            // phr, phim
+        lamc = phr + 2 * NP;
+        tauc = lamc + NP;
+        zh = tauc + NP;
+        dl = zh + NP;
+        kidx = dl + NP;
+        perm = kidx + NP;
+        rnk = perm + NP;
+        rot = rnk + NP;              // DcRot: four words each
+        words = rot + 4 * NP;
+    }
+};
+static_assert(sizeof(DcRot) == 16, "ArRecord counts a rotation as four words");
+__host__ __device__ inline int ar_rec_words(int D) { return ArRecord(D).words; }
 
 // ---- fused tail (AR_FUSED, 128 < D <= 256): S = X^T diag(f) X on the matrix cores, X generated slab by slab in LDS ----
 // In: the solver's LDS arrays after P6 -- fs / w0f / z0s / lamc / tauc in FINAL eigenvalue order c, zh / dl per surviving
@@ -214,11 +249,11 @@ __device__ __forceinline__ void arrow_fused_tail(int D, int nrot, int64_t b, con
 // in the global VT buffer of the dense path (rows c, planes at 0 / D, pitch 2 D) together with w and w0, and rebuild.hip's
 // kernel consumes it.
 template <int MODE>
-__global__ __launch_bounds__(AR_THREADS, MODE == AR_FUSED ? 2 : 1) void arrow_rebuild_kernel(
+__global__ __launch_bounds__(AR_THREADS, MODE == AR_FUSED ? 2 : MODE == AR_SOLVE ? 7 : 1) void arrow_rebuild_kernel(
     int D, const float *__restrict__ lw, const float2 *__restrict__ phi, const float *__restrict__ h,
     float2 *__restrict__ G, float *__restrict__ rn, float *__restrict__ w_out, int32_t *__restrict__ status,
     unsigned long long *__restrict__ ptime, int lower_only, float *VTg, float *__restrict__ w0g) {
-    constexpr bool BIG = MODE == AR_GLOBAL, FUSED = MODE == AR_FUSED;
+    constexpr bool BIG = MODE == AR_GLOBAL, SOLVE = MODE == AR_SOLVE, FUSED = MODE == AR_FUSED || SOLVE;   // (FUSED: what the tail reads)
     extern __shared__ __attribute__((aligned(16))) char smem[];
     __shared__ ArShared sh;
     // developer phase timer (ADMMNET_AR_TIMING=1): cycles of thread 0 between marks
@@ -242,10 +277,9 @@ __global__ __launch_bounds__(AR_THREADS, MODE == AR_FUSED ? 2 : 1) void arrow_re
     float *w0f = fs + ((n + 4) & ~3);
     float *z0s = w0f + ((n + 4) & ~3);
     float *rowb = z0s + ((n + 4) & ~3);
-    float *redb = rowb + 2 * Dp;
-    float *hraw = redb + 8;
-    float *zraw = hraw + NP;
-    float *phr = zraw + NP;
+    float *redb = rowb + (SOLVE ? 0 : 2 * Dp);   // (SOLVE: no rowb -- and no hraw / zraw / src / org of its own, see below)
+    float *own = redb + 8;
+    float *phr = own + (SOLVE ? 0 : 2 * NP);
     float *phim = phr + NP;
     float *ds = phim + NP;
     float *zs = ds + NP;
@@ -257,10 +291,17 @@ __global__ __launch_bounds__(AR_THREADS, MODE == AR_FUSED ? 2 : 1) void arrow_re
     float *x0 = vals + NP;
     float *lamd = zs;   // (after the deflation scan) d[org_j]: origin pole value of root j
     int *perm = reinterpret_cast<int *>(x0 + NP);
-    int *src = perm + NP;
-    int *org = src + NP;
-    int *rnk = org + NP;
+    int *own_i = perm + NP;
+    int *rnk = own_i + (SOLVE ? 0 : 2 * NP);
     int *kidx = rnk + NP;
+    // SOLVE keeps its LDS small enough for seven workgroups per CU: arrays whose lives do not meet share memory.  hraw / zraw
+    // die with P1, before the deflation first writes tau / zh; src dies with kidx and org with the deflation, both before P6
+    // writes w0f / z0s.
+    float *hraw = SOLVE ? tau : own, *zraw = SOLVE ? zh : own + NP;
+    int *src = SOLVE ? reinterpret_cast<int *>(w0f) : own_i, *org = SOLVE ? reinterpret_cast<int *>(z0s) : own_i + NP;
+    // the poles as the root solver reads them (arrow_core.h ArrowPoles), alive from the deflation to the end of P4: in ds (read
+    // last by the deflation, lamc from P6), x0 (written in P6) and rnk (written in P5, behind the barrier that ends P4)
+    float *zz = reinterpret_cast<float *>(rnk), *dR = ds, *zzR = x0;
     DcRot *rot = reinterpret_cast<DcRot *>(kidx + NP);
     float *lamc = ds, *tauc = zl;   // (FUSED, after P6) origin pole value and tau of the root in final position c
 
@@ -282,6 +323,7 @@ __global__ __launch_bounds__(AR_THREADS, MODE == AR_FUSED ? 2 : 1) void arrow_re
     }
     if (__syncthreads_or(bad)) {   // NaN / Inf input: the rank sort below would leave permutation slots unwritten
         if (tid == 0 && status) atomicAdd(status, 1);
+        if (SOLVE && tid == 0) reinterpret_cast<int *>(VTg + b * (int64_t)ar_rec_words(D))[0] = 0;   // the tail leaves at once
         return;
     }
     // ---- P1: sort h ascending (stable rank counting)
@@ -342,6 +384,7 @@ __global__ __launch_bounds__(AR_THREADS, MODE == AR_FUSED ? 2 : 1) void arrow_re
     // slots: 0..k roots, p + 1 for the deflated pole at scan position p in [k, D)
     for (int p = k + tid; p < D; p += AR_THREADS) vals[p + 1] = dl[p];
     for (int p = tid; p < D; p += AR_THREADS) kidx[src[p]] = (p < k) ? p : -(p + 1) - 1;   // sorted position -> pole / slot
+    for (int i = tid; i < k; i += AR_THREADS) arrow_poles_fill(k, i, dl, zl, zz, dR, zzR);
     if (tid < 64) {   // ||zeta|| of the surviving poles
         float s = 0.f;
         for (int i = tid; i < k; i += 64) s = fmaf(zl[i], zl[i], s);
@@ -354,8 +397,8 @@ __global__ __launch_bounds__(AR_THREADS, MODE == AR_FUSED ? 2 : 1) void arrow_re
         if (tid == 0) vals[0] = alpha;
     } else {
         const float znorm = sh.znorm;
+        const ArrowPoles poles{dl, zz, dR, zzR};
         auto put = [&](int jr, int o, float t) {
-            org[jr] = o;
             tau[jr] = t;
             lamd[jr] = dl[o];
             vals[jr] = dl[o] + t;
@@ -369,7 +412,7 @@ __global__ __launch_bounds__(AR_THREADS, MODE == AR_FUSED ? 2 : 1) void arrow_re
             if (jr < first) {
                 int o;
                 float t;
-                arrow_root(k, jr, alpha, znorm, dl, zl, o, t, nullptr, sub, 2, [](float x) {
+                arrow_root(k, jr, alpha, znorm, poles, o, t, nullptr, sub, 2, [](float x) {
                     return x + __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), 0xB1,
                                                                                        0xF, 0xF, false));   // quad_perm [1,0,3,2]
                 });
@@ -378,14 +421,14 @@ __global__ __launch_bounds__(AR_THREADS, MODE == AR_FUSED ? 2 : 1) void arrow_re
         } else if (tid < first) {
             int o;
             float t;
-            arrow_root(k, tid, alpha, znorm, dl, zl, o, t);
+            arrow_root(k, tid, alpha, znorm, poles, o, t);
             put(tid, o, t);
         }
         if (tid < 64) {
             for (int jr = first; jr <= k; ++jr) {
                 int o;
                 float t;
-                arrow_root(k, jr, alpha, znorm, dl, zl, o, t, nullptr, tid, 64, [](float x) { return wave_sum(x); });
+                arrow_root(k, jr, alpha, znorm, poles, o, t, nullptr, tid, 64, [](float x) { return wave_sum(x); });
                 if (tid == 0) put(jr, o, t);
             }
         }
@@ -459,8 +502,33 @@ __global__ __launch_bounds__(AR_THREADS, MODE == AR_FUSED ? 2 : 1) void arrow_re
         }
     }
     __syncthreads();
+    if constexpr (SOLVE) {   // the record of this matrix for arrow_tail_kernel (ArRecord), in the chunk's image buffer
+        if (__syncthreads_or(bad) && tid == 0 && status) atomicAdd(status, 1);
+        const ArRecord R(D);
+        float *rec = VTg + b * (int64_t)R.words;
+        const auto put = [&](int off, const void *src_, int cnt) {
+            const float *sp = static_cast<const float *>(src_);
+            for (int i = tid; i < cnt; i += AR_THREADS) rec[off + i] = sp[i];
+        };
+        if (tid == 0) {
+            reinterpret_cast<int *>(rec)[0] = 1;
+            reinterpret_cast<int *>(rec)[1] = nrot;
+        }
+        put(R.fs, fs, 3 * R.F);   // fs, w0f, z0s
+        put(R.phr, phr, 2 * NP);  // phr, phim
+        put(R.lamc, lamc, NP);
+        put(R.tauc, tauc, NP);
+        put(R.zh, zh, NP);
+        put(R.dl, dl, NP);
+        put(R.kidx, kidx, NP);
+        put(R.perm, perm, NP);
+        put(R.rnk, rnk, NP);
+        put(R.rot, rot, 4 * nrot);
+        mark(2);
+        return;
+    }
     mark(2);
-    if constexpr (FUSED) {
+    if constexpr (MODE == AR_FUSED) {
         if (__syncthreads_or(bad) && tid == 0 && status) atomicAdd(status, 1);
         arrow_fused_tail(D, nrot, b, lw, reinterpret_cast<float *>(rot + NP), fs, w0f, z0s, lamc, tauc, phr, phim, zh, dl,
                          kidx, reinterpret_cast<int *>(hraw), perm, rnk, rot, redb, phi, h, G, rn, lower_only,
@@ -535,6 +603,46 @@ __global__ __launch_bounds__(AR_THREADS, MODE == AR_FUSED ? 2 : 1) void arrow_re
     else rebuild_from_lds(g, b, lw, VTl, fs, w0f, z0s, rowb, redb, phi, h, G, rn, [&](int id) { mark(id); }, lower_only);
 }
 
+// Second kernel of the split first layer: the record into LDS (one linear copy: it is laid out as the tail reads it), then the
+// tail as the one-kernel form runs it.
+__global__ __launch_bounds__(AR_THREADS, 2) void arrow_tail_kernel(int D, const float *__restrict__ lw,
+                                                                   const float2 *__restrict__ phi, const float *__restrict__ h,
+                                                                   float2 *__restrict__ G, float *__restrict__ rn,
+                                                                   unsigned long long *__restrict__ ptime, int lower_only,
+                                                                   const float *__restrict__ recs) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    long long t_prev = ptime ? clock64() : 0;
+    auto mark = [&](int id) {
+        if (ptime && threadIdx.x == 0) {
+            const long long t_now = clock64();
+            atomicAdd(&ptime[id], (unsigned long long)(t_now - t_prev));
+            t_prev = t_now;
+        }
+    };
+    const ArRecord R(D);
+    const int NP = (int)ar_np(D);
+    const int tid = threadIdx.x;
+    const int64_t b = blockIdx.x;
+    const float *rec = recs + b * (int64_t)R.words;
+    const int ok = reinterpret_cast<const int *>(rec)[0], nrot = reinterpret_cast<const int *>(rec)[1];   // (uniform)
+    if (!ok) return;   // non-finite input: counted by the solver kernel, nothing is written
+    float *l = reinterpret_cast<float *>(smem);
+    const int nw = R.rot + 4 * nrot;   // (a multiple of 4, as the record's stride is)
+    for (int i = 4 * tid; i < nw; i += 4 * AR_THREADS)
+        *reinterpret_cast<float4 *>(l + i) = *reinterpret_cast<const float4 *>(rec + i);
+    int *ipos = reinterpret_cast<int *>(l + R.words);
+    float *redb = reinterpret_cast<float *>(ipos + NP);
+    float *slab = redb + 8;
+    __syncthreads();
+    arrow_fused_tail(D, nrot, b, lw, slab, l + R.fs, l + R.fs + R.F, l + R.fs + 2 * R.F, l + R.lamc, l + R.tauc, l + R.phr,
+                     l + R.phr + NP, l + R.zh, l + R.dl, reinterpret_cast<const int *>(l + R.kidx), ipos,
+                     reinterpret_cast<const int *>(l + R.perm), reinterpret_cast<const int *>(l + R.rnk),
+                     reinterpret_cast<const DcRot *>(l + R.rot), redb, phi, h, G, rn, lower_only, [&](int id) { mark(id); });
+}
+static size_t ar_tail_lds_bytes(int D) {
+    return sizeof(float) * ((size_t)ArRecord(D).words + ar_np(D) + 8 + 2 * AF_KS * AF_W);
+}
+
 bool arrow_rebuild_supported(int D) { return D >= 1 && D <= 256; }
 
 // developer phase timer (ADMMNET_AR_TIMING=1): mean cycles of thread 0 per phase, printed after the launch
@@ -557,7 +665,30 @@ int launch_arrow_rebuild(const Route &r, const Switches &sw, int64_t nb, const f
     }
     const BrGeom g(D);
     int rc;
-    // D > 128: one kernel, X in LDS slabs and real S on the matrix cores (AR_FUSED), or the two-kernel form (AR_GLOBAL)
+    // D > 128: X in LDS slabs and real S on the matrix cores (AR_FUSED) -- as solver kernel + tail kernel, or behind
+    // ADMMNET_ARROW_FUSED=2 as the one kernel it was -- or the image in global memory and the dense path's rebuild (AR_GLOBAL)
+    static const char *const nm_fused[6] = {"sort+deflate", "roots", "zhat+rank+norm", "first slab", "slabs + S", "epilogue"};
+    if (r.first == AR_FUSED && !sw.arrow_onekernel) {
+        if (!ws.VT) {
+            set_error("arrow_rebuild: the split first layer needs the chunk's image buffer");
+            return ADMMNET_E_ARG;
+        }
+        ProfScope _prof(KC_REBUILD, st);
+        const size_t lds = ar_solve_lds_bytes(g), lds_tail = ar_tail_lds_bytes(D);
+        ADMM_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(arrow_rebuild_kernel<AR_SOLVE>),
+                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        ADMM_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(arrow_tail_kernel),
+                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_tail));
+        PhaseTimer tm;
+        if ((rc = tm.begin(sw.ar_timing, st, 16))) return rc;
+        hipLaunchKernelGGL(arrow_rebuild_kernel<AR_SOLVE>, dim3((unsigned)nb), dim3(AR_THREADS), lds, st, D, lw, phi, h, G,
+                           rn, w_out, status, tm.dev, lower_only ? 1 : 0, ws.VT, (float *)nullptr);
+        ADMM_HIP(hipGetLastError());
+        hipLaunchKernelGGL(arrow_tail_kernel, dim3((unsigned)nb), dim3(AR_THREADS), lds_tail, st, D, lw, phi, h, G, rn, tm.dev,
+                           lower_only ? 1 : 0, ws.VT);
+        ADMM_HIP(hipGetLastError());
+        return ar_timing_end(tm, st, D, nb, nm_fused);
+    }
     if (r.first == AR_FUSED) {
         ProfScope _prof(KC_REBUILD, st);
         const size_t lds = ar_lds_bytes(g) - sizeof(float) * g.vt_floats() + sizeof(float) * 2 * AF_KS * AF_W;
@@ -568,8 +699,7 @@ int launch_arrow_rebuild(const Route &r, const Switches &sw, int64_t nb, const f
         hipLaunchKernelGGL(arrow_rebuild_kernel<AR_FUSED>, dim3((unsigned)nb), dim3(AR_THREADS), lds, st, D, lw, phi, h, G,
                            rn, w_out, status, tm.dev, lower_only ? 1 : 0, (float *)nullptr, (float *)nullptr);
         ADMM_HIP(hipGetLastError());
-        static const char *const nm[6] = {"sort+deflate", "roots", "zhat+rank+norm", "first slab", "slabs + S", "epilogue"};
-        return ar_timing_end(tm, st, D, nb, nm);
+        return ar_timing_end(tm, st, D, nb, nm_fused);
     }
     if (r.first == AR_GLOBAL) {   // eigenvectors to the global image, then the dense path's rebuild kernel
         {

@@ -19,6 +19,8 @@
 #pragma once
 #include "dc_core.h"
 
+#define ADMMNET_ARROW_POLES 1   // arrow_root takes ArrowPoles (tests/host_model/arrow_core_bits_model.cpp)
+
 namespace admmnet {
 
 struct ArrowEval {
@@ -26,7 +28,9 @@ struct ArrowEval {
 };
 
 // F at lam = d_org + t, split at pole index jsplit (psi: poles 0..jsplit, phi: the rest); `c0` = d_org - alpha.
-// DA / ZA are accessors (index -> value) so that the bottom root can run on the reflected problem.
+// DA / ZA are accessors (index -> pole value d_i, index -> zeta_i^2): the device hands over plain arrays -- the poles as they
+// are, or the reflected problem written out for the bottom root (ArrowPoles below) -- so a pole costs two reads at a uniform
+// offset from a per-lane base and no index arithmetic.
 // A root may be shared by a group of G adjacent lanes: lane `sub` sums the poles sub, sub + G, ... and `red`
 // adds the partial sums across the group (every lane of the group gets the same totals and then takes the
 // same decisions).  Host / single lane: sub = 0, G = 1, red = identity.
@@ -35,16 +39,19 @@ struct ArrowNoReduce {
 };
 
 template <class DA, class ZA, class Red = ArrowNoReduce>
-HD ArrowEval arrow_eval(int k, int jsplit, float c0, float dorg, float t, DA d, ZA z, int sub = 0, int G = 1,
+HD ArrowEval arrow_eval(int k, int jsplit, float c0, float dorg, float t, DA d, ZA zz, int sub = 0, int G = 1,
                         Red red = Red()) {
     float sum = 0.f, asum = 0.f, dall = 0.f, dps = 0.f;
     // (unrolled: one LDS round trip per iteration would otherwise bound the loop, not the arithmetic)
 #pragma unroll 4
     for (int i = sub; i < k; i += G) {
+        // every product and sum below is rounded on its own: the four totals are plain adds in pole order
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
         const float del = (d(i) - dorg) - t;
         const float r = fdiv_fast(1.0f, del);
-        const float zi = z(i);
-        const float term = zi * zi * r;
+        const float term = zz(i) * r;
         const float dterm = term * r;
         sum += term;
         asum += fabsf(term);
@@ -67,7 +74,7 @@ HD ArrowEval arrow_eval(int k, int jsplit, float c0, float dorg, float t, DA d, 
 // the reflected problem.  j < k: interior root in (d_{j-1}, d_j); j = k: top root in (d_{k-1}, ub).
 // Returns the origin pole and tau (lam = d_org + tau), as secular_root does.
 template <class DA, class ZA, class Red = ArrowNoReduce>
-HD void arrow_root_upper(int k, int j, float alpha, float znorm, DA d, ZA z, int &org_out, float &tau_out,
+HD void arrow_root_upper(int k, int j, float alpha, float znorm, DA d, ZA zz, int &org_out, float &tau_out,
                          int *nit = nullptr, int sub = 0, int G = 1, Red red = Red()) {
     if (nit) *nit = 0;
     const bool top = (j == k);
@@ -90,7 +97,7 @@ HD void arrow_root_upper(int k, int j, float alpha, float znorm, DA d, ZA z, int
         }
         hi = hi * (1.0f + 8.0f * kEps32) + 1e-30f;
         t = hi;
-        e = arrow_eval(k, plo, d(org) - alpha, d(org), t, d, z, sub, G, red);
+        e = arrow_eval(k, plo, d(org) - alpha, d(org), t, d, zz, sub, G, red);
         if (e.w <= 0.f) {   // numerical corner: the root sits at the bound
             org_out = org;
             tau_out = hi;
@@ -100,7 +107,7 @@ HD void arrow_root_upper(int k, int j, float alpha, float znorm, DA d, ZA z, int
         plo = j - 1;
         phi_ = j;
         const float half = 0.5f * (d(j) - d(j - 1));
-        e = arrow_eval(k, plo, d(j - 1) - alpha, d(j - 1), half, d, z, sub, G, red);
+        e = arrow_eval(k, plo, d(j - 1) - alpha, d(j - 1), half, d, zz, sub, G, red);
         if (e.w >= 0.f) {   // root in the lower half: measure from d_{j-1}
             org = j - 1;
             lo = 0.f;
@@ -128,7 +135,7 @@ HD void arrow_root_upper(int k, int j, float alpha, float znorm, DA d, ZA z, int
         if (top) {
             // outer root: keep the nearest pole AND the linear term exact, linearise the rest (psi):
             //   (c0 + t) + psi(t0) + psi'(t0)(t - t0) - zeta^2 / t = 0   ->   B t^2 + A t - zeta^2 = 0
-            const float zk = z(k - 1), z2 = zk * zk;
+            const float z2 = zz(k - 1);
             const float psi = e.w - (c0 + t) + fdiv_fast(z2, t);
             const float B = 1.0f + e.dpsi, A = c0 + psi - e.dpsi * t;
             const float disc = sqrtf(A * A + 4.0f * B * z2);
@@ -148,7 +155,7 @@ HD void arrow_root_upper(int k, int j, float alpha, float znorm, DA d, ZA z, int
         if (!(tn > lo && tn < hi)) tn = 0.5f * (lo + hi);
         if (tn == t || tn == lo || tn == hi) break;
         t = tn;
-        e = arrow_eval(k, plo, c0, dorg, t, d, z, sub, G, red);
+        e = arrow_eval(k, plo, c0, dorg, t, d, zz, sub, G, red);
     }
     if (t == 0.f) t = (lo == 0.f) ? 0.5f * hi : 0.5f * lo;
     if (t == 0.f) t = (lo == 0.f) ? 1e-30f : -1e-30f;
@@ -158,8 +165,36 @@ HD void arrow_root_upper(int k, int j, float alpha, float znorm, DA d, ZA z, int
 
 // Root j of k + 1 (0 <= j <= k) of the arrowhead (alpha; d[k] ascending distinct; z[k] > 0).
 // The bottom root is minus the top root of the reflected problem (-alpha, -d reversed); both cases run
-// through the SAME code with a per-lane (sign, index map), so a wave whose lanes hold different roots
-// does not execute the solver twice.
+// through the SAME code, so a wave whose lanes hold different roots does not execute the solver twice.
+//
+// ArrowPoles: the k poles as arrays, direct and reflected -- zz[i] = z_i^2, dR[i] = -d[k-1-i] (exact), zzR[i] = zz[k-1-i].
+// A root picks one pair of bases; every access after that is base[i].
+struct ArrowPoles {
+    const float *d, *zz, *dR, *zzR;
+};
+
+HD void arrow_poles_fill(int k, int i, const float *d, const float *z, float *zz, float *dR, float *zzR) {   // element i of the three
+    const float q = z[i] * z[i];
+    zz[i] = q;
+    zzR[k - 1 - i] = q;
+    dR[k - 1 - i] = -d[i];
+}
+
+template <class Red = ArrowNoReduce>
+HD void arrow_root(int k, int j, float alpha, float znorm, const ArrowPoles &p, int &org_out, float &tau_out,
+                   int *nit = nullptr, int sub = 0, int G = 1, Red red = Red()) {
+    const bool refl = (j == 0);
+    const float *db = refl ? p.dR : p.d, *zb = refl ? p.zzR : p.zz;
+    int orgr;
+    float taur;
+    arrow_root_upper(k, refl ? k : j, refl ? -alpha : alpha, znorm, [db](int i) { return db[i]; },
+                     [zb](int i) { return zb[i]; }, orgr, taur, nit, sub, G, red);
+    org_out = refl ? k - 1 - orgr : orgr;
+    tau_out = refl ? -taur : taur;
+}
+
+// The same root from the poles (d, z) themselves, through a per-access (sign, index map): for callers without the arrays
+// of ArrowPoles.  Value for value the operations of the form above (sg = +-1 multiplies exactly).
 template <class FA, class Red = ArrowNoReduce>
 HD void arrow_root(int k, int j, float alpha, float znorm, FA d, FA z, int &org_out, float &tau_out,
                    int *nit = nullptr, int sub = 0, int G = 1, Red red = Red()) {
@@ -169,7 +204,7 @@ HD void arrow_root(int k, int j, float alpha, float znorm, FA d, FA z, int &org_
     int orgr;
     float taur;
     arrow_root_upper(k, refl ? k : j, sg * alpha, znorm, [&](int i) { return sg * d[refl ? km1 - i : i]; },
-                     [&](int i) { return z[refl ? km1 - i : i]; }, orgr, taur, nit, sub, G, red);
+                     [&](int i) { const float zi = z[refl ? km1 - i : i]; return zi * zi; }, orgr, taur, nit, sub, G, red);
     org_out = refl ? km1 - orgr : orgr;
     tau_out = sg * taur;
 }
@@ -182,17 +217,19 @@ HD float arrow_delta(FA d, FA lamd, FA tau, int i, int j) {
 
 // Gu / Eisenstat zeta-hat_i (>= 0) from the computed roots
 // (sub, G, red): a group of G adjacent lanes shares one i, `red` multiplies the partial products across it.
+// Pole j pairs with root j below i and with root j + 1 above it: two loops over j = sub, sub + G, ... with the own pole
+// left out (its factor was an exact 1), so no index is selected per factor and the product keeps its order.
 template <class FA, class Red = ArrowNoReduce>
 HD float arrow_zhat(int k, int i, FA d, FA lamd, FA tau, int sub = 0, int G = 1, Red red = Red()) {
     const float di = d[i];
     float w = (sub == 0) ? ((di - lamd[i]) - tau[i]) * -((di - lamd[i + 1]) - tau[i + 1])   // (d_i - lam_i)(lam_{i+1} - d_i)
                          : 1.0f;
+    int j = sub;
 #pragma unroll 4
-    for (int j = sub; j < k; j += G) {
-        const int jr = (j < i) ? j : j + 1;   // root paired with pole j
-        const float q = fdiv_fast((di - lamd[jr]) - tau[jr], di - d[j]);
-        w *= (j == i) ? 1.0f : q;
-    }
+    for (; j < i; j += G) w *= fdiv_fast((di - lamd[j]) - tau[j], di - d[j]);
+    if (j == i) j += G;
+#pragma unroll 4
+    for (; j < k; j += G) w *= fdiv_fast((di - lamd[j + 1]) - tau[j + 1], di - d[j]);
     return sqrtf(fabsf(red(w)));
 }
 

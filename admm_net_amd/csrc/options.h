@@ -17,12 +17,12 @@ constexpr int kOptionsCapacity = 4096;   // distinct option sets per process (be
 
 // A switch added to Switches (route.h) joins builtin_switches() and the parser there, and same_switches() and options_describe()
 // here: a field missing from same_switches() would make two different sets share a handle.  The size pins the field list.
-static_assert(sizeof(Switches) == 56, "Switches changed: extend same_switches() and options_describe(), then update this size");
+static_assert(sizeof(Switches) == 60, "Switches changed: extend same_switches() and options_describe(), then update this size");
 
 inline bool same_switches(const Switches &a, const Switches &b) {   // field by field (the struct has padding); tol by its bits
     return a.spectral == b.spectral && a.spectral_fused == b.spectral_fused && !memcmp(&a.spectral_tol, &b.spectral_tol, sizeof(float)) &&
            a.spectral_iters == b.spectral_iters && a.sf_fold == b.sf_fold && a.prep_gather == b.prep_gather && a.sf_smallwg == b.sf_smallwg && a.sf_timing == b.sf_timing &&
-           a.eig_ql == b.eig_ql && a.arrow == b.arrow && a.arrow_fused == b.arrow_fused && a.ar_timing == b.ar_timing &&
+           a.eig_ql == b.eig_ql && a.arrow == b.arrow && a.arrow_fused == b.arrow_fused && a.arrow_onekernel == b.arrow_onekernel && a.ar_timing == b.ar_timing &&
            a.lean == b.lean && a.fuse_back == b.fuse_back && a.br_timing == b.br_timing && a.tridiag_lds == b.tridiag_lds &&
            a.tridiag_sweep == b.tridiag_sweep && a.back_q == b.back_q && a.rebuild_tiles == b.rebuild_tiles &&
            a.pad_min_set == b.pad_min_set && a.pad_min == b.pad_min && a.two_streams == b.two_streams && a.one_stream == b.one_stream && a.tr_occ3 == b.tr_occ3 &&
@@ -110,7 +110,7 @@ inline int64_t options_describe(const Switches &s, char *buf, size_t len) {
                     "ADMMNET_BR_TIMING %d\nADMMNET_TRIDIAG %d\nADMMNET_TRIDIAG_BIG %d\nADMMNET_BACK %d\nADMMNET_REBUILD %d\n"
                     "ADMMNET_PAD_MIN %d\nADMMNET_STREAMS %d\nADMMNET_TR_OCC %d\nADMMNET_TR_PAD_LDS %d\nADMMNET_PN_SPLIT %d\n"
                     "ADMMNET_PN_TIMING %d\nADMMNET_DC_OCC %d\nADMMNET_DC_BLOCKS %d\nADMMNET_DC_POISON %d\nADMMNET_DC_TIMING %d\n",
-                    s.spectral, s.spectral_fused, (double)s.spectral_tol, s.spectral_iters, s.sf_fold, s.sf_smallwg, s.sf_timing, s.eig_ql,   // (ADMMNET_SF_FOLD 1 also where it was set to 2)
+                    s.spectral, s.spectral_fused, (double)s.spectral_tol, s.spectral_iters, s.sf_fold, s.sf_smallwg, s.sf_timing, s.eig_ql,   // (ADMMNET_SF_FOLD and ADMMNET_ARROW_FUSED 1 also where they were set to 2)
                     s.arrow, s.arrow_fused, s.ar_timing, s.lean, s.fuse_back, s.br_timing, s.tridiag_lds, s.tridiag_sweep, s.back_q,
                     s.rebuild_tiles, s.pad_min_set ? s.pad_min : -1000, s.two_streams, s.tr_occ3, s.tr_pad_lds, s.pn_split, s.pn_timing,
                     s.dc_occ, s.dc_blocks, s.dc_poison, s.dc_timing);

@@ -32,7 +32,10 @@ struct Switches {   // (INTEGRATION.md section 6 is the user-facing table of the
     // ADMMNET_ARROW=0: the first G-layer down the dense path like every other (default: Z = 0 gives a plain arrowhead matrix,
     // which arrow.hip solves directly in O(n^2))
     bool arrow;
-    bool arrow_fused;      // ADMMNET_ARROW_FUSED=0, D > 128: arrowhead eigenvectors to the global image + rebuild, not one kernel
+    bool arrow_fused;      // ADMMNET_ARROW_FUSED=0, D > 128: arrowhead eigenvectors to the global image + rebuild, not the slab form
+    // ADMMNET_ARROW_FUSED=2, D > 128: the slab form as ONE kernel (default: a solver kernel at its own occupancy, then the tail
+    // kernel, arrow.hip) -- the same bits, for A/B runs and tests
+    bool arrow_onekernel;
     bool ar_timing;        // ADMMNET_AR_TIMING: developer phase timer of arrow_rebuild_kernel
     // ADMMNET_LEAN=0: G / Z in full storage + the image written by prep (default: G and Z kept as lower triangles; D <= 128: the
     // tridiagonalisation forms A = C - Z / rho itself, prep only streams the lazy Z update; D > 128: "half image", prep.hip PM_HALF)
@@ -71,7 +74,7 @@ inline Switches builtin_switches() {
     s.spectral_tol = 1e-6f;
     s.spectral_iters = 5;
     s.sf_timing = s.ar_timing = s.br_timing = s.pn_timing = s.dc_timing = s.dc_poison = false;
-    s.eig_ql = s.tridiag_lds = s.tridiag_sweep = s.back_q = s.rebuild_tiles = s.two_streams = s.one_stream = s.prep_gather = false;
+    s.eig_ql = s.tridiag_lds = s.tridiag_sweep = s.back_q = s.rebuild_tiles = s.two_streams = s.one_stream = s.prep_gather = s.arrow_onekernel = false;
     s.pad_min_set = false;
     s.pad_min = 0;
     s.tr_occ3 = true;
@@ -103,6 +106,7 @@ inline Switches switches_from_env(const Switches &base, const Lookup &env) {
     s.eig_ql = is("ADMMNET_EIG", "ql", base.eig_ql);
     s.arrow = on("ADMMNET_ARROW", base.arrow);
     s.arrow_fused = on("ADMMNET_ARROW_FUSED", base.arrow_fused);
+    s.arrow_onekernel = env("ADMMNET_ARROW_FUSED") ? atoi(env("ADMMNET_ARROW_FUSED")) == 2 : base.arrow_onekernel;
     s.ar_timing = set("ADMMNET_AR_TIMING", base.ar_timing);
     s.lean = on("ADMMNET_LEAN", base.lean);
     s.fuse_back = on("ADMMNET_FUSE_BACK", base.fuse_back);
