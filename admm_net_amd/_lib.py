@@ -113,6 +113,10 @@ SYMBOLS = {
                                            [c_void_p] * 3 + [c_int64, c_void_p]),
     "admmnet_loss_spectrum_bwd_f64": (c_int32, [c_int32, c_int32, c_int32, c_int32, c_int64] + [c_void_p] * 5 + [c_float] * 3 +
                                                [c_int32, c_void_p, c_int64, c_void_p, c_void_p]),
+    "admmnet_loss_set_partials": (c_int64, [c_int64]),
+    "admmnet_loss_set_f32": (c_int32, [c_int32, c_int32, c_int32, c_int64] + [c_void_p] * 7 + [POINTER(c_double)] + [c_void_p] * 6),
+    "admmnet_loss_set_bwd_f32": (c_int32, [c_int32, c_int32, c_int32, c_int64] + [c_void_p] * 10 + [POINTER(c_double)] +
+                                          [c_void_p] * 5),
     "admmnet_score_partials": (c_int64, [c_int64]),
     "admmnet_score_match_f64": (c_int32, [c_int32, c_int32, c_int64] + [c_void_p] * 5 + [POINTER(c_double)] + [c_void_p] * 6),
     "admmnet_score_ordered_f32": (c_int32, [c_int32, c_int64] + [c_void_p] * 10),

@@ -11,6 +11,7 @@
 #include "common.h"
 #include "options.h"
 #include "score_core.h"
+#include "set_core.h"
 #include "crb_core.h"
 #include "refine_core.h"
 
@@ -1293,6 +1294,51 @@ int admmnet_loss_spectrum_bwd_f64(int32_t xbase, int32_t ybase, int32_t oversamp
     return launch_loss_spectrum_bwd(xbase, ybase, oversample, Lmax, B, g_out, (const float2 *)phi, tau_true, f_true, L_true,
                                     spectral_weight, distribution_weight, target_weight, skip, workspace, (float2 *)g_phi,
                                     (hipStream_t)stream);
+}
+
+// ---- the assignment loss of the head (loss_set.hip) ---------------------------------------------------------------------------
+// one lane per slot and per target (<= 64 each); the slab grid must fit 31 bits
+static int loss_set_args_ok(const char *what, int32_t Lmax, int32_t Lt, int32_t D, int64_t B, bool ptrs, const double *opts) {
+    if (Lmax < 1 || Lmax > SC_MAX || Lt < 1 || Lt > SC_MAX || D < 1 || B < 1 || train_small_rows(B) > 0x7fffffffLL || !ptrs || !opts) {
+        set_error("%s: bad argument (Lmax=%d, Lt=%d, D=%d, B=%lld, or a null pointer)", what, Lmax, Lt, D, (long long)B);
+        return ADMMNET_E_ARG;
+    }
+    if (!set_opts_ok(opts)) {
+        set_error("%s: bad options (sx=%g, sy=%g must be > 0, periods %g, %g >= 0, w_conf=%g >= 0, lambda_reg=%g >= 0, all finite)",
+                  what, opts[0], opts[1], opts[2], opts[3], opts[4], opts[5]);
+        return ADMMNET_E_ARG;
+    }
+    return ADMMNET_OK;
+}
+
+int64_t admmnet_loss_set_partials(int64_t B) {
+    if (B < 1 || train_small_rows(B) > 0x7fffffffLL) return -1;
+    return loss_set_partials(B);
+}
+
+int admmnet_loss_set_f32(int32_t Lmax, int32_t Lt, int32_t D, int64_t B, const float *tau, const float *f, const float *conf,
+                         const float *tau_true, const float *f_true, const int64_t *L_true, const void *phi, const double *opts,
+                         float *out, int32_t *assign, float *norms, int32_t *status, double *partials, void *stream) {
+    if (int rc = loss_set_args_ok("loss_set", Lmax, Lt, D, B,
+                                  tau && f && conf && tau_true && f_true && L_true && phi && out && assign && norms && status &&
+                                      partials,
+                                  opts))
+        return rc;
+    return launch_loss_set(Lmax, Lt, D, B, tau, f, conf, tau_true, f_true, L_true, (const float2 *)phi, opts, out, assign, norms,
+                           status, partials, (hipStream_t)stream);
+}
+
+int admmnet_loss_set_bwd_f32(int32_t Lmax, int32_t Lt, int32_t D, int64_t B, const float *g_out, const float *tau, const float *f,
+                             const float *conf, const float *tau_true, const float *f_true, const int64_t *L_true,
+                             const void *phi, const int32_t *assign, const float *norms, const double *opts, float *g_tau,
+                             float *g_f, float *g_conf, void *g_phi, void *stream) {
+    if (int rc = loss_set_args_ok("loss_set_bwd", Lmax, Lt, D, B,
+                                  g_out && tau && f && conf && tau_true && f_true && L_true && phi && assign && norms && g_tau &&
+                                      g_f && g_conf && g_phi,
+                                  opts))
+        return rc;
+    return launch_loss_set_bwd(Lmax, Lt, D, B, g_out, tau, f, conf, tau_true, f_true, L_true, (const float2 *)phi, assign, norms,
+                               opts, g_tau, g_f, g_conf, (float2 *)g_phi, (hipStream_t)stream);
 }
 
 // ---- estimates against ground truth (score.hip) ------------------------------------------------------------------------------

@@ -310,6 +310,17 @@ int launch_loss_phi(int D, int64_t B, const float2 *phi, const float2 *phi_true,
 int launch_loss_phi_bwd(int D, int64_t B, const float *g_out, const float2 *phi, const float2 *phi_true, float amplitude_weight,
                         float phase_weight, float2 *g_phi, hipStream_t st);
 
+// loss_set.hip (the assignment loss of the head: slots matched to targets by the assignment that minimises the loss; one wave per
+// signal, float64, one row of partials per signal).  opts: HOST double[6] = sx, sy, period_tau, period_f, w_conf, lambda_reg
+int64_t loss_set_partials(int64_t B);                 // doubles of per-signal rows of the forward
+int launch_loss_set(int Lmax, int Lt, int D, int64_t B, const float *tau, const float *f, const float *conf, const float *tau_true,
+                    const float *f_true, const int64_t *L_true, const float2 *phi, const double *opts, float *out, int32_t *assign,
+                    float *norms, int32_t *status, double *part, hipStream_t st);
+int launch_loss_set_bwd(int Lmax, int Lt, int D, int64_t B, const float *g_out, const float *tau, const float *f, const float *conf,
+                        const float *tau_true, const float *f_true, const int64_t *L_true, const float2 *phi, const int32_t *assign,
+                        const float *norms, const double *opts, float *g_tau, float *g_f, float *g_conf, float2 *g_phi,
+                        hipStream_t st);
+
 // loss_spectrum.hip (the spectral, distribution and target terms of the phi loss on the delay-Doppler spectrum; one workgroup
 // per signal, float64).  phi_true == nullptr: no grid terms; L_true == nullptr: no target term.
 constexpr int LS_MAX_TARGETS = 16, LS_MAX_OVERSAMPLE = 4;

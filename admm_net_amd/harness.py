@@ -147,7 +147,7 @@ def load_checkpoint(path, model, optimizer=None, scheduler=None, map_location="c
 
 
 def time_train_step(layers=10, batch=256, steps=20, warmup=3, seed=0, device="cuda:0", route="tensor", grid=(NB, ND), head=False,
-                    optim="torch"):
+                    optim="torch", loss=None, targets=None, min_sep=0.0, checkpoint=None):
     """Wall time of one optimisation step at the reference's own training configuration (trainPhi.py:16-38: 10 x 10 grid,
     num_layers = 10, batch_size = 256, AdamW lr 1e-3 / weight decay 1e-3, gradient clipping at 1.0, :179-190): forward in
     train mode (the differentiable route of admm_net_amd.training: HIP eigensolver + HIP contractions), a phi-alignment
@@ -161,6 +161,10 @@ def time_train_step(layers=10, batch=256, steps=20, warmup=3, seed=0, device="cu
     Under ``torch.distributed.run`` (WORLD_SIZE > 1; backend ADMMNET_DIST_BACKEND, default nccl = RCCL) every rank takes a batch
     of ``batch`` signals of its own and the step runs through ``sharded.ShardedTraining``: the mean loss times ``st.weight``, one
     gradient all-reduce.  The dict then holds ``n_ranks`` and ``global_batch``; ``signals_per_second`` counts the global batch.
+    ``loss`` (with ``head=True``): None, the loss above; "set" (``losses.SetANMLoss``) or "basic" (``losses.BasicANMLoss``), each
+    with ``check_status = False``, on scenes of ``synth.make_scenes_device(targets=(lo, hi), min_sep=...)`` (``targets``: a pair,
+    default (1, 3)) -- a fresh batch of scenes every step, drawn on the device.  ``checkpoint``: a path the model is saved to
+    after the last step (``save_checkpoint``).  Not combined with a sharded run.
     Returns a dict (seconds per step, signals per second, route, geometry)."""
     import os
     import torch.distributed as dist
@@ -177,7 +181,14 @@ def time_train_step(layers=10, batch=256, steps=20, warmup=3, seed=0, device="cu
     dev = torch.device(device)
     torch.manual_seed(seed)
     M, N = grid
-    model = (ADMMNet if head else PhiEstADMMNet)(num_layers=layers, M=M, N=N, L=3).to(dev)
+    if loss not in (None, "set", "basic"):
+        raise ValueError(f"loss must be None, 'set' or 'basic', got {loss!r}")
+    if loss is None and (targets is not None or min_sep != 0.0):
+        raise ValueError("targets= and min_sep= go with loss='set' or loss='basic'")
+    if loss is not None and (not head or world > 1):
+        raise ValueError("loss= needs head=True and a single process")
+    lo, hi = (1, 3) if targets is None else synth._target_range(targets)
+    model = (ADMMNet if head else PhiEstADMMNet)(num_layers=layers, M=M, N=N, L=hi if loss else 3).to(dev)
     model.train_route = route
     model.train()
     if optim not in ("torch", "hip"):
@@ -195,7 +206,29 @@ def time_train_step(layers=10, batch=256, steps=20, warmup=3, seed=0, device="cu
         dist.all_reduce(scale)
         scale = scale / world
 
+    crit, drawn = None, [0]
+    if loss is not None:
+        from . import losses
+        crit = losses.SetANMLoss() if loss == "set" else losses.BasicANMLoss()
+        crit.check_status = False
+
+    def scene_step():
+        opt.zero_grad(set_to_none=True)
+        drawn[0] += 1
+        ys, bs, ss, truth = synth.make_scenes_device(batch, M, N, targets=(lo, hi), min_sep=min_sep,
+                                                     seed=20260104 + seed + 104729 * drawn[0], device=dev)
+        tau, f, conf, phi = model(ys, bs, ss)
+        total, _ = crit({"tau_est": tau, "f_est": f, "confidences": conf, "phi_final": phi},
+                        {"tau_true": truth["tau"], "f_true": truth["f"], "L_true": truth["L_true"]})
+        total.backward()
+        if optim == "torch":
+            torch.nn.utils.clip_grad_norm_(model.parameters(), 1.0)
+        opt.step()
+        return total
+
     def step():
+        if crit is not None:
+            return scene_step()
         opt.zero_grad(set_to_none=True)
         out = model(y, b, sigma) if st is None else st(y, b, sigma)
         if head:
@@ -228,6 +261,10 @@ def time_train_step(layers=10, batch=256, steps=20, warmup=3, seed=0, device="cu
            "loss_first": round(losses[0], 6), "loss_last": round(losses[-1], 6)}
     if st is not None:                                      # (the losses are this rank's mean, not the whole batch's)
         out.update(n_ranks=world, global_batch=st.global_batch)
+    if loss is not None:
+        out.update(loss=loss, targets=[lo, hi], min_sep=float(min_sep))
+    if checkpoint:
+        save_checkpoint(checkpoint, model, opt, epoch=warmup + steps, config={"M": M, "N": N, "num_layers": layers, "L": hi if loss else 3})
     return out
 
 
@@ -308,6 +345,45 @@ def time_spectral_loss_step(batch=256, targets=3, dim=100, steps=200, warmup=10,
     return out
 
 
+def time_set_loss_step(batch=256, targets=3, dim=100, steps=200, warmup=10, repeats=5, seed=0, device="cuda:0"):
+    """Device-event time of one forward + backward of ``losses.SetANMLoss`` (``check_status = False``) on ``route = "hip"`` and
+    ``route = "tensor"`` (whose assignment is a host loop over the batch), and of ``losses.BasicANMLoss`` on ``route = "hip"`` on
+    the same shapes: [batch, targets] head outputs and labels with L_true cycling through 0 .. targets, [batch, dim] complex
+    phi.  ``steps`` forward + backward pairs are enqueued between two events; ``repeats`` such windows give the figure (their
+    median) and its range.  Returns a dict of milliseconds."""
+    from . import losses
+    dev = torch.device(device)
+    g = torch.Generator().manual_seed(seed)
+    r = lambda *shape: torch.rand(*shape, generator=g).to(dev)
+    tau, f, conf = (r(batch, targets).requires_grad_(True) for _ in range(3))
+    truth = {"tau_true": r(batch, targets), "f_true": r(batch, targets) - 0.5,
+             "L_true": (torch.arange(batch) % (targets + 1)).to(dev)}
+    phi = torch.randn(batch, dim, dtype=torch.complex64, generator=g).to(dev).requires_grad_(True)
+    outputs = {"tau_est": tau, "f_est": f, "confidences": conf, "phi_final": phi}
+    out = {"batch": batch, "targets": targets, "dim": dim, "steps": steps, "repeats": repeats}
+    for name, cls, route in (("set_hip", losses.SetANMLoss, "hip"), ("anm_hip", losses.BasicANMLoss, "hip"),
+                             ("set_tensor", losses.SetANMLoss, "tensor")):
+        crit = cls()
+        crit.route, crit.check_status = route, False
+
+        def window(n):
+            start, stop = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            start.record()
+            for _ in range(n):
+                for t in (tau, f, conf, phi):
+                    t.grad = None
+                crit(outputs, truth)[0].backward()
+            stop.record()
+            stop.synchronize()
+            return start.elapsed_time(stop) / n
+
+        window(warmup)
+        times = sorted(window(steps) for _ in range(repeats))
+        out[f"{name}_ms"] = round(times[len(times) // 2], 4)
+        out[f"{name}_range_ms"] = [round(times[0], 4), round(times[-1], 4)]
+    return out
+
+
 def _score_case(batch, n_est, n_true, seed, dev):
     """Scenes drawn like ``synth.make_batch`` with estimates = shuffled truth + N(0, 0.03) and strays, as device tensors."""
     rng = np.random.default_rng(seed)
@@ -365,7 +441,8 @@ def time_score_step(steps=50, warmup=5, repeats=5, host_signals=2048, seed=0, de
 
 
 def evaluate_snr(grid=(NB, ND), layers=10, checkpoint=None, snrs=(5.0, 15.0, 25.0), signals=4096, targets=3, cutoff=1.0,
-                 baseline=None, seed=0, device="cuda:0", targets_min=None, min_sep=0.0, order=None, refine=None, crb=False):
+                 baseline=None, seed=0, device="cuda:0", head=False, targets_min=None, min_sep=0.0, order=None, refine=None,
+                 crb=False):
     """Detection and accuracy against the noise level: per SNR one batch of ``signals`` scenes at exactly that SNR
     (``synth.make_batch_device(snr_range=(S, S))``), ``model.evaluate`` and ``metrics.summary`` -- scene, forward, peak search and
     score without a host loop.  ``baseline="classical"`` scores the peaks of the classical solver's phi (the generator's labels)
@@ -384,7 +461,11 @@ def evaluate_snr(grid=(NB, ND), layers=10, checkpoint=None, snrs=(5.0, 15.0, 25.
     it, and gain ``order_under`` / ``order_exact`` / ``order_over``, the shares of the scenes where ``n_sel`` <, ==, > ``L_true``.
     Every line gains ``targets_min``, ``min_sep``, ``unseparated`` (scenes where a target stayed closer than ``min_sep``) and
     ``ser`` (the mean percentage of symbols decided wrongly); everything is scored against ``L_true``, the bound included.  With
-    both at their defaults the scenes, the lines and their keys are those of ``make_batch_device``."""
+    both at their defaults the scenes, the lines and their keys are those of ``make_batch_device``.
+    ``head=True`` yields, after each SNR's other lines, a line ``method = "head"``: the learned head of ``ADMMNet`` (seed 0, or the
+    checkpoint's, which is then an ``ADMMNet``'s; the ``net`` lines take its layers) through ``ADMMNet.estimate_head``, scored
+    with ``n_est`` = the number of confidences >= 0.5 -- the head is never given a scene's count -- and, on varied scenes, with
+    ``order_under`` / ``order_exact`` / ``order_over`` from that ``n_est``.  Without it every line and key is as before."""
     from . import PhiEstADMMNet, metrics, ops, synth
     from . import order as ordering
     from . import refine as refinement
@@ -403,12 +484,21 @@ def evaluate_snr(grid=(NB, ND), layers=10, checkpoint=None, snrs=(5.0, 15.0, 25.
     M, N = grid
     torch.manual_seed(seed)
     model = PhiEstADMMNet(num_layers=layers, M=M, N=N, L=targets)
-    if checkpoint:
+    head_model = None
+    if head:
+        from . import ADMMNet
+        torch.manual_seed(seed)
+        head_model = ADMMNet(num_layers=layers, M=M, N=N, L=targets)
+        if checkpoint:
+            state = load_checkpoint(checkpoint, head_model)["model_state_dict"]
+            model.load_state_dict({k: v for k, v in state.items() if k in model.state_dict()})
+        head_model.eval()
+    elif checkpoint:
         load_checkpoint(checkpoint, model)
     model.eval()
-    head = {"grid": [M, N], "layers": layers, "signals": signals, "targets": targets, "cutoff": cutoff}
+    common = {"grid": [M, N], "layers": layers, "signals": signals, "targets": targets, "cutoff": cutoff}
     if varied:
-        head.update(targets_min=targets if targets_min is None else int(targets_min), min_sep=float(min_sep))
+        common.update(targets_min=targets if targets_min is None else int(targets_min), min_sep=float(min_sep))
 
     def scored(res, truth, snr, n_sel=None):
         if varied:                                                                     # in summary's one read
@@ -436,7 +526,7 @@ def evaluate_snr(grid=(NB, ND), layers=10, checkpoint=None, snrs=(5.0, 15.0, 25.
 
     def refined(method, rows, y, b, truth, snr):
         fit = refinement.refine_targets(y, b, rows, (M, N), n_est=truth.get("L_true"), symbols=refine)
-        return {"snr": snr, "method": method + "+refine", **head, **scored(match(fit.rows, truth), truth, snr)}
+        return {"snr": snr, "method": method + "+refine", **common, **scored(match(fit.rows, truth), truth, snr)}
 
     est_opts = {"xstep": 1 / (10 * N), "ystep": 1 / (10 * M), "iter": 3}              # estimate's defaults
 
@@ -445,11 +535,11 @@ def evaluate_snr(grid=(NB, ND), layers=10, checkpoint=None, snrs=(5.0, 15.0, 25.
         sel, _ = ordering.select_refined(y, b, cand, (M, N), symbols=refine or "given")
         res = metrics.match_targets(sel.rows_out, truth["tau"], truth["f"], truth.get("L_true"), n_est=sel.n_sel, cutoff=cutoff,
                                     scale=(float(N), float(M)), period=(1.0, 1.0))
-        return {"snr": snr, "method": method + "+order", **head, **scored(res, truth, snr, sel.n_sel)}
+        return {"snr": snr, "method": method + "+order", **common, **scored(res, truth, snr, sel.n_sel)}
 
     for i, snr in enumerate(snrs):
         if varied:
-            y, b, sigma, truth = synth.make_scenes_device(signals, M, N, targets=(head["targets_min"], targets), min_sep=min_sep,
+            y, b, sigma, truth = synth.make_scenes_device(signals, M, N, targets=(common["targets_min"], targets), min_sep=min_sep,
                                                           seed=20260104 + seed + 7919 * i, snr_range=(snr, snr), device=dev,
                                                           labels=baseline is not None)
         else:
@@ -460,7 +550,7 @@ def evaluate_snr(grid=(NB, ND), layers=10, checkpoint=None, snrs=(5.0, 15.0, 25.
         else:                                                                          # evaluate, with the rows kept
             rows, _, _ = model._estimate_rows(y, b, sigma, targets, truth.get("L_true"))
             res = match(rows, truth)
-        yield {"snr": snr, "method": "net", **head, **scored(res, truth, snr)}
+        yield {"snr": snr, "method": "net", **common, **scored(res, truth, snr)}
         if refine is not None:
             yield refined("net", rows, y, b, truth, snr)
         if order is not None:
@@ -470,11 +560,16 @@ def evaluate_snr(grid=(NB, ND), layers=10, checkpoint=None, snrs=(5.0, 15.0, 25.
         if baseline is not None:
             opts = {"xstep": 1 / (10 * N), "ystep": 1 / (10 * M), "iter": 3}            # estimate's defaults
             rows, _ = ops.peak_top(truth["phi"], M, N, opts, top=targets, top_n=truth.get("L_true"))
-            yield {"snr": snr, "method": "classical", **head, **scored(match(rows, truth), truth, snr)}
+            yield {"snr": snr, "method": "classical", **common, **scored(match(rows, truth), truth, snr)}
             if refine is not None:
                 yield refined("classical", rows, y, b, truth, snr)
             if order is not None:
                 yield ordered("classical", truth["phi"], y, b, truth, snr)
+        if head_model is not None:
+            e = head_model._head_rows(y, b, sigma, 0.5)
+            res = metrics.match_targets((e.tau, e.f), truth["tau"], truth["f"], truth.get("L_true"), n_est=e.n_est, cutoff=cutoff,
+                                        scale=(float(N), float(M)), period=(1.0, 1.0))
+            yield {"snr": snr, "method": "head", **common, **scored(res, truth, snr, e.n_est if varied else None)}
 
 
 def _grid(ap, text):
@@ -509,6 +604,12 @@ def main(argv=None):
     c.add_argument("--warmup", type=int, default=3)
     c.add_argument("--optim", choices=("torch", "hip"), default="torch",
                    help="hip: clipping and AdamW on the kernels of admm_net_amd.optim instead of torch's")
+    c.add_argument("--loss", choices=("set", "basic"), default=None,
+                   help="with --head: train with SetANMLoss / BasicANMLoss on scenes of --targets-min .. --targets targets")
+    c.add_argument("--targets", type=int, default=3)
+    c.add_argument("--targets-min", type=int, default=None, metavar="LO")
+    c.add_argument("--min-sep", type=float, default=0.0, metavar="CELLS")
+    c.add_argument("--save", default=None, metavar="PATH", help="save the model's checkpoint after the last step")
     d = sub.add_parser("loss-step")
     d.add_argument("--batch", type=int, default=256)
     d.add_argument("--targets", type=int, default=3)
@@ -516,6 +617,8 @@ def main(argv=None):
     d.add_argument("--steps", type=int, default=200)
     d.add_argument("--spectral", action="store_true",
                    help="time PhiSpectralLoss (device events, median and range of five windows) instead of the two reference losses")
+    d.add_argument("--set", action="store_true", dest="set_loss",
+                   help="time SetANMLoss on both routes beside BasicANMLoss (device events, median and range of five windows)")
     e = sub.add_parser("score-step")
     e.add_argument("--steps", type=int, default=50)
     e.add_argument("--repeats", type=int, default=5)
@@ -536,6 +639,8 @@ def main(argv=None):
                    help="draw LO .. --targets targets per scene; the lines without +order are given each scene's count")
     f.add_argument("--min-sep", type=float, default=0.0, metavar="CELLS",
                    help="keep the targets of a scene at least this many resolution cells apart")
+    f.add_argument("--head", action="store_true",
+                   help="after each SNR's lines, the learned head of ADMMNet (the checkpoint's), its count from the confidences")
     f.add_argument("--order", type=int, default=None, metavar="TOP",
                    help="after each method's lines, TOP candidate peaks with the number of targets selected against the received signal")
     args = ap.parse_args(argv)
@@ -547,12 +652,14 @@ def main(argv=None):
         import json
         for line in evaluate_snr(_grid(ap, args.grid), args.layers, args.checkpoint, args.snr, args.signals, args.targets,
                                  args.cutoff, args.baseline, targets_min=args.targets_min, min_sep=args.min_sep,
-                                 refine=args.refine, crb=args.crb, order=args.order):
+                                 refine=args.refine, crb=args.crb, order=args.order, head=args.head):
             print(json.dumps(line), flush=True)
         return
     if args.cmd == "loss-step":
         import json
-        step = time_spectral_loss_step if args.spectral else time_loss_step
+        if args.spectral and args.set_loss:
+            ap.error("--spectral and --set are two commands")
+        step = time_spectral_loss_step if args.spectral else time_set_loss_step if args.set_loss else time_loss_step
         print(json.dumps(step(args.batch, args.targets, args.dim, args.steps)))
         return
     if args.cmd == "train-step":
@@ -562,8 +669,14 @@ def main(argv=None):
             assert len(grid) == 2 and min(grid) >= 1
         except (ValueError, AssertionError):
             ap.error(f"--grid must be MxN, got {args.grid!r}")
+        scenes = {}
+        if args.loss is not None:
+            scenes = dict(loss=args.loss, targets=(args.targets if args.targets_min is None else args.targets_min, args.targets),
+                          min_sep=args.min_sep)
+        elif args.targets_min is not None or args.min_sep != 0.0 or args.targets != 3:
+            ap.error("--targets, --targets-min and --min-sep go with --loss")
         line = time_train_step(args.layers, args.batch, args.steps, warmup=args.warmup, route=args.route, grid=grid, head=args.head,
-                               optim=args.optim)
+                               optim=args.optim, checkpoint=args.save, **scenes)
         if line.get("n_ranks", 1) == 1 or torch.distributed.get_rank() == 0:      # one JSON line, rank 0's
             print(json.dumps(line))
         if torch.distributed.is_available() and torch.distributed.is_initialized():

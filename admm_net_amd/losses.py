@@ -29,10 +29,12 @@ from __future__ import annotations
 
 import math
 
+import numpy as np
 import torch
 import torch.nn as nn
 
 from . import ops
+from .set_ops import set_options
 
 ROUTES = ("hip", "tensor")
 
@@ -47,6 +49,10 @@ class HipLossKernels:
     # csrc/loss_spectrum.hip: (phi, phi_true, truth, xbase, ybase, weights, oversample) -> out [4], workspace, status [3]
     spectrum = staticmethod(ops.loss_spectrum)
     spectrum_bwd = staticmethod(ops.loss_spectrum_bwd)   # (g_out, phi, truth, ..., oversample, workspace, skip) -> g_phi
+    # csrc/loss_set.hip: (tau, f, conf, tau_true, f_true, L_true, phi, lambda_reg, w_conf, scale, period)
+    #   -> out [4], assign [B, Lmax], norms, status [2], rows [B, 6]
+    set = staticmethod(ops.loss_set)
+    set_bwd = staticmethod(ops.loss_set_bwd)   # (g_out, tau, ..., phi, assign, norms, lambda_reg, ...) -> g_tau, g_f, g_conf, g_phi
 
 
 class TensorLossKernels:
@@ -220,6 +226,142 @@ class TensorLossKernels:
             g = g - ((coef * p["rho"]).sum(dim=1) / p["n2s"]).reshape(B, 1, 1) * p["P"]
         return torch.where(p["live"].reshape(B, 1), g.reshape(B, D), torch.zeros_like(phi))
 
+    # ---- the assignment loss of the head (SetANMLoss; csrc/loss_set.hip) --------------------------------------------------------
+    @staticmethod
+    def period_wrap(d, P):
+        """d into [-P / 2, P / 2) for a period P > 0; P = 0: d itself (sc_wrap of csrc/score_core.h)."""
+        return d - P * torch.floor(d / P + 0.5) if P > 0 else d
+
+    @staticmethod
+    def set_dead(tau, f, conf, tau_true, f_true, L_true):
+        """(n = L_true held to [0, Lt] [B], the signals with a non-finite value among tau, f, conf or their first n truths [B])."""
+        Lt = tau_true.shape[1]
+        n = L_true.clamp(0, Lt)
+        first = torch.arange(Lt, device=tau.device) < n.reshape(-1, 1)
+        dead = ~(torch.isfinite(tau) & torch.isfinite(f) & torch.isfinite(conf)).all(dim=1)
+        return n, dead | (~(torch.isfinite(tau_true) & torch.isfinite(f_true)) & first).any(dim=1)
+
+    @staticmethod
+    def set_assign(tau, f, conf, tau_true, f_true, L_true, w_conf, scale, period):
+        """assign [B, Lmax] int32 from ``set_assign_host``: ONE HOST LOOP OVER THE SIGNALS of the batch, after a device-to-host
+        copy of the six inputs.  This is the float64 yardstick and the CPU stand-in, not a fast path."""
+        n, dead = TensorLossKernels.set_dead(tau, f, conf, tau_true, f_true, L_true)
+        host = [t.detach().cpu().to(torch.float64).numpy() for t in (tau, f, conf, tau_true, f_true)]
+        n_host, dead_host = n.cpu().numpy(), dead.cpu().numpy()
+        assign = np.full(tuple(tau.shape), -1, dtype=np.int32)
+        for b in range(tau.shape[0]):                       # the per-signal host loop
+            if not dead_host[b]:
+                assign[b] = set_assign_host(*(h[b] for h in host), int(n_host[b]), w_conf=w_conf, scale=scale, period=period)[0]
+        return torch.from_numpy(assign).to(tau.device)
+
+    @staticmethod
+    def _set_parts(tau, f, conf, tau_true, f_true, L_true, assign, scale, period):
+        """(n [B], dead [B], matched [B, Lmax], wrapped dtau and df (0 off the matched slots), t = 1 on a matched slot)."""
+        sx, sy, pt, pf, _, _ = set_options(scale, period)
+        n, dead = TensorLossKernels.set_dead(tau, f, conf, tau_true, f_true, L_true)
+        matched = (assign >= 0) & ~dead.reshape(-1, 1)
+        at = assign.clamp(min=0).to(torch.int64)
+        zero = torch.zeros_like(tau)
+        dt = torch.where(matched, TensorLossKernels.period_wrap(tau - tau_true.gather(1, at).to(tau.dtype), pt), zero)
+        df = torch.where(matched, TensorLossKernels.period_wrap(f - f_true.gather(1, at).to(f.dtype), pf), zero)
+        return n, dead, matched, dt, df, matched.to(tau.dtype)
+
+    @staticmethod
+    def set(tau, f, conf, tau_true, f_true, L_true, phi, lambda_reg=0.0, w_conf=0.1, scale=(1.0, 1.0), period=None):
+        """(out [4] = (total, match, conf, reg), assign [B, Lmax] int32, norms [B], status [2] int32, rows [B, 6] = each signal's
+        loss_b, match_b, conf_b, ||phi_b|| as it enters reg, and its two status flags): ``ops.loss_set``'s returns."""
+        sx, sy, _, _, w_conf, lambda_reg = set_options(scale, period, w_conf, lambda_reg)
+        Lmax, Lt = tau.shape[1], tau_true.shape[1]
+        assign = TensorLossKernels.set_assign(tau, f, conf, tau_true, f_true, L_true, w_conf, scale, period)
+        n, dead, matched, dt, df, t = TensorLossKernels._set_parts(tau, f, conf, tau_true, f_true, L_true, assign, scale, period)
+        zero = torch.zeros_like(tau)
+        match_b = ((sx * dt) ** 2 + (sy * df) ** 2).sum(dim=1) / n.clamp(min=1)
+        conf_b = torch.where(dead.reshape(-1, 1), zero, (conf - t) ** 2).sum(dim=1) / Lmax
+        norms = torch.sqrt((phi.real ** 2 + phi.imag ** 2).sum(dim=1))
+        counted = torch.where(dead, torch.zeros_like(norms), norms)
+        outside = (L_true < 0) | (L_true > Lt)
+        match, cf, reg = match_b.mean(), conf_b.mean(), lambda_reg * counted.mean()
+        rows = torch.stack([match_b + w_conf * conf_b, match_b, conf_b, counted, outside.to(tau.dtype), dead.to(tau.dtype)], dim=1)
+        status = torch.stack([outside.sum(), dead.sum()]).to(torch.int32)
+        return torch.stack([match + w_conf * cf + reg, match, cf, reg]), assign, norms, status, rows
+
+    @staticmethod
+    def set_bwd(g_out, tau, f, conf, tau_true, f_true, L_true, phi, assign, norms, lambda_reg=0.0, w_conf=0.1, scale=(1.0, 1.0),
+                period=None):
+        sx, sy, _, _, w_conf, lambda_reg = set_options(scale, period, w_conf, lambda_reg)
+        B, Lmax = tau.shape
+        n, dead, matched, dt, df, t = TensorLossKernels._set_parts(tau, f, conf, tau_true, f_true, L_true, assign, scale, period)
+        g_out = g_out.to(tau.dtype)
+        cm, cc, cr = g_out[0] + g_out[1], g_out[0] * w_conf + g_out[2], g_out[0] + g_out[3]
+        s = cm * 2 / (n.clamp(min=1).reshape(-1, 1) * B)
+        g_conf = torch.where(dead.reshape(-1, 1), torch.zeros_like(conf), cc * 2 * (conf - t) / (Lmax * B))
+        live = ((norms > 0) & ~dead).reshape(-1, 1)
+        unit = phi / torch.where(live, norms.reshape(-1, 1), torch.ones_like(norms).reshape(-1, 1))
+        g_phi = torch.where(live, (cr * lambda_reg / B) * unit, torch.zeros_like(phi))
+        return s * (sx * sx) * dt, s * (sy * sy) * df, g_conf, g_phi
+
+
+def set_assign_host(tau, f, conf, tau_true, f_true, n=None, *, w_conf=0.1, scale=(1.0, 1.0), period=None, with_gap=False):
+    """The assignment of ``SetANMLoss`` for ONE signal in float64 numpy: slots (tau, f, conf, 1-d, all live) against the first ``n``
+    of the targets (1-d; None: all of them; held to [0, Lt]).  Enumerates every assignment where min(Lmax, n) <=
+    ``metrics.BRUTE_MIN`` and there are at most ``metrics.BRUTE_ASSIGNMENTS`` of them, and calls
+    ``scipy.optimize.linear_sum_assignment`` on c_ij = d2_ij / n + (w_conf / Lmax)(1 - 2 conf_i) above that, as
+    ``metrics.match_host`` does.
+
+    Returns (assign [Lmax] int32 = the target of slot i or -1, loss_b from the definition at that assignment); with
+    ``with_gap=True`` also the distance to the best value with ANOTHER assignment relative to loss_b (inf if there is none): by
+    enumeration, else by excluding each matched pair in turn and solving again."""
+    from . import metrics
+    sx, sy, pt, pf, w_conf, _ = set_options(scale, period, w_conf)
+    ts, fs, cs = (np.asarray(v, dtype=np.float64).reshape(-1) for v in (tau, f, conf))
+    tt, ft = (np.asarray(v, dtype=np.float64).reshape(-1) for v in (tau_true, f_true))
+    if not (ts.shape == fs.shape == cs.shape and tt.shape == ft.shape and len(ts) >= 1):
+        raise ValueError("tau, f and conf must have one length >= 1, tau_true and f_true one length")
+    Lmax = len(ts)
+    n = len(tt) if n is None else min(max(int(n), 0), len(tt))
+    tt, ft = tt[:n], ft[:n]
+    if not all(np.isfinite(v).all() for v in (ts, fs, cs, tt, ft)):
+        raise ValueError("a slot or a target is not finite")
+    wl = w_conf / Lmax
+    assign = np.full(Lmax, -1, dtype=np.int32)
+    gap_abs, d2 = math.inf, np.zeros((Lmax, 0))
+    if n > 0:
+        _, _, d2 = metrics.pair_terms(ts, fs, tt, ft, (sx, sy), (pt, pf))
+        cost = d2 / n + (wl * (1.0 - 2.0 * cs)).reshape(-1, 1)
+        k, m = min(Lmax, n), max(Lmax, n)
+        by_rows = cost if Lmax <= n else cost.T                      # rows = the smaller side (on a tie the slots)
+        r = np.arange(k)
+        if k <= metrics.BRUTE_MIN and math.perm(m, k) <= metrics.BRUTE_ASSIGNMENTS:
+            P = metrics._arrangements(m, k)
+            total = by_rows[r, P].sum(axis=1)
+            best = int(np.argmin(total))
+            cols = P[best]
+            if with_gap and len(total) > 1:
+                gap_abs = float(np.delete(total, best).min() - total[best])
+        else:
+            from scipy.optimize import linear_sum_assignment
+            r, cols = linear_sum_assignment(by_rows)
+            if with_gap and m > 1:
+                least = by_rows[r, cols].sum()
+                for i, j in zip(r, cols):
+                    other = by_rows.copy()
+                    other[i, j] = np.inf
+                    try:
+                        ro, co = linear_sum_assignment(other)
+                    except ValueError:                              # no assignment without this pair
+                        continue
+                    gap_abs = min(gap_abs, float(other[ro, co].sum() - least))
+        if Lmax <= n:
+            assign[r] = cols
+        else:
+            assign[cols] = r
+    matched = assign >= 0
+    at = assign[matched]
+    value = float(d2[matched, at].sum() / max(n, 1) + w_conf * ((cs - matched) ** 2).sum() / Lmax)
+    if not with_gap:
+        return assign, value
+    return assign, value, (gap_abs / value if value > 0 else math.inf)
+
 
 def _kernels(route):
     if route not in ROUTES:
@@ -308,6 +450,68 @@ class BasicANMLoss(nn.Module):
                                       model_outputs['phi_final'], ground_truth['tau_true'], ground_truth['f_true'],
                                       ground_truth['L_true'], self.lambda_reg, self.route, self.check_status)
         return total, {'total_loss': total, 'param_loss': param, 'reg_loss': reg}
+
+
+class _SetLossFn(torch.autograd.Function):
+    """(total, match, conf, reg, status, assign) of SetANMLoss; gradients arriving through any of the first four are honoured."""
+
+    @staticmethod
+    def forward(ctx, tau, f, conf, phi, tau_true, f_true, L_true, opts, lk):
+        out, assign, norms, status, _ = lk.set(tau, f, conf, tau_true, f_true, L_true, phi, *opts)
+        ctx.save_for_backward(tau, f, conf, phi, tau_true, f_true, L_true, assign, norms)
+        ctx.opts, ctx.lk = opts, lk
+        ctx.mark_non_differentiable(status, assign)
+        return (*out.unbind(0), status, assign)
+
+    @staticmethod
+    def backward(ctx, g_total, g_match, g_conf, g_reg, _g_status, _g_assign):
+        tau, f, conf, phi, tau_true, f_true, L_true, assign, norms = ctx.saved_tensors
+        g = ctx.lk.set_bwd(_g_out((g_total, g_match, g_conf, g_reg), norms), tau, f, conf, tau_true, f_true, L_true, phi, assign,
+                           norms, *ctx.opts)
+        g_tau, g_f, g_c, g_phi = (x.to(t.dtype) for x, t in zip(g, (tau, f, conf, phi)))
+        return g_tau, g_f, g_c, g_phi, None, None, None, None, None
+
+
+class SetANMLoss(nn.Module):
+    """A permutation-invariant loss for the head of ``ADMMNet`` (csrc/loss_set.hip): ``BasicANMLoss`` compares slot j with truth j,
+    but the truths of a scene come in draw order, so slot j has no meaning.  Here the Lmax slots of a signal are matched to its
+    n = L_true targets (``tau_true``, ``f_true`` [B, Lt], any Lt <= 64) by the assignment sigma that minimises the loss itself:
+
+        match_b = (1 / max(n, 1)) sum over matched (i, j) of (sx wrap(tau_i - tau_true_j))^2 + (sy wrap(f_i - f_true_j))^2
+        conf_b  = (1 / Lmax) sum_i (conf_i - t_i)^2,    t_i = 1 on a matched slot and 0 elsewhere
+        loss_b  = min_sigma [match_b + w_conf conf_b],  total = mean_b loss_b + lambda_reg mean_b ||phi_b||_2
+
+    so matched slots learn tau, f and conf -> 1, unmatched ones conf -> 0, and ``conf`` comes to say how many targets there are
+    (``ADMMNet.estimate_head``).  ``scale = (sx, sy)``; ``period``: None, or (P_tau, P_f) with 0 / None for an axis that does not
+    wrap.  Takes ``BasicANMLoss``'s call and returns (total, dict) with ``total_loss``, ``match_loss``, ``conf_loss``,
+    ``reg_loss``.  ``last_assign`` ([B, Lmax] int32, the target of each slot or -1) and ``last_status`` (int32 [2]: L_true
+    outside [0, Lt]; signals with a non-finite value, which add nothing and get no gradient) are those of the last call, on the
+    device; ``check_status = True`` reads the status once per call and raises ``ValueError`` on either word."""
+
+    def __init__(self, lambda_reg=1e-4, w_conf=0.1, scale=(1.0, 1.0), period=None):
+        super().__init__()
+        set_options(scale, period, w_conf, lambda_reg)
+        self.lambda_reg, self.w_conf, self.scale, self.period = lambda_reg, w_conf, tuple(scale), period
+        self.route = "hip"
+        self.check_status = True
+        self.last_assign = self.last_status = None
+
+    def forward(self, model_outputs, ground_truth):
+        tau, f, conf, phi = (model_outputs[k] for k in ('tau_est', 'f_est', 'confidences', 'phi_final'))
+        tau_true, f_true, L_true = (ground_truth[k] for k in ('tau_true', 'f_true', 'L_true'))
+        _constant(tau_true=tau_true, f_true=f_true)
+        opts = (float(self.lambda_reg), float(self.w_conf), tuple(float(v) for v in self.scale),
+                None if self.period is None else tuple(self.period))
+        total, match, cf, reg, status, assign = _SetLossFn.apply(tau, f, conf, phi, tau_true, f_true, L_true, opts,
+                                                                 _kernels(self.route))
+        self.last_assign, self.last_status = assign, status
+        if self.check_status:
+            outside, nonfinite = status.tolist()            # the call's one device-to-host read
+            if outside:
+                raise ValueError(f"L_true of {outside} sample(s) lies outside [0, {tau_true.shape[1]}]")
+            if nonfinite:
+                raise ValueError(f"{nonfinite} sample(s) hold a non-finite tau, f, confidence or target")
+        return total, {'total_loss': total, 'match_loss': match, 'conf_loss': cf, 'reg_loss': reg}
 
 
 class PhiAlignmentLoss(nn.Module):

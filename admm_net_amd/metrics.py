@@ -14,7 +14,9 @@ order, so comparing them needs an assignment, and that part was never written.
     minimised: solving without it and gating afterwards gives another, wrong answer (estimates 0.26, 0.33 against targets 0.20,
     0.27 with c = 0.05: the one hit is 0.26 on 0.27, while the untruncated optimum pairs 0.26 with 0.20 and 0.33 with 0.27 and
     gating it leaves nothing).
-``ordered_rmse``   the reference's RMSE, slot j against slot j (``ADMMNet``'s head is trained in truth order).
+``ordered_rmse``   the reference's RMSE, slot j against slot j (``ADMMNet``'s head is trained in truth order under
+                   ``BasicANMLoss``; one trained with ``losses.SetANMLoss`` has no slot order and is scored by
+                   ``ADMMNet.evaluate_head``, an assignment with the count taken from the confidences).
 ``summary``        the one host read: detection probability, false alarms, pooled RMSE and GOSPA of a batch.
 ``order_counts``   scenes whose selected number of targets lies below, at and above the true one, without a host read.
 ``match_host``     the float64 numpy statement of ``match_targets`` for one signal.  The tests hold the kernel to it; it is NOT a

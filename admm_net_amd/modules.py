@@ -18,7 +18,7 @@ O(B D)-sized ones as well, ``"native"`` the H layer's MLP and the head too.
 from __future__ import annotations
 
 import ctypes
-from typing import Optional
+from typing import NamedTuple, Optional
 
 import torch
 import torch.nn as nn
@@ -464,3 +464,47 @@ class ADMMNet(_FusedBase):
             return self.forward_autograd(y, b, sigma)
         phi, head = self._run(y, b, sigma)
         return head[0], head[1], head[2], phi
+
+    def _head_rows(self, y, b, sigma, threshold):
+        """``estimate_head`` on the compute device."""
+        with torch.no_grad():
+            phi, head = self._run(y, b, sigma, to_caller=False)
+            return HeadEstimate(*order_by_confidence(head[0], head[1], head[2], threshold), phi)
+
+    def estimate_head(self, y, b, sigma, threshold=0.5):
+        """The learned head's own estimate, for a head trained with ``losses.SetANMLoss`` (matched slots learn conf -> 1, the
+        others conf -> 0, so the confidences say how many targets there are): the inference forward under ``torch.no_grad()``,
+        then plain tensor operations on the compute device, no host read.
+
+        Returns a ``HeadEstimate`` on ``y.device``: tau, f, conf [B, L] float32 ordered by descending ``conf`` (stable: equal
+        values keep slot order); n_est [B] int32, the number of slots with ``conf >= threshold``, so the first n_est rows are
+        the estimate; phi [B, M*N] complex64."""
+        return HeadEstimate(*(t.to(y.device) for t in self._head_rows(y, b, sigma, threshold)))
+
+    def evaluate_head(self, y, b, sigma, tau_true, f_true, L_true=None, *, cutoff, threshold=0.5, scale=None, period=(1.0, 1.0)):
+        """``estimate_head`` scored against the truth: ``metrics.match_targets`` of its rows with ``n_est`` from the confidences,
+        on the device.  ``cutoff``, ``scale`` (None: one resolution cell per axis, (N, M)) and ``period`` as in ``evaluate``.
+        Returns a ``metrics.MatchResult`` of device tensors."""
+        from . import metrics
+        e = self._head_rows(y, b, sigma, threshold)
+        dev = e.tau.device
+        if scale is None:
+            scale = (float(self.N), float(self.M))
+        return metrics.match_targets((e.tau, e.f), tau_true.to(dev), f_true.to(dev), None if L_true is None else L_true.to(dev),
+                                     n_est=e.n_est, cutoff=cutoff, scale=scale, period=period)
+
+
+class HeadEstimate(NamedTuple):
+    tau: torch.Tensor      # [B, L] float32, by descending confidence
+    f: torch.Tensor        # [B, L] float32
+    conf: torch.Tensor     # [B, L] float32
+    n_est: torch.Tensor    # [B] int32: the slots with conf >= threshold
+    phi: torch.Tensor      # [B, M*N] complex64
+
+
+def order_by_confidence(tau, f, conf, threshold=0.5):
+    """(tau, f, conf [B, L] ordered by descending ``conf``, equal values in slot order; n_est [B] int32 = the number of slots
+    with ``conf >= threshold``).  Tensor operations only: no host read."""
+    order = torch.sort(conf, dim=1, descending=True, stable=True).indices
+    n_est = (conf >= threshold).sum(dim=1).to(torch.int32)
+    return tau.gather(1, order), f.gather(1, order), conf.gather(1, order), n_est

@@ -1063,3 +1063,5 @@ def regional_maxima(Z: torch.Tensor):
 
 # ---- the spectral terms of the phi loss (csrc/loss_spectrum.hip); defined in spectral_ops.py on the helpers above ------------------
 from .spectral_ops import loss_spectrum, loss_spectrum_bwd  # noqa: E402,F401
+# ---- the assignment loss of the head (csrc/loss_set.hip); defined in set_ops.py on the helpers above ------------------------------
+from .set_ops import loss_set, loss_set_bwd  # noqa: E402,F401

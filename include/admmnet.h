@@ -533,6 +533,45 @@ int admmnet_loss_spectrum_bwd_f64(int32_t xbase, int32_t ybase, int32_t oversamp
                                   float spectral_weight, float distribution_weight, float target_weight, int32_t skip,
                                   const void *workspace, int64_t workspace_bytes, void *g_phi, void *stream);
 
+/* The assignment loss of the head (csrc/loss_set.hip, scalar core csrc/set_core.h): a permutation-invariant training loss for
+ * slots (tau, f, conf) against targets that come in no particular order.  One wave per signal, all in float64 from the float
+ * inputs, one row of per-signal values each, added over the batch in a fixed order by one workgroup: no atomics, two runs give
+ * the same bits, and a signal's bits depend on neither B, nor its place, nor its neighbours.
+ *   Inputs   tau, f, conf float [B][Lmax] (they get gradients); tau_true, f_true float [B][Lt]; L_true int64 [B]; phi complex64
+ *            [B][D].  1 <= Lmax, Lt <= 64, B >= 1, D >= 1.
+ *   opts     HOST double[6] = {sx, sy, period_tau, period_f, w_conf, lambda_reg}: scales > 0; a period 0 means the plain
+ *            difference, P > 0 wraps it into [-P/2, P/2) (derivative 1); w_conf >= 0; lambda_reg >= 0; all finite.
+ *   Per signal, n = L_true held to [0, Lt], all Lmax slots live:
+ *       d2_ij = (sx wrap(tau_i - tau_true_j))^2 + (sy wrap(f_i - f_true_j))^2, every product rounded on its own;
+ *       an assignment sigma matches k = min(Lmax, n) distinct slots to distinct targets j < n, t_i = 1 on a matched slot, else 0;
+ *       match_b(sigma) = (1 / max(n, 1)) sum over matched (i, j) of d2_ij
+ *       conf_b(sigma)  = (1 / Lmax) sum_i (conf_i - t_i)^2
+ *       loss_b         = min over sigma of [match_b(sigma) + w_conf conf_b(sigma)]
+ *     -- the minimum of ONE expression, so its gradient is the gradient at the minimiser.  Equivalently loss_b = (w_conf / Lmax)
+ *     sum_i conf_i^2 + min_sigma sum_matched c_ij with c_ij = d2_ij / n + (w_conf / Lmax)(1 - 2 conf_i): a linear assignment with a
+ *     per-slot term, solved by the shortest-augmenting-path search of admmnet_score_match_f64.  n = 0: nothing is matched,
+ *     loss_b = (w_conf / Lmax) sum_i conf_i^2.  n > Lmax: the targets left unmatched cost nothing.  There is no truncation.
+ *   Outputs  out[4] = {total, match, conf, reg}: match = mean_b match_b, conf = mean_b conf_b, reg = lambda_reg mean_b ||phi_b||_2,
+ *            total = match + w_conf conf + reg.  assign int32 [B][Lmax]: the target of slot i, else -1.  norms float [B] =
+ *            ||phi_b||_2.  status[2] = {signals with L_true outside [0, Lt], signals with a non-finite value among tau, f, conf or
+ *            their first n truths}.  A signal of the second kind adds 0 to every sum, gets assign = -1 and zero gradients; one of
+ *            the first kind is evaluated with n held to the range.  `partials`: double scratch of admmnet_loss_set_partials(B)
+ *            entries; after the call it holds the rows [B][6] = loss_b, match_b, conf_b, ||phi_b||, and the two status flags.
+ *   admmnet_loss_set_bwd_f32   g_out: DEVICE float[4], the gradients of out[0 .. 3]; assign and norms as the forward left them.
+ *            With cm = g_out[0] + g_out[1], cc = g_out[0] w_conf + g_out[2], cr = g_out[0] + g_out[3]:
+ *              g_tau_i = cm 2 sx^2 wrap(tau_i - tau_true_j) / (n B) on a matched slot, exactly 0 elsewhere; g_f_i the same with sy, f;
+ *              g_conf_i = cc 2 (conf_i - t_i) / (Lmax B);  g_phi = admmnet_loss_anm_bwd_f32's with cr;  the targets get none.
+ * Both are stream-ordered, allocate nothing and read nothing back.  Sizes out of range, a null pointer or bad options are refused
+ * with ADMMNET_E_ARG before any launch, the outputs untouched. */
+int64_t admmnet_loss_set_partials(int64_t B);
+int admmnet_loss_set_f32(int32_t Lmax, int32_t Lt, int32_t D, int64_t B, const float *tau, const float *f, const float *conf,
+                         const float *tau_true, const float *f_true, const int64_t *L_true, const void *phi, const double *opts,
+                         float *out, int32_t *assign, float *norms, int32_t *status, double *partials, void *stream);
+int admmnet_loss_set_bwd_f32(int32_t Lmax, int32_t Lt, int32_t D, int64_t B, const float *g_out, const float *tau, const float *f,
+                             const float *conf, const float *tau_true, const float *f_true, const int64_t *L_true,
+                             const void *phi, const int32_t *assign, const float *norms, const double *opts, float *g_tau,
+                             float *g_f, float *g_conf, void *g_phi, void *stream);
+
 /* Target estimates scored against ground truth (csrc/score.hip, scalar core csrc/score_core.h): one wave per signal, sums over
  * the batch in a fixed order without atomics (float64 across workgroups), so two runs give the same bits.  B >= 1; `partials` is
  * double scratch of admmnet_score_partials(B) entries.  All tensors are dense with their natural alignment.
