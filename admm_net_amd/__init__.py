@@ -9,5 +9,7 @@ from .modules import ADMMNet, PhiEstADMMNet, PeakSearchLayer, PhiLayer, HLayer, 
 from . import optim  # noqa: F401
 from . import order  # noqa: F401
 from .order import select_targets, select_refined  # noqa: F401
+from . import detect  # noqa: F401
+from .detect import cfar_targets, cfar_alpha, cfar_host  # noqa: F401
 
-__all__ = ["ADMMNet", "PhiEstADMMNet", "Options", "select_targets", "select_refined"]
+__all__ = ["ADMMNet", "PhiEstADMMNet", "Options", "select_targets", "select_refined", "cfar_targets", "cfar_alpha", "cfar_host"]

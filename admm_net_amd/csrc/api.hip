@@ -14,6 +14,7 @@
 #include "set_core.h"
 #include "crb_core.h"
 #include "refine_core.h"
+#include "cfar_core.h"
 
 namespace admmnet {
 
@@ -1460,6 +1461,52 @@ int admmnet_order_f64(int32_t Nb, int32_t Nd, int32_t Le, int64_t B, const void 
     return launch_order(Nb, Nd, Le, B, (const float2 *)y, (const float2 *)b, rows_in, n_cand, n_held, symbols, psk_m, psk_phase,
                         penalty, max_order, perm, n_sel, rss, rows_out, (double2 *)C_out, (float2 *)residual, info, status,
                         (hipStream_t)stream);
+}
+
+// ---- a CFAR detector on the periodogram of a scene (cfar.hip) --------------------------------------------------------------------
+static bool cfar_sizes_ok(int32_t Nb, int32_t Nd, int32_t r) {
+    return Nb >= 1 && Nd >= 1 && (int64_t)Nb * Nd <= synth_max_cells() && r >= 1 && r <= CFAR_MAX_OVERSAMPLE &&
+           (int64_t)Nb * Nd * r * r <= CFAR_MAX_CELLS;
+}
+
+int64_t admmnet_cfar_lds_bytes(int32_t Nb, int32_t Nd, int32_t r) {
+    if (!cfar_sizes_ok(Nb, Nd, r)) return -1;
+    return cfar_lds_bytes(Nb, Nd, r) <= cfar_lds_limit() ? cfar_lds_bytes(Nb, Nd, r) : -1;
+}
+
+// the window fits its axis without a training cell counted twice, and holds at least one cell
+static bool cfar_window_ok(int32_t Nb, int32_t Nd, int32_t guard, int32_t train) {
+    if (guard < 0 || train < 1 || (int64_t)guard + train > CFAR_MAX_REACH) return false;
+    const int W = guard + train;
+    if ((Nb > 1 && 2 * W + 1 > Nb) || (Nd > 1 && 2 * W + 1 > Nd)) return false;
+    return cf_train_count(Nb, Nd, guard, train) >= 1;
+}
+
+int admmnet_cfar_f64(int32_t Nb, int32_t Nd, int32_t r, int32_t Le, int64_t B, const void *y, const void *b, const int32_t *symbols,
+                     int32_t psk_m, double psk_phase, int32_t method, int32_t guard, int32_t train, int32_t rank, double alpha,
+                     const double *noise_var, double *rows, int32_t *counts, double *info, double *map_out, int32_t *status,
+                     void *stream) {
+    const bool sizes = cfar_sizes_ok(Nb, Nd, r) && Le >= 1 && Le <= CRB_MAXL;
+    const bool method_ok = method == CF_KNOWN || method == CF_CA || method == CF_OS;
+    const bool window = sizes && method_ok && (method == CF_KNOWN || cfar_window_ok(Nb, Nd, guard, train));
+    const bool rank_ok = window && (method != CF_OS || (rank >= 1 && rank <= cf_train_count(Nb, Nd, guard, train)));
+    if (!rank_ok || B < 1 || B > 2147483647 || psk_m < 2 || psk_m > REFINE_MAX_M || !sc_finite(psk_phase) || !(alpha > 0.0) ||
+        !sc_finite(alpha) || (method == CF_KNOWN) != (noise_var != nullptr) || !y || !b || !rows || !counts || !info || !status) {
+        set_error("cfar: bad argument (Nb=%d, Nd=%d with Nb * Nd <= %lld, r=%d in 1 .. %d with at most %d map cells, Le=%d in 1 .. %d, "
+                  "B=%lld, psk_m=%d in 2 .. %d, psk_phase=%g, method=%d in 0 .. 2, guard=%d >= 0, train=%d >= 1 with guard + train "
+                  "<= %d and 2 (guard + train) + 1 <= every axis longer than 1, rank=%d in 1 .. N, alpha=%g > 0, noise_var given "
+                  "exactly in method 0, or a null pointer)",
+                  Nb, Nd, (long long)synth_max_cells(), r, CFAR_MAX_OVERSAMPLE, CFAR_MAX_CELLS, Le, CRB_MAXL, (long long)B, psk_m,
+                  REFINE_MAX_M, psk_phase, method, guard, train, CFAR_MAX_REACH, rank, alpha);
+        return ADMMNET_E_ARG;
+    }
+    if (cfar_lds_bytes(Nb, Nd, r) > cfar_lds_limit()) {
+        set_error("cfar: a %d x %d grid oversampled %d times needs %lld bytes of LDS, a workgroup has %lld", Nb, Nd, r,
+                  (long long)cfar_lds_bytes(Nb, Nd, r), (long long)cfar_lds_limit());
+        return ADMMNET_E_ARG;
+    }
+    return launch_cfar(Nb, Nd, r, Le, B, (const float2 *)y, (const float2 *)b, symbols, psk_m, psk_phase, method, guard, train, rank,
+                       alpha, noise_var, rows, counts, info, map_out, status, (hipStream_t)stream);
 }
 
 // ---- AdamW and gradient-norm clipping over a tensor list (optim.hip) ---------------------------------------------------------

@@ -363,6 +363,13 @@ int launch_order(int Nb, int Nd, int Le, int64_t B, const float2 *y, const float
                  int32_t *perm, int32_t *n_sel, double *rss, double *rows_out, double2 *C_out, float2 *residual, double *info,
                  int32_t *status, hipStream_t st);
 
+// cfar.hip (a CFAR detector on the zero-padded periodogram of a scene; 1 <= r <= 8, 1 <= Le <= 16)
+int64_t cfar_lds_bytes(int Nb, int Nd, int r);         // dynamic LDS of one workgroup
+int64_t cfar_lds_limit();
+int launch_cfar(int Nb, int Nd, int r, int Le, int64_t B, const float2 *y, const float2 *b, const int32_t *symbols, int psk_m,
+                double psk_phase, int method, int guard, int train, int rank, double alpha, const double *noise_var, double *rows,
+                int32_t *counts, double *info, double *map_out, int32_t *status, hipStream_t st);
+
 // optim.hip (AdamW and gradient-norm clipping over a tensor list; host arrays of device pointers)
 int64_t optim_blocks(int count, const int64_t *numel);   // blocks of the list = doubles of `partials`; -1: bad count or too many
 int launch_optim_gradnorm(int count, const float *const *grads, const int64_t *numel, float max_norm, double *partials,

@@ -14,7 +14,8 @@ CLI:  python -m admm_net_amd.harness time-net  --layers 5 --runs 1000 --out time
       python -m torch.distributed.run --nproc-per-node N -m admm_net_amd.harness train-step ...   (the step through sharded.ShardedTraining; --batch per rank; rank 0's line gains n_ranks, global_batch)
       python -m admm_net_amd.harness loss-step --batch 256 --targets 3 --dim 100 --steps 200                              (one JSON line)
       python -m admm_net_amd.harness score-step [--steps 50] [--repeats 5] [--host-signals 2048]                          (one JSON line)
-      python -m admm_net_amd.harness evaluate --grid 10x10 --layers 10 [--checkpoint P] --snr 5 15 25 --signals 4096 --targets 3 --cutoff 1.0 [--baseline classical] [--refine given|psk] [--crb] [--order TOP]
+      python -m admm_net_amd.harness cfar-step [--signals 4096] [--grid 16x16] [--oversample 4] [--steps 50]              (one JSON line)
+      python -m admm_net_amd.harness evaluate --grid 10x10 --layers 10 [--checkpoint P] --snr 5 15 25 --signals 4096 --targets 3 --cutoff 1.0 [--baseline classical|periodogram [--cfar ca|os|known] [--pfa P]] [--refine given|psk] [--crb] [--order TOP]
                                                                                                     (one JSON line per SNR and method)
 """
 from __future__ import annotations
@@ -384,6 +385,47 @@ def time_set_loss_step(batch=256, targets=3, dim=100, steps=200, warmup=10, repe
     return out
 
 
+def time_cfar_step(signals=4096, grid=(16, 16), oversample=4, top=16, pfa=1e-4, steps=50, warmup=5, repeats=5, seed=0,
+                   device="cuda:0"):
+    """Device-event time of ``admmnet_cfar_f64`` (both kernels) per method on preallocated buffers: ``signals`` scenes of
+    ``make_scenes_device(targets=(1, 3))`` at 15 dB, ``steps`` back-to-back calls between two events; ``repeats`` such windows
+    give the figure (their median) and its range.  Returns a dict of milliseconds, and the mean counts of each method."""
+    from . import _lib, detect, ops, synth
+    dev = torch.device(device)
+    Nb, Nd = grid
+    y, b, _, truth = synth.make_scenes_device(signals, Nb, Nd, targets=(1, 3), seed=20260104 + seed, snr_range=(15.0, 15.0), device=dev)
+    lib = _lib.load()
+    rows = torch.empty(signals, top, 3, dtype=torch.float64, device=dev)
+    counts = torch.empty(signals, 2, dtype=torch.int32, device=dev)
+    info = torch.empty(signals, 2, dtype=torch.float64, device=dev)
+    status = torch.empty(2, dtype=torch.int32, device=dev)
+    out = {"signals": signals, "grid": list(grid), "oversample": oversample, "top": top, "pfa": pfa, "steps": steps, "repeats": repeats,
+           "lds_bytes": lib.admmnet_cfar_lds_bytes(Nb, Nd, oversample)}
+    for method in ("known", "ca", "os"):
+        noise = truth["noise_var"] if method == "known" else None
+        _, _, m, phase, r, guard, train, rank, alpha = detect._settings(grid, top, oversample, method, pfa, 1, 2, None, (4, math.pi / 4),
+                                                                      noise is not None)
+
+        def window(n):
+            start, stop = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            start.record()
+            for _ in range(n):
+                _lib.check(lib.admmnet_cfar_f64(Nb, Nd, r, top, signals, ops._ptr(y), ops._ptr(b), None, m, phase, detect.METHODS[method],
+                                                guard, train, rank, alpha, ops._ptr(noise), ops._ptr(rows), ops._ptr(counts),
+                                                ops._ptr(info), None, ops._ptr(status), ops._stream(dev)), "admmnet_cfar_f64")
+            stop.record()
+            stop.synchronize()
+            return start.elapsed_time(stop) / n
+
+        window(warmup)
+        times = sorted(window(steps) for _ in range(repeats))
+        out[f"{method}_ms"] = round(times[len(times) // 2], 4)
+        out[f"{method}_range_ms"] = [round(times[0], 4), round(times[-1], 4)]
+        out[f"{method}_mean_n_det"] = round(counts[:, 0].double().mean().item(), 3)
+        out[f"{method}_mean_n_over"] = round(counts[:, 1].double().mean().item(), 3)
+    return out
+
+
 def _score_case(batch, n_est, n_true, seed, dev):
     """Scenes drawn like ``synth.make_batch`` with estimates = shuffled truth + N(0, 0.03) and strays, as device tensors."""
     rng = np.random.default_rng(seed)
@@ -441,8 +483,8 @@ def time_score_step(steps=50, warmup=5, repeats=5, host_signals=2048, seed=0, de
 
 
 def evaluate_snr(grid=(NB, ND), layers=10, checkpoint=None, snrs=(5.0, 15.0, 25.0), signals=4096, targets=3, cutoff=1.0,
-                 baseline=None, seed=0, device="cuda:0", head=False, targets_min=None, min_sep=0.0, order=None, refine=None,
-                 crb=False):
+                 baseline=None, seed=0, device="cuda:0", head=False, cfar=("ca", 1e-4), targets_min=None, min_sep=0.0, order=None,
+                 refine=None, crb=False):
     """Detection and accuracy against the noise level: per SNR one batch of ``signals`` scenes at exactly that SNR
     (``synth.make_batch_device(snr_range=(S, S))``), ``model.evaluate`` and ``metrics.summary`` -- scene, forward, peak search and
     score without a host loop.  ``baseline="classical"`` scores the peaks of the classical solver's phi (the generator's labels)
@@ -465,12 +507,29 @@ def evaluate_snr(grid=(NB, ND), layers=10, checkpoint=None, snrs=(5.0, 15.0, 25.
     ``head=True`` yields, after each SNR's other lines, a line ``method = "head"``: the learned head of ``ADMMNet`` (seed 0, or the
     checkpoint's, which is then an ``ADMMNet``'s; the ``net`` lines take its layers) through ``ADMMNet.estimate_head``, scored
     with ``n_est`` = the number of confidences >= 0.5 -- the head is never given a scene's count -- and, on varied scenes, with
-    ``order_under`` / ``order_exact`` / ``order_over`` from that ``n_est``.  Without it every line and key is as before."""
+    ``order_under`` / ``order_exact`` / ``order_over`` from that ``n_est``.  Without it every line and key is as before.
+    ``baseline="periodogram"`` yields, after each SNR's other lines, a line ``method = "periodogram"``: what an OFDM radar
+    runs on ``(y, b)`` alone -- ``detect.cfar_targets`` with ``cfar = (method, pfa)``, 16 rows, its other defaults -- scored with
+    ``n_est = clamp(n_det, 0, 16)``; the detector is never given a scene's count, and on varied scenes the line gains
+    ``order_under`` / ``order_exact`` / ``order_over`` from ``n_det``.  With ``refine`` a line ``periodogram+refine`` follows
+    (those rows and that ``n_est`` through ``refine_targets``), with ``order`` a line ``periodogram+order`` (the first ``order``
+    CFAR rows through ``order.select_refined`` with ``n_cand = min(n_est, order)``: the selection prunes the sidelobe detections
+    of a strong target).  No labels are generated for it, and every other line and key is that of a run without it.  The method
+    "known" takes ``truth["noise_var"]``, which only the varied scenes have: it RAISES on the fixed-count kind (pass
+    ``targets_min=targets`` for scenes of exactly ``targets`` targets from ``make_scenes_device``)."""
     from . import PhiEstADMMNet, metrics, ops, synth
     from . import order as ordering
     from . import refine as refinement
-    if baseline not in (None, "classical"):
-        raise ValueError(f"baseline must be None or 'classical', got {baseline!r}")
+    if baseline not in (None, "classical", "periodogram"):
+        raise ValueError(f"baseline must be None, 'classical' or 'periodogram', got {baseline!r}")
+    from . import detect
+    try:
+        cfar_method, cfar_pfa = cfar
+        cfar_pfa = float(cfar_pfa)
+    except (TypeError, ValueError):
+        raise ValueError(f"cfar must be a pair (method, pfa), got {cfar!r}") from None
+    if cfar_method not in detect.METHODS or not 0.0 < cfar_pfa < 1.0:
+        raise ValueError(f"cfar must be (one of {sorted(detect.METHODS)}, a rate in (0, 1)), got {cfar!r}")
     if refine is not None and refine not in refinement.MODES:
         raise ValueError(f"refine must be None or one of {sorted(refinement.MODES)}, got {refine!r}")
     if order is not None and (isinstance(order, bool) or int(order) != order or not max(1, targets) <= order <= metrics.MAX_TARGETS):
@@ -480,8 +539,12 @@ def evaluate_snr(grid=(NB, ND), layers=10, checkpoint=None, snrs=(5.0, 15.0, 25.
         raise ValueError(f"targets_min must be None or an int in 1 .. targets, got {targets_min!r}")
     if not (min_sep >= 0.0 and math.isfinite(min_sep)):
         raise ValueError(f"min_sep must be finite and >= 0, got {min_sep!r}")
+    if baseline == "periodogram" and cfar_method == "known" and not varied:
+        raise ValueError("cfar method 'known' takes the scenes' noise_var, which the fixed-count scenes do not have: pass "
+                         "targets_min=targets (or min_sep) to draw them with make_scenes_device")
     dev = torch.device(device)
     M, N = grid
+    classical = baseline == "classical"
     torch.manual_seed(seed)
     model = PhiEstADMMNet(num_layers=layers, M=M, N=N, L=targets)
     head_model = None
@@ -537,14 +600,30 @@ def evaluate_snr(grid=(NB, ND), layers=10, checkpoint=None, snrs=(5.0, 15.0, 25.
                                     scale=(float(N), float(M)), period=(1.0, 1.0))
         return {"snr": snr, "method": method + "+order", **common, **scored(res, truth, snr, sel.n_sel)}
 
+    def periodogram(y, b, truth, snr):
+        det = detect.cfar_targets(y, b, (M, N), method=cfar_method, pfa=cfar_pfa,
+                                  noise_var=truth["noise_var"] if cfar_method == "known" else None)
+        n_est = det.n_est
+        score = lambda rows, n: metrics.match_targets(rows, truth["tau"], truth["f"], truth.get("L_true"), n_est=n, cutoff=cutoff,  # noqa: E731
+                                                      scale=(float(N), float(M)), period=(1.0, 1.0))
+        counted = det.n_det if varied else None
+        yield {"snr": snr, "method": "periodogram", **common, **scored(score(det.rows, n_est), truth, snr, counted)}
+        if refine is not None:
+            fit = refinement.refine_targets(y, b, det.rows, (M, N), n_est=n_est, symbols=refine)
+            yield {"snr": snr, "method": "periodogram+refine", **common, **scored(score(fit.rows, n_est), truth, snr, counted)}
+        if order is not None:
+            top = int(order)
+            sel, _ = ordering.select_refined(y, b, det.rows[:, :top], (M, N), symbols=refine or "given", n_cand=n_est.clamp(max=top))
+            yield {"snr": snr, "method": "periodogram+order", **common, **scored(score(sel.rows_out, sel.n_sel), truth, snr, sel.n_sel)}
+
     for i, snr in enumerate(snrs):
         if varied:
             y, b, sigma, truth = synth.make_scenes_device(signals, M, N, targets=(common["targets_min"], targets), min_sep=min_sep,
                                                           seed=20260104 + seed + 7919 * i, snr_range=(snr, snr), device=dev,
-                                                          labels=baseline is not None)
+                                                          labels=classical)
         else:
             y, b, sigma, truth = synth.make_batch_device(signals, M, N, L=targets, seed=20260104 + seed + 7919 * i, snr_range=(snr, snr),
-                                                         device=dev, labels=baseline is not None)
+                                                         device=dev, labels=classical)
         if refine is None and not varied:
             res = model.evaluate(y, b, sigma, truth["tau"], truth["f"], cutoff=cutoff, top=targets)
         else:                                                                          # evaluate, with the rows kept
@@ -557,7 +636,7 @@ def evaluate_snr(grid=(NB, ND), layers=10, checkpoint=None, snrs=(5.0, 15.0, 25.
             with torch.no_grad():
                 phi, _ = model._run(y, b, sigma, to_caller=False)
             yield ordered("net", phi, y, b, truth, snr)
-        if baseline is not None:
+        if classical:
             opts = {"xstep": 1 / (10 * N), "ystep": 1 / (10 * M), "iter": 3}            # estimate's defaults
             rows, _ = ops.peak_top(truth["phi"], M, N, opts, top=targets, top_n=truth.get("L_true"))
             yield {"snr": snr, "method": "classical", **common, **scored(match(rows, truth), truth, snr)}
@@ -570,6 +649,8 @@ def evaluate_snr(grid=(NB, ND), layers=10, checkpoint=None, snrs=(5.0, 15.0, 25.
             res = metrics.match_targets((e.tau, e.f), truth["tau"], truth["f"], truth.get("L_true"), n_est=e.n_est, cutoff=cutoff,
                                         scale=(float(N), float(M)), period=(1.0, 1.0))
             yield {"snr": snr, "method": "head", **common, **scored(res, truth, snr, e.n_est if varied else None)}
+        if baseline == "periodogram":
+            yield from periodogram(y, b, truth, snr)
 
 
 def _grid(ap, text):
@@ -623,6 +704,11 @@ def main(argv=None):
     e.add_argument("--steps", type=int, default=50)
     e.add_argument("--repeats", type=int, default=5)
     e.add_argument("--host-signals", type=int, default=2048)
+    g = sub.add_parser("cfar-step")
+    g.add_argument("--signals", type=int, default=4096)
+    g.add_argument("--grid", default="16x16", help="MxN")
+    g.add_argument("--oversample", type=int, default=4)
+    g.add_argument("--steps", type=int, default=50)
     f = sub.add_parser("evaluate")
     f.add_argument("--grid", default=f"{NB}x{ND}", help="MxN")
     f.add_argument("--layers", type=int, default=10)
@@ -631,7 +717,10 @@ def main(argv=None):
     f.add_argument("--signals", type=int, default=4096)
     f.add_argument("--targets", type=int, default=3)
     f.add_argument("--cutoff", type=float, default=1.0, help="in resolution cells")
-    f.add_argument("--baseline", choices=("classical",), default=None)
+    f.add_argument("--baseline", choices=("classical", "periodogram"), default=None,
+                   help="periodogram: a CFAR detector on the zero-padded periodogram of (y, b), never given a scene's count")
+    f.add_argument("--cfar", choices=("ca", "os", "known"), default="ca", help="the noise level of --baseline periodogram")
+    f.add_argument("--pfa", type=float, default=1e-4, help="its false-alarm rate per map cell")
     f.add_argument("--refine", choices=("given", "psk"), default=None,
                    help="after each method's line, the same rows fitted to the received signal with these symbols")
     f.add_argument("--crb", action="store_true", help="add the Cramer-Rao bound pooled over each method's hits, and RMSE over it")
@@ -648,11 +737,15 @@ def main(argv=None):
         import json
         print(json.dumps(time_score_step(args.steps, repeats=args.repeats, host_signals=args.host_signals)))
         return
+    if args.cmd == "cfar-step":
+        import json
+        print(json.dumps(time_cfar_step(args.signals, _grid(ap, args.grid), args.oversample, steps=args.steps)))
+        return
     if args.cmd == "evaluate":
         import json
         for line in evaluate_snr(_grid(ap, args.grid), args.layers, args.checkpoint, args.snr, args.signals, args.targets,
                                  args.cutoff, args.baseline, targets_min=args.targets_min, min_sep=args.min_sep,
-                                 refine=args.refine, crb=args.crb, order=args.order, head=args.head):
+                                 refine=args.refine, crb=args.crb, order=args.order, head=args.head, cfar=(args.cfar, args.pfa)):
             print(json.dumps(line), flush=True)
         return
     if args.cmd == "loss-step":

@@ -170,7 +170,9 @@ def select_refined(y, b, rows, grid, *, rounds=2, grow=0, symbols="given", penal
               peak_opts, top=1)``, whose spectrum is the matched filter of the atoms) replaces the LAST row of every scene with
               n_sel < Le, then one refinement and selection follow.
     peak_opts the options of ``peak_top``; None: steps of a tenth of a cell and 3 refinements, ``estimate``'s.
-    refine_kw ``psk``, ``iters``, ``tol`` of ``refine_targets``; ``psk`` goes to the selection too.
+    refine_kw ``psk``, ``iters``, ``tol`` of ``refine_targets``; ``psk`` goes to the selection too.  ``n_cand`` ([B] integers, as in
+              ``select_targets``; what ``detect.CfarResult.n_est`` holds) is taken out of it: only the first n_cand rows of a scene
+              are candidates, in every round -- the rows from n_cand on are absent.
 
     Returns (OrderResult of the last selection, RefineResult of the last refinement or None if there was none).  The result's
     ``perm`` is carried through the rounds: perm[j] is the row of the ``rows`` given here that row j of ``rows_out`` started as,
@@ -186,7 +188,14 @@ def select_refined(y, b, rows, grid, *, rounds=2, grow=0, symbols="given", penal
     if peak_opts is None:
         peak_opts = {"xstep": 1 / (10 * Nd), "ystep": 1 / (10 * Nb), "iter": 3}
     psk = refine_kw.get("psk", (4, math.pi / 4))
-    sel = select_targets(y, b, rows, grid, psk=psk, penalty=penalty)
+    n_cand = refine_kw.pop("n_cand", None)
+    if n_cand is not None:
+        _integers(n_cand, "n_cand")
+        if rows.dim() != 3 or tuple(n_cand.shape) != (rows.shape[0],):
+            raise ValueError(f"n_cand must be [B] beside rows [B, Le, 3], got {tuple(n_cand.shape)} and {tuple(rows.shape)}")
+        beyond = torch.arange(rows.shape[1], device=rows.device)[None, :] >= n_cand.to(rows.device)[:, None]
+        rows = torch.where(beyond[:, :, None], math.nan, rows.to(torch.float64))
+    sel = select_targets(y, b, rows, grid, n_cand=n_cand, psk=psk, penalty=penalty)
     Le = sel.rows_out.shape[1]
     slot = torch.arange(Le, device=sel.n_sel.device)
     fit = None

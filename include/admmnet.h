@@ -726,6 +726,60 @@ int admmnet_order_f64(int32_t Nb, int32_t Nd, int32_t Le, int64_t B, const void 
                       double penalty, int32_t max_order, int32_t *perm, int32_t *n_sel, double *rss, double *rows_out, void *C_out,
                       void *residual, double *info, int32_t *status, void *stream);
 
+/* A CFAR detector on the zero-padded 2-D periodogram of a scene (csrc/cfar.hip, scalar core csrc/cfar_core.h): what an OFDM radar
+ * runs -- strip the symbols, take the periodogram, threshold it at a constant false-alarm rate -- and a detector that is not
+ * handed the number of targets.  One workgroup per scene, one launch; y and b are read once; x, the intermediate image and the map
+ * stay in LDS.  All arithmetic is float64; every sum has a fixed order and there are no atomics, so the bits of a scene depend on
+ * neither B, nor its place in the batch, nor its neighbours.
+ *   Data.    Grid (Nb, Nd), D = Nb Nd, i = i_b Nd + i_d, x_i = y_i conj(s_i) exactly as in admmnet_order_f64: s_i = b_i / |b_i|
+ *            where `symbols` is NULL, else s_i = p_k with k = symbols_i and p_k = exp(j (2 pi k / psk_m + psk_phase)).
+ *   Map.     Oversampling r, an integer 1 .. 8; n_f = r Nb, n_tau = r Nd; f_j = -1/2 + j / n_f, tau_i = i / n_tau;
+ *                P[j][i] = |sum_(i_b, i_d) x[i_b Nd + i_d] exp(-j 2 pi (i_b f_j - i_d tau_i))|^2 / D,
+ *            the matched filter of the atoms a(i) = exp(j 2 pi (i_b f - i_d tau)) of the refinement and the selection, normalised
+ *            so that white noise of variance w per complex sample gives E[P] = w.  It is evaluated separably, over i_b (in index
+ *            order) and then over i_d (in index order).  Every twiddle is exp(-+j 2 pi k / n) with k = (i_b j) mod n_f or
+ *            (i_d i) mod n_tau reduced in integer arithmetic (the -1/2 of f_j is the sign (-1)^i_b), from sincospi of k / n --
+ *            never from a recurrence.
+ *   Window.  In resolution cells, not map cells.  Per axis a with N_a > 1: G_a = guard, W_a = guard + train; on an axis with
+ *            N_a = 1: G_a = W_a = 0.  Offsets Omega = {(p, q): |p| <= W_b, |q| <= W_d} \ {(p, q): |p| <= G_b, |q| <= G_d}, N = |Omega|.
+ *            The training cells of (j, i) are P[(j + p r) mod n_f][(i + q r) mod n_tau]: cells r apart are samples of an orthogonal
+ *            DFT, independent under white noise, which makes the factors below exact.  guard >= 0, train >= 1,
+ *            guard + train <= 8 (so N <= 288: the offsets are a table of a fixed size in LDS; the rank selection counts the
+ *            cells below a pivot, about 2 N ln N reads per cell, and needs no storage), 2 W_a + 1 <= N_a on every axis with N_a > 1 (no training cell is counted twice round the
+ *            torus), N >= 1.  Method 0 has no window: guard, train and rank are not read.
+ *   Level.   Z[j][i] and the factor alpha, by `method`:
+ *            0, known: Z = noise_var of the scene,                              alpha = -ln(pfa);
+ *            1, ca:    Z = the mean of the training cells, added with p ascending and, within p, q ascending, then divided by N,
+ *                                                                                 alpha = N (pfa^(-1/N) - 1);
+ *            2, os:    Z = the `rank`-th smallest training cell, 1 <= rank <= N,  alpha solves prod_(m < rank) (N-m)/(N-m+alpha) = pfa.
+ *            alpha is the caller's (detect.cfar_alpha computes it on the host in float64): the entry takes alpha, not pfa.
+ *   Over.    A cell is over iff P > alpha Z.  It is a detection iff it is over and beats each of its 8 torus neighbours (one map
+ *            cell away, wrapping on both axes): c beats c' iff P_c > P_c', or P_c == P_c' and c < c', with c = j n_tau + i.  A
+ *            neighbour that is the cell itself (an axis of one map cell) is skipped.  Detections are ordered by P descending,
+ *            ties to the smaller c; the first Le (1 .. 16) are rows (tau_i, f_j, P), the rows beyond are NaN.
+ *   States.  0, done;
+ *            3, non-finite: an entry of y or b is not finite, b_i = 0 where `symbols` is NULL, or noise_var is not finite;
+ *            4, outside: a symbol not in 0 .. psk_m - 1, or noise_var <= 0 in method 0.  State 4 is looked for first.
+ *            A scene of state 3 or 4 has NaN rows, a NaN level (and map) and counts 0.
+ *       B >= 1, Nb Nd <= 3406, r^2 Nb Nd <= 65535 and admmnet_cfar_lds_bytes(Nb, Nd, r) != -1 (within the 160 KiB of LDS of one
+ *       workgroup: 16 D + 16 r D + 11 r^2 D + 16 r (Nb + Nd) + 3312 bytes and the 16-byte alignment of each array; 8 x 8 with
+ *       r = 2 takes 9 712 bytes, 16 x 16 with r = 4 takes 70 896, 13 x 262 with r = 1 -- the largest grid -- 154 176; 25 x 24 fits
+ *       with r = 4 and 25 x 25 does not), 2 <= psk_m <= 64, a finite psk_phase, a finite alpha > 0, noise_var non-NULL exactly
+ *       in method 0.  Anything else: ADMMNET_E_ARG before a launch.
+ *       y, b          complex64 [B][D];  symbols int32 [B][D] or NULL;  noise_var double [B] (method 0) or NULL.
+ *       rows          double [B][Le][3] = (tau_i, f_j, P).
+ *       counts        int32 [B][2] = n_det (all detections: it may exceed Le), n_over (the cells over the threshold).
+ *       info          double [B][2] = level (the mean of Z over the map: a thread adds its cells c = t, t + 256, .. in that order,
+ *                     the lanes of a wave are added by a butterfly, the waves in order; in method 0 the given value), state.
+ *       map_out       double [B][n_f][n_tau] or NULL.
+ *       status        int32 [2] counts scenes: [0] non-finite, [1] outside -- added from `info` by one workgroup in a fixed order.
+ *   No host read, no allocation, stream-ordered. */
+int64_t admmnet_cfar_lds_bytes(int32_t Nb, int32_t Nd, int32_t r);   /* -1: bad sizes, or more than a workgroup has */
+int admmnet_cfar_f64(int32_t Nb, int32_t Nd, int32_t r, int32_t Le, int64_t B, const void *y, const void *b, const int32_t *symbols,
+                     int32_t psk_m, double psk_phase, int32_t method, int32_t guard, int32_t train, int32_t rank, double alpha,
+                     const double *noise_var, double *rows, int32_t *counts, double *info, double *map_out, int32_t *status,
+                     void *stream);
+
 /* AdamW and gradient-norm clipping over a LIST of float32 tensors (csrc/optim.hip): what a training loop writes as
  * torch.nn.utils.clip_grad_norm_(params, max_norm) and torch.optim.AdamW(...).step().  `count` tensors, tensor i dense with
  * numel[i] >= 0 elements; grads, params, exp_avg, exp_avg_sq are HOST arrays of `count` DEVICE pointers (as `params` of
