@@ -12,8 +12,10 @@
 //       layout.  bf16 is enough HERE AND ONLY HERE: a2 E^2 is the second-order term, |a2| ||E||^2 <= 1e-4 of the result's scale is
 //       checked per matrix (else: eigen-pipeline), so the 2^-9 relative rounding of the operands moves G by < 4e-7 of its scale.
 //   P3  v_mfma_f32_32x32x16_bf16 on the resident accumulators: the 32 x 32 tiles of the lower triangle of the D x D interior are
-//       dealt to the twelve waves (three per wave at D = 256, consecutive ones: they share a tile row) and stay in registers over all slabs; the border row (index D, the
-//       arrow) of E^2 is accumulated by the vector ALUs from the same slabs.
+//       dealt to the twelve waves (three per wave at D = 256, consecutive ones: they share a tile row) and stay in registers over
+//       all slabs; the border row (index D, the arrow) of E^2 is accumulated by the vector ALUs from the same slabs, thread j
+//       column j, behind a barrier of its own: sixteen 16-byte LDS reads per slab (row D and the thread's own row), a quarter
+//       slab requested ahead of the scalar multiply-adds that use it.
 //   P4  ||E^2||_F -> delta, the quadratic model of f and its checks (spectral.hip), then
 //       G = (a0 - a1 c) I + a1 A + a2 E^2 + sum_k (f(lam_k) - a0 - a1 mu_k) v_k v_k^H  straight from the accumulator layout
 //       (A once more from Z), and ||G - C_z||_F for the Z-layer.
@@ -667,9 +669,16 @@ __global__ __launch_bounds__(64 * W, W == 12 ? 1 : 3) void sp_fused_kernel(int D
         if (tid < n) {
             const unsigned *dre = ETre32 + D * P32, *dim = ETim32 + D * P32;
             const unsigned *jre = ETre32 + tid * P32, *jim = ETim32 + tid * P32;
-#pragma unroll 2
-            for (int kp = 0; kp < 16; ++kp) {
-                const unsigned ur = dre[kp], ui = dim[kp], vr = jre[kp], vi = jim[kp];
+            // 16-byte LDS reads (the 80-byte row pitch keeps them aligned), a quarter slab -- four row pairs of row D and of the
+            // thread's own row -- requested ahead of the quarter whose multiply-adds are running: each of the slab's 64 dwords is
+            // read once, in sixteen reads instead of 64, and only the first quarter's round trip is exposed
+            auto quarter = [&](int q, uint4 &ur, uint4 &ui, uint4 &vr, uint4 &vi) {
+                ur = *reinterpret_cast<const uint4 *>(dre + 4 * q);
+                ui = *reinterpret_cast<const uint4 *>(dim + 4 * q);
+                vr = *reinterpret_cast<const uint4 *>(jre + 4 * q);
+                vi = *reinterpret_cast<const uint4 *>(jim + 4 * q);
+            };
+            auto step = [&](unsigned ur, unsigned ui, unsigned vr, unsigned vi) {   // one row pair kp
                 const float ar0 = sf_bf16_lo(ur), ai0 = sf_bf16_lo(ui), br0 = sf_bf16_lo(vr), bi0 = sf_bf16_lo(vi);
                 const float ar1 = sf_bf16_hi(ur), ai1 = sf_bf16_hi(ui), br1 = sf_bf16_hi(vr), bi1 = sf_bf16_hi(vi);
                 {   // SCALAR fused multiply-adds, spelled out: the compiler packs the plain C expression into v_pk_mul_f32 / v_pk_fma_f32
@@ -677,6 +686,7 @@ __global__ __launch_bounds__(64 * W, W == 12 ? 1 : 3) void sp_fused_kernel(int D
                     // wave of the CU was in its bf16 matrix-core phase (one border element's real part in ~1 matrix of 10^4; first seen
                     // inside a workgroup, cured by the barrier above; back with three workgroups per CU; gone with this form: 0 of 32
                     // comparisons of 16384 matrices against 16 of 32 -- tests/gpu_spectral_determinism2.py)
+                    // (kp ascending, the same eight operations per kp: ob keeps its bits whatever the reads look like)
                     asm volatile("v_fma_f32 %0, %1, %2, %0" : "+v"(ob.x) : "v"(ar0), "v"(br0));
                     asm volatile("v_fma_f32 %0, %1, %2, %0" : "+v"(ob.x) : "v"(ai0), "v"(bi0));
                     asm volatile("v_fma_f32 %0, %1, %2, %0" : "+v"(ob.x) : "v"(ar1), "v"(br1));
@@ -686,6 +696,17 @@ __global__ __launch_bounds__(64 * W, W == 12 ? 1 : 3) void sp_fused_kernel(int D
                     asm volatile("v_fma_f32 %0, %1, %2, %0" : "+v"(ob.y) : "v"(ar1), "v"(bi1));
                     asm volatile("v_fma_f32 %0, -%1, %2, %0" : "+v"(ob.y) : "v"(ai1), "v"(br1));
                 }
+            };
+            uint4 ur[2], ui[2], vr[2], vi[2];
+            quarter(0, ur[0], ui[0], vr[0], vi[0]);
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const int c = q & 1;
+                if (q < 3) quarter(q + 1, ur[c ^ 1], ui[c ^ 1], vr[c ^ 1], vi[c ^ 1]);
+                step(ur[c].x, ui[c].x, vr[c].x, vi[c].x);
+                step(ur[c].y, ui[c].y, vr[c].y, vi[c].y);
+                step(ur[c].z, ui[c].z, vr[c].z, vi[c].z);
+                step(ur[c].w, ui[c].w, vr[c].w, vi[c].w);
             }
         }
         mark(5);
