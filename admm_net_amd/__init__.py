@@ -10,6 +10,7 @@ from . import optim  # noqa: F401
 from . import order  # noqa: F401
 from .order import select_targets, select_refined  # noqa: F401
 from . import detect  # noqa: F401
-from .detect import cfar_targets, cfar_alpha, cfar_host  # noqa: F401
+from .detect import cfar_targets, cfar_alpha, cfar_host, cfar_relax, cfar_relax_host  # noqa: F401
 
-__all__ = ["ADMMNet", "PhiEstADMMNet", "Options", "select_targets", "select_refined", "cfar_targets", "cfar_alpha", "cfar_host"]
+__all__ = ["ADMMNet", "PhiEstADMMNet", "Options", "select_targets", "select_refined", "cfar_targets", "cfar_alpha", "cfar_host", "cfar_relax",
+           "cfar_relax_host"]

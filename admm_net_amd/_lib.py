@@ -131,6 +131,9 @@ SYMBOLS = {
     "admmnet_cfar_lds_bytes": (c_int64, [c_int32, c_int32, c_int32]),
     "admmnet_cfar_f64": (c_int32, [c_int32, c_int32, c_int32, c_int32, c_int64] + [c_void_p] * 3 + [c_int32, c_double] + [c_int32] * 4 +
                                    [c_double] + [c_void_p] * 7),
+    "admmnet_cfar_relax_lds_bytes": (c_int64, [c_int32, c_int32, c_int32]),
+    "admmnet_cfar_relax_f64": (c_int32, [c_int32, c_int32, c_int32, c_int32, c_int64] + [c_void_p] * 3 + [c_int32, c_double] +
+                                         [c_int32] * 4 + [c_double, c_void_p, c_int32, c_int32] + [c_void_p] * 7),
     "admmnet_optim_partials": (c_int64, [c_int32, POINTER(c_int64)]),
     "admmnet_optim_gradnorm_f32": (c_int32, [c_int32, POINTER(c_void_p), POINTER(c_int64), c_float] + [c_void_p] * 5),
     "admmnet_optim_scale_f32": (c_int32, [c_int32, POINTER(c_void_p), POINTER(c_int64), c_void_p, c_void_p]),

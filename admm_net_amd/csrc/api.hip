@@ -15,6 +15,7 @@
 #include "crb_core.h"
 #include "refine_core.h"
 #include "cfar_core.h"
+#include "relax_core.h"
 
 namespace admmnet {
 
@@ -1507,6 +1508,42 @@ int admmnet_cfar_f64(int32_t Nb, int32_t Nd, int32_t r, int32_t Le, int64_t B, c
     }
     return launch_cfar(Nb, Nd, r, Le, B, (const float2 *)y, (const float2 *)b, symbols, psk_m, psk_phase, method, guard, train, rank,
                        alpha, noise_var, rows, counts, info, map_out, status, (hipStream_t)stream);
+}
+
+// ---- successive cancellation with cyclic re-fitting on that periodogram (cfar_relax.hip) --------------------------------------------
+int64_t admmnet_cfar_relax_lds_bytes(int32_t Nb, int32_t Nd, int32_t r) {
+    if (!cfar_sizes_ok(Nb, Nd, r)) return -1;
+    return cfar_relax_lds_bytes(Nb, Nd, r) <= cfar_relax_lds_limit() ? cfar_relax_lds_bytes(Nb, Nd, r) : -1;
+}
+
+int admmnet_cfar_relax_f64(int32_t Nb, int32_t Nd, int32_t r, int32_t Le, int64_t B, const void *y, const void *b,
+                           const int32_t *symbols, int32_t psk_m, double psk_phase, int32_t method, int32_t guard, int32_t train,
+                           int32_t rank, double alpha, const double *noise_var, int32_t iters, int32_t sweeps, double *rows, void *amp,
+                           int32_t *counts, double *info, double *map_out, int32_t *status, void *stream) {
+    const bool sizes = cfar_sizes_ok(Nb, Nd, r) && Le >= 1 && Le <= CRB_MAXL;
+    const bool method_ok = method == CF_KNOWN || method == CF_CA || method == CF_OS;
+    const bool window = sizes && method_ok && (method == CF_KNOWN || cfar_window_ok(Nb, Nd, guard, train));
+    const bool rank_ok = window && (method != CF_OS || (rank >= 1 && rank <= cf_train_count(Nb, Nd, guard, train)));
+    if (!rank_ok || B < 1 || B > 2147483647 || psk_m < 2 || psk_m > REFINE_MAX_M || !sc_finite(psk_phase) || !(alpha > 0.0) ||
+        !sc_finite(alpha) || (method == CF_KNOWN) != (noise_var != nullptr) || iters < 0 || iters > RELAX_MAX_ITERS || sweeps < 0 ||
+        sweeps > RELAX_MAX_SWEEPS || !y || !b || !rows || !amp || !counts || !info || !status) {
+        set_error("cfar_relax: bad argument (Nb=%d, Nd=%d with Nb * Nd <= %lld, r=%d in 1 .. %d with at most %d map cells, Le=%d in "
+                  "1 .. %d, B=%lld, psk_m=%d in 2 .. %d, psk_phase=%g, method=%d in 0 .. 2, guard=%d >= 0, train=%d >= 1 with guard + "
+                  "train <= %d and 2 (guard + train) + 1 <= every axis longer than 1, rank=%d in 1 .. N, alpha=%g > 0, noise_var "
+                  "given exactly in method 0, iters=%d in 0 .. %d, sweeps=%d in 0 .. %d, or a null pointer)",
+                  Nb, Nd, (long long)synth_max_cells(), r, CFAR_MAX_OVERSAMPLE, CFAR_MAX_CELLS, Le, CRB_MAXL, (long long)B, psk_m,
+                  REFINE_MAX_M, psk_phase, method, guard, train, CFAR_MAX_REACH, rank, alpha, iters, RELAX_MAX_ITERS, sweeps,
+                  RELAX_MAX_SWEEPS);
+        return ADMMNET_E_ARG;
+    }
+    if (cfar_relax_lds_bytes(Nb, Nd, r) > cfar_relax_lds_limit()) {
+        set_error("cfar_relax: a %d x %d grid oversampled %d times needs %lld bytes of LDS, a workgroup has %lld", Nb, Nd, r,
+                  (long long)cfar_relax_lds_bytes(Nb, Nd, r), (long long)cfar_relax_lds_limit());
+        return ADMMNET_E_ARG;
+    }
+    return launch_cfar_relax(Nb, Nd, r, Le, B, (const float2 *)y, (const float2 *)b, symbols, psk_m, psk_phase, method, guard, train,
+                             rank, alpha, noise_var, iters, sweeps, rows, (double *)amp, counts, info, map_out, status,
+                             (hipStream_t)stream);
 }
 
 // ---- AdamW and gradient-norm clipping over a tensor list (optim.hip) ---------------------------------------------------------

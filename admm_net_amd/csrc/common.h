@@ -370,6 +370,14 @@ int launch_cfar(int Nb, int Nd, int r, int Le, int64_t B, const float2 *y, const
                 double psk_phase, int method, int guard, int train, int rank, double alpha, const double *noise_var, double *rows,
                 int32_t *counts, double *info, double *map_out, int32_t *status, hipStream_t st);
 
+// cfar_relax.hip (successive cancellation with cyclic re-fitting on that periodogram; 0 <= iters <= 16, 0 <= sweeps <= 8)
+int64_t cfar_relax_lds_bytes(int Nb, int Nd, int r);   // dynamic LDS of one workgroup
+int64_t cfar_relax_lds_limit();
+int launch_cfar_relax(int Nb, int Nd, int r, int Le, int64_t B, const float2 *y, const float2 *b, const int32_t *symbols, int psk_m,
+                      double psk_phase, int method, int guard, int train, int rank, double alpha, const double *noise_var, int iters,
+                      int sweeps, double *rows, double *amp, int32_t *counts, double *info, double *map_out, int32_t *status,
+                      hipStream_t st);
+
 // optim.hip (AdamW and gradient-norm clipping over a tensor list; host arrays of device pointers)
 int64_t optim_blocks(int count, const int64_t *numel);   // blocks of the list = doubles of `partials`; -1: bad count or too many
 int launch_optim_gradnorm(int count, const float *const *grads, const int64_t *numel, float max_norm, double *partials,

@@ -14,8 +14,8 @@ CLI:  python -m admm_net_amd.harness time-net  --layers 5 --runs 1000 --out time
       python -m torch.distributed.run --nproc-per-node N -m admm_net_amd.harness train-step ...   (the step through sharded.ShardedTraining; --batch per rank; rank 0's line gains n_ranks, global_batch)
       python -m admm_net_amd.harness loss-step --batch 256 --targets 3 --dim 100 --steps 200                              (one JSON line)
       python -m admm_net_amd.harness score-step [--steps 50] [--repeats 5] [--host-signals 2048]                          (one JSON line)
-      python -m admm_net_amd.harness cfar-step [--signals 4096] [--grid 16x16] [--oversample 4] [--steps 50]              (one JSON line)
-      python -m admm_net_amd.harness evaluate --grid 10x10 --layers 10 [--checkpoint P] --snr 5 15 25 --signals 4096 --targets 3 --cutoff 1.0 [--baseline classical|periodogram [--cfar ca|os|known] [--pfa P]] [--refine given|psk] [--crb] [--order TOP]
+      python -m admm_net_amd.harness cfar-step [--signals 4096] [--grid 16x16] [--oversample 4] [--steps 50] [--cancel [--sweeps S] [--newton I]]   (one JSON line)
+      python -m admm_net_amd.harness evaluate --grid 10x10 --layers 10 [--checkpoint P] --snr 5 15 25 --signals 4096 --targets 3 --cutoff 1.0 [--baseline classical|periodogram [--cfar ca|os|known] [--pfa P] [--cancel [--sweeps S] [--newton I]]] [--refine given|psk] [--crb] [--order TOP]
                                                                                                     (one JSON line per SNR and method)
 """
 from __future__ import annotations
@@ -386,10 +386,12 @@ def time_set_loss_step(batch=256, targets=3, dim=100, steps=200, warmup=10, repe
 
 
 def time_cfar_step(signals=4096, grid=(16, 16), oversample=4, top=16, pfa=1e-4, steps=50, warmup=5, repeats=5, seed=0,
-                   device="cuda:0"):
+                   device="cuda:0", cancel=None):
     """Device-event time of ``admmnet_cfar_f64`` (both kernels) per method on preallocated buffers: ``signals`` scenes of
     ``make_scenes_device(targets=(1, 3))`` at 15 dB, ``steps`` back-to-back calls between two events; ``repeats`` such windows
-    give the figure (their median) and its range.  Returns a dict of milliseconds, and the mean counts of each method."""
+    give the figure (their median) and its range.  Returns a dict of milliseconds, and the mean counts of each method.
+    ``cancel=(iters, sweeps)`` times ``admmnet_cfar_relax_f64`` with those settings the same way instead, and reports the mean
+    ``n_det``, ``maps`` and ``more`` of each method."""
     from . import _lib, detect, ops, synth
     dev = torch.device(device)
     Nb, Nd = grid
@@ -401,6 +403,12 @@ def time_cfar_step(signals=4096, grid=(16, 16), oversample=4, top=16, pfa=1e-4, 
     status = torch.empty(2, dtype=torch.int32, device=dev)
     out = {"signals": signals, "grid": list(grid), "oversample": oversample, "top": top, "pfa": pfa, "steps": steps, "repeats": repeats,
            "lds_bytes": lib.admmnet_cfar_lds_bytes(Nb, Nd, oversample)}
+    if cancel is not None:
+        iters, sweeps = detect._relax_settings(grid, oversample, *cancel)
+        amp = torch.empty(signals, top, dtype=torch.complex128, device=dev)
+        counts = torch.empty(signals, 3, dtype=torch.int32, device=dev)
+        info = torch.empty(signals, 3, dtype=torch.float64, device=dev)
+        out.update(entry="admmnet_cfar_relax_f64", iters=iters, sweeps=sweeps, lds_bytes=lib.admmnet_cfar_relax_lds_bytes(Nb, Nd, oversample))
     for method in ("known", "ca", "os"):
         noise = truth["noise_var"] if method == "known" else None
         _, _, m, phase, r, guard, train, rank, alpha = detect._settings(grid, top, oversample, method, pfa, 1, 2, None, (4, math.pi / 4),
@@ -410,6 +418,12 @@ def time_cfar_step(signals=4096, grid=(16, 16), oversample=4, top=16, pfa=1e-4, 
             start, stop = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             start.record()
             for _ in range(n):
+                if cancel is not None:
+                    _lib.check(lib.admmnet_cfar_relax_f64(Nb, Nd, r, top, signals, ops._ptr(y), ops._ptr(b), None, m, phase,
+                                                          detect.METHODS[method], guard, train, rank, alpha, ops._ptr(noise), iters, sweeps,
+                                                          ops._ptr(rows), ops._ptr(amp), ops._ptr(counts), ops._ptr(info), None,
+                                                          ops._ptr(status), ops._stream(dev)), "admmnet_cfar_relax_f64")
+                    continue
                 _lib.check(lib.admmnet_cfar_f64(Nb, Nd, r, top, signals, ops._ptr(y), ops._ptr(b), None, m, phase, detect.METHODS[method],
                                                 guard, train, rank, alpha, ops._ptr(noise), ops._ptr(rows), ops._ptr(counts),
                                                 ops._ptr(info), None, ops._ptr(status), ops._stream(dev)), "admmnet_cfar_f64")
@@ -422,6 +436,10 @@ def time_cfar_step(signals=4096, grid=(16, 16), oversample=4, top=16, pfa=1e-4, 
         out[f"{method}_ms"] = round(times[len(times) // 2], 4)
         out[f"{method}_range_ms"] = [round(times[0], 4), round(times[-1], 4)]
         out[f"{method}_mean_n_det"] = round(counts[:, 0].double().mean().item(), 3)
+        if cancel is not None:
+            out[f"{method}_mean_more"] = round(counts[:, 1].double().mean().item(), 4)
+            out[f"{method}_mean_maps"] = round(counts[:, 2].double().mean().item(), 3)
+            continue
         out[f"{method}_mean_n_over"] = round(counts[:, 1].double().mean().item(), 3)
     return out
 
@@ -483,8 +501,8 @@ def time_score_step(steps=50, warmup=5, repeats=5, host_signals=2048, seed=0, de
 
 
 def evaluate_snr(grid=(NB, ND), layers=10, checkpoint=None, snrs=(5.0, 15.0, 25.0), signals=4096, targets=3, cutoff=1.0,
-                 baseline=None, seed=0, device="cuda:0", head=False, cfar=("ca", 1e-4), targets_min=None, min_sep=0.0, order=None,
-                 refine=None, crb=False):
+                 baseline=None, seed=0, device="cuda:0", head=False, cfar=("ca", 1e-4), cancel=None, targets_min=None, min_sep=0.0,
+                 order=None, refine=None, crb=False):
     """Detection and accuracy against the noise level: per SNR one batch of ``signals`` scenes at exactly that SNR
     (``synth.make_batch_device(snr_range=(S, S))``), ``model.evaluate`` and ``metrics.summary`` -- scene, forward, peak search and
     score without a host loop.  ``baseline="classical"`` scores the peaks of the classical solver's phi (the generator's labels)
@@ -516,7 +534,11 @@ def evaluate_snr(grid=(NB, ND), layers=10, checkpoint=None, snrs=(5.0, 15.0, 25.
     CFAR rows through ``order.select_refined`` with ``n_cand = min(n_est, order)``: the selection prunes the sidelobe detections
     of a strong target).  No labels are generated for it, and every other line and key is that of a run without it.  The method
     "known" takes ``truth["noise_var"]``, which only the varied scenes have: it RAISES on the fixed-count kind (pass
-    ``targets_min=targets`` for scenes of exactly ``targets`` targets from ``make_scenes_device``)."""
+    ``targets_min=targets`` for scenes of exactly ``targets`` targets from ``make_scenes_device``).
+    ``cancel=(iters, sweeps)``, with ``baseline="periodogram"`` only, yields after the ``periodogram`` lines a line
+    ``periodogram+relax``: ``detect.cfar_relax`` with the same ``cfar``, 16 rows, that many Newton steps and re-fitting sweeps,
+    scored with ``n_est = n_det`` (and, on varied scenes, ``order_under`` / ``order_exact`` / ``order_over`` from it); with
+    ``refine`` a line ``periodogram+relax+refine`` follows.  Every other line is that of a run without it."""
     from . import PhiEstADMMNet, metrics, ops, synth
     from . import order as ordering
     from . import refine as refinement
@@ -542,6 +564,14 @@ def evaluate_snr(grid=(NB, ND), layers=10, checkpoint=None, snrs=(5.0, 15.0, 25.
     if baseline == "periodogram" and cfar_method == "known" and not varied:
         raise ValueError("cfar method 'known' takes the scenes' noise_var, which the fixed-count scenes do not have: pass "
                          "targets_min=targets (or min_sep) to draw them with make_scenes_device")
+    if cancel is not None:
+        if baseline != "periodogram":
+            raise ValueError("cancel belongs to baseline='periodogram'")
+        try:
+            cancel_iters, cancel_sweeps = cancel
+        except (TypeError, ValueError):
+            raise ValueError(f"cancel must be None or a pair (iters, sweeps), got {cancel!r}") from None
+        cancel_iters, cancel_sweeps = detect._relax_settings(grid, 4, cancel_iters, cancel_sweeps)
     dev = torch.device(device)
     M, N = grid
     classical = baseline == "classical"
@@ -615,6 +645,16 @@ def evaluate_snr(grid=(NB, ND), layers=10, checkpoint=None, snrs=(5.0, 15.0, 25.
             top = int(order)
             sel, _ = ordering.select_refined(y, b, det.rows[:, :top], (M, N), symbols=refine or "given", n_cand=n_est.clamp(max=top))
             yield {"snr": snr, "method": "periodogram+order", **common, **scored(score(sel.rows_out, sel.n_sel), truth, snr, sel.n_sel)}
+        if cancel is not None:
+            det = detect.cfar_relax(y, b, (M, N), method=cfar_method, pfa=cfar_pfa, iters=cancel_iters, sweeps=cancel_sweeps,
+                                    noise_var=truth["noise_var"] if cfar_method == "known" else None)
+            n_est = det.n_est
+            counted = det.n_det if varied else None
+            yield {"snr": snr, "method": "periodogram+relax", **common, **scored(score(det.rows, n_est), truth, snr, counted)}
+            if refine is not None:
+                fit = refinement.refine_targets(y, b, det.rows, (M, N), n_est=n_est, symbols=refine)
+                yield {"snr": snr, "method": "periodogram+relax+refine", **common,
+                       **scored(score(fit.rows, n_est), truth, snr, counted)}
 
     for i, snr in enumerate(snrs):
         if varied:
@@ -710,6 +750,10 @@ def main(argv=None):
     g.add_argument("--oversample", type=int, default=4)
     g.add_argument("--steps", type=int, default=50)
     f = sub.add_parser("evaluate")
+    for q, what in ((g, "time admmnet_cfar_relax_f64 instead"), (f, "with --baseline periodogram: add the periodogram+relax lines")):
+        q.add_argument("--cancel", action="store_true", help=f"successive cancellation with cyclic re-fitting: {what}")
+        q.add_argument("--sweeps", type=int, default=2, help="re-fitting sweeps of --cancel")
+        q.add_argument("--newton", type=int, default=3, metavar="I", help="Newton steps per fit of --cancel")
     f.add_argument("--grid", default=f"{NB}x{ND}", help="MxN")
     f.add_argument("--layers", type=int, default=10)
     f.add_argument("--checkpoint", default=None)
@@ -739,13 +783,17 @@ def main(argv=None):
         return
     if args.cmd == "cfar-step":
         import json
-        print(json.dumps(time_cfar_step(args.signals, _grid(ap, args.grid), args.oversample, steps=args.steps)))
+        extra = {"cancel": (args.newton, args.sweeps)} if args.cancel else {}
+        print(json.dumps(time_cfar_step(args.signals, _grid(ap, args.grid), args.oversample, steps=args.steps, **extra)))
         return
     if args.cmd == "evaluate":
         import json
+        if args.cancel and args.baseline != "periodogram":
+            ap.error("--cancel belongs to --baseline periodogram")
         for line in evaluate_snr(_grid(ap, args.grid), args.layers, args.checkpoint, args.snr, args.signals, args.targets,
                                  args.cutoff, args.baseline, targets_min=args.targets_min, min_sep=args.min_sep,
-                                 refine=args.refine, crb=args.crb, order=args.order, head=args.head, cfar=(args.cfar, args.pfa)):
+                                 refine=args.refine, crb=args.crb, order=args.order, head=args.head, cfar=(args.cfar, args.pfa),
+                                 cancel=(args.newton, args.sweeps) if args.cancel else None):
             print(json.dumps(line), flush=True)
         return
     if args.cmd == "loss-step":

@@ -780,6 +780,52 @@ int admmnet_cfar_f64(int32_t Nb, int32_t Nd, int32_t r, int32_t Le, int64_t B, c
                      const double *noise_var, double *rows, int32_t *counts, double *info, double *map_out, int32_t *status,
                      void *stream);
 
+/* Successive cancellation with cyclic re-fitting on that periodogram (csrc/cfar_relax.hip, scalar core csrc/relax_core.h): the
+ * detector above run round after round on a residual.  A detected target is fitted off the grid, subtracted from the residual and
+ * re-fitted with the others (RELAX), so that it neither sits in another target's training ring nor leaves sidelobes to detect.  One
+ * workgroup per scene, one launch, float64, every sum in a fixed order, no atomics: the bits of a scene depend on neither B, nor its
+ * place in the batch, nor its neighbours.
+ *   Data.    x = y conj(s), the sizes, the window, the level Z, the factor alpha and the states exactly as admmnet_cfar_f64.  The
+ *            residual starts as x.
+ *   Filter.  S(tau, f) = sum_i x_i exp(-j 2 pi (i_b f - i_d tau)) over the residual, F = |S|^2 / D; the atom is
+ *            a(tau, f)_i = exp(+j 2 pi (i_b f - i_d tau)).
+ *   Round k = 0, 1, ..:  P_k is the map of admmnet_cfar_f64 of the residual (round 0's map is that entry's map bit for bit), Z and
+ *            alpha are taken by `method` on P_k, the cells with P_k > alpha Z are over.  No cell over: stop.  k == Le: more = 1,
+ *            stop.  Otherwise the highest over cell (ties to the smaller index c = j n_tau + i; under methods 1 and 2 it need not
+ *            be the highest cell of the map) is fitted from (tau_i, f_j), which gives (tau, f) and c = S(tau, f) / D; c a(tau, f)
+ *            is subtracted from the residual and the target appended.  With two or more targets `sweeps` sweeps follow: for every
+ *            target in detection order, c a is added back, the target fitted from its (tau, f), c recomputed, c a subtracted.
+ *   Fit.     At most `iters` Newton steps on F from (tau0, f0).  The gradient and the Hessian follow from the six sums
+ *            S_w = sum_i x_i w_i exp(..), w = 1, i_b, i_d, i_b^2, i_d^2, i_b i_d, taken in ONE pass over D (a thread adds its entries
+ *            i = t, t + 256, .. in that order, the lanes of a wave are added by a butterfly, the waves in order):
+ *                dF/dtau = -(4 pi / D) Im(conj(S) S_d),                dF/df = (4 pi / D) Im(conj(S) S_b),
+ *                h_tt = (8 pi^2 / D) (|S_d|^2 - Re(conj(S) S_dd)),      h_ff = (8 pi^2 / D) (|S_b|^2 - Re(conj(S) S_bb)),
+ *                h_tf = (8 pi^2 / D) (Re(conj(S) S_bd) - Re(conj(S_d) S_b)).
+ *            A step (tau, f) -= H^-1 grad is taken only where H is negative definite, h_tt < 0 and det H > 0; otherwise the fit
+ *            ends where it is.  On an axis of length 1 that coordinate never moves and the test is h < 0 of the other.  After
+ *            every step the point is clamped to tau0 -+ 1 / (2 n_tau), f0 -+ 1 / (2 n_f): half a MAP cell.  c is S / D of the sums
+ *            at the last point.  iters = 0 leaves the grid point; a new detection then takes S from the map's own sums (the second
+ *            sum of `Map` above over the row of the intermediate image), so its height is the cell of P_k bit for bit.
+ *   States.  Those of admmnet_cfar_f64; a scene of state 3 or 4 has NaN rows, amp, level, resid (and map) and counts 0.
+ *       The arguments of admmnet_cfar_f64 under its conditions, and 0 <= iters <= 16, 0 <= sweeps <= 8,
+ *       admmnet_cfar_relax_lds_bytes(Nb, Nd, r) != -1 (16 D + 16 r D + 9 r^2 D + 16 (r + 1) (Nb + Nd) + 3216 bytes and the 16-byte
+ *       alignment of each array: 8 x 8 with r = 2 takes 9 360 bytes, 16 x 16 with r = 4 takes 63 120, 13 x 262 with r = 1 -- the
+ *       largest grid -- 151 664).  Anything else: ADMMNET_E_ARG before a launch.
+ *       rows          double [B][Le][3] = (tau mod 1 in [0, 1), f wrapped into [-1/2, 1/2), |c|^2 D = F(tau, f)) in detection
+ *                     order, the values after the last sweep; NaN beyond n_det.
+ *       amp           complex128 [B][Le] = c, NaN beyond n_det.
+ *       counts        int32 [B][3] = n_det (0 .. Le), more (1: a cell was over after Le targets), maps (the maps computed).
+ *       info          double [B][3] = level (the mean of Z over the last map, added as `info` of admmnet_cfar_f64; method 0: the
+ *                     given value), resid (the mean of |residual|^2 at the end: a noise estimate), state.
+ *       map_out       double [B][n_f][n_tau] or NULL: the last map, the one the stop was decided on.
+ *       status        int32 [2] as admmnet_cfar_f64.
+ *   No host read, no allocation, stream-ordered. */
+int64_t admmnet_cfar_relax_lds_bytes(int32_t Nb, int32_t Nd, int32_t r);   /* -1: bad sizes, or more than a workgroup has */
+int admmnet_cfar_relax_f64(int32_t Nb, int32_t Nd, int32_t r, int32_t Le, int64_t B, const void *y, const void *b,
+                           const int32_t *symbols, int32_t psk_m, double psk_phase, int32_t method, int32_t guard, int32_t train,
+                           int32_t rank, double alpha, const double *noise_var, int32_t iters, int32_t sweeps, double *rows, void *amp,
+                           int32_t *counts, double *info, double *map_out, int32_t *status, void *stream);
+
 /* AdamW and gradient-norm clipping over a LIST of float32 tensors (csrc/optim.hip): what a training loop writes as
  * torch.nn.utils.clip_grad_norm_(params, max_norm) and torch.optim.AdamW(...).step().  `count` tensors, tensor i dense with
  * numel[i] >= 0 elements; grads, params, exp_avg, exp_avg_sq are HOST arrays of `count` DEVICE pointers (as `params` of
