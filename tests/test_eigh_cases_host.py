@@ -170,3 +170,31 @@ def test_divide_and_conquer_variants(union):
         assert has(union, occ=occ, solver="dc", E=128) and has(union, occ=occ, solver="dc_block", E=256), occ
     # one leaf up to n = 15, two from n = 16
     assert has(union, D=14, solver="dc") and has(union, D=15, solver="dc")
+
+
+# ---- the option sets the at-occupancy test leaves out ---------------------------------------------------------------------------
+def test_sets_left_out_at_occupancy_launch_the_kernels_of_the_set_kept(model):
+    """tests/test_gpu_eigh_occupancy.py runs one of two option sets where csrc/route.h gives both the same kernel list at a size:
+    the same eigen dimension, tridiagonalisation, explicit Q, solver and back-transform of ops.eigh, and the same pn_split,
+    dc_blocks, dc_occ and tr_occ.  Every pair of its table is such a pair, the table leaves out no other, and what is kept is
+    itself run."""
+    import test_gpu_eigh_occupancy as O
+    from test_route_host import read_switches
+
+    def kernels(name, D):
+        env = E.environment(name)
+        (r,), sw = read_routes(model, env, [D]), read_switches(model, env)
+        return tuple(r[k] for k in ("eig_dim", "tridiag", "explicit_q", "dc", "back_v")) + \
+            tuple(sw["ADMMNET_" + k] for k in ("PN_SPLIT", "DC_BLOCKS", "DC_OCC", "TR_OCC"))
+
+    for D in O.SIZES:
+        seen, same = {}, {}
+        for name in O.sets_at(D):
+            k = kernels(name, D)
+            if k in seen:
+                same[(name, D)] = seen[k]
+            seen.setdefault(k, name)
+        assert same == {c: kept for c, kept in O.SAME_KERNELS.items() if c[1] == D}, D
+        for (name, _), kept in same.items():
+            assert D in O.sizes_of(kept), (name, D, kept)
+    assert sorted(O.SIZES) == [128, 129, 175, 176, 193, 256] and O.B_EIGH == 2050 and O.B_EIGH % O.P == 0

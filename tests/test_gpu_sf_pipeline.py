@@ -9,7 +9,8 @@ at particular sizes:
      output against the float64 oracle, with the bounds of tests/test_gpu_glayer_route.py, in the three update modes;
   2. a clamped load that leaks into arithmetic, or a select replaced by a multiplication: NaN instead of zeros above the diagonal
      of Z and of the incoming G changes no bit of any result, and nothing above the diagonal or outside the B matrices is written;
-  3. run-to-run equality at scale (the border row of E^2 shares its slabs with the restructured phases).
+  3. run-to-run equality at scale (the border row of E^2 shares its slabs with the restructured phases), and within each run the
+     same bits for every copy of a matrix: the 2048 are the trace's five repeated, and a result may not depend on the neighbours.
 
 All through ops.glayer_spectral on caller-supplied state.  The inputs are the per-layer states of an oracle forward (float64) of
 B = 5 signals; the seeds (SEEDS: of the weights and of the signals, per size) are chosen so that at every size at least 4 of the
@@ -183,7 +184,8 @@ def test_nothing_outside_the_lower_triangle_is_read_or_written(dev, D, waves, mo
 @pytest.mark.parametrize("D", [256, 100])
 def test_three_runs_give_the_same_bits_at_scale(dev, D):
     """2048 matrices (the five of the trace, repeated), the update folded in (mode 1), the forward's own shape: 12 waves at
-    D = 256, 4 at D = 100 with three workgroups per CU."""
+    D = 256, 4 at D = 100 with three workgroups per CU.  Within each run item j, a copy of item j - 5, has its bits in Z, G, rn
+    and flag."""
     NB = 2048
     x = _inputs(D, 1)
     Nb, Nd = GRIDS[D]
@@ -200,6 +202,12 @@ def test_three_runs_give_the_same_bits_at_scale(dev, D):
         flag, st = ops.glayer_spectral(m, x["k"], phi, h, Z, G, rn, 1, alpha, phi_p, h_p)
         torch.cuda.synchronize()
         out = tuple(torch.view_as_real(t).view(torch.int32) if t.is_complex() else t.view(torch.int32) for t in (Z, G, rn, flag))
+        # within the run: item j holds the problem of item j - B, so it owes the same bits whatever ran beside it (compared
+        # directly, as words: NB is no multiple of B)
+        for t, name in zip(out, ("Z", "G", "rn", "flag")):
+            ne = t[B:] != t[:-B]
+            assert not bool(ne.any()), (name, "differs between copies of one matrix", int(ne.sum()),
+                                        "first at item %d" % (B + int(ne.reshape(NB - B, -1).any(1).to(torch.uint8).argmax())))
         if first is None:
             first = out
             assert int((flag == 0).sum()) >= NB // 2
