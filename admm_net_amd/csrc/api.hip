@@ -1409,6 +1409,16 @@ static bool refine_sizes_ok(int32_t Nb, int32_t Nd, int32_t Le) {
     return Le >= 1 && Le <= CRB_MAXL && Nb >= 1 && Nd >= 1 && (int64_t)Nb * Nd <= synth_max_cells();
 }
 
+// the scene kernels (scene_wg.h) keep a scene in the LDS of its workgroup: one that does not fit is refused, `before third after`
+// saying which third size goes with the grid
+static int scene_lds_ok(const char *what, int32_t Nb, int32_t Nd, const char *before, int32_t third, const char *after, int64_t need,
+                        int64_t limit) {
+    if (need <= limit) return ADMMNET_OK;
+    set_error("%s: a %d x %d grid %s%d%s needs %lld bytes of LDS, a workgroup has %lld", what, Nb, Nd, before, third, after,
+              (long long)need, (long long)limit);
+    return ADMMNET_E_ARG;
+}
+
 int64_t admmnet_refine_lds_bytes(int32_t Nb, int32_t Nd, int32_t Le) {
     return refine_sizes_ok(Nb, Nd, Le) ? refine_lds_bytes(Nb, Nd, Le) : -1;
 }
@@ -1425,11 +1435,7 @@ int admmnet_refine_f64(int32_t Nb, int32_t Nd, int32_t Le, int64_t B, const void
                   REFINE_MAX_ITERS, tol);
         return ADMMNET_E_ARG;
     }
-    if (refine_lds_bytes(Nb, Nd, Le) > refine_lds_limit()) {
-        set_error("refine: a %d x %d grid with Le=%d needs %lld bytes of LDS, a workgroup has %lld", Nb, Nd, Le,
-                  (long long)refine_lds_bytes(Nb, Nd, Le), (long long)refine_lds_limit());
-        return ADMMNET_E_ARG;
-    }
+    if (int rc = scene_lds_ok("refine", Nb, Nd, "with Le=", Le, "", refine_lds_bytes(Nb, Nd, Le), refine_lds_limit())) return rc;
     return launch_refine(Nb, Nd, Le, B, (const float2 *)y, (const float2 *)b, rows_in, n_est, mode, psk_m, psk_phase, iters, tol,
                          rows_out, (double2 *)C_out, info, symbols_out, status, (hipStream_t)stream);
 }
@@ -1454,11 +1460,7 @@ int admmnet_order_f64(int32_t Nb, int32_t Nd, int32_t Le, int64_t B, const void 
                   max_order);
         return ADMMNET_E_ARG;
     }
-    if (order_lds_bytes(Nb, Nd, Le) > order_lds_limit()) {
-        set_error("order: a %d x %d grid with Le=%d needs %lld bytes of LDS, a workgroup has %lld", Nb, Nd, Le,
-                  (long long)order_lds_bytes(Nb, Nd, Le), (long long)order_lds_limit());
-        return ADMMNET_E_ARG;
-    }
+    if (int rc = scene_lds_ok("order", Nb, Nd, "with Le=", Le, "", order_lds_bytes(Nb, Nd, Le), order_lds_limit())) return rc;
     return launch_order(Nb, Nd, Le, B, (const float2 *)y, (const float2 *)b, rows_in, n_cand, n_held, symbols, psk_m, psk_phase,
                         penalty, max_order, perm, n_sel, rss, rows_out, (double2 *)C_out, (float2 *)residual, info, status,
                         (hipStream_t)stream);
@@ -1483,29 +1485,36 @@ static bool cfar_window_ok(int32_t Nb, int32_t Nd, int32_t guard, int32_t train)
     return cf_train_count(Nb, Nd, guard, train) >= 1;
 }
 
-int admmnet_cfar_f64(int32_t Nb, int32_t Nd, int32_t r, int32_t Le, int64_t B, const void *y, const void *b, const int32_t *symbols,
-                     int32_t psk_m, double psk_phase, int32_t method, int32_t guard, int32_t train, int32_t rank, double alpha,
-                     const double *noise_var, double *rows, int32_t *counts, double *info, double *map_out, int32_t *status,
-                     void *stream) {
+// what admmnet_cfar_f64 and admmnet_cfar_relax_f64 ask of the arguments they share.  `rest_ok` and `rest` are the checks the entry
+// adds (its own values, its pointers) and the text of those values
+static int cfar_args_ok(const char *what, int32_t Nb, int32_t Nd, int32_t r, int32_t Le, int64_t B, int32_t psk_m, double psk_phase,
+                        int32_t method, int32_t guard, int32_t train, int32_t rank, double alpha, const double *noise_var,
+                        bool rest_ok, const char *rest) {
     const bool sizes = cfar_sizes_ok(Nb, Nd, r) && Le >= 1 && Le <= CRB_MAXL;
     const bool method_ok = method == CF_KNOWN || method == CF_CA || method == CF_OS;
     const bool window = sizes && method_ok && (method == CF_KNOWN || cfar_window_ok(Nb, Nd, guard, train));
     const bool rank_ok = window && (method != CF_OS || (rank >= 1 && rank <= cf_train_count(Nb, Nd, guard, train)));
     if (!rank_ok || B < 1 || B > 2147483647 || psk_m < 2 || psk_m > REFINE_MAX_M || !sc_finite(psk_phase) || !(alpha > 0.0) ||
-        !sc_finite(alpha) || (method == CF_KNOWN) != (noise_var != nullptr) || !y || !b || !rows || !counts || !info || !status) {
-        set_error("cfar: bad argument (Nb=%d, Nd=%d with Nb * Nd <= %lld, r=%d in 1 .. %d with at most %d map cells, Le=%d in 1 .. %d, "
+        !sc_finite(alpha) || (method == CF_KNOWN) != (noise_var != nullptr) || !rest_ok) {
+        set_error("%s: bad argument (Nb=%d, Nd=%d with Nb * Nd <= %lld, r=%d in 1 .. %d with at most %d map cells, Le=%d in 1 .. %d, "
                   "B=%lld, psk_m=%d in 2 .. %d, psk_phase=%g, method=%d in 0 .. 2, guard=%d >= 0, train=%d >= 1 with guard + train "
                   "<= %d and 2 (guard + train) + 1 <= every axis longer than 1, rank=%d in 1 .. N, alpha=%g > 0, noise_var given "
-                  "exactly in method 0, or a null pointer)",
-                  Nb, Nd, (long long)synth_max_cells(), r, CFAR_MAX_OVERSAMPLE, CFAR_MAX_CELLS, Le, CRB_MAXL, (long long)B, psk_m,
-                  REFINE_MAX_M, psk_phase, method, guard, train, CFAR_MAX_REACH, rank, alpha);
+                  "exactly in method 0, %sor a null pointer)",
+                  what, Nb, Nd, (long long)synth_max_cells(), r, CFAR_MAX_OVERSAMPLE, CFAR_MAX_CELLS, Le, CRB_MAXL, (long long)B, psk_m,
+                  REFINE_MAX_M, psk_phase, method, guard, train, CFAR_MAX_REACH, rank, alpha, rest);
         return ADMMNET_E_ARG;
     }
-    if (cfar_lds_bytes(Nb, Nd, r) > cfar_lds_limit()) {
-        set_error("cfar: a %d x %d grid oversampled %d times needs %lld bytes of LDS, a workgroup has %lld", Nb, Nd, r,
-                  (long long)cfar_lds_bytes(Nb, Nd, r), (long long)cfar_lds_limit());
-        return ADMMNET_E_ARG;
-    }
+    return ADMMNET_OK;
+}
+
+int admmnet_cfar_f64(int32_t Nb, int32_t Nd, int32_t r, int32_t Le, int64_t B, const void *y, const void *b, const int32_t *symbols,
+                     int32_t psk_m, double psk_phase, int32_t method, int32_t guard, int32_t train, int32_t rank, double alpha,
+                     const double *noise_var, double *rows, int32_t *counts, double *info, double *map_out, int32_t *status,
+                     void *stream) {
+    if (int rc = cfar_args_ok("cfar", Nb, Nd, r, Le, B, psk_m, psk_phase, method, guard, train, rank, alpha, noise_var,
+                              y && b && rows && counts && info && status, ""))
+        return rc;
+    if (int rc = scene_lds_ok("cfar", Nb, Nd, "oversampled ", r, " times", cfar_lds_bytes(Nb, Nd, r), cfar_lds_limit())) return rc;
     return launch_cfar(Nb, Nd, r, Le, B, (const float2 *)y, (const float2 *)b, symbols, psk_m, psk_phase, method, guard, train, rank,
                        alpha, noise_var, rows, counts, info, map_out, status, (hipStream_t)stream);
 }
@@ -1520,27 +1529,15 @@ int admmnet_cfar_relax_f64(int32_t Nb, int32_t Nd, int32_t r, int32_t Le, int64_
                            const int32_t *symbols, int32_t psk_m, double psk_phase, int32_t method, int32_t guard, int32_t train,
                            int32_t rank, double alpha, const double *noise_var, int32_t iters, int32_t sweeps, double *rows, void *amp,
                            int32_t *counts, double *info, double *map_out, int32_t *status, void *stream) {
-    const bool sizes = cfar_sizes_ok(Nb, Nd, r) && Le >= 1 && Le <= CRB_MAXL;
-    const bool method_ok = method == CF_KNOWN || method == CF_CA || method == CF_OS;
-    const bool window = sizes && method_ok && (method == CF_KNOWN || cfar_window_ok(Nb, Nd, guard, train));
-    const bool rank_ok = window && (method != CF_OS || (rank >= 1 && rank <= cf_train_count(Nb, Nd, guard, train)));
-    if (!rank_ok || B < 1 || B > 2147483647 || psk_m < 2 || psk_m > REFINE_MAX_M || !sc_finite(psk_phase) || !(alpha > 0.0) ||
-        !sc_finite(alpha) || (method == CF_KNOWN) != (noise_var != nullptr) || iters < 0 || iters > RELAX_MAX_ITERS || sweeps < 0 ||
-        sweeps > RELAX_MAX_SWEEPS || !y || !b || !rows || !amp || !counts || !info || !status) {
-        set_error("cfar_relax: bad argument (Nb=%d, Nd=%d with Nb * Nd <= %lld, r=%d in 1 .. %d with at most %d map cells, Le=%d in "
-                  "1 .. %d, B=%lld, psk_m=%d in 2 .. %d, psk_phase=%g, method=%d in 0 .. 2, guard=%d >= 0, train=%d >= 1 with guard + "
-                  "train <= %d and 2 (guard + train) + 1 <= every axis longer than 1, rank=%d in 1 .. N, alpha=%g > 0, noise_var "
-                  "given exactly in method 0, iters=%d in 0 .. %d, sweeps=%d in 0 .. %d, or a null pointer)",
-                  Nb, Nd, (long long)synth_max_cells(), r, CFAR_MAX_OVERSAMPLE, CFAR_MAX_CELLS, Le, CRB_MAXL, (long long)B, psk_m,
-                  REFINE_MAX_M, psk_phase, method, guard, train, CFAR_MAX_REACH, rank, alpha, iters, RELAX_MAX_ITERS, sweeps,
-                  RELAX_MAX_SWEEPS);
-        return ADMMNET_E_ARG;
-    }
-    if (cfar_relax_lds_bytes(Nb, Nd, r) > cfar_relax_lds_limit()) {
-        set_error("cfar_relax: a %d x %d grid oversampled %d times needs %lld bytes of LDS, a workgroup has %lld", Nb, Nd, r,
-                  (long long)cfar_relax_lds_bytes(Nb, Nd, r), (long long)cfar_relax_lds_limit());
-        return ADMMNET_E_ARG;
-    }
+    char rest[96];
+    snprintf(rest, sizeof(rest), "iters=%d in 0 .. %d, sweeps=%d in 0 .. %d, ", iters, RELAX_MAX_ITERS, sweeps, RELAX_MAX_SWEEPS);
+    const bool rest_ok = iters >= 0 && iters <= RELAX_MAX_ITERS && sweeps >= 0 && sweeps <= RELAX_MAX_SWEEPS && y && b && rows && amp &&
+                         counts && info && status;
+    if (int rc = cfar_args_ok("cfar_relax", Nb, Nd, r, Le, B, psk_m, psk_phase, method, guard, train, rank, alpha, noise_var, rest_ok,
+                              rest))
+        return rc;
+    if (int rc = scene_lds_ok("cfar_relax", Nb, Nd, "oversampled ", r, " times", cfar_relax_lds_bytes(Nb, Nd, r), cfar_relax_lds_limit()))
+        return rc;
     return launch_cfar_relax(Nb, Nd, r, Le, B, (const float2 *)y, (const float2 *)b, symbols, psk_m, psk_phase, method, guard, train,
                              rank, alpha, noise_var, iters, sweeps, rows, (double *)amp, counts, info, map_out, status,
                              (hipStream_t)stream);

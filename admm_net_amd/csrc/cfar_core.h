@@ -21,6 +21,7 @@ namespace admmnet {
 
 constexpr int CFAR_THREADS = REFINE_THREADS;
 constexpr int CFAR_INFO = 2;               // level, state
+constexpr int CFAR_INFO_STATE = 1;         // the column of the state
 constexpr int CFAR_COUNTS = 2;             // n_det, n_over
 constexpr int CFAR_STATUS = 2;             // scenes non-finite, scenes outside
 constexpr int CFAR_MAX_OVERSAMPLE = 8;

@@ -2,80 +2,43 @@
 // is with admmnet_order_f64 in include/admmnet.h, the float64 host statement is order.select_host).
 //
 // One scene per workgroup of ORDER_THREADS threads, one launch for the batch.  order_core.h has the scene loop, written over the
-// two ways a workgroup shares a loop (refine.hip's, repeated below as OrderPar): items dealt to the threads with a barrier behind
-// them, and a sum in a fixed order -- a thread adds its items in index order, a butterfly adds the lanes of a wave, the waves are
-// added in wave order.  No atomics: a scene's bits depend on neither B, nor its place, nor its neighbours.  y and b are read from
-// HBM once; x, the twiddle tables of the rows, the Gram matrix and the Cholesky factor stay in LDS (order_layout).  The batch
-// counts of `status` are added from the state column of `info` by one workgroup in a second, tiny launch.
+// ways a workgroup shares a loop (scene_wg.h's ScenePar): items dealt to the threads with a barrier behind them, and a sum in a
+// fixed order.  No atomics: a scene's bits depend on neither B, nor its place, nor its neighbours.  y and b are read from HBM
+// once; x, the twiddle tables of the rows, the Gram matrix and the Cholesky factor stay in LDS (order_carve).  The batch counts of
+// `status` are added from the state column of `info` by scene_wg.h's second, tiny launch.
 #include "common.h"
-#include "batch_sums.h"
 #include "order_core.h"
+#include "scene_wg.h"
 
 namespace admmnet {
 
-constexpr int64_t ORDER_LDS_LIMIT = 160 * 1024;
-constexpr int ORDER_WAVES = ORDER_THREADS / 64;
 static_assert(CRB_MAXL * (CRB_MAXL + 1) / 2 <= ORDER_THREADS, "one thread per pair of rows");
 static_assert(CRB_MAXL <= 32, "the rows taken are kept in a 32-bit mask");
 
-struct OrderPar {
-    double *red;   // [ORDER_WAVES]
+using OrderPar = ScenePar<ORDER_THREADS>;
 
-    template <class F>
-    __device__ __forceinline__ void each(int count, F fn) {
-        for (int item = threadIdx.x; item < count; item += ORDER_THREADS) fn(item);
-        __syncthreads();
-    }
-
-    template <class F>
-    __device__ __forceinline__ double sum(int count, F fn) {
-        double v = 0.0;
-        for (int item = threadIdx.x; item < count; item += ORDER_THREADS) v += fn(item);
-        v = sc_wave_sum(v);
-        if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-        __syncthreads();
-        double total = red[0];
-#pragma unroll
-        for (int w = 1; w < ORDER_WAVES; ++w) total += red[w];
-        __syncthreads();
-        return total;
-    }
-};
-
-// the dynamic LDS of a scene: byte offsets of the arrays of OrderMem, each 16-byte aligned
-struct OrderLayout {
-    size_t x, pt, tab, rs, G, F, c, d, w, C, tau, f, rss, idx, pick, perm, meta, red, total;
-};
-
-static __host__ __device__ OrderLayout order_layout(int Nb, int Nd, int Le) {
+// the dynamic LDS of a scene: the arrays of OrderMem, then the scratch of the sums
+static __host__ __device__ void order_carve(LdsCarver &c, int Nb, int Nd, int Le, OrderMem &m, OrderPar &par) {
     const size_t D = (size_t)Nb * (size_t)Nd, L = (size_t)Le;
-    OrderLayout o;
-    size_t at = 0;
-    auto take = [&](size_t bytes) {
-        const size_t here = at;
-        at += (bytes + 15) & ~(size_t)15;
-        return here;
-    };
-    o.x = take(D * sizeof(RfC));
-    o.pt = take(REFINE_MAX_M * sizeof(RfC));
-    o.tab = take((size_t)od_tab_count(Nb, Nd, Le) * sizeof(RfC));
-    o.rs = take(L * (size_t)Nb * sizeof(RfC));
-    o.G = take(L * L * sizeof(RfC));
-    o.F = take(L * L * sizeof(RfC));
-    o.c = take((L + 1) * L * sizeof(RfC));
-    o.d = take((L + 1) * L * sizeof(double));
-    o.w = take(L * sizeof(RfC));
-    o.C = take(L * sizeof(RfC));
-    o.tau = take(L * sizeof(double));
-    o.f = take(L * sizeof(double));
-    o.rss = take((L + 1) * sizeof(double));
-    o.idx = take(L * sizeof(int));
-    o.pick = take(L * sizeof(int));
-    o.perm = take(L * sizeof(int));
-    o.meta = take(OD_META * sizeof(int));
-    o.red = take(ORDER_WAVES * sizeof(double));
-    o.total = at;
-    return o;
+    m.x = c.take<RfC>(D);
+    m.pt = c.take<RfC>(REFINE_MAX_M);
+    m.tab = c.take<RfC>((size_t)od_tab_count(Nb, Nd, Le));
+    m.rs = c.take<RfC>(L * (size_t)Nb);
+    m.G = c.take<RfC>(L * L);
+    m.F = c.take<RfC>(L * L);
+    m.c = c.take<RfC>((L + 1) * L);
+    m.d = c.take<double>((L + 1) * L);
+    m.w = c.take<RfC>(L);
+    m.C = c.take<RfC>(L);
+    m.tau = c.take<double>(L);
+    m.f = c.take<double>(L);
+    m.rss = c.take<double>(L + 1);
+    m.idx = c.take<int>(L);
+    m.pick = c.take<int>(L);
+    m.perm = c.take<int>(L);
+    m.meta = c.take<int>(OD_META);
+    par.red = c.take<double>(OrderPar::WAVES);
+    par.arg = nullptr;
 }
 
 __global__ __launch_bounds__(ORDER_THREADS) void order_kernel(OrderArgs a, const float2 *__restrict__ y, const float2 *__restrict__ b,
@@ -86,27 +49,10 @@ __global__ __launch_bounds__(ORDER_THREADS) void order_kernel(OrderArgs a, const
                                                               double2 *__restrict__ C_out, float2 *__restrict__ residual,
                                                               double *__restrict__ info) {
     extern __shared__ __attribute__((aligned(16))) char order_lds[];
-    const OrderLayout o = order_layout(a.Nb, a.Nd, a.Le);
-    char *p = order_lds;
+    LdsCarver c{order_lds};
     OrderMem m;
-    m.x = reinterpret_cast<RfC *>(p + o.x);
-    m.pt = reinterpret_cast<RfC *>(p + o.pt);
-    m.tab = reinterpret_cast<RfC *>(p + o.tab);
-    m.rs = reinterpret_cast<RfC *>(p + o.rs);
-    m.G = reinterpret_cast<RfC *>(p + o.G);
-    m.F = reinterpret_cast<RfC *>(p + o.F);
-    m.c = reinterpret_cast<RfC *>(p + o.c);
-    m.d = reinterpret_cast<double *>(p + o.d);
-    m.w = reinterpret_cast<RfC *>(p + o.w);
-    m.C = reinterpret_cast<RfC *>(p + o.C);
-    m.tau = reinterpret_cast<double *>(p + o.tau);
-    m.f = reinterpret_cast<double *>(p + o.f);
-    m.rss = reinterpret_cast<double *>(p + o.rss);
-    m.idx = reinterpret_cast<int *>(p + o.idx);
-    m.pick = reinterpret_cast<int *>(p + o.pick);
-    m.perm = reinterpret_cast<int *>(p + o.perm);
-    m.meta = reinterpret_cast<int *>(p + o.meta);
-    OrderPar par = {reinterpret_cast<double *>(p + o.red)};
+    OrderPar par;
+    order_carve(c, a.Nb, a.Nd, a.Le, m, par);
     const int64_t sig = blockIdx.x, D = (int64_t)a.Nb * a.Nd;
     order_scene(par, a, m, reinterpret_cast<const float *>(y + sig * D), reinterpret_cast<const float *>(b + sig * D),
                 rows_in + sig * a.Le * 3, n_cand ? n_cand + sig : nullptr, n_held ? n_held + sig : nullptr,
@@ -115,44 +61,24 @@ __global__ __launch_bounds__(ORDER_THREADS) void order_kernel(OrderArgs a, const
                 reinterpret_cast<float *>(residual + sig * D), info + sig * ORDER_INFO);
 }
 
-// status[c] = the scenes in state c's slot; the counts are whole numbers, exact in float64 in any order
-__global__ __launch_bounds__(SC_FIN_THREADS) void order_finish_kernel(int64_t B, const double *__restrict__ info,
-                                                                      int32_t *__restrict__ status) {
-    __shared__ double sh[SC_FIN_THREADS];
-    constexpr int slot_state[ORDER_STATUS] = {OD_NONFINITE, OD_OUTSIDE};
-    for (int c = 0; c < ORDER_STATUS; ++c) {
-        double n = 0.0;
-        for (int64_t r = threadIdx.x; r < B; r += SC_FIN_THREADS)
-            n += info[r * ORDER_INFO + 3] == (double)slot_state[c] ? 1.0 : 0.0;
-        sh[threadIdx.x] = n;
-        __syncthreads();
-        for (int o = SC_FIN_THREADS >> 1; o > 0; o >>= 1) {
-            if ((int)threadIdx.x < o) sh[threadIdx.x] += sh[threadIdx.x + o];
-            __syncthreads();
-        }
-        if (threadIdx.x == 0) status[c] = sc_count(sh[0]);
-        __syncthreads();
-    }
+int64_t order_lds_bytes(int Nb, int Nd, int Le) {
+    LdsCarver c{nullptr};
+    OrderMem m;
+    OrderPar par;
+    order_carve(c, Nb, Nd, Le, m, par);
+    return (int64_t)c.at;
 }
-
-int64_t order_lds_bytes(int Nb, int Nd, int Le) { return (int64_t)order_layout(Nb, Nd, Le).total; }
-int64_t order_lds_limit() { return ORDER_LDS_LIMIT; }
+int64_t order_lds_limit() { return SCENE_LDS_LIMIT; }
 
 int launch_order(int Nb, int Nd, int Le, int64_t B, const float2 *y, const float2 *b, const double *rows_in, const int32_t *n_cand,
                  const int32_t *n_held, const int32_t *symbols, int psk_m, double psk_phase, double penalty, int max_order,
                  int32_t *perm, int32_t *n_sel, double *rss, double *rows_out, double2 *C_out, float2 *residual, double *info,
                  int32_t *status, hipStream_t st) {
-    const size_t lds = order_layout(Nb, Nd, Le).total;
-    if (lds > 64 * 1024)
-        ADMM_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(order_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                     (int)lds));
     const OrderArgs a = {Nb, Nd, Le, psk_m, psk_phase, penalty, max_order};
-    hipLaunchKernelGGL(order_kernel, dim3((unsigned)B), dim3(ORDER_THREADS), lds, st, a, y, b, rows_in, n_cand, n_held, symbols, perm,
-                       n_sel, rss, rows_out, C_out, residual, info);
-    ADMM_HIP(hipGetLastError());
-    hipLaunchKernelGGL(order_finish_kernel, dim3(1), dim3(SC_FIN_THREADS), 0, st, B, info, status);
-    ADMM_HIP(hipGetLastError());
-    return ADMMNET_OK;
+    const SceneStates<ORDER_STATUS> states = {{OD_NONFINITE, OD_OUTSIDE}};
+    return launch_scenes<ORDER_THREADS>(order_kernel, (size_t)order_lds_bytes(Nb, Nd, Le), B, st, info, ORDER_INFO, ORDER_INFO_STATE,
+                                        states, status, a, y, b, rows_in, n_cand, n_held, symbols, perm, n_sel, rss, rows_out, C_out,
+                                        residual, info);
 }
 
 }  // namespace admmnet

@@ -19,6 +19,7 @@ namespace admmnet {
 
 constexpr int ORDER_THREADS = REFINE_THREADS;
 constexpr int ORDER_INFO = 4;             // cost, cost / D, rows ranked, state
+constexpr int ORDER_INFO_STATE = 3;       // the column of the state
 constexpr int ORDER_STATUS = 2;           // scenes non-finite, scenes outside
 constexpr double ORDER_COINCIDENT = CRB_PIVOT_MIN;                       // times D: |a~_j|^2 below it, the row is never taken
 constexpr double ORDER_RSS_FLOOR = CRB_PIVOT_MIN * CRB_PIVOT_MIN;        // 2^-80, times |x|^2

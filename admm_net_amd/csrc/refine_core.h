@@ -24,6 +24,7 @@ constexpr int REFINE_MAX_M = 64;          // most constellation points
 constexpr int REFINE_MAX_ITERS = 64;
 constexpr int REFINE_THREADS = 256;       // of a workgroup; the host model emulates as many
 constexpr int REFINE_INFO = 5;            // Q, Q / D, linearisations used, flips, state
+constexpr int REFINE_INFO_STATE = 4;      // the column of the state
 constexpr int REFINE_STATUS = 4;          // scenes outside, non-finite, gave up, limit reached
 constexpr double REFINE_LAMBDA_START = 1e-4;
 constexpr double REFINE_LAMBDA_MAX = 1e8;

@@ -19,6 +19,7 @@
 namespace admmnet {
 
 constexpr int RELAX_INFO = 3;              // level, resid, state
+constexpr int RELAX_INFO_STATE = 2;        // the column of the state
 constexpr int RELAX_COUNTS = 3;            // n_det, more, maps
 constexpr int RELAX_SUMS = 12;             // six complex moments
 constexpr int RELAX_MAX_ITERS = 16;

@@ -1,8 +1,8 @@
-// cfar_model.cpp -- csrc/cfar_core.h on the host, with the workgroup of csrc/cfar.hip emulated: the threads are a loop over the
-// items, a sum adds every thread's items in index order, then the lanes of a wave in the butterfly's pairing, then the waves in
-// order.  A stand-alone program (its own main): tests/test_detect.py builds it with -fsanitize=address,undefined, feeds it the case
-// table and holds its results to detect.cfar_host.  Every array has exactly the entries the kernel's LDS layout gives it, so the
-// sanitizer sees any index outside.
+// cfar_model.cpp -- csrc/cfar_core.h on the host, with the workgroup of csrc/cfar.hip emulated by host_par.h's HostPar<CFAR_THREADS>,
+// which states the order of every shared loop and sum once for the four scene models.  A stand-alone program (its own main):
+// tests/test_detect.py builds it with -fsanitize=address,undefined, feeds it the case table and holds its results to
+// detect.cfar_host.  Every array has exactly the entries the kernel's LDS layout gives it, so the sanitizer sees any index
+// outside.
 //
 //   input   (the file named by argv[1])  the number of scenes, then per scene "Nb Nd r Le method guard train rank alpha symbols
 //           psk_m psk_phase noise_var" (symbols: 0 or 1; noise_var: "none" or a number) and D lines "Re(y) Im(y) Re(b) Im(b) k"
@@ -12,33 +12,10 @@
 #include <cstring>
 #include <vector>
 
+#include "host_par.h"
 #include "cfar_core.h"
 
 using namespace admmnet;
-
-struct HostPar {
-    template <class F>
-    void each(int count, F fn) {
-        for (int item = 0; item < count; ++item) fn(item);
-    }
-
-    template <class F>
-    double sum(int count, F fn) {
-        double v[CFAR_THREADS];
-        for (int t = 0; t < CFAR_THREADS; ++t) {
-            v[t] = 0.0;
-            for (int item = t; item < count; item += CFAR_THREADS) v[t] += fn(item);
-        }
-        double total = 0.0;
-        for (int w = 0; w < CFAR_THREADS / 64; ++w) {
-            double *lane = v + 64 * w;
-            for (int o = 32; o > 0; o >>= 1)
-                for (int i = 0; i < o; ++i) lane[i] += lane[i + o];
-            total = w == 0 ? lane[0] : total + lane[0];
-        }
-        return total;
-    }
-};
 
 static double number(const char *s) { return std::strtod(s, nullptr); }   // reads nan and inf too
 
@@ -94,7 +71,7 @@ int main(int argc, char **argv) {
         std::vector<int32_t> counts(CFAR_COUNTS, -1);
         CfarMem m = {x.data(), img.data(), map.data(), tf.data(), tt.data(), pt.data(), off.data(), flag.data(), list.data(),
                      chunk.data(), slot.data()};
-        HostPar par;
+        HostPar<CFAR_THREADS> par;
         cfar_scene(par, a, m, y.data(), b.data(), has_sym ? sym.data() : nullptr, has_noise ? &noise : nullptr, rows.data(),
                    counts.data(), info.data(), map_out.data());
         std::printf("%d %d %d %.17g\n", (int)info[1], (int)counts[0], (int)counts[1], info[0]);

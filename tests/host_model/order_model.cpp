@@ -1,8 +1,8 @@
-// order_model.cpp -- csrc/order_core.h on the host, with the workgroup of csrc/order.hip emulated: the threads are a loop over the
-// items, a sum adds every thread's items in index order, then the lanes of a wave in the butterfly's pairing, then the waves in
-// order.  A stand-alone program (its own main): tests/test_order.py builds it with -fsanitize=address,undefined, feeds it the case
-// table and holds its results to order.select_host.  Every array has exactly the entries the kernel's LDS layout gives it, so the
-// sanitizer sees any index outside.
+// order_model.cpp -- csrc/order_core.h on the host, with the workgroup of csrc/order.hip emulated by host_par.h's HostPar<ORDER_THREADS>,
+// which states the order of every shared loop and sum once for the four scene models.  A stand-alone program (its own main):
+// tests/test_order.py builds it with -fsanitize=address,undefined, feeds it the case table and holds its results to
+// order.select_host.  Every array has exactly the entries the kernel's LDS layout gives it, so the sanitizer sees any index
+// outside.
 //
 //   input   (the file named by argv[1])  the number of scenes, then per scene "Nb Nd Le n_cand n_held symbols psk_m psk_phase
 //           penalty max_order" (n_cand, n_held: "none" or a number; symbols: 0 or 1), Le lines "tau f height" and D lines
@@ -13,33 +13,10 @@
 #include <cstring>
 #include <vector>
 
+#include "host_par.h"
 #include "order_core.h"
 
 using namespace admmnet;
-
-struct HostPar {
-    template <class F>
-    void each(int count, F fn) {
-        for (int item = 0; item < count; ++item) fn(item);
-    }
-
-    template <class F>
-    double sum(int count, F fn) {
-        double v[ORDER_THREADS];
-        for (int t = 0; t < ORDER_THREADS; ++t) {
-            v[t] = 0.0;
-            for (int item = t; item < count; item += ORDER_THREADS) v[t] += fn(item);
-        }
-        double total = 0.0;
-        for (int w = 0; w < ORDER_THREADS / 64; ++w) {
-            double *lane = v + 64 * w;
-            for (int o = 32; o > 0; o >>= 1)
-                for (int i = 0; i < o; ++i) lane[i] += lane[i + o];
-            total = w == 0 ? lane[0] : total + lane[0];
-        }
-        return total;
-    }
-};
 
 static double number(const char *s) { return std::strtod(s, nullptr); }   // reads nan and inf too
 
@@ -93,7 +70,7 @@ int main(int argc, char **argv) {
         std::vector<int> idx(Le), pick(Le), pm(Le), meta(OD_META);
         OrderMem m = {x.data(), pt.data(), tab.data(), rs.data(), G.data(), F.data(), c.data(), d.data(), wv.data(), C.data(),
                       tau.data(), f.data(), rss.data(), idx.data(), pick.data(), pm.data(), meta.data()};
-        HostPar par;
+        HostPar<ORDER_THREADS> par;
         order_scene(par, a, m, y.data(), b.data(), rows.data(), has_cand ? &n_cand : nullptr, has_held ? &n_held : nullptr,
                     has_sym ? sym.data() : nullptr, perm.data(), &n_sel, rss_out.data(), rows_out.data(), C_out.data(),
                     residual.data(), info.data());

@@ -1,8 +1,8 @@
-// refine_model.cpp -- csrc/refine_core.h on the host, with the workgroup of csrc/refine.hip emulated: the threads are a loop over
-// the items, a sum adds every thread's items in index order, then the lanes of a wave in the butterfly's pairing, then the waves in
-// order.  A stand-alone program (its own main): tests/test_refine.py builds it with -fsanitize=address,undefined, feeds it the case
-// table and holds its results to refine.refine_host.  Every array has exactly the entries the kernel's LDS layout gives it, so the
-// sanitizer sees any index outside.
+// refine_model.cpp -- csrc/refine_core.h on the host, with the workgroup of csrc/refine.hip emulated by host_par.h's HostPar<REFINE_THREADS>,
+// which states the order of every shared loop and sum once for the four scene models.  A stand-alone program (its own main):
+// tests/test_refine.py builds it with -fsanitize=address,undefined, feeds it the case table and holds its results to
+// refine.refine_host.  Every array has exactly the entries the kernel's LDS layout gives it, so the sanitizer sees any index
+// outside.
 //
 //   input   (the file named by argv[1])  the number of scenes, then per scene "Nb Nd Le n_est mode psk_m psk_phase iters tol"
 //           (n_est: "none" or a number), Le lines "tau f height" and D lines "Re(y) Im(y) Re(b) Im(b)"
@@ -12,33 +12,10 @@
 #include <cstring>
 #include <vector>
 
+#include "host_par.h"
 #include "refine_core.h"
 
 using namespace admmnet;
-
-struct HostPar {
-    template <class F>
-    void each(int count, F fn) {
-        for (int item = 0; item < count; ++item) fn(item);
-    }
-
-    template <class F>
-    double sum(int count, F fn) {
-        double v[REFINE_THREADS];
-        for (int t = 0; t < REFINE_THREADS; ++t) {
-            v[t] = 0.0;
-            for (int item = t; item < count; item += REFINE_THREADS) v[t] += fn(item);
-        }
-        double total = 0.0;
-        for (int w = 0; w < REFINE_THREADS / 64; ++w) {
-            double *lane = v + 64 * w;
-            for (int o = 32; o > 0; o >>= 1)
-                for (int i = 0; i < o; ++i) lane[i] += lane[i + o];
-            total = w == 0 ? lane[0] : total + lane[0];
-        }
-        return total;
-    }
-};
 
 static double number(const char *s) { return std::strtod(s, nullptr); }   // reads nan and inf too
 
@@ -104,7 +81,7 @@ int main(int argc, char **argv) {
         std::vector<int> idx(RF_IDX);
         RefineMem m = {z.data(), k.data(), k0.data(), pt.data(), A.data(), tab.data(), rs.data(), cont.data(), tg.data(), trial.data(),
                        g.data(), dsc.data(), step.data(), col.data(), idx.data()};
-        HostPar par;
+        HostPar<REFINE_THREADS> par;
         refine_scene(par, a, m, y.data(), b.data(), rows.data(), has_n ? &n_est : nullptr, rows_out.data(), C_out.data(), info.data(),
                      sym.data());
         std::printf("%d %d %d %.17g\n", (int)info[4], (int)info[2], (int)info[3], info[0]);

@@ -1,9 +1,8 @@
-// relax_model.cpp -- csrc/relax_core.h on the host, with the workgroup of csrc/cfar_relax.hip emulated: the threads are a loop over
-// the items, a sum adds every thread's items in index order, then the lanes of a wave in the butterfly's pairing, then the waves in
-// order; the best item is kept per thread in index order, then among the lanes in the butterfly's pairing, then among the waves.
-// A stand-alone program (its own main): tests/test_relax.py builds it with -fsanitize=address,undefined, feeds it the case table
-// and holds its results to detect.cfar_relax_host.  Every array has exactly the entries the kernel's LDS layout gives it, so the
-// sanitizer sees any index outside.
+// relax_model.cpp -- csrc/relax_core.h on the host, with the workgroup of csrc/cfar_relax.hip emulated by host_par.h's HostPar<CFAR_THREADS>,
+// which states the order of every shared loop and sum once for the four scene models.  A stand-alone program (its own main):
+// tests/test_relax.py builds it with -fsanitize=address,undefined, feeds it the case table and holds its results to
+// detect.cfar_relax_host.  Every array has exactly the entries the kernel's LDS layout gives it, so the sanitizer sees any index
+// outside.
 //
 //   input   (the file named by argv[1])  the number of scenes, then per scene "Nb Nd r Le method guard train rank alpha symbols
 //           psk_m psk_phase noise_var iters sweeps" (symbols: 0 or 1; noise_var: "none" or a number) and D lines
@@ -14,87 +13,10 @@
 #include <cstring>
 #include <vector>
 
+#include "host_par.h"
 #include "relax_core.h"
 
 using namespace admmnet;
-
-struct HostPar {
-    template <class F>
-    void each(int count, F fn) {
-        for (int item = 0; item < count; ++item) fn(item);
-    }
-
-    static double fold(double *v) {   // v[CFAR_THREADS]: lanes by the butterfly, waves in order
-        double total = 0.0;
-        for (int w = 0; w < CFAR_THREADS / 64; ++w) {
-            double *lane = v + 64 * w;
-            for (int o = 32; o > 0; o >>= 1)
-                for (int i = 0; i < o; ++i) lane[i] += lane[i + o];
-            total = w == 0 ? lane[0] : total + lane[0];
-        }
-        return total;
-    }
-
-    template <class F>
-    double sum(int count, F fn) {
-        double v[CFAR_THREADS];
-        for (int t = 0; t < CFAR_THREADS; ++t) {
-            v[t] = 0.0;
-            for (int item = t; item < count; item += CFAR_THREADS) v[t] += fn(item);
-        }
-        return fold(v);
-    }
-
-    template <int N, class F>
-    void sums(int count, F fn, double (&out)[N]) {
-        static double acc[CFAR_THREADS][N];
-        for (int t = 0; t < CFAR_THREADS; ++t) {
-            for (int n = 0; n < N; ++n) acc[t][n] = 0.0;
-            for (int item = t; item < count; item += CFAR_THREADS) fn(item, acc[t]);
-        }
-        for (int n = 0; n < N; ++n) {
-            double v[CFAR_THREADS];
-            for (int t = 0; t < CFAR_THREADS; ++t) v[t] = acc[t][n];
-            out[n] = fold(v);
-        }
-    }
-
-    static bool better(double ov, int oi, double bv, int bi) { return ov > bv || (ov == bv && oi < bi); }
-
-    template <class F>
-    int best(int count, F fn) {
-        double bv[CFAR_THREADS];
-        int bi[CFAR_THREADS];
-        for (int t = 0; t < CFAR_THREADS; ++t) {
-            bv[t] = -1.0;
-            bi[t] = -1;
-            for (int item = t; item < count; item += CFAR_THREADS) {
-                const double v = fn(item);
-                if (v > bv[t]) {
-                    bv[t] = v;
-                    bi[t] = item;
-                }
-            }
-        }
-        double top = -1.0;
-        int at = -1;
-        for (int w = 0; w < CFAR_THREADS / 64; ++w) {
-            double *v = bv + 64 * w;
-            int *k = bi + 64 * w;
-            for (int o = 32; o > 0; o >>= 1)
-                for (int i = 0; i < o; ++i)
-                    if (better(v[i + o], k[i + o], v[i], k[i])) {
-                        v[i] = v[i + o];
-                        k[i] = k[i + o];
-                    }
-            if (w == 0 || better(v[0], k[0], top, at)) {
-                top = v[0];
-                at = k[0];
-            }
-        }
-        return top >= 0.0 ? at : -1;
-    }
-};
 
 static double number(const char *s) { return std::strtod(s, nullptr); }   // reads nan and inf too
 
@@ -154,7 +76,7 @@ int main(int argc, char **argv) {
         RelaxMem m = {{x.data(), img.data(), map.data(), tf.data(), tt.data(), pt.data(), off.data(), flag.data(), nullptr, nullptr,
                        nullptr},
                       u.data(), vd.data(), tg.data()};
-        HostPar par;
+        HostPar<CFAR_THREADS> par;
         relax_scene(par, ra, m, y.data(), b.data(), has_sym ? sym.data() : nullptr, has_noise ? &noise : nullptr, rows.data(),
                     amp.data(), counts.data(), info.data(), map_out.data());
         std::printf("%d %d %d %d %.17g %.17g\n", (int)info[2], (int)counts[0], (int)counts[1], (int)counts[2], info[0], info[1]);
