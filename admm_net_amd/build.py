@@ -15,7 +15,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libadmmnet_hip.so")
 SOURCES = ["api.hip", "prep.hip", "tridiag.hip", "tridiag_reg.hip", "tridiag_big.hip", "tridiag_panel.hip", "wy_apply.hip", "tql.hip", "rotapply.hip", "dc.hip", "rebuild.hip", "rebuild_big.hip", "backrebuild.hip", "vgemm_big.hip", "arrow.hip",
            "zstep.hip", "head.hip", "spectrum.hip", "peaks.hip", "estimate.hip", "synth.hip", "vdvh.hip", "train_layer.hip", "train_small.hip", "train_hlayer.hip", "train_head.hip", "loss.hip", "spectral.hip", "spectral_fused.hip", "optim.hip", "score.hip", "crb.hip", "refine.hip", "order.hip", "loss_spectrum.hip", "loss_set.hip", "cfar.hip", "cfar_relax.hip"]
-HEADERS = ["common.h", "route.h", "options.h", "eig_core.h", "dc_core.h", "arrow_core.h", "rebuild_core.h", "rebuild_lds.h", "lane_reduce.h", "peak_core.h", "slab_partials.h", "batch_sums.h", "score_core.h", "set_core.h", "crb_core.h", "refine_core.h", "order_core.h", "cfar_core.h", "relax_core.h", "scene_wg.h", os.path.join("..", "..", "include", "admmnet.h")]
+HEADERS = ["common.h", "route.h", "options.h", "eig_core.h", "dc_core.h", "arrow_core.h", "rebuild_core.h", "rebuild_lds.h", "lane_reduce.h", "peak_core.h", "slab_partials.h", "batch_sums.h", "batch_product.h", "train_math.h", "score_core.h", "set_core.h", "crb_core.h", "refine_core.h", "order_core.h", "cfar_core.h", "relax_core.h", "scene_wg.h", os.path.join("..", "..", "include", "admmnet.h")]
 FLAGS = ["-O3", "--offload-arch=gfx950", "-fPIC", "-std=c++17", "-Wall", "-Wno-unused-function"]
 # per-file extras: the SLP vectoriser packs the rotation replay into v_pk_* ops that need a
 # register shuffle per plane (7 VALU per rotation instead of 4)

@@ -55,7 +55,7 @@ __global__ __launch_bounds__(CRB_THREADS) void crb_kernel(int Nb, int Nd, int Lt
             crb_pair_decode(pr, &l, &m);
             e += crb_pair_fill(l, m, nt, Nb, Nd, tg, A, ld);
         }
-        const double v = crb_noise_var(noise_is_snr != 0, nz, sc_wave_sum(e), (double)Nb * (double)Nd);
+        const double v = crb_noise_var(noise_is_snr != 0, nz, wave_sum(e), (double)Nb * (double)Nd);
         __syncthreads();
         if (!(v > 0.0 && sc_finite(v))) {
             state = 1;
@@ -108,14 +108,14 @@ __global__ __launch_bounds__(CRB_THREADS) void crb_kernel(int Nb, int Nd, int Lt
     const bool hit = live && match != nullptr && match[sig * Lt + lane] >= 0;
     const bool in_tau = live && sc_finite(b_tau), in_f = live && sc_finite(b_f);   // neither NaN nor the inf of an absent axis
     double acc[CRB_COLS];
-    acc[0] = sc_wave_sum(in_tau ? b_tau : 0.0);
-    acc[1] = sc_wave_sum(in_f ? b_f : 0.0);
-    acc[2] = sc_wave_sum(in_tau ? 1.0 : 0.0);
-    acc[3] = sc_wave_sum(in_f ? 1.0 : 0.0);
-    acc[4] = sc_wave_sum(in_tau && hit ? b_tau : 0.0);
-    acc[5] = sc_wave_sum(in_f && hit ? b_f : 0.0);
-    acc[6] = sc_wave_sum(in_tau && hit ? 1.0 : 0.0);
-    acc[7] = sc_wave_sum(in_f && hit ? 1.0 : 0.0);
+    acc[0] = wave_sum(in_tau ? b_tau : 0.0);
+    acc[1] = wave_sum(in_f ? b_f : 0.0);
+    acc[2] = wave_sum(in_tau ? 1.0 : 0.0);
+    acc[3] = wave_sum(in_f ? 1.0 : 0.0);
+    acc[4] = wave_sum(in_tau && hit ? b_tau : 0.0);
+    acc[5] = wave_sum(in_f && hit ? b_f : 0.0);
+    acc[6] = wave_sum(in_tau && hit ? 1.0 : 0.0);
+    acc[7] = wave_sum(in_f && hit ? 1.0 : 0.0);
 #pragma unroll
     for (int c = 0; c < CRB_STATUS; ++c) acc[CRB_TOTALS + c] = state == c ? 1.0 : 0.0;
     if (lane < CRB_COLS) {
@@ -129,7 +129,7 @@ __global__ __launch_bounds__(CRB_THREADS) void crb_kernel(int Nb, int Nd, int Lt
 __global__ __launch_bounds__(SC_FIN_THREADS) void crb_finish_kernel(int64_t rows, const double *__restrict__ part,
                                                                     double *__restrict__ totals, int32_t *__restrict__ status) {
     __shared__ double sh[SC_FIN_SLICES * CRB_COLS];
-    sc_colsum<CRB_COLS>(rows, part, sh);
+    colsum<CRB_COLS, SC_FIN_SLICES>(rows, part, sh);
     if ((int)threadIdx.x < CRB_TOTALS) totals[threadIdx.x] = sh[threadIdx.x];
     if ((int)threadIdx.x < CRB_STATUS) status[threadIdx.x] = sc_count(sh[CRB_TOTALS + threadIdx.x]);
 }

@@ -345,5 +345,12 @@ HD bool choose_flip(int n, DA D, EA E) {
 // torch.nn.functional.softplus (beta = 1, threshold = 20)
 HD float softplus_f(float x) { return x > 20.0f ? x : log1pf(expf(x)); }
 HD float sigmoid_f(float x) { return 1.0f / (1.0f + expf(-x)); }
+// d softplus_f(x) / dx
+HD float dsoftplus_f(float x) { return x > 20.0f ? 1.0f : sigmoid_f(x); }
+// d sigmoid_f(x) / dx = s (1 - s), from e = exp(-|x|) as e / (1 + e)^2: 1 - s itself loses every digit as s nears 1
+HD float dsigmoid_f(float x) {
+    const float e = expf(-fabsf(x)), d = 1.0f + e;
+    return e / (d * d);
+}
 
 }  // namespace admmnet

@@ -15,19 +15,13 @@
 // sums by xor-shuffle butterflies, one row of partials per workgroup, added in float64 by ONE workgroup that also forms the
 // three outputs.  No atomics: two runs give the same bits.  Every access is a 4-byte or an 8-byte one.
 #include "common.h"
-#include "slab_partials.h"
+#include "batch_sums.h"
 
 namespace admmnet {
 
 constexpr int LA_ANM_COLS = 3;   // sum_b loss_b, sum_b ||phi_b||, signals whose L_true is outside [0, Lmax]
 constexpr int LA_PHI_COLS = 2;   // sum (|phi| - |phi_true|)^2, sum wrap(.)^2
 constexpr float LA_PI = 3.14159265358979323846f, LA_2PI = 6.28318530717958647692f;
-
-__device__ __forceinline__ double la_wave_sum(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
 
 // ((d + pi) mod 2 pi) - pi, the mod floored (the sign of the divisor): fmod's remainder has the sign of the dividend
 __device__ __forceinline__ float la_wrap(float d) {
@@ -43,24 +37,9 @@ __device__ __forceinline__ int la_targets(const int64_t *__restrict__ L_true, in
     return raw < 0 ? 0 : (raw > Lmax ? Lmax : (int)raw);
 }
 
-// column sums of part [rows][COLS] in float64, fixed order (the scheme of ts_colsum_kernel): thread (c, s) adds the rows
-// s, s + NS, ..., a tree halves the NS slices; the sums are left in sh[0 .. COLS).  One workgroup, every thread calls it.
-template <int COLS>
-__device__ __forceinline__ void la_colsum(int64_t rows, const float *__restrict__ part, double *sh) {
-    constexpr int NS = COLS == 2 ? 128 : 64;
-    static_assert(NS * COLS <= TS_THREADS, "one thread per column and slice");
-    const int c = threadIdx.x % COLS, s = threadIdx.x / COLS;
-    const bool live = s < NS;
-    double a = 0.0;
-    if (live)
-        for (int64_t r = s; r < rows; r += NS) a += (double)part[r * COLS + c];
-    if (live) sh[s * COLS + c] = a;
-    __syncthreads();
-    for (int o = NS >> 1; o > 0; o >>= 1) {
-        if (live && s < o) sh[s * COLS + c] += sh[(s + o) * COLS + c];
-        __syncthreads();
-    }
-}
+// row slices of the finishing column sum (colsum of batch_sums.h): one thread per column and slice
+constexpr int LA_ANM_SLICES = 64, LA_PHI_SLICES = 128;
+static_assert(LA_ANM_SLICES * LA_ANM_COLS <= TS_THREADS && LA_PHI_SLICES * LA_PHI_COLS <= TS_THREADS, "one thread per column and slice");
 
 // ---- BasicANMLoss ------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(TS_THREADS) void la_anm_kernel(int Lmax, int D, int64_t B, const float *__restrict__ tau,
@@ -93,7 +72,7 @@ __global__ __launch_bounds__(TS_THREADS) void la_anm_kernel(int Lmax, int D, int
             const float2 p = phi[sig * D + i];
             ss += (double)p.x * (double)p.x + (double)p.y * (double)p.y;
         }
-        const float nrm = (float)sqrt(la_wave_sum(ss));
+        const float nrm = (float)sqrt(wave_sum(ss));
         if (lane == 0) norms[sig] = nrm;
         v[0] = L > 0 ? t / (float)L : t;
         v[1] = nrm;
@@ -106,7 +85,7 @@ __global__ __launch_bounds__(TS_THREADS) void la_anm_finish_kernel(int64_t rows,
                                                                    const float *__restrict__ part, float *__restrict__ out,
                                                                    int32_t *__restrict__ status) {
     __shared__ double sh[TS_THREADS];
-    la_colsum<LA_ANM_COLS>(rows, part, sh);
+    colsum<LA_ANM_COLS, LA_ANM_SLICES>(rows, part, sh);
     if (threadIdx.x == 0) {
         const double param = sh[0] / (double)B, reg = (double)lambda_reg * sh[1] / (double)B;
         out[0] = (float)(param + reg);
@@ -177,7 +156,7 @@ __global__ __launch_bounds__(TS_THREADS) void la_phi_finish_kernel(int64_t rows,
                                                                    float phase_weight, const float *__restrict__ part,
                                                                    float *__restrict__ out) {
     __shared__ double sh[TS_THREADS];
-    la_colsum<LA_PHI_COLS>(rows, part, sh);
+    colsum<LA_PHI_COLS, LA_PHI_SLICES>(rows, part, sh);
     if (threadIdx.x == 0) {
         const double amp = sh[0] / count, ph = sh[1] / count;
         out[0] = (float)((double)amplitude_weight * amp + (double)phase_weight * ph);

@@ -72,7 +72,7 @@ __global__ __launch_bounds__(TS_THREADS) void ls_set_kernel(int Lmax, int Lt, in
         const float2 p = phi[sig * D + i];
         ss += (double)p.x * (double)p.x + (double)p.y * (double)p.y;
     }
-    const float nrm = (float)sqrt(sc_wave_sum(ss));
+    const float nrm = (float)sqrt(wave_sum(ss));
     if (lane == 0) norms[sig] = nrm;
     double v[SET_COLS] = {0.0, 0.0, 0.0, 0.0, s.outside ? 1.0 : 0.0, s.nonfinite ? 1.0 : 0.0};
     int a = -1;
@@ -134,8 +134,8 @@ __global__ __launch_bounds__(TS_THREADS) void ls_set_kernel(int Lmax, int Lt, in
         }
         const int src = a < 0 ? 0 : a;
         const ScDelta d = sc_delta(s.s_tau, s.s_f, __shfl(s.t_tau, src, 64), __shfl(s.t_f, src, 64), o.sc);   // as set_relax saw it
-        const double sum_d2 = sc_wave_sum(a >= 0 ? d.d2 : 0.0);
-        const double sum_c = sc_wave_sum(slot_live ? set_conf_sq(s.s_conf, a >= 0) : 0.0);
+        const double sum_d2 = wave_sum(a >= 0 ? d.d2 : 0.0);
+        const double sum_c = wave_sum(slot_live ? set_conf_sq(s.s_conf, a >= 0) : 0.0);
         set_values(sum_d2, sum_c, n, Lmax, o.w_conf, v);
         v[3] = (double)nrm;
     }
@@ -152,7 +152,7 @@ __global__ __launch_bounds__(SC_FIN_THREADS) void ls_set_finish_kernel(int64_t B
                                                                        const double *__restrict__ rows, float *__restrict__ out,
                                                                        int32_t *__restrict__ status) {
     __shared__ double sh[SC_FIN_SLICES * SET_COLS];
-    sc_colsum<SET_COLS>(B, rows, sh);
+    colsum<SET_COLS, SC_FIN_SLICES>(B, rows, sh);
     if (threadIdx.x == 0) {
         const double match = sh[1] / (double)B, cf = sh[2] / (double)B, reg = lambda_reg * sh[3] / (double)B;
         out[0] = (float)(match + w_conf * cf + reg);

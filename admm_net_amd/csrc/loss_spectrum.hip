@@ -16,6 +16,7 @@
 // plus the target rows 2 c_l conj(z_l) a_l and the derivative of ||phi||^2.  Every sum has a fixed order (a thread's own
 // strided terms, a xor butterfly, the four waves in order): a signal's figures depend on neither B nor its place.
 #include "common.h"
+#include "batch_sums.h"
 
 namespace admmnet {
 
@@ -253,26 +254,14 @@ __global__ __launch_bounds__(LS_THREADS) void ls_fwd_kernel(int xbase, int ybase
     }
 }
 
-// the six columns of rows [B][LS_ROW] added in float64 in a fixed order: thread (c, s) adds the rows s, s + NS, ..., a tree
-// halves the NS slices (la_colsum of loss.hip)
+// the six columns of rows [B][LS_ROW] added in float64 in a fixed order (colsum of batch_sums.h over LS_ROW-strided rows)
 __global__ __launch_bounds__(LS_THREADS) void ls_finish_kernel(int64_t B, const double *__restrict__ rows, float spectral_weight,
                                                                float distribution_weight, float target_weight,
                                                                float *__restrict__ out, int32_t *__restrict__ status) {
     constexpr int NS = 32;
     static_assert(NS * LS_COLS <= LS_THREADS, "one thread per column and slice");
     __shared__ double sh[NS * LS_COLS];
-    const int c = threadIdx.x % LS_COLS, s = threadIdx.x / LS_COLS;
-    const bool live = s < NS;
-    if (live) {
-        double a = 0.0;
-        for (int64_t r = s; r < B; r += NS) a += rows[r * LS_ROW + c];
-        sh[s * LS_COLS + c] = a;
-    }
-    __syncthreads();
-    for (int o = NS >> 1; o > 0; o >>= 1) {
-        if (live && s < o) sh[s * LS_COLS + c] += sh[(s + o) * LS_COLS + c];
-        __syncthreads();
-    }
+    colsum(LS_COLS, NS, B, LS_ROW, rows, sh);
     if (threadIdx.x == 0) {
         const double spec = sh[LS_SPEC] / (double)B, dist = sh[LS_DIST] / (double)B, targ = sh[LS_TARG] / (double)B;
         out[0] = (float)((double)spectral_weight * spec + (double)distribution_weight * dist + (double)target_weight * targ);

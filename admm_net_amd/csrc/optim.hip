@@ -18,10 +18,9 @@
 // multiple of four; four 4-byte accesses of the same elements otherwise (views at odd offsets).  The same thread owns the same
 // elements either way, so the bits of the norm do not depend on the alignment.
 //
-// Sums.  Squares and sums in float64: in-lane in element order, the xor butterfly across the wave (offsets 32 .. 1; written here
-// with __shfl_xor as in loss.hip's la_wave_sum -- the butterflies of lane_reduce.h are float-only DPP / permlane forms), the four
-// waves serially from LDS, one double per block; op_finish_kernel (one workgroup) adds the blocks in the fixed order of
-// ts_colsum_kernel.  No atomics: every run gives the same bits.
+// Sums.  Squares and sums in float64: in-lane in element order, the xor butterfly across the wave (offsets 32 .. 1, the float64
+// wave_sum of common.h), the four waves serially from LDS, one double per block; op_finish_kernel (one workgroup) adds the blocks
+// in the fixed order of colsum (batch_sums.h).  No atomics: every run gives the same bits.
 //
 // Rounding.  The file is compiled with floating-point contraction OFF (the pragma below): every product, sum, quotient and root
 // is rounded to its type on its own, and a multiply-add is fused only where fmaf is written.  (The __fmul_rn family is no tool
@@ -29,6 +28,7 @@
 // into a following sum, and __fsqrt_rn as the native, not correctly rounded, root.)  sqrtf and / are the compiler's correctly
 // rounded defaults; no fast-math flag is given.
 #include "common.h"
+#include "batch_sums.h"
 
 #pragma clang fp contract(off)
 
@@ -122,8 +122,7 @@ __global__ __launch_bounds__(OP_THREADS) void op_sqnorm_kernel(OpListArgs a) {
     double acc = (double)x[0] * (double)x[0];                 // (a float's square is exact in float64)
 #pragma unroll
     for (int j = 1; j < 4; ++j) acc += (double)x[j] * (double)x[j];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
+    acc = wave_sum(acc);
     if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = acc;
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -134,21 +133,14 @@ __global__ __launch_bounds__(OP_THREADS) void op_sqnorm_kernel(OpListArgs a) {
     }
 }
 
-// sumsq = the blocks' sums added in a fixed order (thread s adds the blocks s, s + 256, ..., a tree halves the slices);
+// sumsq = the blocks' sums added in a fixed order (colsum of batch_sums.h: one column, a slice per thread);
 // total_norm = (float) sqrt(sumsq); coef = clamp(max_norm / (total_norm + 1e-6), max = 1) as torch evaluates it in float32:
 // `number / tensor` is reciprocal(tensor) * number there, and clamp keeps a NaN (an infinite norm gives 1 / inf = 0)
 __global__ __launch_bounds__(OP_THREADS) void op_finish_kernel(int64_t rows, const double *__restrict__ partials, float max_norm,
                                                                double *__restrict__ sumsq, float *__restrict__ total_norm,
                                                                float *__restrict__ coef) {
     __shared__ double sh[OP_THREADS];
-    double acc = 0.0;
-    for (int64_t r = threadIdx.x; r < rows; r += OP_THREADS) acc += partials[r];
-    sh[threadIdx.x] = acc;
-    __syncthreads();
-    for (int o = OP_THREADS >> 1; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) sh[threadIdx.x] += sh[threadIdx.x + o];
-        __syncthreads();
-    }
+    colsum<1, OP_THREADS>(rows, partials, sh);
     if (threadIdx.x == 0) {
         const double ss = sh[0];
         const float nrm = (float)sqrt(ss);

@@ -35,7 +35,7 @@ struct ScenePar {
     __device__ __forceinline__ double sum(int count, F fn) {
         double v = 0.0;
         for (int item = threadIdx.x; item < count; item += THREADS) v += fn(item);
-        v = sc_wave_sum(v);
+        v = wave_sum(v);
         if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
         __syncthreads();
         double total = red[0];
@@ -54,7 +54,7 @@ struct ScenePar {
         for (int item = threadIdx.x; item < count; item += THREADS) fn(item, v);
 #pragma unroll
         for (int n = 0; n < N; ++n) {
-            v[n] = sc_wave_sum(v[n]);
+            v[n] = wave_sum(v[n]);
             if ((threadIdx.x & 63) == 0) red[(threadIdx.x >> 6) * N + n] = v[n];
         }
         __syncthreads();

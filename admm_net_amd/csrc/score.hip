@@ -107,8 +107,8 @@ __global__ __launch_bounds__(TS_THREADS) void sc_match_kernel(int Le, int Lt, in
             const int src = col.p < 0 ? 0 : col.p;
             const ScDelta d = sc_delta(__shfl(r_tau, src, 64), __shfl(r_f, src, 64), col.tau, col.f, o);   // as sc_relax saw it
             const bool hit = col.live && col.p >= 0 && sc_hit(d.d2, o.c2);
-            const double n_hit = sc_wave_sum(hit ? 1.0 : 0.0), s_tau = sc_wave_sum(hit ? d.dtau * d.dtau : 0.0),
-                         s_f = sc_wave_sum(hit ? d.df * d.df : 0.0), s_d2 = sc_wave_sum(hit ? d.d2 : 0.0);
+            const double n_hit = wave_sum(hit ? 1.0 : 0.0), s_tau = wave_sum(hit ? d.dtau * d.dtau : 0.0),
+                         s_f = wave_sum(hit ? d.df * d.df : 0.0), s_d2 = wave_sum(hit ? d.d2 : 0.0);
             if (rows_est) {
                 m = hit ? col.p : -1;                       // lane = truth, p = its estimate
             } else {
@@ -134,7 +134,7 @@ __global__ __launch_bounds__(TS_THREADS) void sc_match_kernel(int Le, int Lt, in
 __global__ __launch_bounds__(SC_FIN_THREADS) void sc_match_finish_kernel(int64_t rows, const double *__restrict__ part,
                                                                          double *__restrict__ totals, int32_t *__restrict__ status) {
     __shared__ double sh[SC_FIN_SLICES * SC_MATCH_COLS];
-    sc_colsum<SC_MATCH_COLS>(rows, part, sh);
+    colsum<SC_MATCH_COLS, SC_FIN_SLICES>(rows, part, sh);
     if ((int)threadIdx.x < SC_STATS) totals[threadIdx.x] = sh[threadIdx.x];
     if (threadIdx.x == 0) {
         status[0] = sc_count(sh[SC_STATS]);
@@ -160,7 +160,7 @@ __global__ __launch_bounds__(TS_THREADS) void sc_ordered_kernel(int Lmax, int64_
             dt = (double)tau_est[e] - (double)tau_true[e];
             df = (double)f_est[e] - (double)f_true[e];
         }
-        const double st = sc_wave_sum(dt * dt), sf = sc_wave_sum(df * df);
+        const double st = wave_sum(dt * dt), sf = wave_sum(df * df);
         const double rt = L > 0 ? sqrt(st / (double)L) : NAN, rf = L > 0 ? sqrt(sf / (double)L) : NAN;
         if (lane < 2) per_sample[sig * 2 + lane] = lane == 0 ? rt : rf;
         if (L > 0) {
@@ -176,7 +176,7 @@ __global__ __launch_bounds__(TS_THREADS) void sc_ordered_kernel(int Lmax, int64_
 __global__ __launch_bounds__(SC_FIN_THREADS) void sc_ordered_finish_kernel(int64_t rows, const double *__restrict__ part,
                                                                            double *__restrict__ out, int32_t *__restrict__ status) {
     __shared__ double sh[SC_FIN_SLICES * SC_ORD_COLS];
-    sc_colsum<SC_ORD_COLS>(rows, part, sh);
+    colsum<SC_ORD_COLS, SC_FIN_SLICES>(rows, part, sh);
     if (threadIdx.x == 0) {
         const double count = sh[2];
         out[0] = count > 0.0 ? sh[0] / count : 0.0;

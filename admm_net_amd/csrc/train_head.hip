@@ -11,32 +11,28 @@
 //                              layers: 4 D + 752 + 80 L floats per signal.
 //   backward  hd_bwd_kernel    per signal: g_phi and the pre-activation delta of every linear layer (relu'(0) = 0), the masked
 //                              weights a' and the score gradients g_s;
-//             hb_kernel        every weight gradient as a batch-reduced product C[m][n] = sum_b A[b][m] Bm[b][n] on
-//                              v_mfma_f32_32x32x2_f32 with the batch as the k dimension (operand layout as in train_hlayer.hip's
-//                              bp_kernel), a ones column appended for the bias; the token side's gV_h[d] = sum_b a'_bhd g_ctx_bh
-//                              and gK_h[d] = sum_b g_s_bhd q_bh are products of the same launch.  One wave per (32 x 32 tile,
-//                              slab of HB_SLAB rows of the batch): float32 within a slab, hb_sum_kernel adds the slabs in ascending
-//                              order in float64.  No atomics; the slab length is a constant, so two runs and any grid give the
-//                              same bits.  confidence_net is shared over t: its batch is the B L (signal, target) pairs.
+//             bp_kernel        every weight gradient as a batch-reduced product C[m][n] = sum_b A[b][m] Bm[b][n] with a ones
+//                              column appended for the bias (batch_product.h: the MFMA loop, the slabs and their float64 sums
+//                              are defined there); the token side's gV_h[d] = sum_b a'_bhd g_ctx_bh and gK_h[d] = sum_b g_s_bhd q_bh
+//                              are products of the same launch.  hb_sum_kernel adds the slabs.  confidence_net is shared over
+//                              t: its batch is the B L (signal, target) pairs.
 //             hd_token_kernel  gK, gV [D][128] through the K and V slices of in_proj to g_P, and g_P through position_projection
-//                              to the gradient of the position_encoder parameter; a second hb_kernel launch with the D tokens as
+//                              to the gradient of the position_encoder parameter; a second bp_kernel launch with the D tokens as
 //                              the batch gives gWk, gbk (= sum_d gK), gWv, gbv, gWp, gbp.
 // The descriptors of the products are not stored: hb_desc evaluates descriptor i from the sizes and the buffers' base pointers,
 // on the host to count tiles and in every wave to find its own.
 #include "common.h"
+#include "batch_product.h"
 #include "slab_partials.h"
+#include "train_math.h"
 
 namespace admmnet {
-
-using f32x16 = __attribute__((ext_vector_type(16))) float;
 
 constexpr int HDIM = 128;             // hidden_dim = threads of the per-signal workgroup
 constexpr int HD_HEADS = 4;
 constexpr int HD_DH = 32;           // head dim
 constexpr int HD_MAXL = 16;
 constexpr int HD_RH = 80;           // hidden units of one target: 32 tau, 32 f, 16 confidence
-constexpr int HB_SLAB = 128;        // rows of the batch summed in float32 by one wave
-constexpr int HB_UNROLL = 8;
 constexpr float HD_SCALE = 0.17677669529663687f;   // 1 / sqrt(32)
 
 enum { P_POS = 0, P_FE0W, P_FE0B, P_FE2W, P_FE2B, P_PPW, P_PPB, P_INW, P_INB, P_OUTW, P_OUTB, P_PE0W, P_PE0B, P_PE2W, P_PE2B,
@@ -106,7 +102,7 @@ struct HeadGrad {
 // the backward's scratch: deltas per signal, g_P, the slab partials
 struct HeadWork {
     float *dhid, *dout, *z, *d4, *d2, *d0, *gxf, *gctx, *am, *gs, *dq, *dp2, *dp1, *gP, *partA, *partB, *partC;
-    static __host__ __device__ int64_t slabs(int64_t nb) { return (nb + HB_SLAB - 1) / HB_SLAB; }
+    static __host__ __device__ int64_t slabs(int64_t nb) { return bp_slabs(nb); }
     __host__ __device__ HeadWork(float *c, int D, int L, int64_t B) {
         const HeadGrad G(D, L);
         dhid = c, c += B * L * HD_RH;
@@ -135,20 +131,6 @@ struct HeadWork {
     }
 };
 
-// sum_{i < n} w[i * stride] x[i], x in LDS, four interleaved partial sums
-__device__ __forceinline__ float hd_dot(const float *__restrict__ w, int stride, const float *x, int n) {
-    float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
-    int i = 0;
-    for (; i + 3 < n; i += 4) {
-        a0 = fmaf(w[(int64_t)i * stride], x[i], a0);
-        a1 = fmaf(w[(int64_t)(i + 1) * stride], x[i + 1], a1);
-        a2 = fmaf(w[(int64_t)(i + 2) * stride], x[i + 2], a2);
-        a3 = fmaf(w[(int64_t)(i + 3) * stride], x[i + 3], a3);
-    }
-    for (; i < n; ++i) a0 = fmaf(w[(int64_t)i * stride], x[i], a0);
-    return (a0 + a1) + (a2 + a3);
-}
-__device__ __forceinline__ float hd_sigmoid(float x) { return 1.f / (1.f + expf(-x)); }
 __device__ __forceinline__ float hd_offset(int t, int L) { return (float)((double)t / (double)L); }
 
 // ---- forward -----------------------------------------------------------------------------------------------------------------
@@ -162,8 +144,8 @@ __global__ __launch_bounds__(HDIM) void hd_kv_kernel(int D, int L, int64_t B, He
     S.P[(int64_t)t * HDIM + o] = v;
     __syncthreads();
     const float *inw = hp.p[P_INW], *inb = hp.p[P_INB];
-    S.K[(int64_t)t * HDIM + o] = hd_dot(inw + (int64_t)(HDIM + o) * HDIM, 1, pos, HDIM) + inb[HDIM + o];
-    S.V[(int64_t)t * HDIM + o] = hd_dot(inw + (int64_t)(2 * HDIM + o) * HDIM, 1, pos, HDIM) + inb[2 * HDIM + o];
+    S.K[(int64_t)t * HDIM + o] = dot4(inw + (int64_t)(HDIM + o) * HDIM, 1, pos, HDIM) + inb[HDIM + o];
+    S.V[(int64_t)t * HDIM + o] = dot4(inw + (int64_t)(2 * HDIM + o) * HDIM, 1, pos, HDIM) + inb[2 * HDIM + o];
 }
 
 // keep: [B][4][D] bytes or nullptr; inv = 1 / (1 - p)
@@ -180,15 +162,15 @@ __global__ __launch_bounds__(HDIM) void hd_fwd_kernel(int D, int L, int64_t B, H
         feat[D + i] = p.y;
     }
     __syncthreads();
-    const float x1 = fmaxf(hd_dot(hp.p[P_FE0W] + (int64_t)o * 2 * D, 1, feat, 2 * D) + hp.p[P_FE0B][o], 0.f);
+    const float x1 = fmaxf(dot4(hp.p[P_FE0W] + (int64_t)o * 2 * D, 1, feat, 2 * D) + hp.p[P_FE0B][o], 0.f);
     va[o] = x1;
     S.x1[b * HDIM + o] = x1;
     __syncthreads();
-    const float x = fmaxf(hd_dot(hp.p[P_FE2W] + (int64_t)o * HDIM, 1, va, HDIM) + hp.p[P_FE2B][o], 0.f);
+    const float x = fmaxf(dot4(hp.p[P_FE2W] + (int64_t)o * HDIM, 1, va, HDIM) + hp.p[P_FE2B][o], 0.f);
     vb[o] = x;
     S.x[b * HDIM + o] = x;
     __syncthreads();
-    const float q = (hd_dot(hp.p[P_INW] + (int64_t)o * HDIM, 1, vb, HDIM) + hp.p[P_INB][o]) * HD_SCALE;
+    const float q = (dot4(hp.p[P_INW] + (int64_t)o * HDIM, 1, vb, HDIM) + hp.p[P_INB][o]) * HD_SCALE;
     va[o] = q;
     S.q[b * HDIM + o] = q;
     __syncthreads();
@@ -232,24 +214,24 @@ __global__ __launch_bounds__(HDIM) void hd_fwd_kernel(int D, int L, int64_t B, H
         S.ctx[b * HDIM + o] = a;
     }
     __syncthreads();
-    const float xf = x + (hd_dot(hp.p[P_OUTW] + (int64_t)o * HDIM, 1, va, HDIM) + hp.p[P_OUTB][o]);
+    const float xf = x + (dot4(hp.p[P_OUTW] + (int64_t)o * HDIM, 1, va, HDIM) + hp.p[P_OUTB][o]);
     vb[o] = xf;
     S.xf[b * HDIM + o] = xf;
     __syncthreads();
     if (o < 64) {
-        const float u = fmaxf(hd_dot(hp.p[P_PE0W] + (int64_t)o * HDIM, 1, vb, HDIM) + hp.p[P_PE0B][o], 0.f);
+        const float u = fmaxf(dot4(hp.p[P_PE0W] + (int64_t)o * HDIM, 1, vb, HDIM) + hp.p[P_PE0B][o], 0.f);
         va[o] = u;
         S.u0[b * 64 + o] = u;
     }
     __syncthreads();
     if (o < 32) {
-        const float u = fmaxf(hd_dot(hp.p[P_PE2W] + (int64_t)o * 64, 1, va, 64) + hp.p[P_PE2B][o], 0.f);
+        const float u = fmaxf(dot4(hp.p[P_PE2W] + (int64_t)o * 64, 1, va, 64) + hp.p[P_PE2B][o], 0.f);
         vb[o] = u;
         S.u1[b * 32 + o] = u;
     }
     __syncthreads();
     if (o < 16) {
-        const float u = fmaxf(hd_dot(hp.p[P_PE4W] + (int64_t)o * 32, 1, vb, 32) + hp.p[P_PE4B][o], 0.f);
+        const float u = fmaxf(dot4(hp.p[P_PE4W] + (int64_t)o * 32, 1, vb, 32) + hp.p[P_PE4B][o], 0.f);
         va[o] = u;   // xp
         S.xp[b * 16 + o] = u;
     }
@@ -273,9 +255,9 @@ __global__ __launch_bounds__(HDIM) void hd_fwd_kernel(int D, int L, int64_t B, H
             const int nh = o < 2 ? 32 : 16;
             float a = o == 0 ? hp.p[r + 3][0] : (o == 1 ? hp.p[r + 7][0] : hp.p[P_C2B][0]);
             for (int j = 0; j < nh; ++j) a = fmaf(w2[j], hs[j], a);
-            if (o == 0) tau[b * L + t] = hd_sigmoid(a);
+            if (o == 0) tau[b * L + t] = sigmoid_f(a);
             else if (o == 1) f[b * L + t] = tanhf(a);
-            else conf[b * L + t] = hd_sigmoid(a);
+            else conf[b * L + t] = sigmoid_f(a);
         }
         __syncthreads();
     }
@@ -317,7 +299,7 @@ __global__ __launch_bounds__(HDIM) void hd_bwd_kernel(int D, int L, int64_t B, H
         }
         __syncthreads();
         if (o < 16)
-            gxp += hd_dot(hp.p[r] + o, 16, dh, 32) + hd_dot(hp.p[r + 4] + o, 16, dh + 32, 32) + hd_dot(hp.p[P_C0W] + o, 16, dh + 64, 16);
+            gxp += dot4(hp.p[r] + o, 16, dh, 32) + dot4(hp.p[r + 4] + o, 16, dh + 32, 32) + dot4(hp.p[P_C0W] + o, 16, dh + 64, 16);
         __syncthreads();
     }
     // peak_extractor
@@ -328,22 +310,22 @@ __global__ __launch_bounds__(HDIM) void hd_bwd_kernel(int D, int L, int64_t B, H
     }
     __syncthreads();
     if (o < 32) {
-        const float d = S.u1[b * 32 + o] > 0.f ? hd_dot(hp.p[P_PE4W] + o, 32, va, 16) : 0.f;
+        const float d = S.u1[b * 32 + o] > 0.f ? dot4(hp.p[P_PE4W] + o, 32, va, 16) : 0.f;
         vb[o] = d;
         W.d2[b * 32 + o] = d;
     }
     __syncthreads();
     if (o < 64) {
-        const float d = S.u0[b * 64 + o] > 0.f ? hd_dot(hp.p[P_PE2W] + o, 64, vb, 32) : 0.f;
+        const float d = S.u0[b * 64 + o] > 0.f ? dot4(hp.p[P_PE2W] + o, 64, vb, 32) : 0.f;
         va[o] = d;
         W.d0[b * 64 + o] = d;
     }
     __syncthreads();
-    const float gxf = hd_dot(hp.p[P_PE0W] + o, HDIM, va, 64);   // also the delta of out_proj and the residual's gradient of x
+    const float gxf = dot4(hp.p[P_PE0W] + o, HDIM, va, 64);   // also the delta of out_proj and the residual's gradient of x
     vc[o] = gxf;
     W.gxf[b * HDIM + o] = gxf;
     __syncthreads();
-    const float gctx = hd_dot(hp.p[P_OUTW] + o, HDIM, vc, HDIM);
+    const float gctx = dot4(hp.p[P_OUTW] + o, HDIM, vc, HDIM);
     vb[o] = gctx;
     W.gctx[b * HDIM + o] = gctx;
     __syncthreads();
@@ -387,17 +369,17 @@ __global__ __launch_bounds__(HDIM) void hd_bwd_kernel(int D, int L, int64_t B, H
     }
     __syncthreads();
     // q, the residual and feature_extractor
-    const float gx = gxf + hd_dot(hp.p[P_INW] + o, HDIM, va, HDIM);
+    const float gx = gxf + dot4(hp.p[P_INW] + o, HDIM, va, HDIM);
     const float dp2 = S.x[b * HDIM + o] > 0.f ? gx : 0.f;
     vb[o] = dp2;
     W.dp2[b * HDIM + o] = dp2;
     __syncthreads();
-    const float dp1 = S.x1[b * HDIM + o] > 0.f ? hd_dot(hp.p[P_FE2W] + o, HDIM, vb, HDIM) : 0.f;
+    const float dp1 = S.x1[b * HDIM + o] > 0.f ? dot4(hp.p[P_FE2W] + o, HDIM, vb, HDIM) : 0.f;
     vc[o] = dp1;
     W.dp1[b * HDIM + o] = dp1;
     __syncthreads();
     for (int i = o; i < D; i += HDIM)
-        gphi[b * D + i] = make_float2(hd_dot(hp.p[P_FE0W] + i, 2 * D, vc, HDIM), hd_dot(hp.p[P_FE0W] + D + i, 2 * D, vc, HDIM));
+        gphi[b * D + i] = make_float2(dot4(hp.p[P_FE0W] + i, 2 * D, vc, HDIM), dot4(hp.p[P_FE0W] + D + i, 2 * D, vc, HDIM));
 }
 
 // g_P[d] = gK[d] Wk + gV[d] Wv, g_pos[d] = g_P[d] Wp; one workgroup per token.  g: the gradient buffer (gK, gV summed in it)
@@ -410,24 +392,14 @@ __global__ __launch_bounds__(HDIM) void hd_token_kernel(int D, int L, int64_t B,
     sv[o] = g[G.oA + G.gv + (int64_t)d * HDIM + o];
     __syncthreads();
     const float *inw = hp.p[P_INW];
-    const float gp = hd_dot(inw + (int64_t)HDIM * HDIM + o, HDIM, sk, HDIM) + hd_dot(inw + (int64_t)2 * HDIM * HDIM + o, HDIM, sv, HDIM);
+    const float gp = dot4(inw + (int64_t)HDIM * HDIM + o, HDIM, sk, HDIM) + dot4(inw + (int64_t)2 * HDIM * HDIM + o, HDIM, sv, HDIM);
     sp[o] = gp;
     W.gP[(int64_t)d * HDIM + o] = gp;
     __syncthreads();
-    if (o < 2) g[G.opos + 2 * d + o] = hd_dot(hp.p[P_PPW] + o, 2, sp, HDIM);
+    if (o < 2) g[G.opos + 2 * d + o] = dot4(hp.p[P_PPW] + o, 2, sp, HDIM);
 }
 
 // ---- batch-reduced products --------------------------------------------------------------------------------------------------
-struct HbDesc {
-    const float *A, *Bm;     // A[b * lda + m], Bm[b * ldb + n * cs]
-    int M, N, lda, ldb, cs, ldc;
-    int64_t nb;              // rows of the batch
-    int64_t off, boff;       // C [M][ldc] and the bias [M] (column N, a column of ones; boff < 0: none) in a partial row
-    float *part;             // [slabs(nb)][pstride]
-    int64_t pstride;
-    __host__ __device__ int tiles() const { return ((M + 31) / 32) * ((N + (boff >= 0 ? 1 : 0) + 31) / 32); }
-};
-
 struct HbCtx {
     int D, L;
     int64_t B;
@@ -438,12 +410,12 @@ struct HbCtx {
 // phase 0: the batch sums over the signals (and the (signal, target) pairs); phase 1: over the tokens
 __host__ __device__ inline int hb_count(const HbCtx &c, int phase) { return phase == 0 ? 16 + 3 * c.L + 2 : 3; }
 
-__host__ __device__ inline HbDesc hb_desc(const HbCtx &c, int phase, int i) {
+__host__ __device__ inline BpDesc hb_desc(const HbCtx &c, int phase, int i) {
     const HeadSaved S(c.saved, c.D, c.L, c.B);
     const HeadWork W(c.work, c.D, c.L, c.B);
     const HeadGrad G(c.D, c.L);
     const int D = c.D, L = c.L;
-    HbDesc d;
+    BpDesc d;
     d.cs = 1, d.nb = c.B, d.part = W.partA, d.pstride = G.TA, d.boff = -1;
     auto set = [&](const float *A, int M, int lda, const float *Bm, int N, int ldb, int64_t off, int64_t boff) {
         d.A = A, d.M = M, d.lda = lda, d.Bm = Bm, d.N = N, d.ldb = ldb, d.ldc = N, d.off = off, d.boff = boff;
@@ -489,70 +461,16 @@ __host__ __device__ inline HbDesc hb_desc(const HbCtx &c, int phase, int i) {
     return d;
 }
 
-static int64_t hb_tiles(const HbCtx &c, int phase) {
-    int64_t n = 0;
-    for (int i = 0; i < hb_count(c, phase); ++i) n += hb_desc(c, phase, i).tiles();
-    return n;
-}
-
-// grid (tiles, slabs of the longest batch), one wave each
-__global__ __launch_bounds__(64) void hb_kernel(HbCtx c, int phase) {
-    int tile = blockIdx.x, i = 0;
-    const int n = hb_count(c, phase);
-    HbDesc d = hb_desc(c, phase, 0);
-    for (; i + 1 < n && tile >= d.tiles(); d = hb_desc(c, phase, i)) tile -= d.tiles(), ++i;
-    const int64_t b0 = (int64_t)blockIdx.y * HB_SLAB;
-    if (b0 >= d.nb) return;
-    const int64_t b1 = b0 + HB_SLAB < d.nb ? b0 + HB_SLAB : d.nb;
-    const int ne = d.N + (d.boff >= 0 ? 1 : 0), tn = (ne + 31) / 32;
-    const int m0 = 32 * (tile / tn), n0 = 32 * (tile % tn);
-    const int lane = threadIdx.x, r32 = lane & 31, kh = lane >> 5;
-    const bool mv = m0 + r32 < d.M, nv = n0 + r32 < d.N, ones = d.boff >= 0 && n0 + r32 == d.N;
-    const float *ap = d.A + (mv ? m0 + r32 : 0);
-    const float *bp = d.Bm + (nv ? (int64_t)(n0 + r32) * d.cs : 0);
-    f32x16 acc = {0};
-    const int len = (int)(b1 - b0);
-    for (int k0 = 0; k0 < len; k0 += 2 * HB_UNROLL) {
-        float x[HB_UNROLL], y[HB_UNROLL];
-#pragma unroll
-        for (int u = 0; u < HB_UNROLL; ++u) {
-            const int64_t b = b0 + k0 + 2 * u + kh;
-            const bool bv = b < b1;
-            const int64_t bb = bv ? b : b0;
-            x[u] = ap[bb * d.lda];
-            y[u] = bp[bb * d.ldb];
-            if (!(bv && mv)) x[u] = 0.f;
-            if (ones) y[u] = 1.f;
-            if (!(bv && (nv || ones))) y[u] = 0.f;
-        }
-#pragma unroll
-        for (int u = 0; u < HB_UNROLL; ++u) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(x[u], y[u], acc, 0, 0, 0);
-    }
-    // C/D layout: column = lane & 31, row = (q & 3) + 8 (q >> 2) + 4 (lane >> 5)
-    float *out = d.part + (int64_t)blockIdx.y * d.pstride;
-    const int gn = n0 + r32;
-#pragma unroll
-    for (int q = 0; q < 16; ++q) {
-        const int gm = m0 + (q & 3) + 8 * (q >> 2) + 4 * kh;
-        if (gm >= d.M) continue;
-        if (gn < d.N) out[d.off + (int64_t)gm * d.ldc + gn] = acc[q];
-        else if (gn == d.N && d.boff >= 0) out[d.boff + gm] = acc[q];
-    }
-}
-
-// out[o0 + e (+ shift where e >= cut)] = sum over the slabs of part[slab][e], ascending, in float64; up to two regions per launch
-struct HbRegion {
-    const float *part;
-    int64_t total, slabs, o0, cut, shift;
+struct HbTable {
+    HbCtx c;
+    int phase;
+    __host__ __device__ int count() const { return hb_count(c, phase); }
+    __host__ __device__ BpDesc desc(int i) const { return hb_desc(c, phase, i); }
 };
-__global__ __launch_bounds__(TS_THREADS) void hb_sum_kernel(HbRegion r0, HbRegion r1, float *__restrict__ out) {
-    int64_t e = (int64_t)blockIdx.x * TS_THREADS + threadIdx.x;
-    HbRegion r = r0;
-    if (e >= r0.total) e -= r0.total, r = r1;
-    if (e >= r.total) return;
-    double a = 0.0;
-    for (int64_t s = 0; s < r.slabs; ++s) a += (double)r.part[s * r.total + e];
-    out[r.o0 + e + (e >= r.cut ? r.shift : 0)] = (float)a;
+
+// up to two regions of slab sums per launch
+__global__ __launch_bounds__(TS_THREADS) void hb_sum_kernel(BpRegion r0, BpRegion r1, float *__restrict__ out) {
+    bp_sum_regions((int64_t)blockIdx.x * TS_THREADS + threadIdx.x, r0, r1, out);
 }
 
 // ---- launchers ---------------------------------------------------------------------------------------------------------------
@@ -587,19 +505,20 @@ int launch_train_head_bwd(int D, int L, int64_t B, const float *gtau, const floa
                        1.f / (1.f - p), saved, work, gphi);
     ADMM_HIP(hipGetLastError());
     const HbCtx c{D, L, B, reinterpret_cast<const float *>(phi), params[P_POS], saved, work, g};
-    hipLaunchKernelGGL(hb_kernel, dim3((unsigned)hb_tiles(c, 0), (unsigned)HeadWork::slabs(B * L)), dim3(64), 0, st, c, 0);
+    const HbTable tab0{c, 0}, tab1{c, 1};
+    hipLaunchKernelGGL(bp_kernel<HbTable>, dim3((unsigned)bp_tiles(tab0), (unsigned)HeadWork::slabs(B * L)), dim3(64), 0, st, tab0);
     ADMM_HIP(hipGetLastError());
-    const HbRegion rB{W.partB, G.TB, HeadWork::slabs(B * L), 0, G.TB, 0};
-    const HbRegion rA{W.partA, G.TA, HeadWork::slabs(B), G.oA, G.bq, 2 * HDIM * HDIM};   // bq goes behind Wk and Wv
+    const BpRegion rB{W.partB, G.TB, HeadWork::slabs(B * L), 0, G.TB, 0};
+    const BpRegion rA{W.partA, G.TA, HeadWork::slabs(B), G.oA, G.bq, 2 * HDIM * HDIM};   // bq goes behind Wk and Wv
     hipLaunchKernelGGL(hb_sum_kernel, dim3((unsigned)((G.TA + G.TB + TS_THREADS - 1) / TS_THREADS)), dim3(TS_THREADS), 0, st, rB, rA,
                        g);
     ADMM_HIP(hipGetLastError());
     hipLaunchKernelGGL(hd_token_kernel, dim3(D), dim3(HDIM), 0, st, D, L, B, hp, work, g);
     ADMM_HIP(hipGetLastError());
-    hipLaunchKernelGGL(hb_kernel, dim3((unsigned)hb_tiles(c, 1), (unsigned)HeadWork::slabs(D)), dim3(64), 0, st, c, 1);
+    hipLaunchKernelGGL(bp_kernel<HbTable>, dim3((unsigned)bp_tiles(tab1), (unsigned)HeadWork::slabs(D)), dim3(64), 0, st, tab1);
     ADMM_HIP(hipGetLastError());
-    const HbRegion rC{W.partC, G.TC, HeadWork::slabs(D), G.oC, 2 * HDIM * HDIM, HDIM};     // bk, bv follow bq
-    const HbRegion none{nullptr, 0, 0, 0, 0, 0};
+    const BpRegion rC{W.partC, G.TC, HeadWork::slabs(D), G.oC, 2 * HDIM * HDIM, HDIM};     // bk, bv follow bq
+    const BpRegion none{nullptr, 0, 0, 0, 0, 0};
     hipLaunchKernelGGL(hb_sum_kernel, dim3((unsigned)((G.TC + TS_THREADS - 1) / TS_THREADS)), dim3(TS_THREADS), 0, st, rC, none, g);
     ADMM_HIP(hipGetLastError());
     return ADMMNET_OK;

@@ -19,8 +19,9 @@
 //     odd at every tuned geometry, so a matrix starts 8-byte aligned only: the stream is peeled by one element where the
 //     matrix starts on an odd element, and the body moves 16 bytes (two complex numbers) per lane.
 // Every sum runs in a fixed order -- per thread serially, across a wave by xor-shuffles, across the waves serially from
-// LDS -- and the sum over the batch (g_r) in float64 by one workgroup, as rn_sum_kernel (zstep.hip) does.  No atomics.
+// LDS -- and the sum over the batch (g_r) in float64 by one workgroup (colsum of batch_sums.h).  No atomics.
 #include "common.h"
+#include "batch_sums.h"
 #include "rebuild_core.h"
 
 namespace admmnet {
@@ -39,21 +40,6 @@ __device__ __forceinline__ float2 tl_c(int i, int j, int D, const float2 *__rest
         return make_float2(p.x, -p.y);
     }
     return make_float2(0.f, 0.f);
-}
-
-// sum over the workgroup in a fixed order; every thread must call it; the result is valid in thread 0
-template <int THREADS>
-__device__ __forceinline__ float tl_block_sum(float x, float *sh) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o, 64);
-    const int wave = threadIdx.x >> 6;
-    __syncthreads();   // (sh may still be read from a previous sum)
-    if ((threadIdx.x & 63) == 0) sh[wave] = x;
-    __syncthreads();
-    float s = 0.f;
-    if (threadIdx.x == 0)
-        for (int w = 0; w < THREADS / 64; ++w) s += sh[w];
-    return s;
 }
 
 // ---- matrix: A = herm(C - r Z) -------------------------------------------------------------------------------------------
@@ -144,21 +130,14 @@ __global__ __launch_bounds__(TL_PAIR_THREADS) void tl_matrix_bwd_kernel(int n, i
             if (i == j && i < D) gh[i] = sx;
         }
     }
-    const float s = tl_block_sum<TL_PAIR_THREADS>(acc, sh);
+    const float s = block_sum<TL_PAIR_THREADS / 64, false>(acc, sh);
     if (threadIdx.x == 0) part[blockIdx.x] = s;
 }
 
 // out[0] = -(sum of part[0 .. count)) in float64, fixed order (one workgroup)
 __global__ __launch_bounds__(1024) void tl_negsum_kernel(int64_t count, const float *__restrict__ part, float *__restrict__ out) {
     __shared__ double sh[1024];
-    double a = 0.0;
-    for (int64_t i = threadIdx.x; i < count; i += 1024) a += (double)part[i];
-    sh[threadIdx.x] = a;
-    __syncthreads();
-    for (int o = 512; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) sh[threadIdx.x] += sh[threadIdx.x + o];
-        __syncthreads();
-    }
+    colsum<1, 1024>(count, part, sh);
     if (threadIdx.x == 0) out[0] = (float)(-sh[0]);
 }
 
@@ -204,7 +183,7 @@ __global__ __launch_bounds__(TL_STREAM_THREADS) void tl_resnorm_kernel(int n, bo
     // leftovers: element 0 when head = 1, and everything behind the last pair
     for (int e = sp.head + 2 * sp.npair + threadIdx.x; e < sp.total; e += TL_STREAM_THREADS) one(e, G[e]);
     if (sp.head && threadIdx.x == TL_STREAM_THREADS - 1) one(0, G[0]);
-    const float s = tl_block_sum<TL_STREAM_THREADS>(acc, sh);
+    const float s = block_sum<TL_STREAM_THREADS / 64, false>(acc, sh);
     if (threadIdx.x == 0) rn[b] = sqrtf(s);
 }
 
@@ -314,7 +293,7 @@ __global__ __launch_bounds__(TL_STREAM_THREADS) void tl_zupdate_bwd_kernel(int n
         gphi[i] = make_float2(-s * (col.x + row.x), -s * (col.y - row.y));
         gh[i] = -s * gin[(int64_t)i * n + i].x;
     }
-    const float t = tl_block_sum<TL_STREAM_THREADS>(acc, sh);
+    const float t = block_sum<TL_STREAM_THREADS / 64, false>(acc, sh);
     if (threadIdx.x == 0) gsg[b] = t;
 }
 

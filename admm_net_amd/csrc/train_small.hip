@@ -18,10 +18,11 @@
 // the ranks of a sharded batch): slabs of 256 signals, one thread each.
 // Sums over the batch (the parameter gradients) run in a fixed order without atomics: per lane serially, across the wave by
 // the butterfly, across the slab's four waves serially from LDS into one row of `partials` per workgroup; ts_colsum_kernel (one
-// workgroup) then adds the rows in float64, as tl_negsum_kernel / rn_sum_kernel do.  Two runs give the same bits.
+// workgroup) then adds the rows in float64 in colsum's order (batch_sums.h).  Two runs give the same bits.
 // Every access is a 4-byte (float) or 8-byte (float2) one: the [B, D] tensors need no more than their natural alignment.
 #include "common.h"
-#include "slab_partials.h"
+#include "batch_sums.h"
+#include "train_math.h"
 
 namespace admmnet {
 
@@ -30,33 +31,12 @@ constexpr int TS_EIG_PAR = 50;             // g_thr, gW1[16], gb1[16], gW2[16], 
 constexpr int TS_STEP_PAR = 162;           // g_rho, gW1[32][3], gb1[32], gW2[32], gb2
 static_assert(TS_PER_LANE * 64 >= kMaxD + 1, "a wave must cover one row");
 
-__device__ __forceinline__ float ts_softplus(float x) { return x > 20.f ? x : log1pf(expf(x)); }
-__device__ __forceinline__ float ts_sigmoid(float x) { return 1.f / (1.f + expf(-x)); }
-// d softplus(x) / dx
-__device__ __forceinline__ float ts_dsoftplus(float x) { return x > 20.f ? 1.f : ts_sigmoid(x); }
-// d sigmoid(x) / dx = s (1 - s), from e = exp(-|x|) as e / (1 + e)^2: 1 - s itself loses every digit as s nears 1
-__device__ __forceinline__ float ts_dsigmoid(float x) {
-    const float e = expf(-fabsf(x)), d = 1.f + e;
-    return e / (d * d);
-}
-
-// out[c] = sum over rows of part[row][c] in float64, fixed order: thread (c, s) adds the rows s, s + ns, ..., a tree halves
-// the ns slices (count <= 256; one workgroup)
+// out[c] = sum over rows of part[row][c] in float64 in colsum's fixed order (batch_sums.h), ns slices (count <= 256; one workgroup)
 __global__ __launch_bounds__(TS_THREADS) void ts_colsum_kernel(int count, int ns, int64_t rows, const float *__restrict__ part,
                                                                float *__restrict__ out) {
     __shared__ double sh[TS_THREADS];
-    const int c = threadIdx.x % count, s = threadIdx.x / count;
-    const bool live = s < ns;
-    double a = 0.0;
-    if (live)
-        for (int64_t r = s; r < rows; r += ns) a += (double)part[r * count + c];
-    if (live) sh[s * count + c] = a;
-    __syncthreads();
-    for (int o = ns >> 1; o > 0; o >>= 1) {
-        if (live && s < o) sh[s * count + c] += sh[(s + o) * count + c];
-        __syncthreads();
-    }
-    if (live && s == 0) out[c] = (float)sh[c];
+    colsum(count, ns, rows, count, part, sh);
+    if ((int)threadIdx.x < count) out[threadIdx.x] = (float)sh[threadIdx.x];
 }
 
 static int ts_colsum(int count, int64_t rows, const float *part, float *out, hipStream_t st) {
@@ -89,7 +69,7 @@ __global__ __launch_bounds__(TS_THREADS) void ts_phi_kernel(int D, int64_t B, co
                                                             float2 *__restrict__ phi) {
     const int64_t sig = (int64_t)blockIdx.x * TS_SLAB + (threadIdx.x >> 6);
     if (sig >= B) return;
-    const float rho = ts_softplus(rho_raw[0]);
+    const float rho = softplus_f(rho_raw[0]);
     for (int i = threadIdx.x & 63; i < D; i += 64) {
         const int64_t e = sig * D + i;
         const TsPhi p = ts_phi_at(y[e], b[e], gcol[e], zcol[e], rho);
@@ -105,7 +85,7 @@ __global__ __launch_bounds__(TS_THREADS) void ts_phi_bwd_kernel(int D, int64_t B
                                                                 float2 *__restrict__ gzcol, float *__restrict__ part) {
     __shared__ float sh[TS_SLAB];
     const int64_t sig = (int64_t)blockIdx.x * TS_SLAB + (threadIdx.x >> 6);
-    const float raw = rho_raw[0], rho = ts_softplus(raw);
+    const float raw = rho_raw[0], rho = softplus_f(raw);
     float acc = 0.f;
     if (sig < B)
         for (int i = threadIdx.x & 63; i < D; i += 64) {
@@ -117,7 +97,7 @@ __global__ __launch_bounds__(TS_THREADS) void ts_phi_bwd_kernel(int D, int64_t B
             const float dx = p.coef * g.x + p.dcoef * p.inner.x, dy = p.coef * g.y + p.dcoef * p.inner.y;
             acc = fmaf(u.x, dx, fmaf(u.y, dy, acc));
         }
-    const float v[1] = {wave_sum(acc) * ts_dsoftplus(raw)};
+    const float v[1] = {wave_sum(acc) * dsoftplus_f(raw)};
     ts_slab_partials<1>(v, sh, part);
 }
 
@@ -127,7 +107,7 @@ __global__ __launch_bounds__(TS_THREADS) void ts_hinput_kernel(int D, int64_t B,
                                                                float *__restrict__ t) {
     const int64_t sig = (int64_t)blockIdx.x * TS_SLAB + (threadIdx.x >> 6);
     if (sig >= B) return;
-    const float den = ts_softplus(rho_raw[0]) + kEpsRef;
+    const float den = softplus_f(rho_raw[0]) + kEpsRef;
     for (int i = threadIdx.x & 63; i < D; i += 64) {
         const int64_t e = sig * D + i;
         t[e] = gdg[e] + zdg[e] / den;
@@ -141,7 +121,7 @@ __global__ __launch_bounds__(TS_THREADS) void ts_hinput_bwd_kernel(int D, int64_
                                                                    float *__restrict__ part) {
     __shared__ float sh[TS_SLAB];
     const int64_t sig = (int64_t)blockIdx.x * TS_SLAB + (threadIdx.x >> 6);
-    const float raw = rho_raw[0], den = ts_softplus(raw) + kEpsRef;
+    const float raw = rho_raw[0], den = softplus_f(raw) + kEpsRef;
     float acc = 0.f;
     if (sig < B)
         for (int i = threadIdx.x & 63; i < D; i += 64) {
@@ -151,7 +131,7 @@ __global__ __launch_bounds__(TS_THREADS) void ts_hinput_bwd_kernel(int D, int64_
             gzdg[e] = u / den;
             acc = fmaf(u, zdg[e], acc);
         }
-    const float v[1] = {-wave_sum(acc) * ts_dsoftplus(raw) / (den * den)};
+    const float v[1] = {-wave_sum(acc) * dsoftplus_f(raw) / (den * den)};
     ts_slab_partials<1>(v, sh, part);
 }
 
@@ -193,7 +173,7 @@ __global__ __launch_bounds__(TS_THREADS) void ts_hproject_kernel(int D, int64_t 
     const int64_t sig = (int64_t)blockIdx.x * TS_SLAB + (threadIdx.x >> 6);
     if (sig >= B) return;
     const TsProj p = ts_project(D, t + sig * D, m + sig * D, sigma[sig]);
-    const float s = fminf(ts_sigmoid(pw_raw[0]) / (p.c + kEpsRef), 1.f);
+    const float s = fminf(sigmoid_f(pw_raw[0]) / (p.c + kEpsRef), 1.f);
 #pragma unroll
     for (int k = 0; k < TS_PER_LANE - 1; ++k) {
         const int i = (threadIdx.x & 63) + 64 * k;
@@ -216,7 +196,7 @@ __global__ __launch_bounds__(TS_THREADS) void ts_hproject_bwd_kernel(int D, int6
     float gpw = 0.f;
     if (sig < B) {
         const TsProj p = ts_project(D, t + sig * D, m + sig * D, sigma[sig]);
-        const float sp = ts_sigmoid(pw_raw[0]), den = p.c + kEpsRef, q = sp / den;
+        const float sp = sigmoid_f(pw_raw[0]), den = p.c + kEpsRef, q = sp / den;
         float u[TS_PER_LANE - 1], gs = 0.f;
 #pragma unroll
         for (int k = 0; k < TS_PER_LANE - 1; ++k) {
@@ -227,7 +207,7 @@ __global__ __launch_bounds__(TS_THREADS) void ts_hproject_bwd_kernel(int D, int6
         gs = wave_sum(gs);
         const bool open = q <= 1.f;
         const float s = open ? q : 1.f, gc = open ? -gs * sp / (den * den) : 0.f;
-        if (open) gpw = gs * ts_dsigmoid(pw_raw[0]) / den;
+        if (open) gpw = gs * dsigmoid_f(pw_raw[0]) / den;
 #pragma unroll
         for (int k = 0; k < TS_PER_LANE - 1; ++k) {
             const int i = lane + 64 * k;
@@ -253,7 +233,7 @@ __device__ __forceinline__ TsValueNet ts_load_value_net(const float *__restrict_
 #pragma unroll
     for (int j = 0; j < 16; ++j) p.W1[j] = W1[j], p.b1[j] = b1[j], p.W2[j] = W2[j];
     p.b2 = b2[0];
-    p.st = ts_sigmoid(thr[0]);
+    p.st = sigmoid_f(thr[0]);
     return p;
 }
 
@@ -269,7 +249,7 @@ __global__ __launch_bounds__(TS_THREADS) void ts_eigmap_kernel(int n, int64_t B,
         float o = p.b2;
 #pragma unroll
         for (int j = 0; j < 16; ++j) o = fmaf(p.W2[j], fmaxf(fmaf(p.W1[j], ax, p.b1[j]), 0.f), o);
-        wp[sig * n + i] = ts_softplus(x - p.st) * ts_sigmoid(o);
+        wp[sig * n + i] = softplus_f(x - p.st) * sigmoid_f(o);
     }
 }
 
@@ -296,8 +276,8 @@ __global__ __launch_bounds__(TS_THREADS) void ts_eigmap_bwd_kernel(int n, int64_
                 pre[j] = fmaf(p.W1[j], ax, p.b1[j]);
                 o = fmaf(p.W2[j], fmaxf(pre[j], 0.f), o);
             }
-            const float a = ts_softplus(x - p.st), da = ts_dsoftplus(x - p.st), v = ts_sigmoid(o);
-            const float ga = g * v, go = g * a * ts_dsigmoid(o);
+            const float a = softplus_f(x - p.st), da = dsoftplus_f(x - p.st), v = sigmoid_f(o);
+            const float ga = g * v, go = g * a * dsigmoid_f(o);
             float gax = 0.f;
             acc[0] = fmaf(ga, da, acc[0]);
 #pragma unroll
@@ -314,7 +294,7 @@ __global__ __launch_bounds__(TS_THREADS) void ts_eigmap_bwd_kernel(int n, int64_
         }
 #pragma unroll
     for (int c = 0; c < TS_EIG_PAR; ++c) acc[c] = wave_sum(acc[c]);
-    acc[0] *= -ts_dsigmoid(thr[0]);
+    acc[0] *= -dsigmoid_f(thr[0]);
     ts_slab_partials<TS_EIG_PAR>(acc, sh, part);
 }
 
@@ -326,16 +306,9 @@ __device__ __forceinline__ float ts_step_pre(const float *__restrict__ W1, const
     return fmaf(W1[3 * j + 2], u, fmaf(W1[3 * j + 1], f1, fmaf(W1[3 * j], f0, b1[j])));
 }
 
-// sum of the group's rn: float64, thread t adds rn[t], rn[t + 256], ..., a tree halves the 256 slots
+// sum of the group's rn in float64: colsum's order with one column and a slice per thread
 __device__ __forceinline__ double ts_group_sum(const float *__restrict__ rn, int64_t r, double *sh) {
-    double a = 0.0;
-    for (int64_t i = threadIdx.x; i < r; i += TS_THREADS) a += (double)rn[i];
-    sh[threadIdx.x] = a;
-    __syncthreads();
-    for (int o = TS_THREADS / 2; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) sh[threadIdx.x] += sh[threadIdx.x + o];
-        __syncthreads();
-    }
+    colsum<1, TS_THREADS>(r, rn, sh);
     return sh[0];
 }
 __device__ __forceinline__ float ts_group_mean(const float *__restrict__ rn, int64_t r, double *sh) {
@@ -367,22 +340,43 @@ __global__ __launch_bounds__(TS_THREADS) void ts_stepsize_kernel(int64_t B, int6
     __shared__ double shd[TS_THREADS];
     const int64_t s0 = g ? (int64_t)blockIdx.x * g : 0, r = g ? (B - s0 < g ? B - s0 : g) : B;
     const float *rn = rng + s0;
-    const float den = ts_group_mean(rn, r, shd) + kEpsRef, rho = ts_softplus(rho_raw[0]);
+    const float den = ts_group_mean(rn, r, shd) + kEpsRef, rho = softplus_f(rho_raw[0]);
     for (int64_t i = threadIdx.x; i < r; i += TS_THREADS) {
         const float o = ts_step_o(W1, b1, W2, b2, knorm, rho, rn[i] / den);
-        stepg[s0 + i] = rho * (0.5f + 1.5f * ts_sigmoid(o));
+        stepg[s0 + i] = rho * (0.5f + 1.5f * sigmoid_f(o));
     }
 }
 
-// sum over the workgroup in a fixed order, returned to every thread
-__device__ __forceinline__ float ts_block_sum(float x, float *sh) {
-    x = wave_sum(x);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = x;
-    __syncthreads();
-    float s = 0.f;
-    for (int w = 0; w < TS_SLAB; ++w) s += sh[w];
-    return s;
+// Pass 2 of the step-size backward over the r signals a workgroup holds: thread (j, q) = (t / 8, t % 8) takes the sums of hidden
+// unit j over the signals q, q + 8, ..., joined over q by a butterfly, and thread (j, 0) writes gW1[j], gb1[j], gW2[j] into row.
+// at(i) gives signal i's (dy, u).
+template <typename Index, class At>
+__device__ __forceinline__ void ts_step_hidden_sums(Index r, float knorm, float rho, const float *__restrict__ W1,
+                                                    const float *__restrict__ b1, const float *__restrict__ W2, float *row, At at) {
+    const int j = threadIdx.x >> 3, q = threadIdx.x & 7;
+    const float w2 = W2[j];
+    float s1 = 0.f, s2 = 0.f, s3 = 0.f;
+    for (Index i = q; i < r; i += 8) {
+        const float2 v = at(i);
+        const float dy = v.x, u = v.y, pre = ts_step_pre(W1, b1, j, knorm, rho, u);
+        const float dh = pre > 0.f ? dy * w2 : 0.f;
+        s1 += dh;
+        s2 = fmaf(dy, fmaxf(pre, 0.f), s2);
+        s3 = fmaf(dh, u, s3);
+    }
+#pragma unroll
+    for (int o = 4; o > 0; o >>= 1) {
+        s1 += __shfl_xor(s1, o, 64);
+        s2 += __shfl_xor(s2, o, 64);
+        s3 += __shfl_xor(s3, o, 64);
+    }
+    if (q == 0) {
+        row[1 + 3 * j] = knorm * s1;
+        row[2 + 3 * j] = rho * s1;
+        row[3 + 3 * j] = s3;
+        row[97 + j] = s1;
+        row[129 + j] = s2;
+    }
 }
 
 // from g_step [B], with sg_b = sigmoid(o_b), dy_b = g_step_b rho 1.5 sg_b (1 - sg_b), dh_bj = dy_b W2_j [pre_bj > 0],
@@ -405,12 +399,12 @@ __global__ __launch_bounds__(TS_THREADS) void ts_stepsize_bwd_kernel(int64_t B, 
     const int64_t s0 = g ? (int64_t)blockIdx.x * g : 0, r = g ? (B - s0 < g ? B - s0 : g) : B;
     const float *rn = rng + s0, *gstep = gstepg + s0;
     float *grn = grng + s0, *tmp = tmpg + s0;
-    const float mean = ts_group_mean(rn, r, shd), den = mean + kEpsRef, raw = rho_raw[0], rho = ts_softplus(raw);
+    const float mean = ts_group_mean(rn, r, shd), den = mean + kEpsRef, raw = rho_raw[0], rho = softplus_f(raw);
     float a_rho = 0.f, a_b2 = 0.f, a_gm = 0.f;
     for (int64_t i = threadIdx.x; i < r; i += TS_THREADS) {
         const float x = rn[i], u = x / den, gs = gstep[i];
         const float o = ts_step_o(W1, b1, W2, b2, knorm, rho, u);
-        const float sg = ts_sigmoid(o), dy = gs * rho * 1.5f * ts_dsigmoid(o);
+        const float sg = sigmoid_f(o), dy = gs * rho * 1.5f * dsigmoid_f(o);
         const float gu = ts_step_gu(W1, b1, W2, knorm, rho, u, dy);
         a_rho = fmaf(gs, 0.5f + 1.5f * sg, a_rho);
         a_b2 += dy;
@@ -418,37 +412,13 @@ __global__ __launch_bounds__(TS_THREADS) void ts_stepsize_bwd_kernel(int64_t B, 
         tmp[i] = dy;
         grn[i] = gu;
     }
-    a_rho = ts_block_sum(a_rho, sh);
-    a_b2 = ts_block_sum(a_b2, sh);
-    a_gm = ts_block_sum(a_gm, sh);   // (its barriers also order the writes of tmp before pass 2)
+    a_rho = block_sum<TS_SLAB, true>(a_rho, sh);
+    a_b2 = block_sum<TS_SLAB, true>(a_b2, sh);
+    a_gm = block_sum<TS_SLAB, true>(a_gm, sh);   // (its barriers also order the writes of tmp before pass 2)
     float *row = part + (int64_t)blockIdx.x * TS_STEP_PAR;
-    {
-        const int j = threadIdx.x >> 3, q = threadIdx.x & 7;
-        const float w2 = W2[j];
-        float s1 = 0.f, s2 = 0.f, s3 = 0.f;
-        for (int64_t i = q; i < r; i += 8) {
-            const float dy = tmp[i], u = rn[i] / den, pre = ts_step_pre(W1, b1, j, knorm, rho, u);
-            const float dh = pre > 0.f ? dy * w2 : 0.f;
-            s1 += dh;
-            s2 = fmaf(dy, fmaxf(pre, 0.f), s2);
-            s3 = fmaf(dh, u, s3);
-        }
-#pragma unroll
-        for (int o = 4; o > 0; o >>= 1) {
-            s1 += __shfl_xor(s1, o, 64);
-            s2 += __shfl_xor(s2, o, 64);
-            s3 += __shfl_xor(s3, o, 64);
-        }
-        if (q == 0) {
-            row[1 + 3 * j] = knorm * s1;
-            row[2 + 3 * j] = rho * s1;
-            row[3 + 3 * j] = s3;
-            row[97 + j] = s1;
-            row[129 + j] = s2;
-        }
-    }
+    ts_step_hidden_sums(r, knorm, rho, W1, b1, W2, row, [&](int64_t i) { return make_float2(tmp[i], rn[i] / den); });
     if (threadIdx.x == 0) {
-        row[0] = a_rho * ts_dsoftplus(raw);
+        row[0] = a_rho * dsoftplus_f(raw);
         row[161] = a_b2;
     }
     const float gmean = a_gm / (float)r;
@@ -479,12 +449,13 @@ __global__ __launch_bounds__(TS_THREADS) void ts_stepsize_pair_kernel(int64_t B,
                                                                       float *__restrict__ step) {
     const int64_t i = (int64_t)blockIdx.x * TS_THREADS + threadIdx.x;
     if (i >= B) return;
-    const float den = ts_pair_mean(pair) + kEpsRef, rho = ts_softplus(rho_raw[0]);
+    const float den = ts_pair_mean(pair) + kEpsRef, rho = softplus_f(rho_raw[0]);
     const float o = ts_step_o(W1, b1, W2, b2, knorm, rho, rn[i] / den);
-    step[i] = rho * (0.5f + 1.5f * ts_sigmoid(o));
+    step[i] = rho * (0.5f + 1.5f * sigmoid_f(o));
 }
 
-// ts_block_sum in float64
+// block_sum<TS_SLAB, true> in float64.  The butterfly stays written out: ts_stepsize_bwd_pair_front_kernel sits at the SGPR ceiling,
+// and with a call of wave_sum here the compiler spills 20 SGPRs instead of 10 and gives the kernel a 36-byte private segment.
 __device__ __forceinline__ double ts_block_sum_f64(double x, double *sh) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o, 64);
@@ -506,52 +477,28 @@ __global__ __launch_bounds__(TS_THREADS) void ts_stepsize_bwd_pair_front_kernel(
     __shared__ float sh[TS_SLAB], s_dy[TS_THREADS], s_u[TS_THREADS];
     const int64_t s0 = (int64_t)blockIdx.x * TS_THREADS;
     const int r = B - s0 < TS_THREADS ? (int)(B - s0) : TS_THREADS, t = threadIdx.x;
-    const float den = ts_pair_mean(pair) + kEpsRef, raw = rho_raw[0], rho = ts_softplus(raw);
+    const float den = ts_pair_mean(pair) + kEpsRef, raw = rho_raw[0], rho = softplus_f(raw);
     float a_rho = 0.f, dy = 0.f, u = 0.f;
     double a_gm = 0.0;
     if (t < r) {
         const float x = rn[s0 + t], gs = gstep[s0 + t];
         u = x / den;
         const float o = ts_step_o(W1, b1, W2, b2, knorm, rho, u);
-        dy = gs * rho * 1.5f * ts_dsigmoid(o);
+        dy = gs * rho * 1.5f * dsigmoid_f(o);
         const float gu = ts_step_gu(W1, b1, W2, knorm, rho, u, dy);
-        a_rho = gs * (0.5f + 1.5f * ts_sigmoid(o));
+        a_rho = gs * (0.5f + 1.5f * sigmoid_f(o));
         a_gm = (double)gu * (double)x;
         gu_out[s0 + t] = gu;
     }
     s_dy[t] = dy;
     s_u[t] = u;
-    a_rho = ts_block_sum(a_rho, sh);            // (its barriers also order the writes of s_dy, s_u before pass 2)
-    const float a_b2 = ts_block_sum(dy, sh);
+    a_rho = block_sum<TS_SLAB, true>(a_rho, sh);            // (its barriers also order the writes of s_dy, s_u before pass 2)
+    const float a_b2 = block_sum<TS_SLAB, true>(dy, sh);
     a_gm = ts_block_sum_f64(a_gm, shd);
     float *row = part + (int64_t)blockIdx.x * TS_STEP_PAR;
-    {
-        const int j = t >> 3, q = t & 7;
-        const float w2 = W2[j];
-        float s1 = 0.f, s2 = 0.f, s3 = 0.f;
-        for (int i = q; i < r; i += 8) {
-            const float pre = ts_step_pre(W1, b1, j, knorm, rho, s_u[i]);
-            const float dh = pre > 0.f ? s_dy[i] * w2 : 0.f;
-            s1 += dh;
-            s2 = fmaf(s_dy[i], fmaxf(pre, 0.f), s2);
-            s3 = fmaf(dh, s_u[i], s3);
-        }
-#pragma unroll
-        for (int o = 4; o > 0; o >>= 1) {
-            s1 += __shfl_xor(s1, o, 64);
-            s2 += __shfl_xor(s2, o, 64);
-            s3 += __shfl_xor(s3, o, 64);
-        }
-        if (q == 0) {
-            row[1 + 3 * j] = knorm * s1;
-            row[2 + 3 * j] = rho * s1;
-            row[3 + 3 * j] = s3;
-            row[97 + j] = s1;
-            row[129 + j] = s2;
-        }
-    }
+    ts_step_hidden_sums(r, knorm, rho, W1, b1, W2, row, [&](int i) { return make_float2(s_dy[i], s_u[i]); });
     if (t == 0) {
-        row[0] = a_rho * ts_dsoftplus(raw);
+        row[0] = a_rho * dsoftplus_f(raw);
         row[161] = a_b2;
         part_gm[blockIdx.x] = a_gm;
     }

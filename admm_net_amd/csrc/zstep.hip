@@ -5,20 +5,14 @@
 // forward: the local sum is produced in fp64 by one deterministic workgroup and
 // the caller may all-reduce it before the step kernel runs.
 #include "common.h"
+#include "batch_sums.h"
 
 namespace admmnet {
 
 __global__ __launch_bounds__(1024) void rn_sum_kernel(int64_t B, const float *__restrict__ rn,
                                                       double *__restrict__ sum) {
     __shared__ double sh[1024];
-    double a = 0.0;
-    for (int64_t i = threadIdx.x; i < B; i += 1024) a += (double)rn[i];
-    sh[threadIdx.x] = a;
-    __syncthreads();
-    for (int o = 512; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) sh[threadIdx.x] += sh[threadIdx.x + o];
-        __syncthreads();
-    }
+    colsum<1, 1024>(B, rn, sh);
     if (threadIdx.x == 0) {
         sum[0] = sh[0];
         sum[1] = (double)B;   // (the pair the sharded protocol all-reduces: local sum, local count)
@@ -29,16 +23,13 @@ __global__ void mean_kernel(const double *__restrict__ sum, int64_t B, float *__
     if (threadIdx.x == 0 && blockIdx.x == 0) mean[0] = (float)(sum[0] / (double)B);
 }
 
-__global__ __launch_bounds__(256) void zstep_kernel(int D, int64_t B, const float *__restrict__ lw,
-                                                    const float *__restrict__ rn,
-                                                    const float *__restrict__ mean,
-                                                    float *__restrict__ alpha) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= B) return;
+// alpha[i] from signal i's rn and the mean of its group: the one body of zstep_kernel and zstep_group_kernel
+__device__ __forceinline__ void zstep_at(int D, int64_t i, const float *__restrict__ lw, const float *__restrict__ rn, float mean,
+                                         float *__restrict__ alpha) {
     const LayerLayout L{D};
     const float *rs = lw + L.off_rs();   // W1[32][3] b1[32] w2[32] b2[1]
     const float rho = lw[S_RHO_Z];
-    const float f0 = lw[S_KNORM], f1 = rho, f2 = rn[i] / (mean[0] + kEpsRef);
+    const float f0 = lw[S_KNORM], f1 = rho, f2 = rn[i] / (mean + kEpsRef);
     float acc = rs[160];
 #pragma unroll
     for (int j = 0; j < 32; ++j) {
@@ -50,6 +41,14 @@ __global__ __launch_bounds__(256) void zstep_kernel(int D, int64_t B, const floa
     }
     const float sf = 0.5f + 1.5f * sigmoid_f(acc);
     alpha[i] = rho * sf;
+}
+
+__global__ __launch_bounds__(256) void zstep_kernel(int D, int64_t B, const float *__restrict__ lw,
+                                                    const float *__restrict__ rn,
+                                                    const float *__restrict__ mean,
+                                                    float *__restrict__ alpha) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < B) zstep_at(D, i, lw, rn, mean[0], alpha);
 }
 
 int launch_rn_sum(int64_t B, const float *rn, double *sum, hipStream_t st) {
@@ -133,28 +132,13 @@ int launch_mean_from_pairs(const double *pairs, int64_t ngroups, float *mean, hi
     return ADMMNET_OK;
 }
 
-// zstep_kernel with the mean of signal i's group (the same arithmetic; zstep_kernel keeps its own copy so that a call
-// without sub-batches runs exactly the code it ran before)
+// zstep_kernel with the mean of signal i's group; a call without sub-batches keeps zstep_kernel, which reads mean[0] and divides
+// nothing
 __global__ __launch_bounds__(256) void zstep_group_kernel(int D, int64_t B, int64_t g, const float *__restrict__ lw,
                                                           const float *__restrict__ rn, const float *__restrict__ mean,
                                                           float *__restrict__ alpha) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= B) return;
-    const LayerLayout L{D};
-    const float *rs = lw + L.off_rs();   // W1[32][3] b1[32] w2[32] b2[1]
-    const float rho = lw[S_RHO_Z];
-    const float f0 = lw[S_KNORM], f1 = rho, f2 = rn[i] / (mean[i / g] + kEpsRef);
-    float acc = rs[160];
-#pragma unroll
-    for (int j = 0; j < 32; ++j) {
-        float hj = rs[96 + j];
-        hj = fmaf(rs[3 * j + 0], f0, hj);
-        hj = fmaf(rs[3 * j + 1], f1, hj);
-        hj = fmaf(rs[3 * j + 2], f2, hj);
-        acc = fmaf(rs[128 + j], fmaxf(hj, 0.f), acc);
-    }
-    const float sf = 0.5f + 1.5f * sigmoid_f(acc);
-    alpha[i] = rho * sf;
+    if (i < B) zstep_at(D, i, lw, rn, mean[i / g], alpha);
 }
 
 int launch_zstep_groups(const float *lw, int D, int64_t B, int64_t g, const float *rn, const float *mean, float *alpha,

@@ -13,10 +13,10 @@ _klass = r04.klass
 
 
 def klass(name):
+    if "admmnet::hd_" in name or "admmnet::hb_" in name or "bp_kernel<admmnet::HbTable>" in name:
+        return "train_head"
     if "admmnet::th_" in name or "admmnet::bp_" in name:
         return "train_hlayer"
-    if "admmnet::hd_" in name or "admmnet::hb_" in name:
-        return "train_head"
     return _klass(name)
 
 

@@ -13,7 +13,7 @@
 
 using namespace admmnet;
 
-static double wave_sum(const double *lane) {   // sc_wave_sum: xor-butterfly over 64 lanes, as lane 0 sees it
+static double wave_sum(const double *lane) {   // wave_sum (float64): xor-butterfly over 64 lanes, as lane 0 sees it
     double v[64];
     for (int i = 0; i < 64; ++i) v[i] = lane[i];
     for (int o = 32; o > 0; o >>= 1)
