@@ -28,6 +28,7 @@
 #include "common.h"
 
 #include "arrow_core.h"
+#include "lane_reduce.h"
 #include "rebuild_lds.h"
 
 namespace admmnet {
@@ -413,8 +414,7 @@ __global__ __launch_bounds__(AR_THREADS, MODE == AR_FUSED ? 2 : MODE == AR_SOLVE
                 int o;
                 float t;
                 arrow_root(k, jr, alpha, znorm, poles, o, t, nullptr, sub, 2, [](float x) {
-                    return x + __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), 0xB1,
-                                                                                       0xF, 0xF, false));   // quad_perm [1,0,3,2]
+                    return pair_sum(x);
                 });
                 if (sub == 0) put(jr, o, t);
             }
@@ -441,8 +441,7 @@ __global__ __launch_bounds__(AR_THREADS, MODE == AR_FUSED ? 2 : MODE == AR_SOLVE
         const int G = (2 * k <= AR_THREADS) ? 2 : 1;
         const int sub = (G == 2) ? (tid & 1) : 0;
         auto redm = [G](float x) {
-            const float y = __builtin_bit_cast(
-                float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), 0xB1, 0xF, 0xF, false));
+            const float y = pair_get(x);
             return G == 2 ? x * y : x;
         };
         for (int i = (G == 2) ? (tid >> 1) : tid; i < k; i += AR_THREADS / G) {

@@ -13,8 +13,6 @@
 
 namespace admmnet {
 
-using f32x16 = __attribute__((ext_vector_type(16))) float;
-
 constexpr int BP_SLAB = 128;              // rows of the batch summed in float32 by one wave
 constexpr int BP_UNROLL = 8;              // k steps (pairs of rows) whose operands are loaded ahead of their MFMAs
 

@@ -429,6 +429,11 @@ struct PhaseTimer {
 };
 
 // ---- small device helpers ---------------------------------------------------
+// the float register vectors, declared here only: a (re, im) pair for the packed complex arithmetic of lane_reduce.h, the
+// four / sixteen accumulator registers of a 16 x 16 / 32 x 32 MFMA tile
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef float f32x16 __attribute__((ext_vector_type(16)));
 __device__ __forceinline__ float2 cmul(float2 a, float2 b) {
     return make_float2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x);
 }

@@ -51,8 +51,6 @@ HD void tri_tile(int t, int &I, int &J) {
 
 namespace admmnet {
 
-using f32x16 = __attribute__((ext_vector_type(16))) float;
-
 // fs[c] = f(lambda_c), w0f[c] = w0_c f_c, z0s[c] = w0_c for c < n and zeros for n <= c < count (the k-loops read past n
 // unpredicated); wv / w0v: this matrix' eigenvalues and arrow-row entries of V.  The caller's barrier follows.
 template <int THREADS>

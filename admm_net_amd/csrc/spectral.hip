@@ -272,8 +272,6 @@ __global__ __launch_bounds__(SP_THREADS) void sp_deflate_kernel(int n, float2 *_
 // ---- F4: the lower triangle of E^2 = E^H E for the Hermitian E, and ||E^2||_F^2 ----------------------------------------------
 // O[i][j] = sum_c conj(E[c][i]) E[c][j]: both operands are read along rows of E (coalesced), 32 x 32 tiles of the lower
 // triangle dealt round-robin to the four waves, four real v_mfma_f32_32x32x2_f32 per complex k-step.
-using f32x16 = __attribute__((ext_vector_type(16))) float;
-
 __global__ __launch_bounds__(SP_THREADS) void sp_square_kernel(int n, const float2 *__restrict__ Eg, float2 *__restrict__ Og,
                                                                double *__restrict__ vals) {
     __shared__ float red[4];

@@ -38,32 +38,18 @@ constexpr int SF_MAXM = 4;     // column chunks of 64 per row: columns 0 .. 255;
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x2v __attribute__((ext_vector_type(2)));
-using f32x16 = __attribute__((ext_vector_type(16))) float;
 
 __device__ __forceinline__ unsigned sf_pack_bf16(float a, float b) {   // (a -> low half, b -> high half), round to nearest even
-    const f32x2v p = {a, b};
+    const f32x2 p = {a, b};
     return __builtin_bit_cast(unsigned, __builtin_convertvector(p, bf16x2));
 }
 __device__ __forceinline__ float sf_bf16_lo(unsigned u) { return __uint_as_float(u << 16); }
 __device__ __forceinline__ float sf_bf16_hi(unsigned u) { return __uint_as_float(u & 0xffff0000u); }
 
-// Four wave-wide sums for the price of ~one: returns t with t(row 0) = sum a, t(row 1) = sum b, t(row 2) = sum c,
-// t(row 3) = sum d (rows = the four 16-lane groups of the wave; every lane of a row holds the sum).
-__device__ __forceinline__ float sf_reduce4(float a, float b, float c, float d) {
-    // halves: lanes 0..31 keep (a, b), lanes 32..63 keep (c, d)
-    float a2 = a, c2 = c, b2 = b, d2 = d;
-    asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1\n\tv_permlane32_swap_b32 %2, %3\n\ts_nop 1"
-                 : "+v"(a2), "+v"(c2), "+v"(b2), "+v"(d2));
-    float x = a2 + c2, y = b2 + d2;   // x: [a lo+hi | c lo+hi], y: [b | d]
-    asm volatile("s_nop 1\n\tv_permlane16_swap_b32 %0, %1\n\ts_nop 1" : "+v"(x), "+v"(y));
-    return pn_row16_sum(x + y);       // rows: a, b, c, d
-}
-
-// block-wide sums of four values: every thread gets all four (through LDS; two barriers)
+// block-wide sums of four values: every thread gets all four (wave_sum4 of lane_reduce.h, then LDS; two barriers)
 template <int W>
 __device__ __forceinline__ void sf_block_sum4(float &a, float &b, float &c, float &d, float *red /* [4][W] */) {
-    const float t = sf_reduce4(a, b, c, d);
+    const float t = wave_sum4(a, b, c, d);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     __syncthreads();
     if ((lane & 15) == 0) red[(lane >> 4) * W + wave] = t;
@@ -82,7 +68,7 @@ __device__ __forceinline__ void sf_block_sum4(float &a, float &b, float &c, floa
 // six values in one round (two barriers)
 template <int W>
 __device__ __forceinline__ void sf_block_sum8(float &a, float &b, float &c, float &d, float &e, float &f, float *red /* [8][W] */) {
-    const float t = sf_reduce4(a, b, c, d), u = sf_reduce4(e, f, 0.f, 0.f);
+    const float t = wave_sum4(a, b, c, d), u = wave_sum4(e, f, 0.f, 0.f);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     __syncthreads();
     if ((lane & 15) == 0) {
@@ -266,15 +252,15 @@ __global__ __launch_bounds__(64 * W, W == 12 ? 1 : 3) void sp_fused_kernel(int D
         int tid_o = tid_k;
         asm volatile("" : "+v"(tid_o));
         const int tid = tid_o, lane = tid & 63;
-        v2f x0[SF_MAXM], x1[SF_MAXM], c0[SF_MAXM], c1[SF_MAXM];
+        f32x2 x0[SF_MAXM], x1[SF_MAXM], c0[SF_MAXM], c1[SF_MAXM];
 #pragma unroll
         for (int m = 0; m < SF_MAXM; ++m) {
             const int j = lane + 64 * m;
             const bool v = m < MM && j < n;
-            x0[m] = v ? pk2(cv.X0[j]) : v2f{0.f, 0.f};
-            x1[m] = v ? pk2(cv.X1[j]) : v2f{0.f, 0.f};
-            c0[m] = v2f{0.f, 0.f};
-            c1[m] = v2f{0.f, 0.f};
+            x0[m] = v ? pk2(cv.X0[j]) : f32x2{0.f, 0.f};
+            x1[m] = v ? pk2(cv.X1[j]) : f32x2{0.f, 0.f};
+            c0[m] = f32x2{0.f, 0.f};
+            c1[m] = f32x2{0.f, 0.f};
         }
         float trl = 0.f;
         // (the sweep in three instances: the first pass with the folded Z update carries the rows of the old G as well, and the
@@ -323,9 +309,9 @@ __global__ __launch_bounds__(64 * W, W == 12 ? 1 : 3) void sp_fused_kernel(int D
                     zw[(unsigned)jc] = zn;
                 }
             }
-            const v2f xi0 = pk2(cv.X0[i]), xi1 = pk2(cv.X1[i]);
+            const f32x2 xi0 = pk2(cv.X0[i]), xi1 = pk2(cv.X1[i]);
             const float hi = cv.hh[i];
-            v2f r0 = {0.f, 0.f}, r1 = {0.f, 0.f};
+            f32x2 r0 = {0.f, 0.f}, r1 = {0.f, 0.f};
 #pragma unroll
             for (int m = 0; m < NM; ++m) {
                 if (64 * m <= i) {   // (wave-uniform)
@@ -334,10 +320,10 @@ __global__ __launch_bounds__(64 * W, W == 12 ? 1 : 3) void sp_fused_kernel(int D
                     float2 a = sf_a_elem(i, j, D, zv, ir, corner, hi, (i == D && j < D) ? cv.ph[j] : make_float2(0.f, 0.f));
                     if (j > i) a = make_float2(0.f, 0.f);
                     if (j == i) trl += a.x;
-                    const v2f av = pk2(a);
+                    const f32x2 av = pk2(a);
                     r0 = pk_cfma(r0, av, x0[m]);
                     r1 = pk_cfma(r1, av, x1[m]);
-                    const v2f ac = (j < i) ? av : v2f{0.f, 0.f};
+                    const f32x2 ac = (j < i) ? av : f32x2{0.f, 0.f};
                     c0[m] = pk_cfma_conj(c0[m], ac, xi0);
                     c1[m] = pk_cfma_conj(c1[m], ac, xi1);
                 }
@@ -358,7 +344,7 @@ __global__ __launch_bounds__(64 * W, W == 12 ? 1 : 3) void sp_fused_kernel(int D
                 r0.x += a * xa.x; r0.y += a * xa.y;
                 r1.x += a * xb.x; r1.y += a * xb.y;
             }
-            const float t = sf_reduce4(r0.x, r0.y, r1.x, r1.y);
+            const float t = wave_sum4(r0.x, r0.y, r1.x, r1.y);
             if ((lane & 15) == 0) {   // rows of the wave: Y0.re, Y0.im, Y1.re, Y1.im of row i (this wave owns row i)
                 float *dst = reinterpret_cast<float *>((lane & 32) ? cv.Y1 : cv.Y0);
                 dst[2 * i + ((lane >> 4) & 1)] = t;

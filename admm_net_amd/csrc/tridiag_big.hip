@@ -19,62 +19,14 @@
 #include <string.h>
 
 #include "common.h"
+#include "lane_reduce.h"
 
 namespace admmnet {
 
 constexpr int TB_THREADS = 1024;
 
-__device__ __forceinline__ float row32_sum(float x) {   // all-reduce over the 32 lanes of a half wave
-    x += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), 0x128, 0xF, 0xF, false));
-    x += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), 0x124, 0xF, 0xF, false));
-    x += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), 0x122, 0xF, 0xF, false));
-    x += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), 0x121, 0xF, 0xF, false));
-    // every lane of a 16-lane row now holds its row's sum; add the partner row (0 <-> 1, 2 <-> 3) with
-    // v_permlane16_swap (gfx950: odd rows of the first operand <-> even rows of the second) instead of a
-    // ds_bpermute round trip through the LDS pipeline:  (a, b) = (x, x) -> a = [x0 x0 x2 x2], b = [x1 x1 x3 x3]
-    float a = x, b = x;
-    asm volatile("s_nop 1\n\tv_permlane16_swap_b32 %0, %1\n\ts_nop 1" : "+v"(a), "+v"(b));
-    return a + b;
-}
-// x + (x of the lane 32 away): v_permlane32_swap exchanges the upper half of the first operand with the lower
-// half of the second
-__device__ __forceinline__ float half_pair_sum(float x) {
-    float a = x, b = x;
-    asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1\n\ts_nop 1" : "+v"(a), "+v"(b));
-    return a + b;
-}
-__device__ __forceinline__ float wave_sum_fast(float x) { return half_pair_sum(row32_sum(x)); }   // all 64 lanes
-
-typedef float v2 __attribute__((ext_vector_type(2)));   // packed complex arithmetic, see tridiag_reg.hip
-__device__ __forceinline__ v2 b_tov2(float2 a) { return v2{a.x, a.y}; }
-__device__ __forceinline__ float2 b_tof2(v2 a) { return make_float2(a.x, a.y); }
-__device__ __forceinline__ v2 b_rot(v2 v) { return v2{-v.y, v.x}; }
-__device__ __forceinline__ v2 b_rotc(v2 v) { return v2{v.y, -v.x}; }
-__device__ __forceinline__ v2 b_cmac(v2 acc, v2 m, v2 v, v2 vj) {   // acc + m v, vj = rot(v)
-    acc = __builtin_elementwise_fma(m.xx, v, acc);
-    return __builtin_elementwise_fma(m.yy, vj, acc);
-}
-__device__ __forceinline__ v2 b_cmacc(v2 acc, v2 a, v2 aj, v2 b) {   // acc + a conj(b), aj = rotc(a)
-    acc = __builtin_elementwise_fma(b.xx, a, acc);
-    return __builtin_elementwise_fma(b.yy, aj, acc);
-}
-
-// operand-select forms (see tridiag_reg.hip): complex products straight from (re, im) pairs, no rotated copies.
-// Their results are invisible to the compiler's hazard recogniser: never feed one directly into a DPP read.
-__device__ __forceinline__ v2 b_cmac_sel(v2 acc, v2 m, v2 v) {   // acc + m v
-    asm("v_pk_fma_f32 %0, %1, %2, %0 op_sel_hi:[0,1,1]\n\t"
-        "v_pk_fma_f32 %0, %1, %2, %0 op_sel:[1,1,0] op_sel_hi:[1,0,1] neg_lo:[0,1,0]"
-        : "+v"(acc)
-        : "v"(m), "v"(v));
-    return acc;
-}
-__device__ __forceinline__ v2 b_cmsubc_sel(v2 acc, v2 a, v2 b) {   // acc - a conj(b)
-    asm("v_pk_fma_f32 %0, %2, %1, %0 op_sel_hi:[0,1,1] neg_lo:[1,0,0] neg_hi:[1,0,0]\n\t"
-        "v_pk_fma_f32 %0, %2, %1, %0 op_sel:[1,1,0] op_sel_hi:[1,0,1] neg_lo:[1,0,0] neg_hi:[1,1,0]"
-        : "+v"(acc)
-        : "v"(a), "v"(b));
-    return acc;
-}
+// Lane sums (row32_sum, swap32_sum, wave_sum_swap) and the packed complex arithmetic of ungtr_big_kernel: lane_reduce.h
+// (rule 3 there: never feed an asm product directly into a DPP read).
 
 template <int NA>
 struct TbShared {
@@ -138,7 +90,7 @@ __device__ __forceinline__ void tb_step(float2 (&m)[tb_nslot(NA)], float2 *__res
         const float2 x = col[i];
         pn += x.x * x.x + x.y * x.y;
     }
-    const float xn2 = wave_sum_fast(pn);
+    const float xn2 = wave_sum_swap(pn);
     const float2 alpha = sh.head[par];
     float beta, tr, tim, sr, si;
     householder_c(alpha.x, alpha.y, xn2, beta, tr, tim, sr, si);
@@ -189,8 +141,8 @@ __device__ __forceinline__ void tb_step(float2 (&m)[tb_nslot(NA)], float2 *__res
             float2 t = make_float2(0.f, 0.f);
 #pragma unroll
             for (int a = b + 1; a < NA; ++a) t = cmacc(t, TB_GET(a, b), vr[a]);   // conj(M_ij) v_i -> row j
-            t.x = half_pair_sum(t.x);
-            t.y = half_pair_sum(t.y);
+            t.x = swap32_sum(t.x);
+            t.y = swap32_sum(t.y);
             if (lane < 32) sh.cpart[wave][32 * b + tj] = t;
             __builtin_amdgcn_sched_barrier(0);
         }
@@ -212,8 +164,8 @@ __device__ __forceinline__ void tb_step(float2 (&m)[tb_nslot(NA)], float2 *__res
             sh.pfull[tid] = p;
             dotp = cmacc(dotp, p, vat(tid));
         }
-        dotp.x = wave_sum_fast(dotp.x);
-        dotp.y = wave_sum_fast(dotp.y);
+        dotp.x = wave_sum_swap(dotp.x);
+        dotp.y = wave_sum_swap(dotp.y);
         if (lane == 0) sh.dotbuf[wave] = dotp;
     }
     __syncthreads();   // (C)
@@ -317,47 +269,47 @@ __device__ __forceinline__ void ub_step2(float2 (&p)[4][NB], int u, int D, const
     const float2 tau1 = Mg[(int64_t)D * D + u];
     const float2 tau2 = has2 ? Mg[(int64_t)D * D + u2] : make_float2(0.f, 0.f);
     if (tau1.x == 0.f && tau1.y == 0.f && tau2.x == 0.f && tau2.y == 0.f) return;   // uniform
-    v2 va[NB], vb[NB];
+    f32x2 va[NB], vb[NB];
 #pragma unroll
     for (int b = B0; b < NB; ++b) {
         const int j = 32 * b + tj;
-        va[b] = (j < D) ? b_tov2(Mg[(int64_t)u * D + j]) : v2{0.f, 0.f};
-        vb[b] = (j < D) ? b_tov2(Mg[(int64_t)u2 * D + j]) : v2{0.f, 0.f};
+        va[b] = (j < D) ? pk2(Mg[(int64_t)u * D + j]) : f32x2{0.f, 0.f};
+        vb[b] = (j < D) ? pk2(Mg[(int64_t)u2 * D + j]) : f32x2{0.f, 0.f};
     }
     // s12 = v1^H v2 (every lane of a 32-lane row ends up with the full sum)
-    v2 s12 = {0.f, 0.f};
+    f32x2 s12 = {0.f, 0.f};
 #pragma unroll
-    for (int b = B0; b < NB; ++b) s12 = b_cmacc(s12, vb[b], b_rotc(vb[b]), va[b]);
+    for (int b = B0; b < NB; ++b) s12 = pk_cfma_open(s12, va[b], vb[b], rotc(vb[b]));
     s12.x = row32_sum(s12.x);
     s12.y = row32_sum(s12.y);
-    const v2 c1 = v2{tau1.x, -tau1.y}, c2 = v2{tau2.x, -tau2.y};
+    const f32x2 c1 = f32x2{tau1.x, -tau1.y}, c2 = f32x2{tau2.x, -tau2.y};
 #pragma unroll
     for (int a = 0; a < 4; ++a) {
         // row r of P is still e_r while u > r (v_u vanishes above its unit entry): row blocks above the
         // reflector's block have nothing to do (uniform per workgroup)
         if (2 * a + g < B0) continue;
-        v2 y1 = {0.f, 0.f}, y2 = {0.f, 0.f};
+        f32x2 y1 = {0.f, 0.f}, y2 = {0.f, 0.f};
 #pragma unroll
         for (int b = B0; b < NB - 1; ++b) {
-            y1 = b_cmac_sel(y1, b_tov2(p[a][b]), va[b]);
-            y2 = b_cmac_sel(y2, b_tov2(p[a][b]), vb[b]);
+            y1 = pk_cfma(y1, pk2(p[a][b]), va[b]);
+            y2 = pk_cfma(y2, pk2(p[a][b]), vb[b]);
         }
         // last term by the compiler: the DPP reduction reads y1 / y2 next
-        y1 = b_cmac(y1, b_tov2(p[a][NB - 1]), va[NB - 1], b_rot(va[NB - 1]));
-        y2 = b_cmac(y2, b_tov2(p[a][NB - 1]), vb[NB - 1], b_rot(vb[NB - 1]));
+        y1 = pk_cfma_open(y1, pk2(p[a][NB - 1]), va[NB - 1], rot(va[NB - 1]));
+        y2 = pk_cfma_open(y2, pk2(p[a][NB - 1]), vb[NB - 1], rot(vb[NB - 1]));
         y1.x = row32_sum(y1.x);
         y1.y = row32_sum(y1.y);
         y2.x = row32_sum(y2.x);
         y2.y = row32_sum(y2.y);
-        const v2 t1 = b_tov2(cmul(b_tof2(c1), b_tof2(y1)));
-        const float2 cor = cmul(b_tof2(t1), b_tof2(s12));
-        const v2 t2 = b_tov2(cmul(b_tof2(c2), make_float2(y2.x - cor.x, y2.y - cor.y)));
+        const f32x2 t1 = pk2(cmul(unpk2(c1), unpk2(y1)));
+        const float2 cor = cmul(unpk2(t1), unpk2(s12));
+        const f32x2 t2 = pk2(cmul(unpk2(c2), make_float2(y2.x - cor.x, y2.y - cor.y)));
 #pragma unroll
         for (int b = B0; b < NB; ++b) {
-            v2 x = b_tov2(p[a][b]);
-            x = b_cmsubc_sel(x, t1, va[b]);
-            x = b_cmsubc_sel(x, t2, vb[b]);
-            p[a][b] = b_tof2(x);
+            f32x2 x = pk2(p[a][b]);
+            x = pk_cfms_conj(x, va[b], t1);
+            x = pk_cfms_conj(x, vb[b], t2);
+            p[a][b] = unpk2(x);
         }
     }
 }

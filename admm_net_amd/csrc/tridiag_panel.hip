@@ -46,8 +46,6 @@
 
 namespace admmnet {
 
-using f32x4 = __attribute__((ext_vector_type(4))) float;
-
 constexpr int PN_D = 256;
 constexpr int PN_PITCH = 18;       // float2 per panel row: 16 columns + 2 pad (144 B rows: 16-byte aligned, spread over banks)
 constexpr int PN_TAIL_TILES = 36;  // lower block triangle of the 128 x 128 trailing matrix handed from stage to stage
@@ -79,28 +77,6 @@ struct PnShared {
     float2 alpha;
 };
 
-// x + (x of the neighbouring lane l ^ 1): DPP quad_perm [1, 0, 3, 2]
-__device__ __forceinline__ float pn_pair_sum(float x) {
-    return x + __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), 0xB1, 0xF, 0xF, false));
-}
-__device__ __forceinline__ float pn_wave_sum(float x) { return pn_group_sum(pn_row16_sum(x)); }
-
-__device__ __forceinline__ float2 pn_fma_c(float2 acc, float2 a, float2 b) {      // acc + a b
-    acc.x = fmaf(a.x, b.x, fmaf(-a.y, b.y, acc.x));
-    acc.y = fmaf(a.x, b.y, fmaf(a.y, b.x, acc.y));
-    return acc;
-}
-__device__ __forceinline__ float2 pn_fms_cc(float2 acc, float2 a, float2 b) {    // acc - a conj(b)
-    acc.x = fmaf(-a.x, b.x, fmaf(-a.y, b.y, acc.x));
-    acc.y = fmaf(a.x, b.y, fmaf(-a.y, b.x, acc.y));
-    return acc;
-}
-__device__ __forceinline__ float2 pn_fms_c(float2 acc, float2 a, float2 b) {     // acc - a b
-    acc.x = fmaf(-a.x, b.x, fmaf(a.y, b.y, acc.x));
-    acc.y = fmaf(-a.x, b.y, fmaf(-a.y, b.x, acc.y));
-    return acc;
-}
-
 // householder_c (eig_core.h) without branches, so that the scheduler can run its dependent chain in the shadow of other
 // work of the same basic block: same arithmetic in the normal range (q2 rsqrt(q2) with one Newton step), power-of-two
 // pre / post scaling instead of the exact-sqrt fallback outside it, the H = I case by selects at the end.
@@ -123,16 +99,17 @@ __device__ __forceinline__ void pn_householder(float ar, float ai, float xnorm2,
     si = ident ? 0.f : -di * iden;
 }
 
-__device__ __forceinline__ v2f pn_lo(f32x4 a) { return v2f{a.x, a.y}; }
-__device__ __forceinline__ v2f pn_hi(f32x4 a) { return v2f{a.z, a.w}; }
+__device__ __forceinline__ f32x2 pn_lo(f32x4 a) { return f32x2{a.x, a.y}; }
+__device__ __forceinline__ f32x2 pn_hi(f32x4 a) { return f32x2{a.z, a.w}; }
 // one 16 x 16 tile (tre, tim: rows 4 g + q of column c16) in the matrix-vector product, packed FMAs over row pairs:
 //   ROW form   P[q] += T[q][c] vJ[c]            (Pr, Pi: rows 01 | 23; a diagonal tile is stored at half its value, so
 //                                                 that its two forms add up to T v: see the load)
 //   COL form   C    += sum_q conj(T[q][c]) vI[q]  (vIr, vIi: the four row entries of v, planar pairs; Cr, Ci pairs)
-__device__ __forceinline__ void pn_tile_mv(f32x4 tre, f32x4 tim, float2 vJ, v2f vIr01, v2f vIr23, v2f vIi01,
-                                           v2f vIi23, v2f &Pr01, v2f &Pr23, v2f &Pi01, v2f &Pi23, v2f &Cr, v2f &Ci) {
-    const v2f r01 = pn_lo(tre), r23 = pn_hi(tre), i01 = pn_lo(tim), i23 = pn_hi(tim);
-    const v2f jx = v2f{vJ.x, vJ.x}, jy = v2f{vJ.y, vJ.y};
+__device__ __forceinline__ void pn_tile_mv(f32x4 tre, f32x4 tim, float2 vJ, f32x2 vIr01, f32x2 vIr23, f32x2 vIi01,
+                                           f32x2 vIi23, f32x2 &Pr01, f32x2 &Pr23, f32x2 &Pi01, f32x2 &Pi23, f32x2 &Cr,
+                                           f32x2 &Ci) {
+    const f32x2 r01 = pn_lo(tre), r23 = pn_hi(tre), i01 = pn_lo(tim), i23 = pn_hi(tim);
+    const f32x2 jx = f32x2{vJ.x, vJ.x}, jy = f32x2{vJ.y, vJ.y};
     Pr01 = __builtin_elementwise_fma(r01, jx, Pr01);
     Pi01 = __builtin_elementwise_fma(r01, jy, Pi01);
     Pr23 = __builtin_elementwise_fma(r23, jx, Pr23);
@@ -150,39 +127,6 @@ __device__ __forceinline__ void pn_tile_mv(f32x4 tre, f32x4 tim, float2 vJ, v2f 
     Ci = __builtin_elementwise_fma(r23, vIi23, Ci);
     Cr = __builtin_elementwise_fma(i23, vIi23, Cr);
     Ci = __builtin_elementwise_fma(-i23, vIr23, Ci);
-}
-
-// Four per-lane partial vectors (one per block column, each to be summed over the four 16-lane rows of the wave)
-// reduced together: 3 swaps + 3 adds instead of 8 + 8.  Result: row 0 holds the total of x0, row 1 of x2, row 2 of x1,
-// row 3 of x3 (v_permlane32_swap: upper half of the first operand <-> lower half of the second; v_permlane16_swap: odd
-// rows of the first <-> even rows of the second).
-__device__ __forceinline__ float pn_quad_group_sum(float x0, float x1, float x2, float x3) {
-    asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1\n\ts_nop 1" : "+v"(x0), "+v"(x1));
-    asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1\n\ts_nop 1" : "+v"(x2), "+v"(x3));
-    float a = x0 + x1, b = x2 + x3;
-    asm volatile("s_nop 1\n\tv_permlane16_swap_b32 %0, %1\n\ts_nop 1" : "+v"(a), "+v"(b));
-    return a + b;
-}
-
-// ... two such quadruples (re / im) in the same two asm blocks
-__device__ __forceinline__ void pn_quad_group_sum2(const float (&x)[4], const float (&y)[4], float &tx, float &ty) {
-    float x0 = x[0], x1 = x[1], x2 = x[2], x3 = x[3], y0 = y[0], y1 = y[1], y2 = y[2], y3 = y[3];
-    asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1\n\tv_permlane32_swap_b32 %2, %3\n\t"
-                 "v_permlane32_swap_b32 %4, %5\n\tv_permlane32_swap_b32 %6, %7\n\ts_nop 1"
-                 : "+v"(x0), "+v"(x1), "+v"(x2), "+v"(x3), "+v"(y0), "+v"(y1), "+v"(y2), "+v"(y3));
-    float a = x0 + x1, b = x2 + x3, c = y0 + y1, d = y2 + y3;
-    asm volatile("s_nop 1\n\tv_permlane16_swap_b32 %0, %1\n\tv_permlane16_swap_b32 %2, %3\n\ts_nop 1"
-                 : "+v"(a), "+v"(b), "+v"(c), "+v"(d));
-    tx = a + b;
-    ty = c + d;
-}
-
-// One step of the transposing butterfly sum: this lane keeps `lo` (hi lanes: `hi`), its DPP partner sends the value it
-// does not keep; returns kept + received.
-template <int CTRL>
-__device__ __forceinline__ float pn_keep_add(bool hi_lane, float lo, float hi) {
-    const float keep = hi_lane ? hi : lo, send = hi_lane ? lo : hi;
-    return keep + __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, send), CTRL, 0xF, 0xF, false));
 }
 
 // slot s of wave w: tile (IB, s) for s <= IB, tile (IA, NT - s) otherwise   (IA = w, IB = NT - 1 - w)
@@ -293,7 +237,7 @@ __global__ __launch_bounds__(32 * NT, 2) void tridiag_panel_kernel(float2 *__res
             const int r2 = tid - DL, c2 = 16 * p + j + 1;
             float2 x = sh.Ap[r2][j + 1];
             if (r2 >= c2) {
-                v2f acc = v2f{0.f, 0.f}, acc2 = v2f{0.f, 0.f};
+                f32x2 acc = f32x2{0.f, 0.f}, acc2 = f32x2{0.f, 0.f};
                 for (int j0 = 0; j0 < j; j0 += 4) {   // four columns per pass: all 16 loads in flight together
                     float2 vr[4], wr[4], vc[4], wc[4];    // (columns >= j of the panel are zero: no masks)
 #pragma unroll
@@ -341,7 +285,7 @@ __global__ __launch_bounds__(32 * NT, 2) void tridiag_panel_kernel(float2 *__res
             if (tid < DL) {
                 float2 x = (p >= 0) ? (j > 0 ? sh.xnext[r] : sh.Ap[r][j]) : sh.colbuf[r];
                 if (r >= c && p >= 0 && j > 0) {   // reflector j - 1 from registers: (V, W)[c][j - 1] = (hu, wu)
-                    v2f a = pk_cfma_conj(v2f{0.f, 0.f}, pk2(wu), pk2(vreg));
+                    f32x2 a = pk_cfma_conj(f32x2{0.f, 0.f}, pk2(wu), pk2(vreg));
                     a = pk_cfma_conj(a, pk2(hu), pk2(wreg));
                     x.x -= a.x;
                     x.y -= a.y;
@@ -356,7 +300,7 @@ __global__ __launch_bounds__(32 * NT, 2) void tridiag_panel_kernel(float2 *__res
                 if (HEAD && p < 0 && r == 0) sh.dbuf[0] = corner;
                 if (r == u) sh.alpha = x;
                 float pn = (r > u) ? (x.x * x.x + x.y * x.y) : 0.f;
-                pn = pn_wave_sum(pn);
+                pn = wave_sum_swap(pn);
                 if (lane == 0) sh.red[wave] = pn;
             }
             if (u >= DL) break;        // c = DL - 1: only d[D] was due (uniform)
@@ -375,7 +319,7 @@ __global__ __launch_bounds__(32 * NT, 2) void tridiag_panel_kernel(float2 *__res
 #pragma unroll
                     for (int q0 = 0, ps = 0; q0 < 32; q0 += 4 * NW, ++ps) {   // (one pass with eight waves)
                         const int q = (q0 + 4 * wave + g) & 31, jj = q & 15;
-                        v2f acc = v2f{0.f, 0.f}, acc2 = v2f{0.f, 0.f};
+                        f32x2 acc = f32x2{0.f, 0.f}, acc2 = f32x2{0.f, 0.f};
                         // 8-wave stage: only the dots of the panel's existing columns touch LDS (both panels + x are 64 KB
                         // per reflector if every lane group reads: -2 %); the smaller stages lose more from the branch
                         // between the reflector chain and these loads than they gain (+7 %)
@@ -421,7 +365,7 @@ __global__ __launch_bounds__(32 * NT, 2) void tridiag_panel_kernel(float2 *__res
 #pragma unroll
                 for (int q0 = 0, ps = 0; q0 < 32; q0 += 4 * NW, ++ps) {
                     const int qq = q0 + 4 * wave + g, jj = qq & 15;
-                    const float sx = pn_row16_sum(dacc[ps].x), sy = pn_row16_sum(dacc[ps].y);
+                    const float sx = row16_sum(dacc[ps].x), sy = row16_sum(dacc[ps].y);
                     if (c16 == 0 && qq < 32 && jj < j && p >= 0) sh.g[qq] = make_float2(sx, sy);
                 }
             }
@@ -444,16 +388,16 @@ __global__ __launch_bounds__(32 * NT, 2) void tridiag_panel_kernel(float2 *__res
             // ---- D: y = M v with the resident half (+ the panel dots W^H v, V^H v)
             {
                 const int J0 = u >> 4;
-                v2f Ar01, Ar23, Ai01, Ai23, Br01, Br23, Bi01, Bi23;   // v at the rows of block rows IA / IB (planar pairs)
+                f32x2 Ar01, Ar23, Ai01, Ai23, Br01, Br23, Bi01, Bi23;   // v at the rows of block rows IA / IB (planar pairs)
                 {
                     const float2 *va = &sh.vbuf[16 * IA + 4 * g], *vb = &sh.vbuf[16 * IB + 4 * g];
                     const float2 a0 = va[0], a1 = va[1], a2 = va[2], a3 = va[3];
                     const float2 b0 = vb[0], b1 = vb[1], b2 = vb[2], b3 = vb[3];
-                    Ar01 = v2f{a0.x, a1.x}; Ar23 = v2f{a2.x, a3.x}; Ai01 = v2f{a0.y, a1.y}; Ai23 = v2f{a2.y, a3.y};
-                    Br01 = v2f{b0.x, b1.x}; Br23 = v2f{b2.x, b3.x}; Bi01 = v2f{b0.y, b1.y}; Bi23 = v2f{b2.y, b3.y};
+                    Ar01 = f32x2{a0.x, a1.x}; Ar23 = f32x2{a2.x, a3.x}; Ai01 = f32x2{a0.y, a1.y}; Ai23 = f32x2{a2.y, a3.y};
+                    Br01 = f32x2{b0.x, b1.x}; Br23 = f32x2{b2.x, b3.x}; Bi01 = f32x2{b0.y, b1.y}; Bi23 = f32x2{b2.y, b3.y};
                 }
-                const v2f z2 = v2f{0.f, 0.f};
-                v2f PAr01 = z2, PAr23 = z2, PAi01 = z2, PAi23 = z2, PBr01 = z2, PBr23 = z2, PBi01 = z2, PBi23 = z2;
+                const f32x2 z2 = f32x2{0.f, 0.f};
+                f32x2 PAr01 = z2, PAr23 = z2, PAi01 = z2, PAi23 = z2, PBr01 = z2, PBr23 = z2, PBi01 = z2, PBi23 = z2;
 #pragma unroll
                 for (int JQ = 0; JQ < NT; JQ += 4) {
                     if (JQ + 3 >= J0 && JQ <= IB) {   // (uniform) four block columns per pass: one joint lane reduction
@@ -464,7 +408,7 @@ __global__ __launch_bounds__(32 * NT, 2) void tridiag_panel_kernel(float2 *__res
 #pragma unroll
                         for (int k = 0; k < 4; ++k) {
                             const int J = JQ + k;
-                            v2f Cr = z2, Ci = z2;
+                            f32x2 Cr = z2, Ci = z2;
                             if (J >= J0 && J <= IB) {   // (uniform)
                                 const float2 vJ = vJq[k];
                                 pn_tile_mv(tr[J], ti[J], vJ, Br01, Br23, Bi01, Bi23, PBr01, PBr23, PBi01, PBi23, Cr, Ci);
@@ -476,7 +420,7 @@ __global__ __launch_bounds__(32 * NT, 2) void tridiag_panel_kernel(float2 *__res
                             cy[k] = Ci.x + Ci.y;
                         }
                         float tx, ty;
-                        pn_quad_group_sum2(cx, cy, tx, ty);
+                        quad_rows_sum2(cx, cy, tx, ty);
                         const int Jl = JQ + ((g & 1) << 1) + (g >> 1);   // lane row g holds block column JQ + {0, 2, 1, 3}[g]
                         if (Jl >= J0 && Jl <= IB) sh.ycol[wave][16 * Jl + c16] = make_float2(tx, ty);
                     }
@@ -497,23 +441,27 @@ __global__ __launch_bounds__(32 * NT, 2) void tridiag_panel_kernel(float2 *__res
                         const float vA[8] = {PAr01.x, PAi01.x, PAr01.y, PAi01.y, PAr23.x, PAi23.x, PAr23.y, PAi23.y};
                         float w8[8], w4[4], w2[2];
 #pragma unroll
-                        for (int m = 0; m < 8; ++m) w8[m] = pn_keep_add<0x140>(b3, vB[m], vA[m]);   // row_mirror
+                        for (int m = 0; m < 8; ++m) w8[m] = keep_add<0x140>(b3, vB[m], vA[m]);   // row_mirror
 #pragma unroll
-                        for (int m = 0; m < 4; ++m) w4[m] = pn_keep_add<0x141>(b2, w8[m], w8[m + 4]);   // row_half_mirror
+                        for (int m = 0; m < 4; ++m) w4[m] = keep_add<0x141>(b2, w8[m], w8[m + 4]);   // row_half_mirror
 #pragma unroll
-                        for (int m = 0; m < 2; ++m) w2[m] = pn_keep_add<0x1B>(b1, w4[m], w4[m + 2]);   // quad_perm [3,2,1,0]
-                        total = pn_keep_add<0xB1>(b0, w2[0], w2[1]);                                 // quad_perm [1,0,3,2]
+                        for (int m = 0; m < 2; ++m) w2[m] = keep_add<0x1B>(b1, w4[m], w4[m + 2]);   // quad_perm [3,2,1,0]
+                        total = keep_add<0xB1>(b0, w2[0], w2[1]);                                 // quad_perm [1,0,3,2]
                         const int q = (c16 >> 1) & 3, I = b3 ? IA : IB;
                         reinterpret_cast<float *>(&sh.yrow[16 * I + 4 * g + q])[c16 & 1] = total;
                     } else if (IB >= J0) {   // (uniform) one block row: value (c16 & 7) on lane pairs {c16, c16 ^ 8}
                         float w4[4], w2[2];
 #pragma unroll
-                        for (int m = 0; m < 4; ++m) w4[m] = pn_keep_add<0x141>(b2, vB[m], vB[m + 4]);
+                        for (int m = 0; m < 4; ++m) w4[m] = keep_add<0x141>(b2, vB[m], vB[m + 4]);
 #pragma unroll
-                        for (int m = 0; m < 2; ++m) w2[m] = pn_keep_add<0x1B>(b1, w4[m], w4[m + 2]);
-                        total = pn_keep_add<0xB1>(b0, w2[0], w2[1]);
+                        for (int m = 0; m < 2; ++m) w2[m] = keep_add<0x1B>(b1, w4[m], w4[m + 2]);
+                        total = keep_add<0xB1>(b0, w2[0], w2[1]);
+                        // + lane c16 ^ 8 (row_ror:8): dpp_get<0x128>(total) of lane_reduce.h, written out.  As a call inside this
+                        // branch of the kernel body it changes the control-flow lowering of the whole kernel (10 534 assembly
+                        // lines differ, SGPR spills 23 -> 21 and 10 -> 2, two more ds_write_b32): kept so that the file's
+                        // device code stays byte-identical.
                         total += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, total), 0x128,
-                                                                                        0xF, 0xF, false));   // + lane c16 ^ 8 (row_ror:8)
+                                                                                        0xF, 0xF, false));
                         const int q = (c16 >> 1) & 3;
                         if (!b3) reinterpret_cast<float *>(&sh.yrow[16 * IB + 4 * g + q])[c16 & 1] = total;
                     }
@@ -523,8 +471,8 @@ __global__ __launch_bounds__(32 * NT, 2) void tridiag_panel_kernel(float2 *__res
                                        make_float2(PBr23.x, PBi23.x), make_float2(PBr23.y, PBi23.y)};
 #pragma unroll
                         for (int q = 0; q < 4; ++q) {
-                            P[q].x = pn_row16_sum(P[q].x);
-                            P[q].y = pn_row16_sum(P[q].y);
+                            P[q].x = row16_sum(P[q].x);
+                            P[q].y = row16_sum(P[q].y);
                         }
                         if (c16 == 0) {
 #pragma unroll
@@ -536,8 +484,8 @@ __global__ __launch_bounds__(32 * NT, 2) void tridiag_panel_kernel(float2 *__res
                                        make_float2(PAr23.x, PAi23.x), make_float2(PAr23.y, PAi23.y)};
 #pragma unroll
                         for (int q = 0; q < 4; ++q) {
-                            P[q].x = pn_row16_sum(P[q].x);
-                            P[q].y = pn_row16_sum(P[q].y);
+                            P[q].x = row16_sum(P[q].x);
+                            P[q].y = row16_sum(P[q].y);
                         }
                         if (c16 == 0) {
 #pragma unroll
@@ -572,8 +520,8 @@ __global__ __launch_bounds__(32 * NT, 2) void tridiag_panel_kernel(float2 *__res
                     const int m = 4 * ((wave - RW) + RW * ps) + g, k = c16;
                     const float2 tk = sh.Tl[m][k], gk = sh.Gp[k][j];
                     float2 acc = (k >= m && k < j) ? cmul(tk, gk) : make_float2(0.f, 0.f);
-                    acc.x = pn_row16_sum(acc.x);
-                    acc.y = pn_row16_sum(acc.y);
+                    acc.x = row16_sum(acc.x);
+                    acc.y = row16_sum(acc.y);
                     const float2 t = cmul(gam, acc);
                     if (c16 == 0) sh.Tl[m][j] = (m == j) ? gam : (m < j ? make_float2(-t.x, -t.y) : make_float2(0.f, 0.f));
                 }
@@ -596,7 +544,7 @@ __global__ __launch_bounds__(32 * NT, 2) void tridiag_panel_kernel(float2 *__res
                     }
                     mark(6);
                     if (p >= 0) {
-                        v2f acc = v2f{0.f, 0.f}, acc2 = v2f{0.f, 0.f};
+                        f32x2 acc = f32x2{0.f, 0.f}, acc2 = f32x2{0.f, 0.f};
                         for (int j0 = 0; j0 < j; j0 += 4) {
                             float2 vr[4], wr[4], g1[4], g2[4];   // (columns >= j of the panel and of g are zero)
 #pragma unroll
@@ -616,7 +564,7 @@ __global__ __launch_bounds__(32 * NT, 2) void tridiag_panel_kernel(float2 *__res
                         y.y -= acc.y + acc2.y;
                     }
                     {
-                        const v2f ty = pk_cfma(v2f{0.f, 0.f}, pk2(tau), pk2(y));
+                        const f32x2 ty = pk_cfma(f32x2{0.f, 0.f}, pk2(tau), pk2(y));
                         y = make_float2(ty.x, ty.y);
                     }
                     mark(12);
@@ -624,9 +572,9 @@ __global__ __launch_bounds__(32 * NT, 2) void tridiag_panel_kernel(float2 *__res
                 preg = y;
                 if (r == u) sh.pu = y;
                 float2 dp = cmacc(make_float2(0.f, 0.f), y, vreg);   // conj(p) v
-                dp.x = pn_row16_sum(dp.x);
-                dp.y = pn_row16_sum(dp.y);
-                pn_group_sum2(dp.x, dp.y);
+                dp.x = row16_sum(dp.x);
+                dp.y = row16_sum(dp.y);
+                rows_sum2(dp.x, dp.y);
                 if (lane == 0) sh.red2[wave] = dp;
             }
             mark(5);
@@ -640,13 +588,13 @@ __global__ __launch_bounds__(32 * NT, 2) void tridiag_panel_kernel(float2 *__res
                     dot.x += sh.red2[q].x;
                     dot.y += sh.red2[q].y;
                 }
-                const v2f alv = pk_cfma(v2f{0.f, 0.f}, pk2(tau), pk2(dot)) * -0.5f;
+                const f32x2 alv = pk_cfma(f32x2{0.f, 0.f}, pk2(tau), pk2(dot)) * -0.5f;
                 {
-                    const v2f t = pk_cfma(pk2(sh.pu), alv, pk2(hu));
+                    const f32x2 t = pk_cfma(pk2(sh.pu), alv, pk2(hu));
                     wu = make_float2(t.x, t.y);
                 }
                 if (tid < DL) {
-                    const v2f wv = pk_cfma(pk2(preg), alv, pk2(vreg));
+                    const f32x2 wv = pk_cfma(pk2(preg), alv, pk2(vreg));
                     wreg = (r >= u) ? make_float2(wv.x, wv.y) : make_float2(0.f, 0.f);
                     sh.Vp[r][j] = vreg;
                     sh.Wp[r][j] = wreg;

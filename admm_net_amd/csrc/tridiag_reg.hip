@@ -17,114 +17,14 @@
 #include <type_traits>
 
 #include "common.h"
+#include "lane_reduce.h"
 
 namespace admmnet {
 
 constexpr int TR_THREADS = 256;
 
-// DPP lane exchanges: no LDS traffic, no barrier.  CTRL 0x121/2/4/8 = row_ror:1/2/4/8 (rotate inside
-// each row of 16 lanes), 0x142 / 0x143 = row_bcast:15 / row_bcast:31 (last lane of a row -> next row(s)).
-template <int CTRL, int ROWMASK = 0xF>
-__device__ __forceinline__ float dpp_get(float x) {
-    return __builtin_bit_cast(float,
-                              __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), CTRL, ROWMASK, 0xF, false));
-}
-// sum over the 16 lanes of a DPP row; every lane of the row receives the total
-__device__ __forceinline__ float row16_sum(float x) {
-    x += dpp_get<0x128>(x);
-    x += dpp_get<0x124>(x);
-    x += dpp_get<0x122>(x);
-    x += dpp_get<0x121>(x);
-    return x;
-}
-// sum over the whole wave as a wave-uniform value (row totals chained through row_bcast, then a readlane)
-__device__ __forceinline__ float wave_sum_dpp(float x) {
-    x = row16_sum(x);
-    x += dpp_get<0x142, 0xA>(x);   // rows 1, 3 += row 0, 2
-    x += dpp_get<0x143, 0xC>(x);   // rows 2, 3 += rows 0 + 1
-    return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, x), 63));
-}
-
-// two wave sums at once: the chains interleave, so no DPP hazard stalls between dependent steps
-__device__ __forceinline__ void wave_sum_dpp2(float &x, float &y) {
-    x += dpp_get<0x128>(x); y += dpp_get<0x128>(y);
-    x += dpp_get<0x124>(x); y += dpp_get<0x124>(y);
-    x += dpp_get<0x122>(x); y += dpp_get<0x122>(y);
-    x += dpp_get<0x121>(x); y += dpp_get<0x121>(y);
-    x += dpp_get<0x142, 0xA>(x); y += dpp_get<0x142, 0xA>(y);
-    x += dpp_get<0x143, 0xC>(x); y += dpp_get<0x143, 0xC>(y);
-    x = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, x), 63));
-    y = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, y), 63));
-}
-
-// Complex arithmetic on (re, im) register pairs written so that hipcc emits ONE v_pk_fma_f32 per
-// half of a complex multiply-add (op_sel broadcasts, no shuffles): f32 vector peak on gfx950 needs
-// the packed form.  `rot(v)` = (-v.y, v.x) = i v and `rotc(v)` = (v.y, -v.x) = -i v are formed once
-// per vector element and reused across a whole block row / column.
-typedef float v2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ v2 tov2(float2 a) { return v2{a.x, a.y}; }
-__device__ __forceinline__ float2 tof2(v2 a) { return make_float2(a.x, a.y); }
-__device__ __forceinline__ v2 rot(v2 v) { return v2{-v.y, v.x}; }
-__device__ __forceinline__ v2 rotc(v2 v) { return v2{v.y, -v.x}; }
-// acc + m * v, given vj = rot(v)
-__device__ __forceinline__ v2 pk_cmac(v2 acc, v2 m, v2 v, v2 vj) {
-    acc = __builtin_elementwise_fma(m.xx, v, acc);
-    return __builtin_elementwise_fma(m.yy, vj, acc);
-}
-// acc + a * conj(b), given aj = rotc(a):  a conj(b) = b.x (a.x, a.y) + b.y (a.y, -a.x)
-__device__ __forceinline__ v2 pk_cmacc(v2 acc, v2 a, v2 aj, v2 b) {
-    acc = __builtin_elementwise_fma(b.xx, a, acc);
-    return __builtin_elementwise_fma(b.yy, aj, acc);
-}
-// The same two products with the i * v / -i * a rotations folded into the operand selects and negate
-// bits of v_pk_fma_f32 (the compiler materialises the rotated pair with a v_mov + v_xor per use):
-//   acc + m * v        = fma(m.xx, (v.x, v.y), acc), then fma(m.yy, (-v.y, v.x), .)
-//   acc + a * conj(b)  = fma(b.xx, (a.x, a.y), acc), then fma(b.yy, (a.y, -a.x), .)
-// The hazard recogniser does not see inside inline asm: a value that a DPP / lane instruction reads next
-// must come out of a compiler-emitted VALU op (see the last term of the HEMV loops).
-__device__ __forceinline__ v2 pk_cmac_sel(v2 acc, v2 m, v2 v) {
-    asm("v_pk_fma_f32 %0, %1, %2, %0 op_sel_hi:[0,1,1]\n\t"
-        "v_pk_fma_f32 %0, %1, %2, %0 op_sel:[1,1,0] op_sel_hi:[1,0,1] neg_lo:[0,1,0]"
-        : "+v"(acc)
-        : "v"(m), "v"(v));
-    return acc;
-}
-__device__ __forceinline__ v2 pk_cmacc_sel(v2 acc, v2 a, v2 b) {
-    asm("v_pk_fma_f32 %0, %2, %1, %0 op_sel_hi:[0,1,1]\n\t"
-        "v_pk_fma_f32 %0, %2, %1, %0 op_sel:[1,1,0] op_sel_hi:[1,0,1] neg_hi:[0,1,0]"
-        : "+v"(acc)
-        : "v"(a), "v"(b));
-    return acc;
-}
-// m * v (no accumulator to clear first)
-__device__ __forceinline__ v2 pk_cmul_sel(v2 m, v2 v) {
-    v2 acc;
-    asm("v_pk_mul_f32 %0, %1, %2 op_sel_hi:[0,1]\n\t"
-        "v_pk_fma_f32 %0, %1, %2, %0 op_sel:[1,1,0] op_sel_hi:[1,0,1] neg_lo:[0,1,0]"
-        : "=&v"(acc)
-        : "v"(m), "v"(v));
-    return acc;
-}
-// acc - a * conj(b): the same pair with the broadcast operand negated (neg_lo / neg_hi on src0)
-__device__ __forceinline__ v2 pk_cmsubc_sel(v2 acc, v2 a, v2 b) {
-    asm("v_pk_fma_f32 %0, %2, %1, %0 op_sel_hi:[0,1,1] neg_lo:[1,0,0] neg_hi:[1,0,0]\n\t"
-        "v_pk_fma_f32 %0, %2, %1, %0 op_sel:[1,1,0] op_sel_hi:[1,0,1] neg_lo:[1,0,0] neg_hi:[1,1,0]"
-        : "+v"(acc)
-        : "v"(a), "v"(b));
-    return acc;
-}
-// stage-wise row reduction of NA complex values: the NA chains interleave, so no DPP hazard stalls
-template <int NA, int A0>
-__device__ __forceinline__ void row16_sum_all(v2 (&acc)[NA]) {
-#pragma unroll
-    for (int a = A0; a < NA; ++a) { acc[a].x += dpp_get<0x128>(acc[a].x); acc[a].y += dpp_get<0x128>(acc[a].y); }
-#pragma unroll
-    for (int a = A0; a < NA; ++a) { acc[a].x += dpp_get<0x124>(acc[a].x); acc[a].y += dpp_get<0x124>(acc[a].y); }
-#pragma unroll
-    for (int a = A0; a < NA; ++a) { acc[a].x += dpp_get<0x122>(acc[a].x); acc[a].y += dpp_get<0x122>(acc[a].y); }
-#pragma unroll
-    for (int a = A0; a < NA; ++a) { acc[a].x += dpp_get<0x121>(acc[a].x); acc[a].y += dpp_get<0x121>(acc[a].y); }
-}
+// Lane sums and packed complex arithmetic: lane_reduce.h (rule 3 there: the last term of a sum of products that a DPP
+// reduction reads next is written with pk_cfma_open).
 
 // LDS vectors of one workgroup (double-buffered by reflector parity: one barrier separates a write
 // from the reads of the previous use)
@@ -194,7 +94,7 @@ __device__ __forceinline__ void tr_step(float2 (&m)[NA][NA], TrShared<NA> &sh, i
     // every vector entry in both passes (x is already in LDS / memory; only the head changes).
     const float g2 = sr * sr + si * si;
     const float2 tau = make_float2(tr * g2, tim * g2);
-    const v2 hu = v2{alpha.x - beta, alpha.y};
+    const f32x2 hu = f32x2{alpha.x - beta, alpha.y};
     if (tid == 0) {
         ecol[u] = beta;
         dcol[u] = (u == 0) ? corner : sh.dprev[par];
@@ -202,58 +102,58 @@ __device__ __forceinline__ void tr_step(float2 (&m)[NA][NA], TrShared<NA> &sh, i
     }
     // keep the reflector for the Q accumulation: row u of the (consumed) global image
     if (tid < D) {
-        v2 x = tov2(col[tid]);
+        f32x2 x = pk2(col[tid]);
         if (tid == u) x = hu;
-        Mg[(int64_t)u * D + tid] = tof2(x);
+        Mg[(int64_t)u * D + tid] = unpk2(x);
     }
     if (tr == 0.f && tim == 0.f) return;   // H = I (uniform)
 
-    v2 vr[NA], vc[NA];
+    f32x2 vr[NA], vc[NA];
 #pragma unroll
     for (int a = A0; a < NA; ++a) {
-        vr[a] = tov2(col[16 * a + ti]);
-        vc[a] = tov2(col[16 * a + tj]);
+        vr[a] = pk2(col[16 * a + ti]);
+        vc[a] = pk2(col[16 * a + tj]);
         if (a == A0) {   // the unit position can only sit in the first active block
             if (16 * a + ti == u) vr[a] = hu;
             if (16 * a + tj == u) vc[a] = hu;
         }
     }
-    const v2 vcj = rot(vc[NA - 1]);
+    const f32x2 vcj = rot(vc[NA - 1]);
     // p = tau * M v : partial over my columns, summed along the 16 fast lanes (all lanes of a row
     // of the thread grid end up with the p of their matrix rows)
-    v2 pr[NA];
+    f32x2 pr[NA];
 #pragma unroll
     for (int a = A0; a < NA; ++a) {
         if constexpr (A0 < NA - 1) {
-            v2 acc = pk_cmul_sel(tov2(m[a][A0]), vc[A0]);
+            f32x2 acc = pk_cmul(pk2(m[a][A0]), vc[A0]);
 #pragma unroll
-            for (int b = A0 + 1; b < NA - 1; ++b) acc = pk_cmac_sel(acc, tov2(m[a][b]), vc[b]);
-            pr[a] = pk_cmac(acc, tov2(m[a][NA - 1]), vc[NA - 1], vcj);   // last term by the compiler (DPP reads pr next)
+            for (int b = A0 + 1; b < NA - 1; ++b) acc = pk_cfma(acc, pk2(m[a][b]), vc[b]);
+            pr[a] = pk_cfma_open(acc, pk2(m[a][NA - 1]), vc[NA - 1], vcj);   // last term by the compiler (DPP reads pr next)
         } else {
-            pr[a] = pk_cmac(v2{0.f, 0.f}, tov2(m[a][NA - 1]), vc[NA - 1], vcj);
+            pr[a] = pk_cfma_open(f32x2{0.f, 0.f}, pk2(m[a][NA - 1]), vc[NA - 1], vcj);
         }
     }
     row16_sum_all<NA, A0>(pr);
-    const v2 tauv = tov2(tau), tauj = rot(tauv);
-    v2 dotp = {0.f, 0.f}, psel = {0.f, 0.f};
+    const f32x2 tauv = pk2(tau);
+    f32x2 dotp = {0.f, 0.f}, psel = {0.f, 0.f};
 #pragma unroll
     for (int a = A0; a < NA; ++a) {
-        pr[a] = pk_cmul_sel(pr[a], tauv);   // tau * acc
+        pr[a] = pk_cmul(pr[a], tauv);   // tau * acc
         // conj(p) v = v.x (p.x, -p.y) + v.y (p.y, p.x); every lane of the 16 adds the same term,
         // the total is scaled by 1/16 below (exact)
         if (a < NA - 1) {
-            dotp = pk_cmacc_sel(dotp, vr[a], pr[a]);   // + v_i conj(p_i)
+            dotp = pk_cfma_conj(dotp, pr[a], vr[a]);   // + conj(p_i) v_i
         } else {   // last term by the compiler (DPP reads dotp next)
-            dotp = __builtin_elementwise_fma(vr[a].xx, v2{pr[a].x, -pr[a].y}, dotp);
-            dotp = __builtin_elementwise_fma(vr[a].yy, v2{pr[a].y, pr[a].x}, dotp);
+            dotp = __builtin_elementwise_fma(vr[a].xx, f32x2{pr[a].x, -pr[a].y}, dotp);
+            dotp = __builtin_elementwise_fma(vr[a].yy, f32x2{pr[a].y, pr[a].x}, dotp);
         }
         psel = (tj == a) ? pr[a] : psel;
     }
-    if (tj >= A0 && tj < NA) sh.pbuf[par][16 * tj + ti] = tof2(psel);   // lane a of a row publishes p of block row a
+    if (tj >= A0 && tj < NA) sh.pbuf[par][16 * tj + ti] = unpk2(psel);   // lane a of a row publishes p of block row a
     {
         float dx = dotp.x, dy = dotp.y;
         wave_sum_dpp2(dx, dy);
-        dotp = v2{dx, dy};
+        dotp = f32x2{dx, dy};
     }
     if (lane == 0) sh.dotbuf[par][wave] = make_float2(dotp.x * 0.0625f, dotp.y * 0.0625f);
     __syncthreads();   // (B) p and the dot partials visible
@@ -264,31 +164,31 @@ __device__ __forceinline__ void tr_step(float2 (&m)[NA][NA], TrShared<NA> &sh, i
         dot.y += sh.dotbuf[par][q].y;
     }
     float2 al = cmul(tau, dot);
-    const v2 alv = v2{-0.5f * al.x, -0.5f * al.y}, alj = rot(alv);
+    const f32x2 alv = f32x2{-0.5f * al.x, -0.5f * al.y};
     // M -= v w^H + w v^H on the active block:  x += (-v_i) conj(w_j) + (-w_i) conj(v_j)
     // (w = p + alpha v, zero on the finished rows / columns i < u, which only block A0 can hold)
-    v2 wc[NA];
+    f32x2 wc[NA];
 #pragma unroll
     for (int b = A0; b < NA; ++b) {
         const int j = 16 * b + tj;
-        v2 w = pk_cmac_sel(tov2(sh.pbuf[par][j]), vc[b], alv);   // p_j + alpha v_j
-        if (b == A0) w = (j >= u) ? w : v2{0.f, 0.f};
+        f32x2 w = pk_cfma(pk2(sh.pbuf[par][j]), vc[b], alv);   // p_j + alpha v_j
+        if (b == A0) w = (j >= u) ? w : f32x2{0.f, 0.f};
         wc[b] = w;
     }
 #pragma unroll
     for (int a = A0; a < NA; ++a) {
         const int i = 16 * a + ti;
-        v2 w = pk_cmac_sel(pr[a], vr[a], alv);   // p_i + alpha v_i
-        if (a == A0) w = (i >= u) ? w : v2{0.f, 0.f};
-        const v2 wra = w;
-        const v2 vra = vr[a];
+        f32x2 w = pk_cfma(pr[a], vr[a], alv);   // p_i + alpha v_i
+        if (a == A0) w = (i >= u) ? w : f32x2{0.f, 0.f};
+        const f32x2 wra = w;
+        const f32x2 vra = vr[a];
 #pragma unroll
         for (int b = A0; b < NA; ++b) {
-            v2 x = tov2(m[a][b]);
-            x = pk_cmsubc_sel(x, vra, wc[b]);
-            x = pk_cmsubc_sel(x, wra, vc[b]);
+            f32x2 x = pk2(m[a][b]);
+            x = pk_cfms_conj(x, wc[b], vra);
+            x = pk_cfms_conj(x, vc[b], wra);
             if (a == b && ti == tj) x.y = 0.f;
-            m[a][b] = tof2(x);
+            m[a][b] = unpk2(x);
         }
     }
 }
@@ -327,28 +227,28 @@ __device__ __forceinline__ void q_step(float2 (&m)[NA][NA], const TrShared<NA> &
     q_load<NA, AP, FULL>(vn, u - 1, D, Mg);
     const float2 tau = sh.taus[u];
     if (!(tau.x == 0.f && tau.y == 0.f)) {
-        v2 vc[NA], y[NA];
+        f32x2 vc[NA], y[NA];
 #pragma unroll
-        for (int b = A0; b < NA; ++b) vc[b] = tov2(vcs[b]);
-        const v2 vjl = rot(vc[NA - 1]);
+        for (int b = A0; b < NA; ++b) vc[b] = pk2(vcs[b]);
+        const f32x2 vjl = rot(vc[NA - 1]);
 #pragma unroll
         for (int a = A0; a < NA; ++a) {
             if constexpr (A0 < NA - 1) {
-                v2 acc = pk_cmul_sel(tov2(m[a][A0]), vc[A0]);
+                f32x2 acc = pk_cmul(pk2(m[a][A0]), vc[A0]);
 #pragma unroll
-                for (int b = A0 + 1; b < NA - 1; ++b) acc = pk_cmac_sel(acc, tov2(m[a][b]), vc[b]);
-                y[a] = pk_cmac(acc, tov2(m[a][NA - 1]), vc[NA - 1], vjl);   // last term by the compiler (DPP reads y next)
+                for (int b = A0 + 1; b < NA - 1; ++b) acc = pk_cfma(acc, pk2(m[a][b]), vc[b]);
+                y[a] = pk_cfma_open(acc, pk2(m[a][NA - 1]), vc[NA - 1], vjl);   // last term by the compiler (DPP reads y next)
             } else {
-                y[a] = pk_cmac(v2{0.f, 0.f}, tov2(m[a][NA - 1]), vc[NA - 1], vjl);
+                y[a] = pk_cfma_open(f32x2{0.f, 0.f}, pk2(m[a][NA - 1]), vc[NA - 1], vjl);
             }
         }
         row16_sum_all<NA, A0>(y);
-        const v2 nct = v2{-tau.x, tau.y}, nctj = rot(nct);   // -conj(tau)
+        const f32x2 nct = f32x2{-tau.x, tau.y};   // -conj(tau)
 #pragma unroll
         for (int a = A0; a < NA; ++a) {
-            const v2 nty = pk_cmul_sel(y[a], nct);
+            const f32x2 nty = pk_cmul(y[a], nct);
 #pragma unroll
-            for (int b = A0; b < NA; ++b) m[a][b] = tof2(pk_cmacc_sel(tov2(m[a][b]), nty, vc[b]));   // -= conj(tau) y conj(v_b)
+            for (int b = A0; b < NA; ++b) m[a][b] = unpk2(pk_cfma_conj(pk2(m[a][b]), vc[b], nty));   // -= conj(tau) y conj(v_b)
         }
     }
 #pragma unroll

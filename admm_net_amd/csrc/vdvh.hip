@@ -17,8 +17,6 @@
 
 namespace admmnet {
 
-using f32x16 = __attribute__((ext_vector_type(16))) float;
-
 constexpr int VD_THREADS = 256;
 
 __global__ __launch_bounds__(VD_THREADS) void vdvh_kernel(int n, const float2 *__restrict__ Vg, const float *__restrict__ dg,

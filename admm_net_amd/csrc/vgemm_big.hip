@@ -13,8 +13,6 @@
 
 namespace admmnet {
 
-using f32x16 = __attribute__((ext_vector_type(16))) float;
-
 constexpr int VB_THREADS = 256;
 constexpr int VB_KS = 16;              // K rows per slab
 constexpr int VB_DP = 256;             // plane width of the B slab (real | imaginary)

@@ -24,8 +24,6 @@
 
 namespace admmnet {
 
-using f32x4 = __attribute__((ext_vector_type(4))) float;
-
 constexpr int WY_D = 256;
 constexpr int WY_THREADS = 256;
 constexpr int WY_PITCH = 18;    // float2 per LDS row of the panel (as tridiag_panel.hip)
@@ -206,11 +204,11 @@ __global__ __launch_bounds__(64) void wy_lastcol_kernel(const float2 *__restrict
     const float *WT = Wbuf + bm * (int64_t)3 * n * n + wm.x;
     const int rlo = wm.y & 0xffff, rhi = min(wm.y >> 16, n);
     float *Vb = VT + bm * ((int64_t)n * 2 * D);
-    v2f xv[4];
+    f32x2 xv[4];
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
         const int r = 1 + lane + 64 * k;
-        xv[k] = v2f{(r >= rlo && r < rhi) ? WT[r] : 0.f, 0.f};
+        xv[k] = f32x2{(r >= rlo && r < rhi) ? WT[r] : 0.f, 0.f};
     }
     float2 va[WL_BATCH][4], vb[WL_BATCH][4], ta[WL_BATCH], tb[WL_BATCH];
     auto gload = [&](float2(&buf)[WL_BATCH][4], float2(&tt)[WL_BATCH], int u0) {   // reflectors u0, u0 - 1, ...
@@ -225,13 +223,14 @@ __global__ __launch_bounds__(64) void wy_lastcol_kernel(const float2 *__restrict
     auto apply = [&](const float2(&buf)[WL_BATCH][4], const float2(&tt)[WL_BATCH]) {
 #pragma unroll
         for (int i = 0; i < WL_BATCH; ++i) {
-            v2f d0 = pk_cfma_conj(v2f{0.f, 0.f}, pk2(buf[i][0]), xv[0]), d1 = pk_cfma_conj(v2f{0.f, 0.f}, pk2(buf[i][1]), xv[1]);
+            f32x2 d0 = pk_cfma_conj(f32x2{0.f, 0.f}, pk2(buf[i][0]), xv[0]);
+            f32x2 d1 = pk_cfma_conj(f32x2{0.f, 0.f}, pk2(buf[i][1]), xv[1]);
             d0 = pk_cfma_conj(d0, pk2(buf[i][2]), xv[2]);
             d1 = pk_cfma_conj(d1, pk2(buf[i][3]), xv[3]);
-            float dx = pn_row16_sum(d0.x + d1.x), dy = pn_row16_sum(d0.y + d1.y);
-            pn_group_sum2(dx, dy);
+            float dx = row16_sum(d0.x + d1.x), dy = row16_sum(d0.y + d1.y);
+            rows_sum2(dx, dy);
             const float2 sc = cmul(tt[i], make_float2(dx, dy));   // tau (v^H x)
-            const v2f nsc = v2f{-sc.x, -sc.y};
+            const f32x2 nsc = f32x2{-sc.x, -sc.y};
 #pragma unroll
             for (int k = 0; k < 4; ++k) xv[k] = pk_cfma(xv[k], nsc, pk2(buf[i][k]));   // x -= tau (v^H x) v
         }
